@@ -43,6 +43,27 @@ LDS_PEAK_GBS = 256 * 256 * 2.4   # 256 CUs x 256 B/clk (ds_read_b64, MI355X_MICR
 FP64_VALU_PEAK_TFLOPS = 78.6
 
 LINE_CAP = 8192      # the driver keeps an 8 KB tail of stdout: the LAST line must fit in it with room to spare
+DUMP_CAP_BYTES = 64 << 20   # --dump-outputs: all arrays together
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: write every (name -> array with one row per chain) as dirname/<name><suffix>.npy in float64.  When
+    they would exceed DUMP_CAP_BYTES, the same fixed, seeded sample of chains is kept in every array, and the chosen
+    chain indices are written as chain_index<suffix>.npy.  -> the names written"""
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrays.values()}
+    assert len(n) == 1, "every dumped array has one row per chain"
+    n = n.pop()
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if row_bytes * n > DUMP_CAP_BYTES:
+        keep = (DUMP_CAP_BYTES - 4096) // (row_bytes + 8)     # (4 KB for the .npy headers)
+        idx = np.sort(np.random.default_rng(20240601).choice(n, size=keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["chain_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + suffix + ".npy"), a)
+    return sorted(arrays)
 
 
 def _r(x, sig=5):
@@ -350,7 +371,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3,
-                    help="timed regions of --steps steps each; `value` is their median")
+                    help="the --steps timed steps are split into this many timed regions (at most one per step); "
+                         "`ms_per_step` is the median over the regions of a region's time per step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned after its last step (chain positions, likelihood vectors, "
+                         "acceptance counts) as DIR/<name>.npy in float64, at most %d MB" % (DUMP_CAP_BYTES >> 20))
     ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"),
                     help="where the complete result object (all legs, notes) is written; stdout gets the compact line")
     ap.add_argument("--chains", type=int, default=512, help="chains per GPU per step")
@@ -414,6 +439,10 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         raise SystemExit(subprocess.call(cmd))
+    # the CPU baseline forks one worker per core: it runs before this process opens the GPU, so that no worker inherits
+    # the device
+    spec = make_spec(args)
+    cpu_base = cpu_baseline(spec) if world == 1 and not args.no_cpu_baseline else None
     # BEATAMD_BENCH_BACKEND=gloo (tests/test_gpu_dist.py): every rank uses cuda:0 -- N ranks share ONE GPU and the
     # collectives are staged through host memory (beat_amd.parallel._staged; RCCL refuses duplicate devices).
     # The contract (n_gpus, global chains, value = all ranks' chain-steps / max time, a stage transition whose
@@ -442,7 +471,6 @@ def main():
     ctx.use_torch_stream()
     env_knobs = sorted(k for k in os.environ if k.startswith("BEATAMD_G"))
 
-    spec = make_spec(args)
     t_build = time.perf_counter()
     prob, host = build_problem(spec, device_library=True, ctx=ctx)
     f = prob.compile(ctx, prewhiten="inplace" if args.prewhiten else False)
@@ -467,9 +495,11 @@ def main():
         return torch.cat(parts, 0)
 
     def run_leg(spec_leg, f_leg, n_chains, n_steps, n_warm, seed_offset, beta=2e-6, repeats=1):
-        """`repeats` timed regions of n_steps astep batches of n_chains chains each (every region bracketed by a barrier
-        and a device synchronisation on both sides); everything resident in HBM beforehand.
-        -> dict(dt = median region, dts, kernel times over all regions, in-box fraction, acceptance)"""
+        """n_steps timed astep batches of n_chains chains each, split into `repeats` consecutive regions (at most one per
+        step; every region bracketed by a barrier and a device synchronisation on both sides); everything resident in HBM
+        beforehand.
+        -> dict(dt = median region, dts, region_steps, kernel times over all regions, in-box fraction, acceptance, the
+        chains' end state)"""
         box = host_of[spec_leg]
         lay_l = box.get("layout", lay)   # the legs of the main library share its parameter layout; only the prior box differs
         Q0 = torch.from_numpy(draw_population(spec_leg, lay_l, box["lower"], box["upper"], n_chains,
@@ -479,7 +509,7 @@ def main():
         L0 = f_leg.batch(Q0)
         # proposal rows: proposal_samples_array[stage_sample] of every chain (metropolis.py:289-313)
         first = seed_offset - 1000      # (the global index of this leg's first chain)
-        nsw = n_steps * repeats + n_warm
+        nsw = n_steps + n_warm
         delta = seeded_blocks(lambda shp, g: torch.randn(shp, generator=g, device=dev, dtype=torch.float64),
                               n_chains, first, (nsw, lay_l.size)).permute(1, 0, 2).contiguous()
         delta = delta * (args.step_scale * (up_s - lo_s))
@@ -504,12 +534,14 @@ def main():
         ctx.reset_timing()
         n_acc = 0
         dts = []
-        for rep in range(repeats):
+        n_reg = max(1, min(repeats, n_steps))
+        edges = [n_warm + n_steps * r // n_reg for r in range(n_reg + 1)]
+        for rep in range(n_reg):
             if use_dist:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for i in range(n_warm + rep * n_steps, n_warm + (rep + 1) * n_steps):
+            for i in range(edges[rep], edges[rep + 1]):
                 step(i)
             torch.cuda.synchronize()
             if use_dist:
@@ -521,19 +553,26 @@ def main():
         times = {k: ctx.kernel_time(k) for k in ("sweep", "tables", "grouptables", "gfstack", "quadform",
                                                  "finish", "astep")}
         ctx.enable_timing(False)
-        return dict(dt=sorted(dts)[len(dts) // 2], dts=dts, times=times, in_box=in_box,
-                    accept_last=n_acc / float(n_chains), steps_timed=n_steps * repeats,
-                    kernel=ctx.last_kernel(), stats=ctx.gf_group_stats(), Q=Q0, L=L0)
+        return dict(dt=sorted(dts)[len(dts) // 2], dts=dts, region_steps=[b - a for a, b in zip(edges, edges[1:])],
+                    times=times, in_box=in_box, accept_last=n_acc / float(n_chains), steps_timed=n_steps,
+                    kernel=ctx.last_kernel(), stats=ctx.gf_group_stats(), Q=Q0, L=L0, accepted=accepted)
 
     host_of = {spec: host}
-    # `value`: the MEDIAN of `--repeats` timed regions of exactly K steps each (max over ranks per region)
+    # exactly K timed steps in `--repeats` regions; `ms_per_step`: the MEDIAN over the regions of a region's time per step
+    # (max over ranks per region), `value` follows from it
     R = max(1, args.repeats)
     main_leg = run_leg(spec, f, B, K, W, seed_offset=1000 + rank * B, repeats=R)
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step: every chain's state, likelihood vector and count
+        dump_outputs(args.dump_outputs, {"positions": main_leg["Q"].cpu().numpy(), "likelihoods": main_leg["L"].cpu().numpy(),
+                                         "accepted": main_leg["accepted"].cpu().numpy()},
+                     suffix="" if world == 1 else "_rank%d" % rank)
     tmax = torch.tensor(main_leg["dts"], device="cpu" if backend == "gloo" else dev, dtype=torch.float64)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     region_s = [float(x) for x in tmax.tolist()]
-    dt_max = sorted(region_s)[len(region_s) // 2]
+    per_step = sorted(t / n for t, n in zip(region_s, main_leg["region_steps"]))
+    dt_max = per_step[len(per_step) // 2] * K     # (the time of K steps at the median rate)
 
     # ---- SMC stage transition on the end points of the timed steps (select_end_points ->
     # calc_beta -> proposal factor -> resample -> restart points, smc.py:133-324): all-gather over
@@ -684,7 +723,7 @@ def main():
             },
             "roofline": roof,
             "kernel_ms_per_step": {k: (v[0] / main_leg["steps_timed"]) for k, v in main_leg["times"].items() if v[1]},
-            "repeats": R, "region_s": region_s,
+            "repeats": len(region_s), "region_s": region_s, "region_steps": main_leg["region_steps"],
             "in_box_fraction": main_leg["in_box"],
             "accept_rate_last_step": main_leg["accept_last"],
             "stage_transition_ms": stage_ms,
@@ -1162,13 +1201,15 @@ def main():
                 "chain_steps_per_s": 1024 / (min(gleg.values()) * 1e-6)}
         if "sharded" in legs:
             # libraries sharded by TARGET (SURVEY 8(e) fallback for libraries beyond one GPU): tools/time_sharded.py in
-            # processes of their own -- 1 rank replicated (fused step), then 2 and 8 ranks holding the rows of their targets,
-            # ALL ON THIS ONE GPU (gloo, the all-gather staged through host memory): the step in pieces + one all-gather
+            # processes of their own -- 1 rank replicated (fused step), then 2 and 4 ranks holding the rows of their targets,
+            # ALL ON THIS ONE GPU (gloo, the all-gather staged through host memory): the step in pieces + one all-gather.
+            # (Four ranks at most: the launcher's agent opens the GPU too, so with this process N ranks are N + 2 processes
+            # holding the device -- eight made ten, more than a shared node allows; four make six.)
             import subprocess
             sh = {}
             tool = os.path.join(ROOT, "tools", "time_sharded.py")
             env_s = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-            for nr in (1, 2, 8):
+            for nr in (1, 2, 4):
                 cmd = [sys.executable, tool] if nr == 1 else \
                     [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nr), "--master-addr",
                      "127.0.0.1", "--master-port", str(29650 + nr), tool]
@@ -1299,8 +1340,8 @@ def main():
                               "prior spanning the library axis (U(0,4) s)" % (spr.lib_bytes / 1e9))
             out["realistic_grid_leg"] = rr
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(spec)
+        if cpu_base is not None:
+            out["cpu_baseline"] = cpu_base
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         # the complete object (every leg with its notes, plans, splits) goes to disk; stdout ends with ONE compact line
         full_path = None

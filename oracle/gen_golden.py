@@ -129,6 +129,22 @@ def gen_sweep_ties():
     save("sweep_ties", **cases)
 
 
+def gen_sweep_random():
+    """the 150 random grids of tests/test_oracle_ref.py (same seed, same draws) through the C extension: slowness and
+    times of all grids concatenated, meta rows (patch size, hypocentre dip / strike index, n dip, n strike)"""
+    rng = np.random.default_rng(42)
+    slows, times, meta = [], [], []
+    for _ in range(150):
+        nd, ns = int(rng.integers(2, 21)), int(rng.integers(2, 21))
+        slow = 1.0 / rng.uniform(0.5, 6.0, nd * ns)
+        psz = float(rng.uniform(0.5, 3.0))
+        hd, hs = int(rng.integers(0, nd)), int(rng.integers(0, ns))
+        slows.append(slow)
+        times.append(fast_sweep_ext.fast_sweep(slow, psz, hd, hs, nd, ns))
+        meta.append([psz, hd, hs, nd, ns])
+    save("sweep_random", slow=np.concatenate(slows), times=np.concatenate(times), meta=np.array(meta, dtype=np.float64))
+
+
 # ---------------------------------------------------------------- positions2idxs
 def gen_positions():
     rng = np.random.default_rng(7)
@@ -333,6 +349,7 @@ if __name__ == "__main__":
         sys.exit(0)
     gen_sweep()
     gen_sweep_ties()
+    gen_sweep_random()
     gen_positions()
     gen_stack()
     gen_cov()

@@ -105,3 +105,28 @@ def test_committed_round6_line_is_what_the_driver_needs():
     legs = d["legs"]
     for name in ("config4.N120.multilinear_512_chains", "config4.N120.nn_512_chains"):
         assert legs[name].get("pmc") == 1 and legs[name]["frac"] > 0.3, (name, legs[name])
+
+
+def test_dump_outputs_float64_and_capped(tmp_path):
+    """--dump-outputs: float64 arrays named after the outputs; above the cap the same seeded sample of chains in every array
+    (twice the same rows), with the chosen chain indices beside them"""
+    import numpy as np
+
+    import bench
+    rng = np.random.default_rng(3)
+    Q, L, acc = rng.standard_normal((512, 7)), rng.standard_normal((512, 3)), rng.integers(0, 9, 512).astype(np.int32)
+    names = bench.dump_outputs(str(tmp_path / "a"), {"positions": Q, "likelihoods": L, "accepted": acc})
+    assert names == ["accepted", "likelihoods", "positions"]
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["positions"], Q) and np.array_equal(got["accepted"], acc)
+    big = rng.standard_normal((2 * bench.DUMP_CAP_BYTES // (8 * 1000), 1000))
+    ids = np.arange(big.shape[0])
+    for d in ("b", "c"):
+        names = bench.dump_outputs(str(tmp_path / d), {"positions": big, "ids": ids})
+        assert names == ["chain_index", "ids", "positions"]
+        assert sum(os.path.getsize(str(tmp_path / d / (n + ".npy"))) for n in names) <= bench.DUMP_CAP_BYTES
+    sel = np.load(str(tmp_path / "b" / "chain_index.npy")).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "ids.npy")), sel)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "positions.npy")), big[sel])
+    assert np.array_equal(np.load(str(tmp_path / "c" / "chain_index.npy")), sel)

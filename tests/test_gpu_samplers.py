@@ -483,7 +483,7 @@ def test_bench_two_ranks_over_rccl():
 
     import torch
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs 2 GPUs")
+        pytest.skip("needs 2 GPUs, found %d" % torch.cuda.device_count())
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29577", os.path.join(root, "bench.py"),
