@@ -82,9 +82,11 @@ struct LikeTail {
     const int32_t *chain_bad = nullptr;
 };
 
-// logp_forw_func on device pointers
+// logp_forw_func on device pointers.  `active` (device [C], nullable): chains whose rows of LL the caller will not read;
+// kernels that honour it skip those chains and leave their rows unspecified (the fused Metropolis step passes the
+// in-box flags of its proposals)
 int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, double *LL,
-                    LikeTail *tail = nullptr)
+                    LikeTail *tail = nullptr, const int32_t *active = nullptr)
 {
     const int64_t nllk = m.nllk();
     const int64_t np = m.layout.nparams;
@@ -129,6 +131,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             k.st.shift_off = wm.shift_off;
             k.st.nslot = wm.nslot; k.st.tslot = wm.tslot; k.st.slot_shift_off = wm.slot_shift_off;
             k.st.chain_bad = chain_bad;
+            k.active = active;
             k.interp = wm.interp;
             k.f32 = wm.f32;
             k.C = C;
@@ -1108,7 +1111,10 @@ static int astep_impl(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0,
     // the `like` sum rides in the accept kernel (one launch fewer) while the row fits its LDS stage
     LikeTail tail;
     const bool fold = nllk * 8 <= 48 * 1024;
-    BA_TRY(ffi_logp_device(ctx, *m, C, qprop, lprop, fold ? &tail : nullptr));
+    // proposals outside the prior box are parked on their current point and always rejected: their likelihood rows are
+    // never read (k_accept), so the stacking kernel may skip them (BEATAMD_SKIP_PARKED=0: evaluate every chain)
+    const int32_t *active = GfKnobs::get(gf_knobs(ctx).skip_parked, 1) != 0 ? inb : nullptr;
+    BA_TRY(ffi_logp_device(ctx, *m, C, qprop, lprop, fold ? &tail : nullptr, active));
     BA_TRY(launch_accept(ctx, C, np, nllk, (double *)d_q0, (double *)d_l0, qprop, lprop, inb,
                          (const double *)d_lu, beta, (const double *)d_be, (int32_t *)d_acc,
                          fold ? &tail.grp : nullptr, tail.chain_bad, acc_sum, n_acc, advance));

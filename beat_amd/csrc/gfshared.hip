@@ -1214,6 +1214,12 @@ k_gfstack_ws(GsArgs a)
     // group in flight while it finishes step s -- the LDS pipe does not drain at every barrier.
     double w;
     uint32_t xs;
+    // a wavefront none of whose positions holds a chain (behind the last chain, or behind the active chains of a packed
+    // group: k_ws_pack) gathers nothing: it only keeps the workgroup's barrier count -- the one of step 0 and one per
+    // step, as below -- and joins the epilogue (it stages its share of the data tile there; it stores nothing)
+    if (__ballot(c < a.C) == 0) {
+        for (int s = 0; s <= nsteps; s++) __builtin_amdgcn_s_barrier();
+    } else {
     fetch_tabs(tab_slot(0), tab_w(0, 0));
     xs = row_address(lds0);
     w = landed_weight(xs);
@@ -1326,6 +1332,7 @@ k_gfstack_ws(GsArgs a)
                    "+v"(ya[7]), "+v"(yb[0]), "+v"(yb[1]), "+v"(yb[2]), "+v"(yb[3]), "+v"(yb[4]), "+v"(yb[5]),
                    "+v"(yb[6]), "+v"(yb[7]), "+v"(sl_n), "+v"(wl_n));
     __builtin_amdgcn_sched_barrier(0);
+    }
 
     // ---- epilogue: lane = chain c, acc[i] = synthetics[c, t, n0 + i]
     const bool live = (c < a.C);
@@ -1910,6 +1917,31 @@ __global__ void __launch_bounds__(256) k_ws_scan(const uint32_t *npass, uint32_t
     if (tid == 0) nv[gt] = run;
 }
 
+// The active chains of every 512-chain group first, in the group's order, then ~0 (one workgroup per group): the chains of a
+// group that the caller does not need (a mask, GfStackCall::active) leave the group's distinct rows and, as whole
+// wavefronts behind the active ones, the gather of k_gfstack_ws.  Group membership is unchanged.
+__global__ void __launch_bounds__(WS_CG) k_ws_pack(const uint32_t *order, const int32_t *active, int64_t C, uint32_t *out)
+{
+    __shared__ uint32_t wsum[WS_CG / 64];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wv = tid >> 6;
+    const int64_t pos = (int64_t)blockIdx.x * WS_CG + tid;
+    const uint32_t c = order ? order[pos] : (pos < C ? (uint32_t)pos : 0xffffffffu);
+    const bool on = c != 0xffffffffu && (int64_t)c < C && active[c] != 0;
+    const uint64_t m = __ballot(on);
+    if (lane == 0) wsum[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (int q = 0; q < WS_CG / 64; q++) {
+        const uint32_t x = wsum[q];
+        if (q < wv) before += x;
+        total += x;
+    }
+    uint32_t *o = out + (int64_t)blockIdx.x * WS_CG;
+    if (on) o[before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = c;
+    if ((uint32_t)tid >= total) o[tid] = 0xffffffffu;
+}
+
 // MAP: the distinct rows through a presence map over the D * S rows of the patch in LDS (libraries up to WS_MAP_MAX rows
 // per patch: every one so far); else by ranking the 512 row ids against each other (no bound, ~20 x the LDS traffic)
 constexpr int64_t WS_MAP_MAX = 16384;
@@ -1932,8 +1964,11 @@ __global__ void __launch_bounds__(WS_CG) k_ws_tables(WsTabArgs a)
     const int64_t t = gt % a.T;
     const int64_t g = gt / a.T;
     const int64_t pos_in_batch = g * WS_CG + tid;
-    const bool live = pos_in_batch < a.C;
-    const int64_t c = live ? (a.order ? (int64_t)a.order[pos_in_batch] : pos_in_batch) : 0;
+    // (an order entry ~0 is a position without a chain: behind the last chain of a group, or behind the active chains of a
+    // packed group -- k_ws_pack)
+    const uint32_t oc = a.order ? a.order[pos_in_batch] : (uint32_t)pos_in_batch;
+    const bool live = pos_in_batch < a.C && oc != 0xffffffffu;
+    const int64_t c = live ? (int64_t)oc : 0;
     const uint32_t v = live ? a.rowoff[(c * a.T + t) * a.P + p] : 0xffffffffu;
     // (the chain's slips are requested here, next to its row id: behind the barriers below they were one more exposed round
     // trip per patch)
@@ -2004,7 +2039,8 @@ __global__ void __launch_bounds__(WS_CG) k_ws_tables(WsTabArgs a)
         }
         for (int q = 0; q < WS_CG / 64; q++) U += wsum[q];
     }
-    const int npass = (int)((U + (uint32_t)a.cap - 1) / (uint32_t)a.cap);
+    // (a group without one active chain still gets one pass of no rows: tables with zero rows, zero-row slots, zero weights)
+    const int npass = U == 0 ? 1 : (int)((U + (uint32_t)a.cap - 1) / (uint32_t)a.cap);
     if constexpr (!FILL) {
         if (tid == 0) {
             a.npass[gtp] = (uint32_t)npass;
@@ -2013,7 +2049,7 @@ __global__ void __launch_bounds__(WS_CG) k_ws_tables(WsTabArgs a)
         return;
     }
     if (tid == 0) a.utotal[gtp] = U;
-    const int per = ((int)U + npass - 1) / npass;       // rows of a pass (the last may hold fewer)
+    const int per = U == 0 ? 1 : ((int)U + npass - 1) / npass;   // rows of a pass (the last may hold fewer)
     if constexpr (!MAP) {
         if (first) lst[pos] = v;
     }
@@ -2085,7 +2121,7 @@ __global__ void __launch_bounds__(WS_CG) k_ws_tables(WsTabArgs a)
             // padded with the last id: the loaders fetch entries ahead of the count
             const int j = tid;
             uint32_t *e = a.uent + ((vs * WS_LW + (j % WS_LW)) * kstr + (j / WS_LW)) * 2;
-            e[0] = lst[base + (j < n ? j : n - 1)];
+            e[0] = n > 0 ? lst[base + (j < n ? j : n - 1)] : 0u;
             e[1] = j < n ? (uint32_t)slt[base + j] : 0u;
         }
     }
@@ -2239,6 +2275,11 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     ta.w = (double *)p;
     {
         ScopedTimer tm(ctx, "grouptables");
+        if (k.active) {
+            BA_TRY(ctx->get_scratch(SL_WS_PACK, (size_t)ngroups * WS_CG * sizeof(uint32_t), &p));
+            hipLaunchKernelGGL(k_ws_pack, dim3((unsigned)ngroups), dim3(WS_CG), 0, ctx->stream, ta.order, k.active, k.C, (uint32_t *)p);
+            ta.order = (const uint32_t *)p;
+        }
         const bool map = ta.DS <= WS_MAP_MAX && !GfKnobs::is(kn.ws_map, 0);   // (BEATAMD_WS_MAP=0: tests of the ranking path)
         const size_t mlds = map ? (size_t)ta.DS * sizeof(uint16_t) : 0;
         if (maxpass > 1) {

@@ -534,6 +534,7 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
     const SeisLib &L = *call.libs[0];
     SeisLib views[4];
     GfStackCall v = call;
+    v.active = nullptr;   // (k_split_combine reads every chain's partial synthetics)
     for (int i = 0; i < call.nvar; i++) {
         views[i] = *call.libs[i];
         views[i].T = L.T * R;

@@ -92,6 +92,9 @@ struct GfStackCall {
     int patch_split = 1;
     const GfKnobs *knobs = nullptr;   // set by launch_gfstack (gf_knobs(ctx)): the selection functions read them here
     const int32_t *tslot = nullptr;   // set by launch_gfstack: table slot of a target when targets share tables (device [T])
+    // optional [C] mask (the fused Metropolis step: proposals inside the prior box).  A kernel that honours it may leave the
+    // outputs of chains with active[c] == 0 unwritten; one that ignores it evaluates them (their points are in the grid).
+    const int32_t *active = nullptr;
 };
 int launch_gfstack(beatamd_ctx *ctx, const GfStackCall &call);
 int launch_sum_tiles(beatamd_ctx *ctx, const double *partial, int64_t n, int ntile, double *quad,

@@ -385,6 +385,15 @@ __global__ void __launch_bounds__(256) k_accept(int64_t C, int64_t nparams, int6
 {
     extern __shared__ __attribute__((aligned(16))) double s_l[];
     const int64_t c = blockIdx.x;
+    // a proposal outside the box is rejected without a look at its likelihood row: the forward model may have skipped it
+    // (ffi_logp_device's `active`), the row then holds whatever an earlier step left there
+    if (!inbounds[c]) {
+        if (threadIdx.x == 0) {
+            accepted[c] = 0;
+            if (step_dev && c == 0) *step_dev += 1u;
+        }
+        return;
+    }
     double lp;
     if (grp.n > 0) {
         for (int64_t k = threadIdx.x; k < nllk - 1; k += 256) s_l[k] = Lprop[c * nllk + k];
@@ -408,7 +417,7 @@ __global__ void __launch_bounds__(256) k_accept(int64_t C, int64_t nparams, int6
     }
     const double b = betas ? betas[c] : beta;  // per-replica beta for parallel tempering
     const double mr = b * (lp - L0[c * nllk + nllk - 1]);
-    const bool acc = inbounds[c] && isfinite(mr) && (log_u[c] < mr);
+    const bool acc = isfinite(mr) && (log_u[c] < mr);
     if (acc) {
         for (int64_t k = threadIdx.x; k < nparams; k += 256) Q0[c * nparams + k] = Qprop[c * nparams + k];
         __syncthreads();  // all lanes have read L0[like] before it is overwritten
