@@ -20,10 +20,18 @@ HBM when the timed region starts.
     python bench.py                        # 1 GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --full                 # + every other leg (see below)
+
+A plain run does only what the headline needs: set-up, the warm-up and timed steps, the
+``--dump-outputs`` arrays and the result line (with the headline kernel's roofline, from the
+timed steps' own kernel times).  Everything else this file measures runs only with ``--full``:
+the CPU baseline, the SMC stage transition, the streaming-kernel roofline leg, the 2048-chain
+and narrow-prior legs and the labelled legs of the other configurations (``--variant-legs``);
+the ``--no-*`` options leave out single ones of them.
 
 Chains are sharded over ranks (weak scaling: fixed chains per GPU); there is no collective
 inside a step -- the SMC stage transition (all-gather of end points, once per ~100-400
-steps) is timed separately and reported as ``stage_transition_ms``.
+steps) is timed separately (``--full``) and reported as ``stage_transition_ms``.
 """
 import argparse
 import json
@@ -396,6 +404,9 @@ def main():
                     help="proposal standard deviation as a fraction of the prior span of every parameter")
     ap.add_argument("--prewhiten", action="store_true",
                     help="toeplitz only: whiten the library once (W.G), no dense W.r per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: the CPU baseline, the SMC stage transition and the "
+                         "labelled legs below (a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-streaming-leg", action="store_true",
                     help="skip the reuse-free streaming-kernel leg (roofline_streaming)")
@@ -442,7 +453,7 @@ def main():
     # the CPU baseline forks one worker per core: it runs before this process opens the GPU, so that no worker inherits
     # the device
     spec = make_spec(args)
-    cpu_base = cpu_baseline(spec) if world == 1 and not args.no_cpu_baseline else None
+    cpu_base = cpu_baseline(spec) if args.full and world == 1 and not args.no_cpu_baseline else None
     # BEATAMD_BENCH_BACKEND=gloo (tests/test_gpu_dist.py): every rank uses cuda:0 -- N ranks share ONE GPU and the
     # collectives are staged through host memory (beat_amd.parallel._staged; RCCL refuses duplicate devices).
     # The contract (n_gpus, global chains, value = all ranks' chain-steps / max time, a stage transition whose
@@ -577,19 +588,20 @@ def main():
     # ---- SMC stage transition on the end points of the timed steps (select_end_points ->
     # calc_beta -> proposal factor -> resample -> restart points, smc.py:133-324): all-gather over
     # the ranks + the device kernels; outside the timed steps (it happens once per ~100-400 steps)
-    smc = SMC(f, lo, up, n_chains=world * B, device=dev, random_seed=7)
-    for rep in range(2):   # first pass allocates
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        smc.beta = 0.0
-        smc.select_end_points(main_leg["Q"], main_leg["L"])
-        smc.transition()
-        Qn, Ln = smc.restart_points()
-        torch.cuda.synchronize()
-        stage_ms = (time.perf_counter() - t1) * 1e3
-    assert Qn.shape == main_leg["Q"].shape and smc.Q_all.shape[0] == world * B
-    # the gathered end points of all ranks (identical on every rank): sums as a sharding-independent fingerprint
-    pop_sum = (float(smc.Q_all.sum().item()), float(smc.L_all[:, -1].sum().item()), float(smc.beta))
+    if args.full:
+        smc = SMC(f, lo, up, n_chains=world * B, device=dev, random_seed=7)
+        for rep in range(2):   # first pass allocates
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            smc.beta = 0.0
+            smc.select_end_points(main_leg["Q"], main_leg["L"])
+            smc.transition()
+            Qn, Ln = smc.restart_points()
+            torch.cuda.synchronize()
+            stage_ms = (time.perf_counter() - t1) * 1e3
+        assert Qn.shape == main_leg["Q"].shape and smc.Q_all.shape[0] == world * B
+        # the gathered end points of all ranks (identical on every rank): sums as a sharding-independent fingerprint
+        pop_sum = (float(smc.Q_all.sum().item()), float(smc.L_all[:, -1].sum().item()), float(smc.beta))
 
     def stack_roofline(spec_leg, leg, n_chains):
         """roofline of the stacking kernel of one leg: every candidate bound with its fraction, the
@@ -726,12 +738,14 @@ def main():
             "repeats": len(region_s), "region_s": region_s, "region_steps": main_leg["region_steps"],
             "in_box_fraction": main_leg["in_box"],
             "accept_rate_last_step": main_leg["accept_last"],
-            "stage_transition_ms": stage_ms,
-            "stage_transition": {"ranks_in_all_gather": world if use_dist else 1, "gathered_chains": int(smc.Q_all.shape[0]),
-                                 "population_checksum": {"sum_Q": pop_sum[0], "sum_like": pop_sum[1], "next_beta": pop_sum[2]},
-                                 "backend": (backend if use_dist else None)},
             "setup_s": t_build,
         }
+        if args.full:
+            out["stage_transition_ms"] = stage_ms
+            out["stage_transition"] = {
+                "ranks_in_all_gather": world if use_dist else 1, "gathered_chains": int(smc.Q_all.shape[0]),
+                "population_checksum": {"sum_Q": pop_sum[0], "sum_like": pop_sum[1], "next_beta": pop_sum[2]},
+                "backend": (backend if use_dist else None)}
         q_ms, q_n = main_leg["times"]["quadform"]
         if q_n:
             # dense-W misfit: chain-batched W.R on the FP64 matrix cores; W upper triangular -> half
@@ -759,7 +773,7 @@ def main():
 
     # ---- reuse-free streaming leg: k_gfstack in (chain, target, tile) order, every chain's rows
     # streamed from HBM -- the roofline of SURVEY 8(d)'s algorithmic bytes, driver-observed
-    if world == 1 and not args.no_streaming_leg and spec.covariance == "scalar":
+    if args.full and world == 1 and not args.no_streaming_leg and spec.covariance == "scalar":
         saved = {k: os.environ.get(k) for k in ("BEATAMD_GF_KERNEL", "BEATAMD_GF_ORDER")}
         os.environ["BEATAMD_GF_KERNEL"], os.environ["BEATAMD_GF_ORDER"] = "0", "0"
         ctx.reload_knobs()      # (the context reads its knobs once)
@@ -785,14 +799,14 @@ def main():
             attach_traffic(out["roofline_streaming"], os.path.join(args.profiles_dir, PROFILE_ROUND + "_bench_c512_nn_gfstack0_summary.json"))
     # ---- the same population in larger batches: chain groups of one (target, tile) share an XCD,
     # rows common to several groups come from its L2 (labelled leg; `value` stays the 512-chain batch)
-    if world == 1 and not args.no_batch_leg and spec.covariance == "scalar" and B < 2048:
+    if args.full and world == 1 and not args.no_batch_leg and spec.covariance == "scalar" and B < 2048:
         leg = run_leg(spec, f, 2048, max(K // 2, 3), 1, seed_offset=1000)
         ms, n = leg["times"]["gfstack"]
         out["batch_2048_leg"] = {"chains": 2048, "chain_steps_per_s": 2048 * max(K // 2, 3) / leg["dt"],
                                  "gfstack_avg_launch_ms": ms / max(n, 1), "kernel": leg["kernel"],
                                  "distinct_rows_per_patch_mean": leg["stats"]["mean_rows"]}
     # ---- round 1's narrow prior, labelled, for continuity with BENCH_r01
-    if world == 1 and not args.no_narrow_leg and args.prior == "survey" and spec.covariance == "scalar":
+    if args.full and world == 1 and not args.no_narrow_leg and args.prior == "survey" and spec.covariance == "scalar":
         import copy
         a2 = copy.copy(args)
         a2.prior = "narrow"
@@ -809,7 +823,7 @@ def main():
             "hbm_required_bytes_per_launch": leg["stats"]["row_bytes"]}
     # ---- labelled legs of the other configurations (never `value`): same library in HBM, same population
     legs = set(x for x in args.variant_legs.split(",") if x)
-    if world == 1 and not args.no_variant_legs and legs and spec.interpolation == "nearest_neighbor" \
+    if args.full and world == 1 and not args.no_variant_legs and legs and spec.interpolation == "nearest_neighbor" \
             and spec.covariance == "scalar" and not args.prewhiten:
         import copy
 

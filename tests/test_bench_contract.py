@@ -85,6 +85,24 @@ def test_bench_line_stays_below_the_cap_whatever_the_legs():
     json.loads(bench.compact_line(out), parse_constant=lambda c: (_ for _ in ()).throw(ValueError(c)))
 
 
+def test_plain_run_line_carries_the_contract_fields():
+    """the object of a plain run (no --full: no CPU baseline, stage transition or legs) still makes a line with every
+    contract field and the headline kernel's roofline; nothing of the legs appears in it"""
+    import json
+
+    import bench
+    out = {k: v for k, v in _stub_result().items()
+           if not k.endswith("_leg") and k not in ("cpu_baseline", "speedup_vs_cpu_baseline", "stage_transition",
+                                                   "stage_transition_ms", "roofline_streaming")}
+    d = json.loads(bench.compact_line(out, "/somewhere/bench_full.json"),
+                   parse_constant=lambda c: (_ for _ in ()).throw(ValueError(c)))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config",
+              "roofline"):
+        assert k in d, k
+    assert d["value"] == out["value"] and d["ms_per_step"] == out["ms_per_step"] and d["dtype"] == "f64"
+    assert d["legs"] == {} and "cpu_baseline" not in d and "stage_transition_ms" not in d and "roofline_streaming" not in d
+
+
 def test_committed_round6_line_is_what_the_driver_needs():
     """the line of the round's own `python bench.py` run on the GPU box (profiles/r6_bench_default.json): strict JSON below
     the driver's 8 KB tail, counter-based roofline of the headline kernel, cpu_baseline, the short-trace legs with counter

@@ -106,14 +106,17 @@ def test_target_sharded_library_equals_the_replicated_model(tmp_path):
     assert np.isfinite(two["lp"]).all() and two["pop"].shape[0] == 256
 
 
-def _bench(extra, env_extra, nproc_flag):
+def _bench(extra, env_extra, nproc_flag, full=False, legs_off=True):
+    """one bench.py run at a reduced shape -> its line; `full`: with --full (the stage transition), `legs_off`: with the
+    --no-* options of the legs"""
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     env.update(env_extra)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc_flag), "--steps", "4", "--warmup", "1",
-           "--targets", "4", "--samples", "256", "--no-cpu-baseline", "--no-streaming-leg", "--no-batch-leg",
-           "--no-narrow-leg", "--no-variant-legs"] + extra
+           "--targets", "4", "--samples", "256"] + (["--full"] if full else []) + \
+          (["--no-cpu-baseline", "--no-streaming-leg", "--no-batch-leg", "--no-narrow-leg", "--no-variant-legs"]
+           if legs_off else []) + extra
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -127,8 +130,8 @@ def test_bench_two_ranks_on_one_gpu_keeps_the_contract(tmp_path):
     chain-steps over the slowest rank's time, a stage transition whose all-gather really had two ranks; and the
     gathered end points (proposal rows are seeded per block of 64 GLOBAL chains, the population per global chain)
     equal those of ONE rank stepping all 256 chains, bit for bit."""
-    two = _bench(["--chains", "128"], {"BEATAMD_BENCH_BACKEND": "gloo"}, 2)
-    one = _bench(["--chains", "256"], {}, 1)
+    two = _bench(["--chains", "128"], {"BEATAMD_BENCH_BACKEND": "gloo"}, 2, full=True)
+    one = _bench(["--chains", "256"], {}, 1, full=True)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1 and two["steps"] == one["steps"] == 4
     assert two["config"]["global_chains"] == one["config"]["global_chains"] == 256
     assert two["config"]["chains_per_gpu"] == 128 and two["scaling"] == "weak"
@@ -147,8 +150,8 @@ def test_bench_four_ranks_on_one_gpu(tmp_path):
     four ranks, value = all ranks' chain-steps over the slowest rank's time; the gathered end points equal those of ONE
     rank stepping all 512 chains bit for bit.  (Four ranks, not eight: the launcher's agent opens the GPU as well, so N
     ranks are N + 2 processes holding the device with this one; eight made ten, more than a shared node allows.)"""
-    four = _bench(["--chains", "128"], {"BEATAMD_BENCH_BACKEND": "gloo"}, 4)
-    one = _bench(["--chains", "512"], {}, 1)
+    four = _bench(["--chains", "128"], {"BEATAMD_BENCH_BACKEND": "gloo"}, 4, full=True)
+    one = _bench(["--chains", "512"], {}, 1, full=True)
     assert four["n_gpus"] == 4 and four["config"]["global_chains"] == one["config"]["global_chains"] == 512
     assert four["config"]["chains_per_gpu"] == 128 and four["scaling"] == "weak"
     assert four["stage_transition"]["ranks_in_all_gather"] == 4 and four["stage_transition"]["gathered_chains"] == 512
@@ -185,3 +188,27 @@ def test_bench_dump_outputs_are_the_timed_path_end_state(tmp_path):
     assert L.shape == a["likelihoods"].shape
     np.testing.assert_allclose(a["likelihoods"], L, rtol=1e-9, atol=1e-9)
     f.release()
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py` without `--full` times the headline steps and nothing else: no CPU baseline, no stage transition, no
+    labelled leg, although no --no-* option is given; `--full` adds the stage transition and the legs of the main library
+    (the CPU baseline and the configuration legs left out here), and the timed path ends in the same arrays either way"""
+    runs = {}
+    for k, full in (("plain", False), ("full", True)):
+        extra = ["--chains", "128", "--dump-outputs", str(tmp_path / k), "--full-json", str(tmp_path / (k + ".json"))]
+        if full:
+            extra += ["--no-cpu-baseline", "--no-variant-legs"]
+        line = _bench(extra, {}, 1, full=full, legs_off=False)
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["roofline"]["kernel"]
+        assert abs(line["value"] - 128 / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+        runs[k] = (line, json.load(open(str(tmp_path / (k + ".json")))))
+    line, obj = runs["plain"]
+    extras = ("cpu_baseline", "speedup_vs_cpu_baseline", "stage_transition", "stage_transition_ms", "roofline_streaming")
+    assert not [k for k in obj if k in extras or k.endswith("_leg")], sorted(obj)
+    assert line["legs"] == {} and "cpu_baseline" not in line and "stage_transition_ms" not in line
+    line, obj = runs["full"]
+    assert {"stage_transition", "roofline_streaming", "batch_2048_leg", "narrow_prior_leg"} <= set(obj), sorted(obj)
+    assert line["stage_transition_ms"] > 0 and {"batch_2048", "narrow_prior"} <= set(line["legs"])
+    for n in ("positions", "likelihoods", "accepted"):
+        assert np.array_equal(np.load(str(tmp_path / "plain" / (n + ".npy"))), np.load(str(tmp_path / "full" / (n + ".npy")))), n

@@ -474,7 +474,7 @@ def test_library_files_round_trip_through_hbm(ctx, tmp_path):
 
 # ----------------------------------------------------------------------------- multi-GPU readiness
 def test_bench_two_ranks_over_rccl():
-    """bench.py --gpus 2 under torchrun (one rank per GPU, RCCL): skipped on 1-GPU boxes.  Checks
+    """bench.py --gpus 2 --full under torchrun (one rank per GPU, RCCL): skipped on 1-GPU boxes.  Checks
     the line's contract fields and that the stage transition ran over both ranks."""
     import json
     import os
@@ -487,7 +487,7 @@ def test_bench_two_ranks_over_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29577", os.path.join(root, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--chains", "64", "--no-cpu-baseline",
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--chains", "64", "--full", "--no-cpu-baseline",
            "--targets", "4", "--samples", "256"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]

@@ -3,7 +3,7 @@
 # results land under gpurun_out/<tag>, summaries worth keeping are copied to profiles/ by hand.
 #
 #   round [profile-tag]             full `-m gpu` suite + smoke() + default bench.py (+ `profile <tag>` when given)
-#   profile <tag>                   the round's rocprofv3 evidence: kernel stats of the default bench command and, with
+#   profile <tag>                   the round's rocprofv3 evidence: kernel stats of `bench.py --full` and, with
 #                                   separate FETCH_SIZE / WRITE_SIZE passes, of the nn / multilinear / Toeplitz runs and the
 #                                   geometry stage -> gpurun_out/prof_<tag>/out/<tag>_* (tools/summarize_rocpd2.py)
 #   profile6 <tag> a|b|c|d          round 6's evidence in four parts (see the mode)
@@ -48,13 +48,13 @@ round)
   timeout 900 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err || tail -5 gpurun_out/bench_default.err
   python -c "
 import json; d=json.loads(open('gpurun_out/bench_default.json').read().strip().splitlines()[-1])
-print('value %.0f ms/step %.3f' % (d['value'], d['ms_per_step']), d['roofline']['kernel'], d['roofline']['frac'], d['cpu_baseline']['value'])"
+print('value %.0f ms/step %.3f' % (d['value'], d['ms_per_step']), d['roofline']['kernel'], d['roofline']['frac'])"
   [ -n "$1" ] && bash $0 profile $1 > gpurun_out/profile.log 2>&1 && tail -3 gpurun_out/profile.log
   ;;
 profile)
   tag=$1; O=$R/gpurun_out/prof_$tag
   rm -rf $O; mkdir -p $O; cd /tmp
-  B="python $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-variant-legs --no-narrow-leg --no-batch-leg"
+  B="python $R/bench.py --steps 30 --warmup 3 --full --no-cpu-baseline --no-variant-legs --no-narrow-leg --no-batch-leg"
   prof() { t=$1; shift; mkdir -p $O/$t
     timeout 600 rocprofv3 --kernel-trace --stats -d $O/$t/stats -o bench -- "$@" > $O/$t/stats_run.log 2>&1
     timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/$t/fetch -o bench -- "$@" > $O/$t/fetch_run.log 2>&1
@@ -64,7 +64,7 @@ profile)
   prof c512_ml $B --interp multilinear --no-streaming-leg
   prof c512_toeplitz $B --covariance toeplitz --no-streaming-leg
   mkdir -p $O/default $O/geometry
-  timeout 900 rocprofv3 --kernel-trace --stats -d $O/default/stats -o bench -- python $R/bench.py --no-cpu-baseline > $O/default/stats_run.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -d $O/default/stats -o bench -- python $R/bench.py --full --no-cpu-baseline > $O/default/stats_run.log 2>&1
   timeout 300 rocprofv3 --kernel-trace --stats -d $O/geometry/stats -o bench -- python $R/tools/geo_app.py 1024 200 > $O/geometry/stats_run.log 2>&1
   S="python $R/tools/summarize_rocpd2.py"
   $S $O/c512_nn $O/out ${tag}_bench_c512_nn k_gfstack_ws "k_gfstack<0" k_fast_sweep k_accept > $O/sum_c512_nn.log 2>&1
@@ -83,7 +83,7 @@ profile5)
   # runs on the tutorial-grid library (row passes); kernel stats of the default command and of the configs[3] leg
   tag=$1; O=$R/gpurun_out/prof_$tag
   rm -rf $O; mkdir -p $O; cd /tmp
-  B="python $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-variant-legs --no-narrow-leg --no-batch-leg"
+  B="python $R/bench.py --steps 30 --warmup 3 --full --no-cpu-baseline --no-variant-legs --no-narrow-leg --no-batch-leg"
   G="--samples 512 --ndurations 17 --nstarttimes 41 --duration-min 0 --duration-sampling 0.25 --no-streaming-leg"
   prof() { t=$1; shift; mkdir -p $O/$t
     timeout 600 rocprofv3 --kernel-trace --stats -d $O/$t/stats -o bench -- "$@" > $O/$t/stats_run.log 2>&1
@@ -97,8 +97,8 @@ profile5)
   prof grid_nn_c2048 $B $G --chains 2048
   prof grid_ml_c2048 $B $G --chains 2048 --interp multilinear
   mkdir -p $O/default $O/config4
-  timeout 900 rocprofv3 --kernel-trace --stats -d $O/default/stats -o bench -- python $R/bench.py --no-cpu-baseline > $O/default/stats_run.log 2>&1
-  timeout 600 rocprofv3 --kernel-trace --stats -d $O/config4/stats -o bench -- python $R/bench.py --no-cpu-baseline --variant-legs config4 --no-streaming-leg --no-batch-leg --no-narrow-leg --steps 10 > $O/config4/stats_run.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats -d $O/default/stats -o bench -- python $R/bench.py --full --no-cpu-baseline > $O/default/stats_run.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d $O/config4/stats -o bench -- python $R/bench.py --full --no-cpu-baseline --variant-legs config4 --no-streaming-leg --no-batch-leg --no-narrow-leg --steps 10 > $O/config4/stats_run.log 2>&1
   S="python $R/tools/summarize_rocpd2.py"
   $S $O/c512_nn $O/out ${tag}_bench_c512_nn k_gfstack_ws "k_gfstack<0" k_ws_tables k_fast_sweep > $O/sum_c512_nn.log 2>&1
   $S $O/c512_ml $O/out ${tag}_bench_c512_ml k_gfstack_runs k_gm_tables > $O/sum_c512_ml.log 2>&1
@@ -120,12 +120,12 @@ profile6)
   #   a  headline run, multilinear run, configs[3] at 120 samples (tools/time_config4.py = the bench leg's problem)
   #   b  the tutorial-grid runs (512 and 2048 chains, nn and multilinear)
   #   c  configs[3] at 4096 samples
-  #   d  kernel stats of the default command, then the default bench.py line itself (reads the summaries of a-c from
+  #   d  kernel stats of the full command, then the `bench.py --full` line itself (reads the summaries of a-c from
   #      profiles/: copy them there first)
   # -> gpurun_out/prof_<tag>/out
   tag=$1; part=$2; O=$R/gpurun_out/prof_$tag
   mkdir -p $O/out; cd /tmp
-  B="python $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-variant-legs --no-narrow-leg --no-batch-leg"
+  B="python $R/bench.py --steps 30 --warmup 3 --full --no-cpu-baseline --no-variant-legs --no-narrow-leg --no-batch-leg"
   G="--samples 512 --ndurations 17 --nstarttimes 41 --duration-min 0 --duration-sampling 0.25 --no-streaming-leg"
   prof() { t=$1; shift; rm -rf $O/$t; mkdir -p $O/$t
     timeout 600 rocprofv3 --kernel-trace --stats -d $O/$t/stats -o bench -- "$@" > $O/$t/stats_run.log 2>&1
@@ -165,10 +165,10 @@ profile6)
     # legs (the full command under rocprofv3 did not end within 15 minutes and the profiler then waits for its child beyond
     # any timeout -- this part was lost twice)
     cd $R
-    timeout -k 10 1000 python bench.py --full-json $O/out/${tag}_bench_default_full.json > $O/out/${tag}_bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
+    timeout -k 10 1000 python bench.py --full --full-json $O/out/${tag}_bench_default_full.json > $O/out/${tag}_bench_default.json 2> $O/bench_default.err || tail -5 $O/bench_default.err
     tail -c 600 $O/out/${tag}_bench_default.json
     mkdir -p $O/default; cd /tmp
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/default/stats -o bench -- python $R/bench.py --no-cpu-baseline --steps 10 --repeats 1 --variant-legs multilinear,toeplitz,default_config,prewhitened,geometry,fp32,config4,realistic_grid --full-json /tmp/bench_full_prof.json > $O/default/stats_run.log 2>&1
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/default/stats -o bench -- python $R/bench.py --full --no-cpu-baseline --steps 10 --repeats 1 --variant-legs multilinear,toeplitz,default_config,prewhitened,geometry,fp32,config4,realistic_grid --full-json /tmp/bench_full_prof.json > $O/default/stats_run.log 2>&1
     $S $O/default $O/out ${tag}_bench_default "k_quadform<128>" k_gfstack_runs "k_gemm_f64<0>" k_gfstack_ws > $O/sum_default.log 2>&1
     ;;
   esac
