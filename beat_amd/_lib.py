@@ -97,6 +97,7 @@ _PROTOS = {
     "beatamd_ctx_gf_plan": [_vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64],
     "beatamd_ctx_gf_tune_log": [_vp, C.c_char_p, _i64],
     "beatamd_gf_patch_ranges": [_i64, _i64, _i64, C.c_int32],
+    "beatamd_seis_gflib_set_split_targets": [_vp, _i32, _i64],
     "beatamd_ctx_reload_knobs": [_vp],
     "beatamd_ctx_gf_chain_groups": [_vp, _i64, _vp, _vp, _i64, _vp],
     "beatamd_smc_calc_beta": [_vp, _i64, _vp, _i64, _f64, _f64, C.POINTER(_f64), _vp],
@@ -143,6 +144,10 @@ def load():
         except ImportError:
             pass
         lib = C.CDLL(LIB_PATH)
+        # (an entry point added within one ABI revision: a library built before it lacks the symbol)
+        missing = [name for name in _PROTOS if not hasattr(lib, name)]
+        if missing:
+            raise BeatAmdError("libbeat_amd.so lacks %s: rebuild with `make -C beat_amd/csrc`" % ", ".join(missing))
         for name, args in _PROTOS.items():
             fn = getattr(lib, name)
             fn.argtypes = args

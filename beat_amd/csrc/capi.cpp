@@ -294,6 +294,18 @@ int beatamd_seis_gflib_create(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t D,
     return BEATAMD_OK;
 }
 
+int beatamd_seis_gflib_set_split_targets(beatamd_ctx *ctx, int32_t lib_id, int64_t ntargets)
+{
+    ENTER(ctx);
+    SeisLib *l = get_obj(ctx->seislibs, lib_id);
+    BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
+    BA_CHECK(ntargets >= 0, BEATAMD_EINVAL, "gflib_set_split_targets: negative target count");
+    BA_CHECK(ntargets == 0 || ntargets >= l->T, BEATAMD_EINVAL,
+             "gflib_set_split_targets: %lld targets, fewer than the library's %lld", (long long)ntargets, (long long)l->T);
+    l->split_T = ntargets;
+    return BEATAMD_OK;
+}
+
 static int seis_ensure_storage(beatamd_ctx *ctx, SeisLib *l)
 {
     if (l->g) return BEATAMD_OK;

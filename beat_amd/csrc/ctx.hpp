@@ -54,6 +54,8 @@ struct DevBuf {
 
 struct SeisLib {
     int64_t T = 0, P = 0, D = 0, S = 0, N = 0;
+    // target count the patch-range rule sees (gf_patch_split): 0 = T; the whole wavemap's T for a rank's block of targets
+    int64_t split_T = 0;
     double st_min = 0, st_dt = 1, du_min = 0, du_dt = 1;
     double *g = nullptr;  // HBM, (T,P,D,S,N) C-order, N fastest
     float *g32 = nullptr; // optional float copy of g (beatamd_seis_gflib_store_f32; g then holds float-representable values)

@@ -408,13 +408,18 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call);
 // of short traces -- the reference's realistic case: 60 s at 2 Hz = 120 samples, SURVEY 8(d) config 4 -- has T * ceil(N / 64)
 // = 70 of them for 256 CUs, each fetching its index tables cold.  Such libraries are stacked in R patch RANGES: the
 // library [T, P, D, S, N] viewed as [T*R, P/R, D, S, N] (the same memory), R times as many and R times shorter walks, the
-// ranges' partial synthetics summed in range order by k_split_combine, which also carries the epilogue.  R depends on the
-// library's shape ONLY (never on the batch): a chain's result cannot depend on the batch it is in; every stacking kernel
-// takes the view unchanged (tables per virtual slot), so the kernels stay bitwise equal to each other.
+// ranges' partial synthetics summed in range order by k_split_combine, which also carries the epilogue.  R sets the
+// summation order over the patches, so it depends on the shape of the WHOLE problem only -- never on the batch (a chain's
+// result cannot depend on the batch it is in) and never on how the targets are sharded over ranks: the rule sees the
+// library's split_T (beatamd_seis_gflib_set_split_targets: the whole wavemap's target count for every rank's block of a
+// target-sharded library, models/sharded.py), not the T of the block.  Every stacking kernel takes the view unchanged
+// (tables per virtual slot), so the kernels stay bitwise equal to each other.
 // Rule: N <= 256 and at least 32 patches per range; among the divisors R of P (<= 32) the one that minimises
 //   ceil(walks * R / CUs) * (P / R + 5)
 // -- the stacking kernels keep one workgroup per CU, a walk costs its steps plus ~5 steps of prologue / epilogue (measured on
 // configs[3] with 120 samples, 70 walks x 400 patches: R = 4: 1.00, 5: 0.80, 8: 0.82, 10: 0.69, 16: 0.76, 25: 0.72 ms).
+// BEATAMD_GF_SPLIT=k forces k ranges where k divides P and N <= 256 (k_split_combine holds one trace in its 256 threads);
+// elsewhere the library is stacked as it is.
 int gf_patch_ranges(int64_t T, int64_t P, int64_t N, int num_cu)
 {
     if (N > 256 || P < 64) return 1;
@@ -435,8 +440,8 @@ static int gf_patch_split(const SeisLib &L, const GfKnobs &kn, int num_cu)
 {
     const int knob = GfKnobs::get(kn.gf_split, -1);
     if (knob == 0 || knob == 1) return 1;
-    if (knob > 1) return (L.P % knob == 0) ? knob : 1;
-    return gf_patch_ranges(L.T, L.P, L.N, num_cu);
+    if (knob > 1) return (L.P % knob == 0 && L.N <= 256) ? knob : 1;
+    return gf_patch_ranges(L.split_T > 0 ? L.split_T : L.T, L.P, L.N, num_cu);
 }
 
 __global__ void __launch_bounds__(256) k_split_tslot(int64_t Tv, int R, const int32_t *tslot, int32_t *out)

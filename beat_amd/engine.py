@@ -140,6 +140,9 @@ class Context(object):
                                                   float(duration_sampling), C.byref(lid)))
         return lid.value
 
+    def seis_gflib_set_split_targets(self, lib_id, ntargets):
+        check(self._lib.beatamd_seis_gflib_set_split_targets(self._h, lib_id, int(ntargets)))
+
     def seis_gflib_upload(self, lib_id, array, offset=0):
         a = f64(array)
         count = int(a.numel()) if _is_dev(a) else int(a.size)

@@ -111,6 +111,9 @@ class SeismicGFLibrary(GFLibrary):
         super(SeismicGFLibrary, self).__init__(config or SeismicGFLibraryConfig())
         self._tmins = None
         self._device_tensor = None  # keeps an adopted torch tensor alive
+        # target count that decides how the library's patches are cut into ranges for short traces
+        # (beatamd_seis_gflib_set_split_targets): None = ntargets; the whole wavemap's for a rank's block of targets
+        self.split_ntargets = None
 
     # -- reference properties (base.py:376-470)
     @property
@@ -195,6 +198,8 @@ class SeismicGFLibrary(GFLibrary):
         self.lib_id = ctx.seis_gflib_create(self.dimensions, self.starttime_min,
                                             self.starttime_sampling, self.duration_min,
                                             self.duration_sampling)
+        if self.split_ntargets is not None:
+            ctx.seis_gflib_set_split_targets(self.lib_id, self.split_ntargets)
         if self._device_tensor is not None:
             ctx.seis_gflib_adopt(self.lib_id, self._device_tensor)
         else:

@@ -47,6 +47,9 @@ def shard_wavemap(wm, rank, world):
                                      duration_sampling=gf.duration_sampling, starttime_min=gf.starttime_min,
                                      duration_min=gf.duration_min, component=getattr(gf.config, "component", v))
         part = SeismicGFLibrary(cfg)
+        # the patch ranges of short traces are chosen for the WHOLE wavemap: every rank sums a target's patches in the
+        # order of the replicated library
+        part.split_ntargets = getattr(gf, "split_ntargets", None) or T
         if getattr(gf, "_device_tensor", None) is not None:
             part.adopt_device_tensor(gf._device_tensor[a:b])
         else:

@@ -110,6 +110,11 @@ int beatamd_ctx_gf_tune_log(beatamd_ctx *ctx, char *buf, int64_t buflen);
  * ceil(walks * R / num_cu) * (P / R + 5); 1 = the library as it is.  What a call did is in beatamd_ctx_gf_plan.  No reference
  * counterpart (beat/ffi/base.py:607-709 stacks one chain on one core). */
 int32_t beatamd_gf_patch_ranges(int64_t ntargets, int64_t npatches, int64_t nsamples, int32_t num_cu);
+/* The target count the rule above sees for a library (default 0: its own T).  R sets the order in which a target's patches
+ * are summed, so a rank's block of a library sharded by target (beat_amd/models/sharded.py) is given the whole wavemap's
+ * target count: every rank then picks the R of the replicated library, and the likelihoods stay bitwise those of the
+ * replicated model.  ntargets = 0 or >= the library's T.  No reference counterpart (the reference does not shard). */
+int beatamd_seis_gflib_set_split_targets(beatamd_ctx *ctx, int32_t lib_id, int64_t ntargets);
 
 /* how a batch of C chains is cut into its chain groups (scheduling only; results never depend on it): recursive
  * bisection of the batch along the key in which a part's chains spread wider -- the fused model path hands the hypocentre

@@ -3,7 +3,11 @@ whole model) or "targets" (every rank compiles the rows of ITS targets only, bea
 the one GPU of the box through gloo (collectives staged through host memory) unless BEATAMD_TEST_BACKEND=nccl.
 Evaluates a population, runs a few SMC stages with all chains on every rank and writes rank 0's results; the test
 compares replicated and sharded runs (reference semantics: beat/models/seismic.py:1332-1349 one logpt per dataset,
-beat/models/problems.py:227-247 like = sum of the composites)."""
+beat/models/problems.py:227-247 like = sum of the composites).
+
+BEATAMD_TEST_SPEC = "split" (BEATAMD_TEST_INTERP = "nearest_neighbor" | "multilinear") evaluates a library of SHORT traces
+instead -- 40 targets x 128 patches x 120 samples, stacked in patch ranges (gfstack.hip launch_gfstack_split) -- and records
+the stacking plan next to the likelihoods; no SMC run."""
 import os
 import sys
 
@@ -34,23 +38,50 @@ def main():
         rank, world, _ = parallel.init(backend)
     dev = torch.device("cuda", local)
     ctx = beat_amd.get_context(local)
-    # 5 targets over 2 ranks (3 + 2), two slip variables, station shifts, dense covariance, geodetic + Laplacian replicated
-    spec = SyntheticSpec((5,), (5,), (1.0,), T=5, N=96, D=3, S=25, covariance="toeplitz", slip_varnames=("uparr", "uperp"),
-                         station_shifts=True, geodetic_nobs=(20, 31), laplacian=True, interpolation="multilinear")
+    split = os.environ.get("BEATAMD_TEST_SPEC", "") == "split"
+    if split:
+        # 40 targets over 2 ranks (20 + 20) of 120 samples and 128 patches: the replicated library is stacked in 2 patch
+        # ranges, a block of 20 targets on its own would pick 4; 20 stations, each shared by targets t and t + 20 (one on
+        # each rank); bidiagonal (Toeplitz) misfit in the ranges' combine kernel
+        spec = SyntheticSpec((8,), (16,), (1.0,), T=40, N=120, D=3, S=25, covariance="toeplitz",
+                             slip_varnames=("uparr", "uperp"), station_shifts=True, geodetic_nobs=(20, 31), laplacian=True,
+                             interpolation=os.environ.get("BEATAMD_TEST_INTERP", "multilinear"))
+    else:
+        # 5 targets over 2 ranks (3 + 2), two slip variables, station shifts, dense covariance, geodetic + Laplacian
+        # replicated
+        spec = SyntheticSpec((5,), (5,), (1.0,), T=5, N=96, D=3, S=25, covariance="toeplitz",
+                             slip_varnames=("uparr", "uperp"), station_shifts=True, geodetic_nobs=(20, 31), laplacian=True,
+                             interpolation="multilinear")
+    T = spec.T
     prob, host = build_problem(spec)
     lay = host["layout"]
     lo, up = lay.bounds(host["lower"], host["upper"])
     f = TargetShardedLogp(prob, ctx) if mode == "targets" else prob.compile(ctx)
     if mode == "targets":
-        assert f.world == world and f.nllk == 5 + 2 + 1 + 1 and sum(f.n_local) == {1: [5], 2: [3, 2]}[world][rank]
+        blocks = {1: [T], 2: [T - T // 2, T // 2]}[world]
+        assert f.world == world and f.nllk == T + 2 + 1 + 1 and sum(f.n_local) == blocks[rank]
     Q = torch.from_numpy(draw_population(spec, lay, host["lower"], host["upper"], 300)).to(dev)
     Q[7, lay.offset("durations")] = 99.0           # a chain outside the library grid: like = NaN on every rank
     LL = f.batch(Q)
+    plan = ctx.gf_plan(passes=False)["plan"]       # (the seismic wavemap's stacking launch of this evaluation)
     try:
         ctx.synchronize()      # the out-of-library index is reported once (IndexError, like the reference) ...
         raise AssertionError("expected the IndexError of the chain outside the library grid")
     except IndexError:
         pass                   # ... and leaves NaN in that chain's `like`
+    if split:
+        # every rank's plan (rank 0 writes the file: the plans of the others are gathered as text)
+        plans = [plan]
+        if world > 1:
+            plans = [None] * world
+            dist.all_gather_object(plans, plan)
+        if rank == 0:
+            np.savez(os.environ["BEATAMD_TEST_OUT"], LL=LL.cpu().numpy(), plans=np.array(plans))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        print("SHARD_GPU_WORKER_OK rank", rank, flush=True)
+        return
     if mode == "targets":
         # a start time that leaves the grid on the targets of ONE rank only -- a station correction of
         # a station whose channels all live on the last rank (targets 3, 4) -- sets the status word there alone; the

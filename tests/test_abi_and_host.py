@@ -234,3 +234,36 @@ def test_patch_ranges_of_short_trace_libraries():
         cost = lambda d: -(-walks * d // cu) * (P // d + 5)
         cands = [d for d in range(1, 33) if P % d == 0 and (d == 1 or P // d >= 32)]
         assert best in cands and all(cost(best) <= cost(d) for d in cands), (T, P, N, cu, best)
+
+
+def test_sharded_libraries_split_patches_as_the_whole_wavemap():
+    """A rank's block of a target-sharded library (beat_amd.models.sharded) carries the WHOLE wavemap's target count for the
+    patch-range rule: the ranges fix the summation order over the patches, so a block of 20 of 40 targets must not pick its
+    own R.  The rule's table on the shapes of tests/test_gpu_dist.py (40 x 128 x 120: 2 ranges replicated, 4 for a block of
+    20) and of configs[3] (35 x 400 x 120: 10, 5 for a block of 17 or 18)."""
+    from beat_amd import _lib
+    from beat_amd.models.sharded import shard_problem, target_block
+    from beat_amd.synthetic import SyntheticSpec, build_problem
+    R = _lib.load().beatamd_gf_patch_ranges
+    assert R(40, 128, 120, 256) == 2 and R(20, 128, 120, 256) == 4
+    assert R(35, 400, 120, 256) == 10 and R(18, 400, 120, 256) == 5 and R(17, 400, 120, 256) == 5
+    for T in (35, 40, 64):
+        for dip, strike in (((8,), (16,)), ((20,), (20,))):
+            # (one duration, two start times, two samples: the host objects only, a few MB)
+            spec = SyntheticSpec(dip, strike, (1.0,), T=T, N=2, D=1, S=2, st_dt=100.0, slip_varnames=("uparr", "uperp"),
+                                 station_shifts=True)
+            prob, _ = build_problem(spec)
+            P = spec.P
+            for world in range(1, 9):
+                for rank in range(world):
+                    a, b = target_block(T, rank, world)
+                    wm = shard_problem(prob, rank, world).wavemaps[0]
+                    assert wm.n_t == b - a
+                    for v in ("uparr", "uperp"):
+                        gf = wm.gfs[v]
+                        assert gf.dimensions[:2] == (b - a, P) and gf.split_ntargets == T, (T, P, world, rank, v)
+                        assert R(gf.split_ntargets, P, 120, 256) == R(T, P, 120, 256)
+                    # sharding a block again keeps the whole wavemap's count
+                    again = shard_problem(shard_problem(prob, rank, world), 0, 1).wavemaps[0]
+                    assert again.gfs["uparr"].split_ntargets == T
+            assert all(gf.split_ntargets is None for gf in prob.wavemaps[0].gfs.values())

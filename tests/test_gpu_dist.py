@@ -66,11 +66,11 @@ def test_two_ranks_over_rccl_equal_one_rank(tmp_path):
     _compare(one, two)
 
 
-def _run_shard(nproc, mode, out, backend="gloo"):
+def _run_shard(nproc, mode, out, backend="gloo", **extra):
     env = dict(os.environ)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BEATAMD_GF_SPLIT"):
         env.pop(k, None)
-    env.update(BEATAMD_TEST_BACKEND=backend, BEATAMD_TEST_OUT=out, BEATAMD_TEST_MODE=mode, OMP_NUM_THREADS="1")
+    env.update(BEATAMD_TEST_BACKEND=backend, BEATAMD_TEST_OUT=out, BEATAMD_TEST_MODE=mode, OMP_NUM_THREADS="1", **extra)
     worker = os.path.join(ROOT, "tests", "_shard_gpu_worker.py")
     if nproc == 1:
         cmd = [sys.executable, worker]
@@ -104,6 +104,32 @@ def test_target_sharded_library_equals_the_replicated_model(tmp_path):
         assert np.array_equal(one[k], two[k]), k
     np.testing.assert_allclose(one["betas"], rep["betas"], rtol=1e-12)
     assert np.isfinite(two["lp"]).all() and two["pop"].shape[0] == 256
+
+
+@pytest.mark.parametrize("interp", ["nearest_neighbor", "multilinear"])
+def test_target_sharded_short_traces_keep_the_patch_ranges(tmp_path, interp):
+    """A library of SHORT traces sharded by target: 40 targets x 128 patches x 120 samples, stacked in patch ranges
+    (gfstack.hip launch_gfstack_split).  The ranges set the summation order over a target's patches; the replicated library
+    picks R = 2, a block of 20 targets on its own would pick R = 4.  Every rank must stack in the replicated model's ranges,
+    and every dataset's logpt and `like` must be BITWISE those of the replicated model (README), NaN for the
+    chain outside the library grid"""
+    env = dict(BEATAMD_TEST_SPEC="split", BEATAMD_TEST_INTERP=interp)
+    rep = _run_shard(1, "replicated", str(tmp_path / "rep.npz"), **env)
+    one = _run_shard(1, "targets", str(tmp_path / "s1.npz"), **env)
+    two = _run_shard(2, "targets", str(tmp_path / "s2.npz"), **env)
+    (rplan,) = rep["plans"]
+    assert "stacked in 2 ranges of 64" in rplan, rplan
+    want = rplan[rplan.index("patches stacked in"):].split(" (")[0]          # "patches stacked in 2 ranges of 64"
+    for sh, n in ((one, 1), (two, 2)):
+        assert len(sh["plans"]) == n
+        for plan in sh["plans"]:
+            assert want in plan, (want, plan)
+        assert sh["LL"].shape == rep["LL"].shape == (300, 40 + 4)
+        assert np.array_equal(np.isnan(sh["LL"][:, -1]), np.isnan(rep["LL"][:, -1])) and np.isnan(rep["LL"][7, -1])
+        assert int(np.isnan(rep["LL"][:, -1]).sum()) == 1
+        ok = ~np.isnan(rep["LL"][:, -1])
+        for col in range(rep["LL"].shape[1]):
+            assert np.array_equal(sh["LL"][ok, col], rep["LL"][ok, col]), (n, col)
 
 
 def _bench(extra, env_extra, nproc_flag, full=False, legs_off=True):
