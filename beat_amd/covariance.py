@@ -1,6 +1,16 @@
 """
 Noise-covariance structures and estimators -- counterpart of beat/covariance.py (the parts
 that feed the sampler's likelihood weights).  The O(n^2) estimators run on the GPU.
+
+What is bitwise the reference and what is not (tests/test_gpu_covariance_edges.py):
+
+- ``autocovariance[_batch]``: bitwise the reference's double loop (covariance.py:716-736) for host and
+  device input alike.  The mean of a device trace is taken by the kernel in numpy's summation order;
+  ``torch.mean`` sums in another order and changed about a third of the values in the last bit.
+- ``scaled_toeplitz_batch``: bitwise ``toeplitz(coeffs) * stds[:, None] * stds[None, :]``.
+- ``running_window_rms_batch`` (device): running sums instead of ``numpy.convolve``; equal to rounding.
+- the whitening operator and log-determinant (``chol_inverse_batch[_flags]``): another factorisation
+  order than the reference's ``cholesky(inv(C))``; within c n u kappa(C) (u = 2^-53, c = 4) of it.
 """
 import numpy as np
 

@@ -1176,7 +1176,7 @@ int beatamd_autocovariance_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const 
                                  const double *mean, double *out)
 {
     ENTER(ctx);
-    BA_CHECK(data && mean && out && nd >= 0 && n >= 0, BEATAMD_EINVAL, "autocovariance: bad argument");
+    BA_CHECK(data && out && nd >= 0 && n >= 0, BEATAMD_EINVAL, "autocovariance: bad argument");
     if (nd == 0 || n == 0) return BEATAMD_OK;
     const void *d_d, *d_m;
     void *d_o;

@@ -455,16 +455,63 @@ int launch_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int64_t nllk, do
 }
 
 // ---------------------------------------------------------------- noise covariance estimation
+// numpy's float64 sum of a contiguous row, so that sum / n is numpy.mean(row) to the bit (the reference's
+// data.mean(), covariance.py:730): numpy's pairwise_sum applied to pieces of at most 8192 elements (the
+// reduction's buffer size), the pieces added in order to 0.0.  pairwise_sum: below 8 elements a plain loop from
+// 0.0; up to 128 eight strided accumulators, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the tail; above
+// that the two halves split at n/2 rounded down to a multiple of 8.
+__device__ double np_block_sum(const double *a, int64_t n)
+{
+    double res = 0.0;
+    if (n < 8) {
+        for (int64_t i = 0; i < n; i++) res += a[i];
+        return res;
+    }
+    double r[8];
+    for (int j = 0; j < 8; j++) r[j] = a[j];
+    int64_t i = 8;
+    for (; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; j++) r[j] += a[i + j];
+    res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; i++) res += a[i];
+    return res;
+}
+
+// the recursion unrolled by depth: a half is at most n/2 + 8 long, so a piece of 8192 reaches blocks of <= 128
+// after 7 halvings (D = 8 leaves one to spare; pairwise_sum<0> is never reached with more than 128)
+template <int D> __device__ __attribute__((noinline)) double np_pairwise_sum(const double *a, int64_t n)
+{
+    if (n <= 128) return np_block_sum(a, n);
+    int64_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise_sum<D - 1>(a, n2) + np_pairwise_sum<D - 1>(a + n2, n - n2);
+}
+template <> __device__ double np_pairwise_sum<0>(const double *a, int64_t n) { return np_block_sum(a, n); }
+
 // covariance.py:716-736 autocovariance: autocov[j] = (1/n) sum_k (d[j+k]-m)(d[k]-m).  One thread
 // per lag walks k in the reference's order with separate multiply and add (no contraction), so the
-// result is bitwise the reference's O(n^2) Python loop; the trace sits in LDS.
+// result is bitwise the reference's O(n^2) Python loop; the trace sits in LDS.  mean == nullptr (device
+// traces): thread 0 takes the row's mean from LDS in numpy's order first.
 __global__ void __launch_bounds__(256) k_autocovariance(const double *data, int64_t n,
                                                        const double *mean, double *out)
 {
     extern __shared__ __attribute__((aligned(16))) double s_d[];
+    __shared__ double s_mean;
     const int64_t d = blockIdx.y;
     const double *x = data + d * n;
-    const double m = mean[d];
+    if (mean) {
+        if (threadIdx.x == 0) s_mean = mean[d];
+    } else {
+        for (int64_t k = threadIdx.x; k < n; k += 256) s_d[k] = x[k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double s = 0.0;
+            for (int64_t c = 0; c < n; c += 8192) s += np_pairwise_sum<8>(s_d + c, n - c < 8192 ? n - c : 8192);
+            s_mean = s / (double)n;
+        }
+    }
+    __syncthreads();
+    const double m = s_mean;
     for (int64_t k = threadIdx.x; k < n; k += 256) s_d[k] = x[k] - m;
     __syncthreads();
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;

@@ -278,10 +278,9 @@ class Context(object):
     def autocovariance_batch(self, data):
         d = f64(data)
         self._adopt_stream(d)
-        if _is_dev(d):
-            mean = d.mean(dim=1).contiguous()
-        else:
-            mean = np.ascontiguousarray(d.mean(axis=1))
+        # device traces: the kernel takes each row's mean in numpy's summation order (torch.mean sums in another
+        # order and moved the result in the last bits); host traces: numpy's own mean
+        mean = None if _is_dev(d) else np.ascontiguousarray(d.mean(axis=1))
         out = _empty_like(d, tuple(d.shape))
         check(self._lib.beatamd_autocovariance_batch(self._h, int(d.shape[0]), int(d.shape[1]), ptr(d),
                                                      ptr(mean), ptr(out)))

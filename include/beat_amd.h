@@ -354,7 +354,8 @@ int beatamd_ffi_mstep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, doubl
  * structure, seismic.py:1509-1534 -> covariance.py:397-427): the reference runs O(n^2) Python
  * loops per dataset.
  * replaces: covariance.autocovariance(data)            beat/covariance.py:716-736
- *   data [nd,n], mean [nd] (= data.mean(), computed by the caller) -> out [nd,n]
+ *   data [nd,n], mean [nd] (= data.mean(), computed by the caller) or NULL (each row's mean
+ *   is then taken on the device in numpy's summation order: numpy.mean to the bit) -> out [nd,n]
  *   same term order as the reference loop: bitwise equal results                             */
 int beatamd_autocovariance_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *data,
                                  const double *mean, double *out);
