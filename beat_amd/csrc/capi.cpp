@@ -46,6 +46,21 @@ int32_t add_obj(std::vector<std::unique_ptr<T>> &v, std::unique_ptr<T> o)
     return (int32_t)v.size() - 1;
 }
 
+// host copy of a small argument array that may live on either side
+template <class T>
+int host_copy(beatamd_ctx *ctx, const T *p, size_t n, std::vector<T> &out)
+{
+    out.resize(n);
+    if (n == 0) return BEATAMD_OK;
+    if (is_device_ptr(p)) {
+        BA_HIP(hipMemcpyAsync(out.data(), p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        BA_HIP(hipStreamSynchronize(ctx->stream));
+    } else {
+        memcpy(out.data(), p, n * sizeof(T));
+    }
+    return BEATAMD_OK;
+}
+
 #define ENTER(ctx)                                                    \
     BA_CHECK((ctx) != nullptr, BEATAMD_EINVAL, "ctx is NULL");        \
     BA_HIP(hipSetDevice((ctx)->device))
@@ -172,7 +187,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
         double *mu = (double *)p, *res = mu + C * g.Nobs;
         if (m.geo_is_geometry) {
             // synthetics, line of sight and weighted residual in one kernel
-            BA_TRY(launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data, g.odws, res));
+            BA_TRY(launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data, g.odws, res, g.corr));
         } else {
             // every slip variable's G.T . slips in one launch (geodetic.py:1065-1070 sums them)
             const GeoLib *gls[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -182,7 +197,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                 BA_CHECK(gls[v], BEATAMD_EINVAL, "geodetic composite refers to a destroyed GF library");
             }
             BA_TRY(launch_geo_stack(ctx, gls, m.layout.nvar, C, slips, 0, mu));
-            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data, g.odws, mu, res));
+            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data, g.odws, mu, res, Q, np, g.corr));
         }
         // small dense datasets (SAR scenes / GNSS of a few hundred points): every dataset's
         // quadratic form and MVN epilogue in one launch; otherwise per dataset on the 64-row tiles
@@ -888,6 +903,72 @@ int beatamd_ffi_model_add_geodetic_geometry(beatamd_ctx *ctx, int32_t model_id, 
     return BEATAMD_OK;
 }
 
+int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_id, int32_t nterm,
+                                               const int32_t *dataset, const int32_t *ncol,
+                                               const double *basis, const int64_t *coef_off,
+                                               const double *coef_fixed)
+{
+    ENTER(ctx);
+    FfiModel *m = get_obj(ctx->models, model_id);
+    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    BA_CHECK(m->has_geo, BEATAMD_EINVAL, "add_geodetic_corrections: the model has no geodetic composite");
+    Geodetic &g = m->geo;
+    BA_CHECK(!g.corr_set, BEATAMD_EINVAL, "add_geodetic_corrections: the composite already has its corrections");
+    BA_CHECK(nterm >= 0 && nterm <= GEO_CORR_MAX, BEATAMD_EINVAL,
+             "add_geodetic_corrections: %d terms, the table holds %d", nterm, GEO_CORR_MAX);
+    BA_CHECK(nterm == 0 || (dataset && ncol && basis && coef_off && coef_fixed), BEATAMD_EINVAL,
+             "add_geodetic_corrections: bad argument");
+    if (nterm == 0) {
+        g.corr_set = true;
+        return BEATAMD_OK;
+    }
+    std::vector<int32_t> ds, nc;
+    std::vector<int64_t> off;
+    std::vector<double> fix;
+    BA_TRY(host_copy(ctx, dataset, (size_t)nterm, ds));
+    BA_TRY(host_copy(ctx, ncol, (size_t)nterm, nc));
+    BA_TRY(host_copy(ctx, coef_off, (size_t)nterm * 4, off));
+    BA_TRY(host_copy(ctx, coef_fixed, (size_t)nterm * 4, fix));
+    const int nd = (int)g.sizes.size();
+    std::vector<int64_t> start((size_t)nd, 0);
+    for (int d = 1; d < nd; d++) start[d] = start[d - 1] + g.sizes[d - 1];
+    std::vector<GeoCorrTerm> terms((size_t)nterm);
+    int64_t nbasis = 0;
+    for (int j = 0; j < nterm; j++) {
+        BA_CHECK(ds[j] >= 0 && ds[j] < nd, BEATAMD_EINVAL,
+                 "add_geodetic_corrections: term %d names dataset %d of %d", j, ds[j], nd);
+        BA_CHECK(j == 0 || ds[j] >= ds[j - 1], BEATAMD_EINVAL,
+                 "add_geodetic_corrections: the dataset indices decrease at term %d", j);
+        BA_CHECK(nc[j] >= 1 && nc[j] <= 4, BEATAMD_EINVAL,
+                 "add_geodetic_corrections: term %d has %d basis columns (1..4)", j, nc[j]);
+        GeoCorrTerm &t = terms[(size_t)j];
+        memset(&t, 0, sizeof(t));
+        t.start = start[ds[j]];
+        t.n = g.sizes[ds[j]];
+        t.K = nc[j];
+        for (int k = 0; k < 4; k++) {
+            const int64_t o = k < nc[j] ? off[(size_t)j * 4 + k] : -1;
+            BA_CHECK(o >= -1 && o < m->layout.nparams, BEATAMD_EINVAL,
+                     "add_geodetic_corrections: coefficient %d of term %d: offset %lld outside q", k, j, (long long)o);
+            t.off[k] = o;
+            t.fix[k] = k < nc[j] ? fix[(size_t)j * 4 + k] : 0.0;
+        }
+        nbasis += t.n * t.K;
+    }
+    BA_TRY(dev_alloc_copy(ctx, basis, (size_t)nbasis * 8, (void **)&g.corr_basis));
+    int64_t bo = 0;
+    for (int j = 0; j < nterm; j++) {
+        terms[(size_t)j].B = g.corr_basis + bo;
+        bo += terms[(size_t)j].n * terms[(size_t)j].K;
+    }
+    GeoCorrTerm *d_terms = nullptr;
+    BA_TRY(dev_alloc_copy(ctx, terms.data(), terms.size() * sizeof(GeoCorrTerm), (void **)&d_terms));
+    g.corr.terms = d_terms;
+    g.corr.nterm = nterm;
+    g.corr_set = true;
+    return BEATAMD_OK;
+}
+
 int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t lap_id)
 {
     ENTER(ctx);
@@ -928,6 +1009,8 @@ int beatamd_ffi_model_destroy(beatamd_ctx *ctx, int32_t model_id)
     if (m->geo.data) (void)hipFree(m->geo.data);
     if (m->geo.odws) (void)hipFree(m->geo.odws);
     if (m->geo.hp_off) (void)hipFree(m->geo.hp_off);
+    if (m->geo.corr.terms) (void)hipFree((void *)m->geo.corr.terms);
+    if (m->geo.corr_basis) (void)hipFree(m->geo.corr_basis);
     if (m->geom.kind) (void)hipFree(m->geom.kind);
     if (m->geom.poff) (void)hipFree(m->geom.poff);
     if (m->geom.pfix) (void)hipFree(m->geom.pfix);

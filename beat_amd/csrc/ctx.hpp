@@ -105,6 +105,23 @@ struct Wavemap {
     bool f32 = false;   // read the libraries' float copies where a kernel supports it
 };
 
+// one correction term of a geodetic dataset (geodetic.py:411-427 apply_corrections; corrections.py:46-87 ramp,
+// :143-205 strain rate): corr[c,i] = sum_k B[i,k] * coef_k over the dataset's observations [start, start + n),
+// coef_k = q[c, off[k]] or, with off[k] < 0, fix[k].  The table lives in device memory; the residual kernels read it
+// through wave-uniform (scalar) loads
+constexpr int GEO_CORR_MAX = 32;   // terms per composite (beatamd_ffi_model_add_geodetic_corrections)
+struct GeoCorrTerm {
+    int64_t start, n;
+    const double *B;      // device [K, n]: column k at B + k*n
+    int64_t off[4];
+    double fix[4];
+    int32_t K, pad_;
+};
+struct GeoCorr {
+    const GeoCorrTerm *terms = nullptr;   // device [nterm]
+    int32_t nterm = 0;
+};
+
 struct Geodetic {
     std::vector<int32_t> libs;
     double *data = nullptr, *odws = nullptr;  // [Nobs]
@@ -112,6 +129,10 @@ struct Geodetic {
     std::vector<int64_t> sizes;
     std::vector<int32_t> wsets;
     int64_t *hp_off = nullptr;  // device [nd]
+    // dataset corrections (hierarchical parameters), in the order they are subtracted
+    bool corr_set = false;
+    GeoCorr corr;
+    double *corr_basis = nullptr;    // device, the terms' basis columns concatenated
 };
 
 // geometry-mode sources of the geodetic composite (analytic half space)

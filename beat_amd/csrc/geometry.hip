@@ -36,6 +36,8 @@ struct GeomSrcArgs {
     // with res: the weighted residual (data - mu) * odw is stored instead of mu
     const double *data, *odw;
     double *res;
+    // k_geom_los<.., CORR = true>: the correction terms of the datasets, subtracted from res (unread otherwise)
+    GeoCorr corr;
 };
 
 struct Vec3 { double x, y, z; };
@@ -230,7 +232,9 @@ constexpr int GL_MAXC = 48;
 
 // SHARED = false: more (chain, source) pairs per workgroup than the LDS table holds (very few observation
 // points): every thread computes its own source constants
-template <int WAVES, bool SHARED>
+// CORR = true: the datasets' correction terms are subtracted in the residual epilogue (geodetic.py:1076-1077); a
+// template parameter so that the instances of a model without terms are the code they were (register budget: DESIGN 3.1c)
+template <int WAVES, bool SHARED, bool CORR>
 __global__ void __launch_bounds__(256, WAVES) k_geom_los(GeomSrcArgs a)
 {
     __shared__ SrcConst sc[SHARED ? GL_MAXC : 1];
@@ -268,7 +272,9 @@ __global__ void __launch_bounds__(256, WAVES) k_geom_los(GeomSrcArgs a)
     // (heart.py:4220-4224) and los = [Sn, Se, Su] (heart.py:1381-1410)
     const double *l = a.los + k * 3;
     const double mu = (un * l[0] + ue * l[1]) + uz * l[2];
-    if (a.res)
+    if (CORR)
+        a.res[i] = geo_corrected_residual(a.corr, a.Q, a.nparams, c, k, a.data[k], mu, a.odw[k]);
+    else if (a.res)
         a.res[i] = (a.data[k] - mu) * a.odw[k];
     else
         a.mu[i] = mu;
@@ -310,14 +316,16 @@ int launch_geom_disp(beatamd_ctx *ctx, int nsrc, const int32_t *kind, const int6
 }
 
 int launch_geom_los(beatamd_ctx *ctx, const GeomSources &g, const double *Q, int64_t nparams,
-                    int64_t C, double *mu, const double *data, const double *odw, double *res)
+                    int64_t C, double *mu, const double *data, const double *odw, double *res, GeoCorr gc)
 {
     if (C == 0) return BEATAMD_OK;
+    BA_CHECK(gc.nterm == 0 || (res && C <= 2147483647), BEATAMD_EINVAL,
+             "geom_los: corrections act on the residual, of fewer than 2^31 chains");
     GeomSrcArgs a;
     a.nsrc = g.nsrc; a.kind = g.kind; a.poff = g.poff; a.pfix = g.pfix;
     a.Q = Q; a.nparams = nparams; a.C = C; a.Nobs = g.Nobs;
     a.east = g.east; a.north = g.north; a.los = g.los; a.nu = g.nu; a.mu = mu;
-    a.data = data; a.odw = odw; a.res = res;
+    a.data = data; a.odw = odw; a.res = res; a.corr = gc;
     const int64_t n = C * g.Nobs;
     ScopedTimer tm(ctx, "geomlos");
     // waves per SIMD the register budget is cut for (the corner terms are long dependent fp64 chains)
@@ -326,14 +334,17 @@ int launch_geom_los(beatamd_ctx *ctx, const GeomSources &g, const double *Q, int
     // chains a workgroup of 256 (chain, point) pairs can touch, times the sources
     const int64_t ncs_max = ((255 + g.Nobs - 1) / g.Nobs + 1) * g.nsrc;
     static const bool force_own = getenv("BEATAMD_GEOM_OWN") != nullptr;
-    if (ncs_max > GL_MAXC || force_own)
-        hipLaunchKernelGGL((k_geom_los<2, false>), grid, dim3(256), 0, ctx->stream, a);
-    else if (waves >= 4)
-        hipLaunchKernelGGL((k_geom_los<4, true>), grid, dim3(256), 0, ctx->stream, a);
-    else if (waves == 3)
-        hipLaunchKernelGGL((k_geom_los<3, true>), grid, dim3(256), 0, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((k_geom_los<2, true>), grid, dim3(256), 0, ctx->stream, a);
+    const bool corr = gc.nterm > 0;
+#define GEOM_LOS(W, S)                                                                                   \
+    do {                                                                                                 \
+        if (corr) hipLaunchKernelGGL((k_geom_los<W, S, true>), grid, dim3(256), 0, ctx->stream, a);      \
+        else hipLaunchKernelGGL((k_geom_los<W, S, false>), grid, dim3(256), 0, ctx->stream, a);          \
+    } while (0)
+    if (ncs_max > GL_MAXC || force_own) GEOM_LOS(2, false);
+    else if (waves >= 4) GEOM_LOS(4, true);
+    else if (waves == 3) GEOM_LOS(3, true);
+    else GEOM_LOS(2, true);
+#undef GEOM_LOS
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

@@ -180,9 +180,70 @@ int launch_scalar_quad(beatamd_ctx *ctx, int64_t C, int64_t nd, int64_t M, const
 // geodetic: mu[c,k] (+)= sum_p slips(c,p) G[p,k]
 int launch_geo_stack(beatamd_ctx *ctx, const GeoLib *const *libs, int nvar, int64_t C, const ChainVec *slips, int accumulate,
                      double *mu);
-// res[c,k] = (data[k] - mu[c,k]) * odw[k]
+// res[c,k] = (data[k] - mu[c,k]) * odw[k], minus the dataset's correction terms (gc.nterm > 0)
 int launch_geo_residual(beatamd_ctx *ctx, int64_t C, int64_t Nobs, const double *data,
-                        const double *odw, const double *mu, double *res);
+                        const double *odw, const double *mu, double *res, const double *Q = nullptr,
+                        int64_t nparams = 0, GeoCorr gc = GeoCorr());
+
+#ifdef __HIPCC__
+// The weighted residual of observation k of chain c with the correction terms of k's dataset subtracted one after the
+// other in table order (geodetic.py:1072-1077, 411-427):
+//     corr = ((B[k,0]*coef0 + B[k,1]*coef1) + B[k,2]*coef2) + B[k,3]*coef3 ;  res = ((d - mu) * odw) - corr
+// with plain products and sums (no contraction, whatever the including file's default): for a ramp, whose last column
+// is 1, that is numpy's (d - mu)*odw - (locy*az + locx*rg + off) bit for bit.
+// The term table is the same for every lane: it is read through the constant address space, i.e. scalar loads.  The
+// coefficients q[c, off] are wave-uniform wherever the wavefront lies inside one chain (the flat (chain, observation)
+// index lets a wavefront straddle two): that wavefront reads them through scalar loads from the first lane's chain,
+// a straddling one per lane.  The basis columns are the only per-lane loads either way.
+template <bool UNIFORM>
+__device__ __forceinline__ double geo_corr_subtract(const GeoCorr &gc, const double *Qc, int64_t k, double r)
+{
+#pragma clang fp contract(off)
+    typedef const __attribute__((address_space(4))) GeoCorrTerm *TermPtr;
+    typedef const __attribute__((address_space(4))) double *ConstPtr;
+    TermPtr terms = (TermPtr)gc.terms;
+    for (int j = 0; j < gc.nterm; j++) {
+        // the whole row and all four coefficient slots at once, ahead of any branch: the compiler batches them into
+        // three rounds of scalar loads per term instead of one per field (an unused slot has offset -1 and the fixed
+        // value 0; q[0] stands in for its load)
+        struct { int64_t start, n; const double *B; int64_t off[4]; double fix[4]; int K; } t;
+        t.start = terms[j].start; t.n = terms[j].n; t.B = terms[j].B; t.K = terms[j].K;
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) { t.off[kk] = terms[j].off[kk]; t.fix[kk] = terms[j].fix[kk]; }
+        double coef[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; kk++) {
+            const int64_t o = t.off[kk] < 0 ? 0 : t.off[kk];
+            const double q = UNIFORM ? ((ConstPtr)Qc)[o] : Qc[o];
+            coef[kk] = t.off[kk] < 0 ? t.fix[kk] : q;
+        }
+        const int64_t row = k - t.start;
+        if (row < 0 || row >= t.n) continue;
+        // columns beyond K: column 0 is read in their place and the sum is not taken
+        const double *B = t.B + row;
+        const double p0 = B[0] * coef[0];
+        const double p1 = B[(t.K > 1 ? 1 : 0) * t.n] * coef[1];
+        const double p2 = B[(t.K > 2 ? 2 : 0) * t.n] * coef[2];
+        const double p3 = B[(t.K > 3 ? 3 : 0) * t.n] * coef[3];
+        double corr = p0;
+        corr = t.K > 1 ? corr + p1 : corr;
+        corr = t.K > 2 ? corr + p2 : corr;
+        corr = t.K > 3 ? corr + p3 : corr;
+        r = r - corr;
+    }
+    return r;
+}
+
+__device__ __forceinline__ double geo_corrected_residual(const GeoCorr &gc, const double *Q, int64_t nparams, int64_t c,
+                                                         int64_t k, double d, double mu, double odw)
+{
+#pragma clang fp contract(off)
+    const double r = (d - mu) * odw;
+    const int c0 = __builtin_amdgcn_readfirstlane((int)c);
+    if (__all(c == (int64_t)c0)) return geo_corr_subtract<true>(gc, Q + (int64_t)c0 * nparams, k, r);
+    return geo_corr_subtract<false>(gc, Q + c * nparams, k, r);
+}
+#endif
 // laplacian: out[c*ld] = sum_v -0.5*(-logdet + P*(log2pi+2h) + (1/exp(2h))*quad[c,v])
 int launch_laplacian_finish(beatamd_ctx *ctx, int64_t C, int64_t nvar, int64_t P, double logdet,
                             const double *quad, HpSrc hp, double *out, int64_t ld);
@@ -214,10 +275,10 @@ int launch_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int64_t nllk, do
                   int32_t *acc_sum = nullptr, int64_t *n_acc = nullptr, bool advance_step = false);
 
 // geometry.hip: line-of-sight synthetics of rectangular / Mogi sources, mu [C, Nobs]
-// with res (and data, odw [Nobs]): res = (data - mu) * odw is stored instead of mu
+// with res (and data, odw [Nobs]): res = (data - mu) * odw is stored instead of mu, minus the correction terms gc
 int launch_geom_los(beatamd_ctx *ctx, const GeomSources &g, const double *Q, int64_t nparams,
                     int64_t C, double *mu, const double *data = nullptr, const double *odw = nullptr,
-                    double *res = nullptr);
+                    double *res = nullptr, GeoCorr gc = GeoCorr());
 // displacement components (n, e, up) per (parameter set, source, point): out [C, nsrc, Nobs, 3]
 int launch_geom_disp(beatamd_ctx *ctx, int nsrc, const int32_t *kind, const int64_t *poff,
                      const double *params, int64_t C, int64_t nobs, const double *east,

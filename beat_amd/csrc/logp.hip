@@ -176,24 +176,30 @@ int launch_geo_stack(beatamd_ctx *ctx, const GeoLib *const *libs, int nvar, int6
     return BEATAMD_OK;
 }
 
-// geodetic.py:1072-1074: (sdata - mu) * sodws
+// geodetic.py:1072-1074: (sdata - mu) * sodws ; :1076-1077 apply_corrections where the composite has terms (the
+// branch on gc.nterm is the same for every thread of the launch)
 __global__ void __launch_bounds__(256) k_geo_residual(int64_t C, int64_t Nobs, const double *data,
                                                      const double *odw, const double *mu,
-                                                     double *res)
+                                                     double *res, const double *Q, int64_t nparams, GeoCorr gc)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= C * Nobs) return;
     const int64_t k = i % Nobs;
-    res[i] = (data[k] - mu[i]) * odw[k];
+    if (gc.nterm > 0)
+        res[i] = geo_corrected_residual(gc, Q, nparams, i / Nobs, k, data[k], mu[i], odw[k]);
+    else
+        res[i] = (data[k] - mu[i]) * odw[k];
 }
 
 int launch_geo_residual(beatamd_ctx *ctx, int64_t C, int64_t Nobs, const double *data,
-                        const double *odw, const double *mu, double *res)
+                        const double *odw, const double *mu, double *res, const double *Q,
+                        int64_t nparams, GeoCorr gc)
 {
     const int64_t n = C * Nobs;
     if (n == 0) return BEATAMD_OK;
+    BA_CHECK(gc.nterm == 0 || (Q && C <= 2147483647), BEATAMD_EINVAL, "geo_residual: corrections need q and fewer than 2^31 chains");
     hipLaunchKernelGGL(k_geo_residual, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       ctx->stream, C, Nobs, data, odw, mu, res);
+                       ctx->stream, C, Nobs, data, odw, mu, res, Q, nparams, gc);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

@@ -342,6 +342,27 @@ class Context(object):
             ptr(north), ptr(los), float(nu), ptr(data), ptr(odws), int(sizes.size), ptr(sizes), ptr(ws),
             ptr(hp)))
 
+    def ffi_model_add_geodetic_corrections(self, model_id, dataset, ncol, basis, coef_off, coef_fixed):
+        """dataset corrections of the model's geodetic composite: per term its dataset index, column count, basis
+        (n x K, one array per term), coefficient offsets in q (-1: fixed) and fixed values (K each)"""
+        nterm = len(dataset)
+        ds = np.ascontiguousarray(dataset, dtype=np.int32)
+        nc = np.ascontiguousarray(ncol, dtype=np.int32)
+        off = -np.ones((nterm, 4), dtype=np.int64)
+        fix = np.zeros((nterm, 4))
+        cols = []
+        for j in range(nterm):
+            k = int(nc[j])
+            off[j, :k] = coef_off[j]
+            fix[j, :k] = coef_fixed[j]
+            B = np.asarray(basis[j], dtype=np.float64)
+            if B.ndim != 2 or B.shape[1] != k:
+                raise ValueError("correction term %d: basis of shape %s, expected (n, %d)" % (j, B.shape, k))
+            cols.append(np.ravel(B, order="F"))
+        flat = np.ascontiguousarray(np.concatenate(cols)) if cols else np.zeros(0)
+        check(self._lib.beatamd_ffi_model_add_geodetic_corrections(
+            self._h, model_id, nterm, ptr(ds), ptr(nc), ptr(flat), ptr(off), ptr(fix)))
+
     def ffi_model_set_laplacian(self, model_id, lap_id):
         check(self._lib.beatamd_ffi_model_set_laplacian(self._h, model_id, lap_id))
 

@@ -15,6 +15,7 @@ import numpy as np
 
 from .. import _lib
 from ..engine import get_context
+from .corrections import correction_tables
 from .problem import LogpForwFunc
 
 # parameter slots of one source, in the order the kernel reads them
@@ -42,10 +43,12 @@ class GeodeticGeometryProblem(object):
     east, north [km], los (Nobs, 3); data, odws (Nobs,); sizes per dataset;
     weights   list of (n_k, n_k) chol_inverse matrices or scalars; slog_pdets; hypers as in
               FFIProblem; for a Mogi source the volume change [m^3] is the ``slip`` slot
+    corrections  None or one list of set-up correction objects (models.corrections) per dataset; their variables
+              are sampled where the layout holds them and constant where ``fixed`` does
     """
 
     def __init__(self, layout, sources, east, north, los, data, odws, sizes, weights, slog_pdets,
-                 hypers, fixed=None, nu=0.25, lower=None, upper=None):
+                 hypers, fixed=None, nu=0.25, lower=None, upper=None, corrections=None):
         self.layout = layout
         self.sources = list(sources)
         self.east = np.ascontiguousarray(east, dtype=np.float64)
@@ -58,6 +61,7 @@ class GeodeticGeometryProblem(object):
         self.fixed = dict(fixed or {})
         self.nu = float(nu)
         self.lower, self.upper = lower, upper
+        self.corrections = corrections
         # what LogpForwFunc expects of a problem
         self.wavemaps, self.geodetic, self.laplacian = [], self, None
 
@@ -105,4 +109,7 @@ class GeodeticGeometryProblem(object):
         ctx.ffi_model_add_geodetic_geometry(mid, [KIND[s] for s in self.sources], off, fix, self.east,
                                             self.north, self.los, self.nu, self.data, self.odws,
                                             self.sizes, self._wsets, hp_off)
+        if self.corrections is not None:
+            ctx.ffi_model_add_geodetic_corrections(
+                mid, *correction_tables(self.corrections, self.sizes, self.layout, self.fixed))
         return LogpForwFunc(ctx, mid, self)

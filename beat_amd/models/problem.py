@@ -20,6 +20,7 @@ import numpy as np
 
 from .. import _lib
 from ..engine import get_context
+from .corrections import correction_tables
 
 logger = logging.getLogger("beat_amd.models")
 
@@ -151,9 +152,13 @@ class GeodeticData(object):
     data/odws  (Nobs,) concatenated over datasets (heart.concatenate_datasets :3356-3384)
     sizes      samples per dataset (Bij.srmap split)
     weights    list of (n_k, n_k) chol_inverse matrices or scalars
+    corrections  None or one list of set-up correction objects (models.corrections) per dataset, subtracted from
+               the weighted residual in list order (geodetic.py:411-427, 1076-1077); their variables are sampled
+               where the layout holds them and constant where ``fixed`` {name: value} does (lower == upper in
+               the reference, geodetic.py:401-405)
     """
 
-    def __init__(self, gfs, data, odws, sizes, weights, slog_pdets, hypers):
+    def __init__(self, gfs, data, odws, sizes, weights, slog_pdets, hypers, corrections=None, fixed=None):
         self.gfs = gfs
         self.data = np.ascontiguousarray(data, dtype=np.float64)
         self.odws = np.ascontiguousarray(odws, dtype=np.float64)
@@ -161,6 +166,8 @@ class GeodeticData(object):
         self.weights = weights
         self.slog_pdets = [float(s) for s in slog_pdets]
         self.hypers = list(hypers)
+        self.corrections = corrections
+        self.fixed = dict(fixed or {})
         self._wsets = []
 
 
@@ -270,6 +277,8 @@ class FFIProblem(object):
             owned_geo = list(g._wsets)
             hp_off = [lay.offset(n, i) for n, i in g.hypers]
             ctx.ffi_model_add_geodetic(mid, libs, g.data, g.odws, g.sizes, g._wsets, hp_off)
+            if g.corrections is not None:
+                ctx.ffi_model_add_geodetic_corrections(mid, *correction_tables(g.corrections, g.sizes, lay, g.fixed))
         if self.laplacian is not None:
             L, logdet = self.laplacian
             self._lap = ctx.laplacian_create(L, logdet)

@@ -291,6 +291,28 @@ int beatamd_ffi_model_add_geodetic_geometry(beatamd_ctx *ctx, int32_t model_id, 
                                             const double *odws, int32_t ndatasets,
                                             const int64_t *dataset_sizes, const int32_t *wset_ids,
                                             const int64_t *hp_off);
+/* correction terms of the geodetic composite's datasets, the reference's hierarchical dataset corrections
+ * (GeodeticComposite.apply_corrections, beat/models/geodetic.py:411-427, called at :1076-1077 between the weighted
+ * residual and multivariate_normal_chol; beat/models/corrections.py:46-87 orbital ramp, :143-205 strain rate).
+ * Valid once, after add_geodetic / add_geodetic_geometry.  Term j belongs to dataset dataset[j] (its n observations
+ * are that dataset's block of the concatenated vector) and has K = ncol[j] basis columns and K coefficients;
+ * coefficient k is q[coef_off[j*4+k]], or coef_fixed[j*4+k] where the offset is -1 (lower == upper in the
+ * reference, geodetic.py:401-405).  For chain c and observation i of the dataset
+ *     corr[c,i] = ((B[i,0]*coef0 + B[i,1]*coef1) + B[i,2]*coef2) + B[i,3]*coef3      plain products and sums
+ *     res[c,i]  = ((data[i] - mu[c,i]) * odw[i]) - corr[c,i]                        the term is not weighted
+ * and the terms of a dataset are subtracted one after the other in list order (the reference's iter_corrections:
+ * ramp, then strain rate).  Ramp: K = 3, B = [locy, locx, 1], coefficients (azimuth_ramp, range_ramp, offset) --
+ * bit for bit numpy's expression.  Strain rate: K = 4, the velocity-gradient tensor folded into four columns on
+ * the host, coefficients (exx, eyy, exy, rotation) -- equal to the reference to rounding.  The Euler-pole term is
+ * not offered: its coefficients are not linear in the sampled pole position.
+ * The subtraction happens in the kernel that forms the residual; the stand-alone synthetics are unchanged.
+ *   dataset [nterm] non-decreasing   ncol [nterm] 1..4   coef_off, coef_fixed [nterm*4]
+ *   basis: the terms concatenated, term j is dataset_sizes[dataset[j]] x ncol[j], column-major
+ * At most 32 terms.  nterm = 0 declares a composite without corrections. */
+int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_id, int32_t nterm,
+                                               const int32_t *dataset, const int32_t *ncol,
+                                               const double *basis, const int64_t *coef_off,
+                                               const double *coef_fixed);
 int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t lap_id);
 int beatamd_ffi_model_nllk(beatamd_ctx *ctx, int32_t model_id, int64_t *nllk);
 int beatamd_ffi_model_destroy(beatamd_ctx *ctx, int32_t model_id);
