@@ -109,6 +109,13 @@ _PROTOS = {
     "beatamd_proposal_draw_univariate": [_vp, _i64, _i64, _i32, _vp, C.c_uint64, C.c_uint32, _i64, _vp, _vp],
     "beatamd_gather_rows": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
     "beatamd_metropolis_tune": [_vp, _i64, _vp, _vp, _i32],
+    "beatamd_ffi_model_nterm": [_vp, _i32, _pi64],
+    "beatamd_ffi_llks_batch": [_vp, _i32, _i64, _vp, _vp],
+    "beatamd_hyper_model_create": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _pi32],
+    "beatamd_hyper_model_destroy": [_vp, _i32],
+    "beatamd_hyper_logp_batch": [_vp, _i32, _i64, _vp, _vp, _vp],
+    "beatamd_hyper_chain_batch": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_uint64,
+                                  C.c_uint32, _i64, _i32, _i32, _i32, _vp, _vp],
     "beatamd_like_assemble": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp],
     "beatamd_metropolis_propose": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "beatamd_metropolis_accept": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp],

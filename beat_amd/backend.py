@@ -178,10 +178,12 @@ def population_shapes(layout, out_names):
     groups = OrderedDict()
     for i, name in enumerate(out_names):
         key = ("seis_like" if name.startswith("seis_like")
-               else "geo_like" if name.startswith("geo_like") else name)
+               else "geo_like" if name.startswith("geo_like")
+               else "laplacian_like" if name.startswith("laplacian_like") else name)
         groups.setdefault(key, []).append(i)
     for k, idx in groups.items():
-        shapes[k] = () if k in ("like", "laplacian_like") else (len(idx),)
+        # (the hyper model keeps one laplacian_like entry per slip variable, laplacian.py:156-170: a vector there)
+        shapes[k] = () if k == "like" or (k == "laplacian_like" and len(idx) == 1) else (len(idx),)
     return shapes, groups
 
 
@@ -222,7 +224,7 @@ def write_population(homepath, stage, layout, out_names, population, lpoints, ba
             for j in range(n_draws):
                 pt = layout.rmap(population[j, c])
                 lp = [pt[k] for k in layout.varsizes]
-                lp += [lpoints[j, c, idx] if k in ("seis_like", "geo_like") else lpoints[j, c, idx[0]]
+                lp += [lpoints[j, c, idx] if shapes[k] != () else lpoints[j, c, idx[0]]
                        for k, idx in groups.items()]
                 ch.write(lp)
         return path
@@ -237,7 +239,7 @@ def write_population(homepath, stage, layout, out_names, population, lpoints, ba
         o = layout.offset(k)
         data[k] = population[:, :, o:o + layout.varsizes[k]].transpose(1, 0, 2)
     for k, idx in groups.items():
-        data[k] = lpoints[:, :, idx].transpose(1, 0, 2) if k in ("seis_like", "geo_like") else lpoints[:, :, idx[0]].T
+        data[k] = lpoints[:, :, idx].transpose(1, 0, 2) if shapes[k] != () else lpoints[:, :, idx[0]].T
     rec = data.view(np.uint8).reshape(n_chains, n_draws * data.dtype.itemsize)
 
     def write_some(first):

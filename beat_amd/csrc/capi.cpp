@@ -90,6 +90,17 @@ int wset_quad(beatamd_ctx *ctx, const WeightSet &w, int64_t C, const double *X, 
     return launch_quadform(ctx, q);
 }
 
+// columns of the hyper model's misfit vector: one per seismic dataset, one per geodetic dataset, one per slip variable
+// of the Laplacian
+int64_t model_nterm(const FfiModel &m)
+{
+    int64_t n = 0;
+    for (auto &w : m.wavemaps) n += w.T;
+    if (m.has_geo) n += (int64_t)m.geo.sizes.size();
+    if (m.lap >= 0) n += m.layout.nvar;
+    return n;
+}
+
 // what remains after the composites wrote their columns: the `like` sum.  A caller that passes a
 // LikeTail does that sum itself (the Metropolis step folds it into its accept kernel)
 struct LikeTail {
@@ -100,10 +111,15 @@ struct LikeTail {
 // logp_forw_func on device pointers.  `active` (device [C], nullable): chains whose rows of LL the caller will not read;
 // kernels that honour it skip those chains and leave their rows unspecified (the fused Metropolis step passes the
 // in-box flags of its proposals)
+// `llks` (device [C, nterm], nullable): the hyper model's cached misfits instead of the likelihood -- every composite
+// stops in front of its epilogue and stores the quadratic form it would have handed to it (update_llks: seismic.py:510-525,
+// geodetic.py:429-444, laplacian.py:141-154); LL is then not written and the hyper-parameters are not read
 int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, double *LL,
-                    LikeTail *tail = nullptr, const int32_t *active = nullptr)
+                    LikeTail *tail = nullptr, const int32_t *active = nullptr, double *llks = nullptr)
 {
     const int64_t nllk = m.nllk();
+    const int64_t nterm = model_nterm(m);
+    int64_t tcol = 0;
     const int64_t np = m.layout.nparams;
     void *p = nullptr;
     LikeGroups grp;
@@ -175,9 +191,13 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                 BA_TRY(launch_gfstack(ctx, k));
                 BA_TRY(wset_quad(ctx, *ws, C, k.out, wm.T * wm.N, wm.N, quad));
             }
-            BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.N, quad, ws->slog, HpSrc{Q, np, wm.hp_off},
-                                     LL + col, nllk));
+            if (llks)
+                BA_TRY(launch_store_misfits(ctx, C, wm.T, quad, llks + tcol, nterm));
+            else
+                BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.N, quad, ws->slog, HpSrc{Q, np, wm.hp_off},
+                                         LL + col, nllk));
             col += wm.T;
+            tcol += wm.T;
         }
         grp.end[grp.n++] = (int32_t)col;
     }
@@ -220,6 +240,9 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             qs.nd = (int)g.sizes.size();
             qs.C = C; qs.X = res; qs.xs_c = g.Nobs; qs.Q = Q; qs.nparams = np;
             qs.LL = LL + col; qs.ld = nllk;
+            if (llks) {
+                qs.LL = llks + tcol; qs.ld = nterm; qs.misfit_only = true;
+            }
             BA_TRY(launch_quadform_small(ctx, qs));
         } else {
             BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * sizeof(double), &p));
@@ -228,12 +251,16 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             for (size_t d = 0; d < g.sizes.size(); d++) {
                 WeightSet *ws = get_obj(ctx->wsets, g.wsets[d]);
                 BA_TRY(wset_quad(ctx, *ws, C, res + o, g.Nobs, 0, quad));
-                BA_TRY(launch_mvn_finish(ctx, C, 1, ws->M, quad, ws->slog,
-                                         HpSrc{Q, np, g.hp_off + d}, LL + col + (int64_t)d, nllk));
+                if (llks)
+                    BA_TRY(launch_store_misfits(ctx, C, 1, quad, llks + tcol + (int64_t)d, nterm));
+                else
+                    BA_TRY(launch_mvn_finish(ctx, C, 1, ws->M, quad, ws->slog,
+                                             HpSrc{Q, np, g.hp_off + d}, LL + col + (int64_t)d, nllk));
                 o += g.sizes[d];
             }
         }
         col += (int64_t)g.sizes.size();
+        tcol += (int64_t)g.sizes.size();
         grp.end[grp.n++] = (int32_t)col;
     }
     if (m.lap >= 0) {
@@ -250,13 +277,21 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
         q.X = sl; q.xs_c = nvar * lp->P; q.xs_d = lp->P;
         q.quad = quad; q.q_stride = nvar;
         BA_TRY(launch_quadform(ctx, q));
-        BA_TRY(launch_laplacian_finish(ctx, C, nvar, lp->P, lp->logdet, quad,
-                                       HpSrc{Q + m.layout.h_laplacian_off, np, nullptr}, LL + col,
-                                       nllk));
+        if (llks)   // one column per slip variable: the hyper model keeps them apart (laplacian.py:151-170)
+            BA_TRY(launch_store_misfits(ctx, C, nvar, quad, llks + tcol, nterm));
+        else
+            BA_TRY(launch_laplacian_finish(ctx, C, nvar, lp->P, lp->logdet, quad,
+                                           HpSrc{Q + m.layout.h_laplacian_off, np, nullptr}, LL + col,
+                                           nllk));
         col += 1;
+        tcol += nvar;
         grp.end[grp.n++] = (int32_t)col;
     }
     BA_CHECK(col == nllk - 1, BEATAMD_EINVAL, "internal: llk layout mismatch");
+    if (llks) {
+        BA_CHECK(tcol == nterm, BEATAMD_EINVAL, "internal: misfit layout mismatch");
+        return launch_misfits_mark_bad(ctx, C, nterm, llks, chain_bad);
+    }
     if (tail) {
         tail->grp = grp;
         tail->chain_bad = chain_bad;
@@ -1113,6 +1148,138 @@ int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
     BA_TRY(stage_out(ctx, SL_OUT0, LL, (size_t)C * m->nllk() * 8, &d_l, &rec));
     BA_TRY(ffi_logp_device(ctx, *m, C, (const double *)d_q, (double *)d_l));
     return finish_out(ctx, &rec, 1);
+}
+
+int beatamd_ffi_model_nterm(beatamd_ctx *ctx, int32_t model_id, int64_t *nterm)
+{
+    BA_CHECK(ctx && nterm, BEATAMD_EINVAL, "bad argument");
+    FfiModel *m = get_obj(ctx->models, model_id);
+    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    *nterm = model_nterm(*m);
+    return BEATAMD_OK;
+}
+
+int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *llks)
+{
+    ENTER(ctx);
+    FfiModel *m = get_obj(ctx->models, model_id);
+    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    BA_CHECK(Q && llks && C >= 0, BEATAMD_EINVAL, "ffi_llks: bad argument");
+    BA_TRY(model_check_layout(*m));
+    if (C == 0) return BEATAMD_OK;
+    const void *d_q;
+    void *d_l;
+    Arg rec;
+    BA_TRY(stage_in(ctx, SL_IN0, Q, (size_t)C * m->layout.nparams * 8, &d_q));
+    BA_TRY(stage_out(ctx, SL_OUT0, llks, (size_t)C * model_nterm(*m) * 8, &d_l, &rec));
+    BA_TRY(ffi_logp_device(ctx, *m, C, (const double *)d_q, nullptr, nullptr, nullptr, (double *)d_l));
+    return finish_out(ctx, &rec, 1);
+}
+
+// ------------------------------------------------------------------ the hyper-parameter model (hyper.hip)
+int beatamd_hyper_model_create(beatamd_ctx *ctx, int64_t nterm, int64_t nh, const int64_t *M, const double *slog,
+                               const int32_t *kind, const int32_t *hp_index, int32_t ngroups, const int32_t *group_end,
+                               int32_t *id)
+{
+    ENTER(ctx);
+    BA_CHECK(M && slog && kind && hp_index && group_end && id && nterm > 0 && nh > 0 && ngroups >= 1 && ngroups <= 8,
+             BEATAMD_EINVAL, "hyper_model_create: bad argument");
+    BA_CHECK(nterm <= 2048, BEATAMD_EINVAL, "hyper_model_create: %lld terms (at most 2048)", (long long)nterm);
+    std::vector<double> Md((size_t)nterm);
+    for (int64_t k = 0; k < nterm; k++) {
+        BA_CHECK(kind[k] == 0 || kind[k] == 1, BEATAMD_EINVAL, "hyper_model_create: term %lld: kind must be 0 (dataset) or 1 "
+                 "(Laplacian)", (long long)k);
+        BA_CHECK(hp_index[k] >= 0 && hp_index[k] < nh, BEATAMD_EINVAL, "hyper_model_create: term %lld: hyper-parameter %d of %lld",
+                 (long long)k, hp_index[k], (long long)nh);
+        Md[k] = (double)M[k];
+    }
+    auto h = std::make_unique<HyperModel>();
+    h->nterm = nterm; h->nh = nh; h->ngroups = ngroups;
+    for (int g = 0; g < ngroups; g++) {
+        BA_CHECK(group_end[g] > 0 && group_end[g] <= nterm && (g == 0 || group_end[g] >= group_end[g - 1]), BEATAMD_EINVAL,
+                 "hyper_model_create: composite boundaries must ascend inside the term vector");
+        h->group_end[g] = group_end[g];
+    }
+    BA_CHECK(group_end[ngroups - 1] == nterm, BEATAMD_EINVAL, "hyper_model_create: the last composite ends at nterm");
+    // registered first: whatever a failing upload leaves behind is freed by _destroy / with the context
+    HyperModel *hm = h.get();
+    const int32_t hid = add_obj(ctx->hypers, std::move(h));
+    void *p = nullptr;
+    int rc = dev_alloc_copy(ctx, Md.data(), (size_t)nterm * 8, &p);
+    if (rc == BEATAMD_OK) { hm->M = (double *)p; rc = dev_alloc_copy(ctx, slog, (size_t)nterm * 8, &p); }
+    if (rc == BEATAMD_OK) { hm->slog = (double *)p; rc = dev_alloc_copy(ctx, kind, (size_t)nterm * 4, &p); }
+    if (rc == BEATAMD_OK) { hm->kind = (int32_t *)p; rc = dev_alloc_copy(ctx, hp_index, (size_t)nterm * 4, &p); }
+    if (rc == BEATAMD_OK) hm->hp_index = (int32_t *)p;
+    if (rc != BEATAMD_OK) {
+        if (hm->M) (void)hipFree(hm->M);
+        if (hm->slog) (void)hipFree(hm->slog);
+        if (hm->kind) (void)hipFree(hm->kind);
+        ctx->hypers[hid].reset();
+        return rc;
+    }
+    *id = hid;
+    return BEATAMD_OK;
+}
+
+int beatamd_hyper_model_destroy(beatamd_ctx *ctx, int32_t id)
+{
+    ENTER(ctx);
+    HyperModel *h = get_obj(ctx->hypers, id);
+    BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    if (h->M) (void)hipFree(h->M);
+    if (h->slog) (void)hipFree(h->slog);
+    if (h->kind) (void)hipFree(h->kind);
+    if (h->hp_index) (void)hipFree(h->hp_index);
+    ctx->hypers[id].reset();
+    return BEATAMD_OK;
+}
+
+int beatamd_hyper_logp_batch(beatamd_ctx *ctx, int32_t id, int64_t C, const double *H, const double *llks, double *LL)
+{
+    ENTER(ctx);
+    HyperModel *h = get_obj(ctx->hypers, id);
+    BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
+    BA_CHECK(H && llks && LL && C >= 0, BEATAMD_EINVAL, "hyper_logp: bad argument");
+    if (C == 0) return BEATAMD_OK;
+    const void *d_h, *d_l;
+    void *d_o;
+    Arg rec;
+    BA_TRY(stage_in(ctx, SL_IN0, H, (size_t)C * h->nh * 8, &d_h));
+    BA_TRY(stage_in(ctx, SL_IN1, llks, (size_t)C * h->nterm * 8, &d_l));
+    BA_TRY(stage_out(ctx, SL_OUT0, LL, (size_t)C * (h->nterm + 1) * 8, &d_o, &rec));
+    BA_TRY(launch_hyper_logp(ctx, *h, C, (const double *)d_h, (const double *)d_l, (double *)d_o));
+    return finish_out(ctx, &rec, 1);
+}
+
+int beatamd_hyper_chain_batch(beatamd_ctx *ctx, int32_t id, int64_t C, int64_t n_steps, double *H, double *LL,
+                              double *scaling, int32_t *accepted_since_tune, const double *llks, const double *lower,
+                              const double *upper, int32_t kind, const double *scales, uint64_t seed, uint32_t step0,
+                              int64_t first_chain, int32_t tune_interval, int32_t steps_until_tune, int32_t buffer_thinning,
+                              double *trace, int64_t *n_accepted)
+{
+    ENTER(ctx);
+    HyperModel *h = get_obj(ctx->hypers, id);
+    BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
+    BA_CHECK(H && LL && scaling && accepted_since_tune && llks && lower && upper && scales && C >= 0 && n_steps >= 0 &&
+             first_chain >= 0 && tune_interval >= 0 && buffer_thinning >= 1, BEATAMD_EINVAL, "hyper_chain: bad argument");
+    BA_CHECK(tune_interval == 0 || (steps_until_tune >= 0 && steps_until_tune <= tune_interval), BEATAMD_EINVAL,
+             "hyper_chain: steps_until_tune must lie in [0, tune_interval]");
+    BA_CHECK(kind >= BEATAMD_PROPOSAL_NORMAL && kind <= BEATAMD_PROPOSAL_LAPLACE, BEATAMD_EINVAL,
+             "hyper_chain: kind must be Normal (0), Cauchy (1) or Laplace (2)");
+    BA_CHECK(hyper_chain_applicable(h->nh, h->nterm), BEATAMD_EINVAL,
+             "hyper_chain: %lld hyper-parameters / %lld terms exceed what a chain's wavefront holds (%d each): take the "
+             "step-by-step path", (long long)h->nh, (long long)h->nterm, HYPER_CHAIN_MAX);
+    BA_CHECK(is_device_ptr(H) && is_device_ptr(LL) && is_device_ptr(scaling) && is_device_ptr(accepted_since_tune) &&
+             is_device_ptr(llks) && is_device_ptr(lower) && is_device_ptr(upper) && is_device_ptr(scales) &&
+             (!trace || is_device_ptr(trace)) && (!n_accepted || is_device_ptr(n_accepted)), BEATAMD_EINVAL,
+             "hyper_chain: device pointers only");
+    HyperChainCall k;
+    k.C = C; k.n_steps = n_steps; k.H = H; k.LL = LL; k.scaling = scaling; k.acc_since = accepted_since_tune;
+    k.llks = llks; k.lower = lower; k.upper = upper; k.scales = scales; k.kind = kind; k.seed = seed;
+    k.first_chain = (uint64_t)first_chain; k.step0 = step0; k.tune_interval = tune_interval;
+    k.steps_until_tune = steps_until_tune; k.buffer_thinning = buffer_thinning; k.trace = trace; k.n_acc = n_accepted;
+    return launch_hyper_chain(ctx, *h, k);
 }
 
 // proposal source of a step: rows handed in (delta, log_u) or drawn here (factor / scales + Philox key)

@@ -304,6 +304,13 @@ int beatamd_ctx_destroy(beatamd_ctx *c)
             if (m->d_patch_off) (void)hipFree(m->d_patch_off);
             if (m->d_patch_size) (void)hipFree(m->d_patch_size);
         }
+    for (auto &h : c->hypers)
+        if (h) {
+            if (h->M) (void)hipFree(h->M);
+            if (h->slog) (void)hipFree(h->slog);
+            if (h->kind) (void)hipFree(h->kind);
+            if (h->hp_index) (void)hipFree(h->hp_index);
+        }
     for (auto &s : c->scratch) s.release();
     for (auto &kv : c->timers)
         for (auto &pr : kv.second.pending) {

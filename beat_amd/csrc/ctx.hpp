@@ -163,6 +163,14 @@ struct FfiModel {
     int64_t nllk() const;
 };
 
+// the hyper-parameter model (hyper.hip): term k = kind[k] formula on hyper-parameter hp_index[k] of the nh-vector
+struct HyperModel {
+    int64_t nterm = 0, nh = 0;
+    double *M = nullptr, *slog = nullptr;          // device [nterm]
+    int32_t *kind = nullptr, *hp_index = nullptr;  // device [nterm]
+    int32_t ngroups = 0, group_end[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // composites inside the term vector (exclusive ends)
+};
+
 // A/B and test knobs of the stacking path (BEATAMD_G* / BEATAMD_WS_* environment variables; DESIGN.md 3.1b lists them).
 // Read ONCE when the context is created (and again on beatamd_ctx_reload_knobs); a context created with
 // BEATAMD_KNOBS_LIVE=1 in the environment -- the test suite, the A/B tools -- re-reads them at every stacking call so
@@ -202,6 +210,7 @@ struct beatamd_ctx {
     std::vector<std::unique_ptr<beatamd::WeightSet>> wsets;
     std::vector<std::unique_ptr<beatamd::Laplacian>> laps;
     std::vector<std::unique_ptr<beatamd::FfiModel>> models;
+    std::vector<std::unique_ptr<beatamd::HyperModel>> hypers;
     int num_cu = 256;
     // name of the stacking kernel of the most recent launch (tests assert which kernel ran)
     char last_gf_kernel[96] = "";

@@ -160,6 +160,7 @@ struct QuadformSmallCall {
     int64_t nparams = 0;
     double *LL = nullptr;
     int64_t ld = 0;
+    bool misfit_only = false;   // LL[c*ld + d] = |W_d x_{c,d}|^2 without the epilogue (slog, hp_off, Q unread)
 };
 bool quadform_small_applicable(int nd, const int64_t *M);
 int launch_quadform_small(beatamd_ctx *ctx, const QuadformSmallCall &call);
@@ -244,6 +245,9 @@ __device__ __forceinline__ double geo_corrected_residual(const GeoCorr &gc, cons
     return geo_corr_subtract<false>(gc, Q + c * nparams, k, r);
 }
 #endif
+// the hyper model's cached misfits: dst[c*ld + k] = src[c*n + k], k < n; then NaN into the rows of flagged chains
+int launch_store_misfits(beatamd_ctx *ctx, int64_t C, int64_t n, const double *src, double *dst, int64_t ld);
+int launch_misfits_mark_bad(beatamd_ctx *ctx, int64_t C, int64_t n, double *llks, const int32_t *chain_bad);
 // laplacian: out[c*ld] = sum_v -0.5*(-logdet + P*(log2pi+2h) + (1/exp(2h))*quad[c,v])
 int launch_laplacian_finish(beatamd_ctx *ctx, int64_t C, int64_t nvar, int64_t P, double logdet,
                             const double *quad, HpSrc hp, double *out, int64_t ld);
@@ -345,5 +349,26 @@ int launch_draw_propose(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, int 
                         double *log_u, int32_t *inbounds);
 int launch_philox_chain(beatamd_ctx *ctx, int64_t C, uint64_t seed, uint32_t step, uint64_t first_chain,
                         int df, double *log_u, double *row_scale);
+
+
+// ---- hyper.hip: the hyper-parameter model on cached misfits
+// LL[c, :] = (terms, like) of H [C, nh] given llks [C, nterm]   (k_hyper_logp)
+int launch_hyper_logp(beatamd_ctx *ctx, const HyperModel &m, int64_t C, const double *H, const double *llks, double *LL);
+// n_steps Metropolis steps of every chain in one launch (k_hyper_chain); device pointers
+constexpr int HYPER_CHAIN_MAX = 1024;   // hyper-parameters and terms a chain's wavefront holds in LDS, each
+struct HyperChainCall {
+    int64_t C = 0, n_steps = 0;
+    double *H = nullptr, *LL = nullptr, *scaling = nullptr;
+    int32_t *acc_since = nullptr;
+    const double *llks = nullptr, *lower = nullptr, *upper = nullptr, *scales = nullptr;
+    int kind = 0;
+    uint64_t seed = 0, first_chain = 0;
+    uint32_t step0 = 0;
+    int tune_interval = 0, steps_until_tune = 0, buffer_thinning = 1;
+    double *trace = nullptr;
+    int64_t *n_acc = nullptr;
+};
+bool hyper_chain_applicable(int64_t nh, int64_t nterm);
+int launch_hyper_chain(beatamd_ctx *ctx, const HyperModel &m, const HyperChainCall &call);
 
 }  // namespace beatamd

@@ -229,6 +229,40 @@ int launch_laplacian_finish(beatamd_ctx *ctx, int64_t C, int64_t nvar, int64_t P
     return BEATAMD_OK;
 }
 
+// update_llks (seismic.py:510-525, geodetic.py:429-444, laplacian.py:141-154) for a batch: the quadratic forms the
+// likelihood kernels left in `quad` go into their columns of llks [C, nterm] as they are
+__global__ void __launch_bounds__(256) k_store_misfits(int64_t C, int64_t n, const double *src, double *dst, int64_t ld)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= C * n) return;
+    const int64_t c = i / n, k = i - c * n;
+    dst[c * ld + k] = src[i];
+}
+
+int launch_store_misfits(beatamd_ctx *ctx, int64_t C, int64_t n, const double *src, double *dst, int64_t ld)
+{
+    if (C * n == 0) return BEATAMD_OK;
+    hipLaunchKernelGGL(k_store_misfits, dim3((unsigned)((C * n + 255) / 256)), dim3(256), 0, ctx->stream, C, n, src, dst, ld);
+    BA_HIP(hipGetLastError());
+    return BEATAMD_OK;
+}
+
+// a chain whose times left the library grid: NaN in all its columns (as its `like` in k_like_sum)
+__global__ void __launch_bounds__(256) k_misfits_mark_bad(int64_t C, int64_t n, double *llks, const int32_t *chain_bad)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= C * n) return;
+    if (chain_bad[i / n]) llks[i] = __builtin_nan("");
+}
+
+int launch_misfits_mark_bad(beatamd_ctx *ctx, int64_t C, int64_t n, double *llks, const int32_t *chain_bad)
+{
+    if (C * n == 0 || !chain_bad) return BEATAMD_OK;
+    hipLaunchKernelGGL(k_misfits_mark_bad, dim3((unsigned)((C * n + 255) / 256)), dim3(256), 0, ctx->stream, C, n, llks, chain_bad);
+    BA_HIP(hipGetLastError());
+    return BEATAMD_OK;
+}
+
 // problems.py:227-247: like = sum over composites of (composite llk vector).sum()
 __global__ void __launch_bounds__(256) k_like_sum(int64_t C, int64_t nllk, LikeGroups grp,
                                                  double *LL, const int32_t *chain_bad)

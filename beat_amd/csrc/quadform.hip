@@ -217,6 +217,7 @@ struct QsArgs {
     double *LL;         // logpts of dataset d -> LL[c * ld + d]
     int64_t ld;
     int pitch;
+    int misfit;         // store |W_d x|^2 itself instead of the logpt (the hyper model's cached misfits)
 };
 
 // QS_KB k-steps (4 columns each) of A operands are in flight while the previous batch multiplies: the
@@ -289,6 +290,10 @@ __global__ void __launch_bounds__(64 * QS_MAXW) k_quadform_small(QsArgs a)
         if (c < a.C) {
             double quad = 0.0;
             for (int w = 0; w < nwave; w++) quad += red[w * QS_CB + tid];
+            if (a.misfit) {
+                a.LL[c * a.ld + d] = quad;
+                return;
+            }
             const double h = a.Q[c * a.nparams + a.hp_off[d][0]];
             const double norm = (double)(int16_t)M * (2 * h + 1.8378770664093453);
             a.LL[c * a.ld + d] = (-0.5) * (a.slog[d][0] + norm + (1 / exp(h * 2)) * quad);
@@ -316,6 +321,7 @@ int launch_quadform_small(beatamd_ctx *ctx, const QuadformSmallCall &k)
         mmax = std::max(mmax, k.M[d]);
     }
     a.C = k.C; a.X = k.X; a.xs_c = k.xs_c; a.Q = k.Q; a.nparams = k.nparams; a.LL = k.LL; a.ld = k.ld;
+    a.misfit = k.misfit_only ? 1 : 0;
     static const int kb = getenv("BEATAMD_QS_KB") ? atoi(getenv("BEATAMD_QS_KB")) : 8;
     a.pitch = (int)(((mmax + 4 * QS_KBMAX - 1) / (4 * QS_KBMAX)) * (4 * QS_KBMAX) + 17);   // >= the zero-padded row, = 17 mod 32
     // one wave per 16-row tile of the largest dataset, at most 16 (then tiles round robin)

@@ -15,6 +15,7 @@
 // width), so every rank of a multi-GPU run computes bit-identical stage decisions from the same
 // gathered arrays.
 #include "kernels.hpp"
+#include "philox.hpp"
 
 namespace beatamd {
 
@@ -233,21 +234,13 @@ int launch_gather_rows(beatamd_ctx *ctx, int64_t nout, int64_t ncol, const doubl
     return BEATAMD_OK;
 }
 
-// metropolis.py:294-306 with pymc's tune table (restated from its documentation):
-//   acc < 0.001 x0.1 | < 0.05 x0.5 | < 0.2 x0.9 | > 0.95 x10 | > 0.75 x2 | > 0.5 x1.1
+// metropolis.py:294-306 with pymc's tune table (tune_factor, philox.hpp)
 __global__ void __launch_bounds__(256) k_tune_scaling(int64_t C, double *scaling, int32_t *accepted,
                                                      double interval)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    const double acc = (double)accepted[c] / interval;
-    double f = 1.0;
-    if (acc < 0.001) f = 0.1;
-    else if (acc < 0.05) f = 0.5;
-    else if (acc < 0.2) f = 0.9;
-    else if (acc > 0.95) f = 10.0;
-    else if (acc > 0.75) f = 2.0;
-    else if (acc > 0.5) f = 1.1;
+    const double f = tune_factor((double)accepted[c] / interval);
     scaling[c] = scaling[c] * f;
     accepted[c] = 0;
 }
@@ -278,33 +271,7 @@ int launch_accumulate_i32(beatamd_ctx *ctx, int64_t C, const int32_t *a, int32_t
 }
 
 // ---------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
-// SC'11) -- counter-based, so a draw is a pure function of (seed, step, chain, element): the
-// proposal rows of a chain do not depend on how chains are sharded over GPUs.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t (&out)[4])
-{
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// 53-bit uniform in (0, 1): ((hi >> 5) * 2^26 + (lo >> 6) + 0.5) * 2^-53
-__device__ __forceinline__ double u53(uint32_t hi, uint32_t lo)
-{
-    return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-}
-
+// Philox4x32-10 draws (generator, uniforms and the proposal families' transforms: philox.hpp)
 // counter layout: (pair index inside the row, global chain id, step, stream); key = seed
 //   stream 0: proposal normals z[c, 2j], z[c, 2j+1] from pair j of chain c (Box-Muller cos / sin)
 //   stream 1: chi-square normals of the multivariate-t divisor (base.py:35-71)
@@ -339,8 +306,7 @@ __global__ void __launch_bounds__(256) k_philox_chain(int64_t C, uint64_t seed, 
     const uint64_t gc = first_chain + (uint64_t)c;
     uint32_t r[4];
     if (log_u) {
-        philox4x32_10(0u, (uint32_t)gc, step, 2u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-        log_u[c] = log(u53(r[0], r[1]));
+        log_u[c] = philox_log_u((uint32_t)gc, step, (uint32_t)seed, (uint32_t)(seed >> 32));
     }
     if (row_scale) {
         double x = 0.0;
@@ -399,29 +365,19 @@ __global__ void __launch_bounds__(256) k_philox_univariate(double *delta, int64_
     if (i >= C * npair) return;
     const int64_t c = i / npair, j = i - c * npair;
     const uint64_t gc = first_chain + (uint64_t)c;
-    uint32_t r[4];
-    philox4x32_10((uint32_t)j, (uint32_t)gc, step, 3u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-    double a, b;
-    if (kind == 0) {
-        const double rad = sqrt(-2.0 * log(u1));
-        const double th = 6.283185307179586476925286766559 * u2;
-        a = rad * cos(th);
-        b = rad * sin(th);
-    } else if (kind == 1) {
-        a = tan(3.14159265358979323846 * (u1 - 0.5));
-        b = tan(3.14159265358979323846 * (u2 - 0.5));
-    } else if (kind == 2) {
-        uint32_t q[4];
-        philox4x32_10((uint32_t)j, (uint32_t)gc, step, 4u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
-        a = log(u53(q[0], q[1])) - log(u1);     // E1 - E2 with E = -log u
-        b = log(u53(q[2], q[3])) - log(u2);
-    } else {
+    // (the entries admit kind 0..3 only; before the families moved to philox.hpp any other value fell into this
+    // Poisson branch, now it would take the Laplace one)
+    if (kind == 3) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)j, (uint32_t)gc, step, 3u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+        const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
         const double la = scale[2 * j], lb = (2 * j + 1 < np) ? scale[2 * j + 1] : 0.0;
         delta[c * np + 2 * j] = poisson_from_uniform(u1, la, status) - la;
         if (2 * j + 1 < np) delta[c * np + 2 * j + 1] = poisson_from_uniform(u2, lb, status) - lb;
         return;
     }
+    double a, b;
+    philox_univariate_pair(kind, (uint32_t)j, (uint32_t)gc, step, (uint32_t)seed, (uint32_t)(seed >> 32), a, b);
     delta[c * np + 2 * j] = a * scale[2 * j];
     if (2 * j + 1 < np) delta[c * np + 2 * j + 1] = b * scale[2 * j + 1];
 }
@@ -479,15 +435,6 @@ struct DrawProposeArgs {
     double *Qprop, *log_u;
     int32_t *inbounds;
 };
-
-__device__ __forceinline__ void box_muller(const uint32_t (&r)[4], double &a, double &b)
-{
-    const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-    const double rad = sqrt(-2.0 * log(u1));
-    const double th = 6.283185307179586476925286766559 * u2;
-    a = rad * cos(th);
-    b = rad * sin(th);
-}
 
 __global__ void __launch_bounds__(256) k_draw_propose(DrawProposeArgs a)
 {

@@ -609,6 +609,65 @@ class Context(object):
                                                   1.0 if per_chain else float(beta), ptr(f64(beta)) if per_chain else None,
                                                   ptr(accepted)))
 
+    # -- hyper-parameter estimation (csrc/hyper.hip)
+    def ffi_model_nterm(self, model_id):
+        n = C.c_int64()
+        check(self._lib.beatamd_ffi_model_nterm(self._h, model_id, C.byref(n)))
+        return n.value
+
+    def ffi_llks_batch(self, model_id, Q, out=None):
+        """the cached misfits |W r|^2 of every dataset (and |L s_v|^2 per slip variable) at the points Q [C, nparams]
+        -> [C, nterm]: update_llks of every composite (seismic.py:510-525, geodetic.py:429-444, laplacian.py:141-154)"""
+        self._adopt_stream(Q)
+        Q = f64(Q)
+        Cn = int(Q.shape[0])
+        if out is None:
+            out = _empty_like(Q, (Cn, self.ffi_model_nterm(model_id)))
+        check(self._lib.beatamd_ffi_llks_batch(self._h, model_id, Cn, ptr(Q), ptr(out)))
+        return out
+
+    def hyper_model_create(self, nh, M, slog, kind, hp_index, group_end):
+        M = np.ascontiguousarray(M, dtype=np.int64)
+        slog = np.ascontiguousarray(slog, dtype=np.float64)
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+        hp_index = np.ascontiguousarray(hp_index, dtype=np.int32)
+        ge = np.ascontiguousarray(group_end, dtype=np.int32)
+        if not (M.size == slog.size == kind.size == hp_index.size):
+            raise ValueError("hyper model: M, slog, kind and hp_index have one entry per term")
+        hid = C.c_int32()
+        check(self._lib.beatamd_hyper_model_create(self._h, M.size, int(nh), M.ctypes.data, slog.ctypes.data, kind.ctypes.data,
+                                                   hp_index.ctypes.data, ge.size, ge.ctypes.data, C.byref(hid)))
+        return hid.value
+
+    def hyper_model_destroy(self, hyper_id):
+        check(self._lib.beatamd_hyper_model_destroy(self._h, hyper_id))
+
+    def hyper_logp_batch(self, hyper_id, H, llks, out=None):
+        """H [C, nh], llks [C, nterm] -> LL [C, nterm + 1] (terms, like): hyper_normal / _eval_prior for C chains"""
+        self._adopt_stream(H, llks)
+        H, llks = f64(H), f64(llks)
+        if _is_dev(H) != _is_dev(llks):
+            raise ValueError("hyper_logp: H and llks must live on the same side")
+        Cn = int(H.shape[0])
+        if out is None:
+            out = _empty_like(H, (Cn, int(llks.shape[1]) + 1))
+        check(self._lib.beatamd_hyper_logp_batch(self._h, hyper_id, Cn, ptr(H), ptr(llks), ptr(out)))
+        return out
+
+    def hyper_chain_batch(self, hyper_id, n_steps, H, LL, scaling, accepted_since_tune, llks, lower, upper, kind, scales,
+                          seed, step0, first_chain, tune_interval, steps_until_tune, buffer_thinning=1, trace=None,
+                          n_accepted=None):
+        """n_steps Metropolis steps of every chain in one launch (beatamd_hyper_chain_batch); device tensors, in place on
+        H, LL, scaling, accepted_since_tune"""
+        self._adopt_stream(H, LL)
+        for a in (H, LL, scaling, llks, lower, upper, scales):
+            f64(a)
+        check(self._lib.beatamd_hyper_chain_batch(
+            self._h, hyper_id, int(H.shape[0]), int(n_steps), ptr(H), ptr(LL), ptr(scaling), ptr(accepted_since_tune),
+            ptr(llks), ptr(lower), ptr(upper), int(kind), ptr(scales), int(seed) & (2 ** 64 - 1), int(step0) & 0xffffffff,
+            int(first_chain), int(tune_interval), int(steps_until_tune), int(buffer_thinning),
+            None if trace is None else ptr(trace), None if n_accepted is None else ptr(n_accepted)))
+
     def halfspace_displacements_batch(self, kinds, params, east, north, nu=0.25):
         """params (C, nsrc, 10) -> (C, nsrc, nobs, 3) = (north, east, up) [m]"""
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)

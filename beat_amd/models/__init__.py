@@ -4,3 +4,4 @@ from .distributions import get_hyper_name, multivariate_normal_chol  # noqa: F40
 from .geometry import GeodeticGeometryProblem, los_vectors  # noqa: F401,E402
 from .corrections import (RampConfig, RampCorrection, StrainRateConfig,  # noqa: F401,E402
                           StrainRateCorrection)
+from .hypers import HyperModel, dataset_hypers, estimate_hypers  # noqa: F401,E402

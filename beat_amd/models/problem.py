@@ -461,6 +461,25 @@ class LogpForwFunc(object):
             raise RuntimeError("a weight update of this model did not complete: %s" % self._dirty)
         return self.ctx.ffi_logp_batch(self.model_id, Q, self.nllk, out)
 
+    @property
+    def nterm(self):
+        """columns of ``update_llks``: seismic datasets, geodetic datasets, one per slip variable of the Laplacian"""
+        return self.ctx.ffi_model_nterm(self.model_id)
+
+    def update_llks(self, Q, out=None):
+        """the hyper model's cached misfits at the points Q (C, nparams) -> (C, nterm): ``update_llks`` of every
+        composite (seismic.py:510-525, geodetic.py:429-444, laplacian.py:141-154) for a batch of chains -- the
+        quadratic forms |W r|^2 the likelihood hands to its epilogues, from the same kernels (the geodetic ones with
+        the odw factor, unlike the reference's: DESIGN.md).  The hyper-parameter entries of Q are not read.  numpy in
+        -> numpy out, torch-cuda in -> tensor on the same device."""
+        if self.model_id is None:
+            raise RuntimeError("this compiled model was released")
+        if Q.shape[-1] != self.nparams:
+            raise ValueError("expected %d parameters, got %d" % (self.nparams, Q.shape[-1]))
+        if self._dirty:
+            raise RuntimeError("a weight update of this model did not complete: %s" % self._dirty)
+        return self.ctx.ffi_llks_batch(self.model_id, Q, out)
+
     def update_weights(self, wavemap_index, weights, slog_pdet):
         """seismic.py:1509-1534 update_weights: new chol_inverse + slog_pdet per dataset.  Kind
         and size must match the uploaded set (checked by the library).  numpy arrays or torch-cuda

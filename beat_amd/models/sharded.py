@@ -194,6 +194,11 @@ class TargetShardedLogp(object):
         w = weights[a:b] if hasattr(weights, "__getitem__") else weights
         self.local.update_weights(wavemap_index, w, slog_pdet[a:b])
 
+    def update_llks(self, Q, out=None):
+        raise NotImplementedError("update_llks of a target-sharded model is not offered yet (the seismic columns would be "
+                                  "all-gathered like the likelihood vector): estimate the hyper-parameters on the "
+                                  "replicated model, or on self.local for this rank's targets")
+
     def synthetics(self, Q, wavemap_index=0, residuals=False):
         raise NotImplementedError("synthetics of a target-sharded model: evaluate the local model (self.local.synthetics) for "
                                   "this rank's targets %s" % (self.blocks[wavemap_index][self.rank],))

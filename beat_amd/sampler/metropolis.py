@@ -40,6 +40,7 @@ class BatchedMetropolis(object):
         self.seed = int(seed)
         self.factor, self.df = None, 0
         self.kind, self.uscale = None, None   # per-parameter proposal family and its scales
+        self.use_chain_batch = True   # take target.chain_batch (a whole run in one launch) where it applies
 
     # -- proposal
     def _set_univariate(self, proposal_name, scale=None):
@@ -92,18 +93,53 @@ class BatchedMetropolis(object):
             self.ops.tune(self.scaling, self.accepted_since_tune, self.tune_interval)
             self.steps_until_tune = self.tune_interval
 
-    def run(self, Q, L, beta, n_steps, n_acc, use_graph=False):
+    def _chain_batch_applies(self, Q, beta):
+        """a target whose chains need nothing but themselves (the hyper model: ``chain_batch``) runs a whole ``run`` as
+        one launch: device tensors, one of the per-parameter Normal / Cauchy / Laplace families, beta = 1"""
+        t = self.target
+        return (self.use_chain_batch and callable(getattr(t, "chain_batch", None)) and Q.is_cuda
+                and self.kind in (0, 1, 2) and np.ndim(beta) == 0 and not hasattr(beta, "data_ptr") and float(beta) == 1.0
+                and t.chain_applicable())
+
+    def _advance_counters(self, n_steps):
+        """the host-side counters after n_steps steps taken elsewhere, as if ``step`` had run n_steps times"""
+        self.n_steps_total += n_steps
+        if not self.tune or n_steps <= self.steps_until_tune:
+            self.steps_until_tune -= n_steps
+        else:
+            r = (n_steps - self.steps_until_tune) % self.tune_interval
+            self.steps_until_tune = 0 if r == 0 else self.tune_interval - r
+
+    def run(self, Q, L, beta, n_steps, n_acc, use_graph=False, trace=None, buffer_thinning=1):
         """n_steps steps of every chain, in place on Q, L; accepted moves are added to the 0-d int64
-        tensor n_acc.  On the device a step is ONE C call (beatamd_ffi_mstep_batch: draws, proposal,
+        tensor n_acc.  trace (ndraws, chains, nparams + nllk), optional: the state after step s is recorded iff
+        (n_steps - 1 - s) % buffer_thinning == 0 (the reference's buffer[-1::-buffer_thinning] reversed,
+        beat/backend.py:113-115; ndraws = ceil(n_steps / buffer_thinning)) -- eager loop or ``chain_batch`` only.  On the device a step is ONE C call (beatamd_ffi_mstep_batch: draws, proposal,
         forward model, accept, acceptance counters).  use_graph (CUDA only): a chunk of steps is captured
         ONCE per call in a HIP graph and replayed, with the Philox step counter resident on the
         device (beatamd_ctx_set_step_counter), so the draws are exactly those of the eager loop;
         the step-size tuning runs between replays."""
         torch = self.torch
         n_steps = int(n_steps)
-        if not (use_graph and Q.is_cuda and n_steps >= 3 and hasattr(self.ops, "ctx")):
-            for _ in range(n_steps):
+        bt = max(1, int(buffer_thinning))
+        if trace is not None and tuple(trace.shape) != (-(-n_steps // bt), Q.shape[0], Q.shape[1] + L.shape[1]):
+            raise ValueError("run: trace must have shape (ceil(n_steps / buffer_thinning), chains, nparams + nllk) = %s, got %s"
+                             % ((-(-n_steps // bt), Q.shape[0], Q.shape[1] + L.shape[1]), tuple(trace.shape)))
+        if n_steps > 0 and self._chain_batch_applies(Q, beta):
+            self.target.chain_batch(Q, L, n_steps, self.scaling, self.accepted_since_tune, self.lower, self.upper,
+                                    self.kind, self.uscale, self.seed, self.n_steps_total, self.first_chain,
+                                    self.tune_interval if self.tune else 0, self.steps_until_tune if self.tune else 0,
+                                    bt, trace, n_acc)
+            self._advance_counters(n_steps)
+            return
+        if trace is not None or not (use_graph and Q.is_cuda and n_steps >= 3 and hasattr(self.ops, "ctx")):
+            npar = Q.shape[1]
+            for s in range(n_steps):
                 self.step(Q, L, beta, n_acc)
+                if trace is not None and (n_steps - 1 - s) % bt == 0:
+                    row = trace[(s - (n_steps - 1) % bt) // bt]
+                    row[:, :npar].copy_(Q)
+                    row[:, npar:].copy_(L)
             return
         self.step(Q, L, beta, n_acc)      # eager: allocations, measured kernel choices
         ctx = self.ops.ctx

@@ -466,6 +466,66 @@ int beatamd_metropolis_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int6
 int beatamd_metropolis_tune(beatamd_ctx *ctx, int64_t C, double *scaling, int32_t *accepted,
                             int32_t tune_interval);
 
+/* ---------------------------------------------------------------- hyper-parameter estimation ----
+ * `beat sample --hypers`: the source is fixed at one point per chain, each dataset's whitened misfit |W r|^2 is
+ * cached once, and Metropolis runs on the noise scalings h_* alone (estimate_hypers, beat/models/base.py:304-379;
+ * init_chain_hypers, beat/sampler/base.py:398-418; built_hyper_model, beat/models/problems.py:261-297).
+ *
+ * replaces: update_llks of every composite for C points at once
+ *           beat/models/seismic.py:510-525, beat/models/geodetic.py:429-444, beat/models/laplacian.py:141-154
+ *   Q [C,nparams] -> llks [C,nterm] (host or device pointers): one column per seismic dataset (wavemap by wavemap),
+ *   one per geodetic dataset, ONE PER SLIP VARIABLE of the Laplacian (|L s_v|^2; the likelihood sums these into one
+ *   laplacian_like, the hyper model keeps them apart, laplacian.py:151-170); nterm from beatamd_ffi_model_nterm.
+ *   The values are the quadratic forms the likelihood hands to its epilogues, from the same kernels (scalar and
+ *   bidiagonal covariances in the stacking epilogue, dense W in the matrix-core quadratic form, pre-whitened
+ *   libraries, the small-dataset geodetic kernel, the geometry-mode composite); station time shifts and dataset
+ *   corrections are part of the residual as in the likelihood.  The hyper-parameter entries of Q are not read.
+ *   A chain whose times leave the library grid gets NaN in all its columns and raises the status word as
+ *   beatamd_ffi_logp_batch does.
+ *   DEVIATION: the reference's geodetic update_llks forms data - synthetics WITHOUT the odw factor
+ *   (geodetic.py:221, 439-443) although its likelihood uses (data - mu) * odw (:1072).  Here the cached misfit is
+ *   the likelihood's own, so that the hyper model IS the full model at a fixed source point; with odw = 1 the two
+ *   agree. */
+int beatamd_ffi_model_nterm(beatamd_ctx *ctx, int32_t model_id, int64_t *nterm);
+int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *llks);
+/* replaces: hyper_normal                      beat/models/distributions.py:176-222 (through
+ *           Composite.get_hyper_formula, beat/models/base.py:110-123) and the Laplacian's _eval_prior /
+ *           get_hyper_formula, beat/models/laplacian.py:88-96, 156-170
+ *   Term k reads hyper-parameter hp_index[k] of the nh-vector (get_hyper_name / Counter order, distributions.py:24-25,
+ *   195-210):
+ *     kind 0 (dataset)    -0.5 * (slog[k] + (M[k] * 2 * h) + (1 / exp(h * 2)) * llk)         no M log 2pi; M uncast
+ *     kind 1 (Laplacian)  -0.5 * (-slog[k] + (M[k] * (LOG_2PI + 2 * h)) + (1 / exp(h * 2) * llk))
+ *   in this operation order.  group_end [ngroups <= 8]: exclusive ends of the composites inside the term vector;
+ *   like = the composites' sums added in composite order (problems.py:286-296), each composite summed by a fixed
+ *   rule of (nterm, group_end) alone: 64 strided partial sums (term k to partial k mod 64, ascending), joined by a
+ *   butterfly (xor 32, 16, ..., 1).  M, slog, kind, hp_index, group_end are host arrays.  At most 2048 terms. */
+int beatamd_hyper_model_create(beatamd_ctx *ctx, int64_t nterm, int64_t nh, const int64_t *M, const double *slog,
+                               const int32_t *kind, const int32_t *hp_index, int32_t ngroups, const int32_t *group_end,
+                               int32_t *id);
+int beatamd_hyper_model_destroy(beatamd_ctx *ctx, int32_t id);
+/*   H [C,nh], llks [C,nterm] -> LL [C,nterm+1]: the terms, then like (host or device pointers) */
+int beatamd_hyper_logp_batch(beatamd_ctx *ctx, int32_t id, int64_t C, const double *H, const double *llks, double *LL);
+/* replaces: n_steps calls of Metropolis.astep per chain       beat/sampler/metropolis.py:294-306, 313-385
+ *   ALL n_steps steps of all C chains in ONE launch (the chains are independent: one wavefront each, no barrier
+ *   between them).  Device pointers only.  In / out: H [C,nh], LL [C,nterm+1], scaling [C], accepted_since_tune [C];
+ *   in: llks [C,nterm], lower / upper [nh], kind 0/1/2 (Normal / Cauchy / Laplace) with scales [nh]; out: trace
+ *   [ndraws, C, nh+nterm+1] (nullable) and n_accepted [1] (+= moves, nullable).
+ *   Step s is step step0 + s of the step-by-step path (beatamd_proposal_draw_univariate, beatamd_metropolis_propose,
+ *   beatamd_hyper_logp_batch, beatamd_metropolis_accept with beta = 1, beatamd_metropolis_tune) for chain
+ *   first_chain + c, bit for bit: the same Philox counters and transforms, q = q0 + delta * scaling, a proposal outside
+ *   the box is rejected without evaluation, accept iff isfinite(mr) and log u < mr.  tune_interval > 0: the tune table
+ *   is applied in front of a step whenever steps_until_tune has run down to 0 (then reset to tune_interval);
+ *   tune_interval = 0: no tuning.  The draw after step s is recorded iff (n_steps - 1 - s) % buffer_thinning == 0 -- the
+ *   reference's buffer[-1::-buffer_thinning] reversed (thin_buffer, beat/backend.py:100-118, with the whole run in
+ *   the buffer): ndraws = ceil(n_steps / buffer_thinning).
+ *   A chain's wavefront holds at most 1024 hyper-parameters and 1024 terms: beyond that BEATAMD_EINVAL (take the
+ *   step-by-step path). */
+int beatamd_hyper_chain_batch(beatamd_ctx *ctx, int32_t id, int64_t C, int64_t n_steps, double *H, double *LL,
+                              double *scaling, int32_t *accepted_since_tune, const double *llks, const double *lower,
+                              const double *upper, int32_t kind, const double *scales, uint64_t seed, uint32_t step0,
+                              int64_t first_chain, int32_t tune_interval, int32_t steps_until_tune, int32_t buffer_thinning,
+                              double *trace, int64_t *n_accepted);
+
 /* ---------------------------------------------------------------- library whitening ------
  * rows [nrows, N] (device, in place) <- rows . W^T, W [N,N] = chol_inverse of one dataset: the
  * dense W.r of multivariate_normal_chol (distributions.py:128) applied once to every library row
