@@ -5,28 +5,6 @@ using namespace beatamd;
 
 namespace {
 
-int dev_alloc_copy(beatamd_ctx *ctx, const void *src, size_t bytes, void **dst)
-{
-    void *d = nullptr;
-    hipError_t e = hipMalloc(&d, bytes ? bytes : 8);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return BEATAMD_ENOMEM;
-    }
-    if (src && bytes) {
-        e = hipMemcpyAsync(d, src, bytes, hipMemcpyDefault, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            set_error("hipMemcpy(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-            return BEATAMD_EHIP;
-        }
-    }
-    *dst = d;
-    return BEATAMD_OK;
-}
-
 template <class T>
 T *get_obj(std::vector<std::unique_ptr<T>> &v, int32_t id)
 {
@@ -44,6 +22,15 @@ int32_t add_obj(std::vector<std::unique_ptr<T>> &v, std::unique_ptr<T> o)
         }
     v.push_back(std::move(o));
     return (int32_t)v.size() - 1;
+}
+
+// *_destroy: drain the stream, then the object goes and frees its device arrays
+template <class T>
+int destroy_obj(beatamd_ctx *ctx, std::vector<std::unique_ptr<T>> &v, int32_t id)
+{
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    v[id].reset();
+    return BEATAMD_OK;
 }
 
 // host copy of a small argument array that may live on either side
@@ -70,13 +57,13 @@ int wset_quad(beatamd_ctx *ctx, const WeightSet &w, int64_t C, const double *X, 
               int64_t xs_d, double *quad)
 {
     if (w.kind == BEATAMD_W_SCALAR)
-        return launch_scalar_quad(ctx, C, w.nd, w.M, X, xs_c, xs_d, w.w, quad);
+        return launch_scalar_quad(ctx, C, w.nd, w.M, X, xs_c, xs_d, w.w.get(), quad);
     // banded whitening operators (the reference's "exponential" noise structure gives bidiagonal ones): two products per
     // sample instead of a row of the dense matrix
     if (w.band >= 0 && w.wb && GfKnobs::get(gf_knobs(ctx).qf_band, 1) != 0)
-        return launch_quadform_banded(ctx, w.wb, w.band, w.M, w.nd, C, X, xs_c, xs_d, quad, w.nd);
+        return launch_quadform_banded(ctx, w.wb.get(), w.band, w.M, w.nd, C, X, xs_c, xs_d, quad, w.nd);
     QuadformCall q;
-    q.A = w.w;
+    q.A = w.w.get();
     q.a_stride = w.M * w.M;
     q.M = w.M;
     q.nd = w.nd;
@@ -159,19 +146,19 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             k.st.nparams = np;
             k.order_key[0] = ChainVec{Q, np, m.layout.nuc_strike_off};   // (scheduling hint of k_gfstack_runs)
             k.order_key[1] = ChainVec{Q, np, m.layout.nuc_dip_off};
-            k.st.shift_off = wm.shift_off;
-            k.st.nslot = wm.nslot; k.st.tslot = wm.tslot; k.st.slot_shift_off = wm.slot_shift_off;
+            k.st.shift_off = wm.shift_off.get();
+            k.st.nslot = wm.nslot; k.st.tslot = wm.tslot.get(); k.st.slot_shift_off = wm.slot_shift_off.get();
             k.st.chain_bad = chain_bad;
             k.active = active;
             k.interp = wm.interp;
             k.f32 = wm.f32;
             k.C = C;
-            k.data = wm.data;
+            k.data = wm.data.get();
             BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * wm.T * sizeof(double), &p));
             double *quad = (double *)p;
             if (ws->kind == BEATAMD_W_SCALAR) {
                 k.mode = GF_RESID_SCALAR;
-                k.wscalar = ws->w;
+                k.wscalar = ws->w.get();
                 k.quad = quad;
                 BA_TRY(launch_gfstack(ctx, k));
             } else if (ws->band == 1 && ws->wb && ws->M == wm.N && ws->nd == wm.T &&
@@ -179,7 +166,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                 // bidiagonal whitening operators (the "exponential" noise structure): the misfit rides in the stacking
                 // kernel where it has the epilogue, else residual store + k_quadform_banded (launch_gfstack decides)
                 k.mode = GF_RESID_BAND1;
-                k.band_w = ws->wb;
+                k.band_w = ws->wb.get();
                 k.quad = quad;
                 BA_TRY(ctx->get_scratch(SL_RESID, (size_t)C * wm.T * wm.N * sizeof(double), &p));
                 k.out = (double *)p;
@@ -194,7 +181,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             if (llks)
                 BA_TRY(launch_store_misfits(ctx, C, wm.T, quad, llks + tcol, nterm));
             else
-                BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.N, quad, ws->slog, HpSrc{Q, np, wm.hp_off},
+                BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.N, quad, ws->slog.get(), HpSrc{Q, np, wm.hp_off.get()},
                                          LL + col, nllk));
             col += wm.T;
             tcol += wm.T;
@@ -207,7 +194,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
         double *mu = (double *)p, *res = mu + C * g.Nobs;
         if (m.geo_is_geometry) {
             // synthetics, line of sight and weighted residual in one kernel
-            BA_TRY(launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data, g.odws, res, g.corr));
+            BA_TRY(launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data.get(), g.odws.get(), res, g.corr));
         } else {
             // every slip variable's G.T . slips in one launch (geodetic.py:1065-1070 sums them)
             const GeoLib *gls[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -217,7 +204,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                 BA_CHECK(gls[v], BEATAMD_EINVAL, "geodetic composite refers to a destroyed GF library");
             }
             BA_TRY(launch_geo_stack(ctx, gls, m.layout.nvar, C, slips, 0, mu));
-            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data, g.odws, mu, res, Q, np, g.corr));
+            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data.get(), g.odws.get(), mu, res, Q, np, g.corr));
         }
         // small dense datasets (SAR scenes / GNSS of a few hundred points): every dataset's
         // quadratic form and MVN epilogue in one launch; otherwise per dataset on the 64-row tiles
@@ -230,8 +217,8 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                      "geodetic dataset %zu: weight set missing or of the wrong size", d);
             small = small && ws->kind != BEATAMD_W_SCALAR;
             if (small) {
-                qs.A[d] = ws->w; qs.M[d] = ws->M; qs.xoff[d] = o; qs.upper_tri[d] = ws->upper_tri;
-                qs.slog[d] = ws->slog; qs.hp_off[d] = g.hp_off + d;
+                qs.A[d] = ws->w.get(); qs.M[d] = ws->M; qs.xoff[d] = o; qs.upper_tri[d] = ws->upper_tri;
+                qs.slog[d] = ws->slog.get(); qs.hp_off[d] = g.hp_off.get() + d;
             }
             o += g.sizes[d];
         }
@@ -254,8 +241,8 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                 if (llks)
                     BA_TRY(launch_store_misfits(ctx, C, 1, quad, llks + tcol + (int64_t)d, nterm));
                 else
-                    BA_TRY(launch_mvn_finish(ctx, C, 1, ws->M, quad, ws->slog,
-                                             HpSrc{Q, np, g.hp_off + d}, LL + col + (int64_t)d, nllk));
+                    BA_TRY(launch_mvn_finish(ctx, C, 1, ws->M, quad, ws->slog.get(),
+                                             HpSrc{Q, np, g.hp_off.get() + d}, LL + col + (int64_t)d, nllk));
                 o += g.sizes[d];
             }
         }
@@ -273,7 +260,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
         BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * nvar * sizeof(double), &p));
         double *quad = (double *)p;
         QuadformCall q;
-        q.A = lp->L; q.a_stride = 0; q.M = lp->P; q.nd = nvar; q.C = C;
+        q.A = lp->L.get(); q.a_stride = 0; q.M = lp->P; q.nd = nvar; q.C = C;
         q.X = sl; q.xs_c = nvar * lp->P; q.xs_d = lp->P;
         q.quad = quad; q.q_stride = nvar;
         BA_TRY(launch_quadform(ctx, q));
@@ -314,16 +301,16 @@ int beatamd_fast_sweep_batch(beatamd_ctx *ctx, const double *slowness, double pa
     BA_CHECK(num_strk > 0 && num_dip > 0 && C >= 0, BEATAMD_EINVAL, "fast_sweep: bad dimensions");
     if (C == 0) return BEATAMD_OK;
     const int64_t n = (int64_t)num_strk * num_dip;
-    const void *d_s, *d_hi, *d_hj;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, slowness, (size_t)C * n * 8, &d_s));
-    BA_TRY(stage_in(ctx, SL_IN1, h_strk, (size_t)C * 4, &d_hi));
-    BA_TRY(stage_in(ctx, SL_IN2, h_dip, (size_t)C * 4, &d_hj));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)C * n * 8, &d_o, &rec));
-    BA_TRY(launch_sweep_explicit(ctx, (const double *)d_s, patch_size, (const int32_t *)d_hi,
-                                 (const int32_t *)d_hj, num_strk, num_dip, C, (double *)d_o));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_s;
+    const int32_t *d_hi, *d_hj;
+    double *d_o;
+    BA_TRY(st.in(slowness, (size_t)C * n, &d_s));
+    BA_TRY(st.in(h_strk, (size_t)C, &d_hi));
+    BA_TRY(st.in(h_dip, (size_t)C, &d_hj));
+    BA_TRY(st.out(out, (size_t)C * n, &d_o));
+    BA_TRY(launch_sweep_explicit(ctx, d_s, patch_size, d_hi, d_hj, num_strk, num_dip, C, d_o));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ GF libraries
@@ -337,7 +324,7 @@ int beatamd_seis_gflib_create(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t D,
              "GF library dimensions must be positive");
     BA_CHECK(st_dt > 0 && du_dt > 0, BEATAMD_EINVAL, "sampling intervals must be positive");
     BA_CHECK(D < 32768 && S < 32768, BEATAMD_EINVAL, "int16 index range exceeded");
-    std::unique_ptr<SeisLib> l(new SeisLib());
+    std::unique_ptr<SeisStore> l(new SeisStore());
     l->T = T; l->P = P; l->D = D; l->S = S; l->N = N;
     l->st_min = st_min; l->st_dt = st_dt; l->du_min = du_min; l->du_dt = du_dt;
     *lib_id = add_obj(ctx->seislibs, std::move(l));
@@ -356,19 +343,13 @@ int beatamd_seis_gflib_set_split_targets(beatamd_ctx *ctx, int32_t lib_id, int64
     return BEATAMD_OK;
 }
 
-static int seis_ensure_storage(beatamd_ctx *ctx, SeisLib *l)
+static int seis_ensure_storage(SeisStore *l)
 {
     if (l->g) return BEATAMD_OK;
-    const size_t bytes = (size_t)l->elems() * sizeof(double);
-    hipError_t e = hipMalloc((void **)&l->g, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        l->g = nullptr;
-        set_error("GF library of %.2f GB does not fit in HBM: %s", bytes / 1e9,
-                  hipGetErrorString(e));
-        return BEATAMD_ENOMEM;
-    }
-    l->owned = true;
+    const hipError_t e = l->own.try_alloc((size_t)l->elems());
+    BA_CHECK(e == hipSuccess, BEATAMD_ENOMEM, "GF library of %.2f GB does not fit in HBM: %s",
+             (size_t)l->elems() * sizeof(double) / 1e9, hipGetErrorString(e));
+    l->g = l->own.get();
     return BEATAMD_OK;
 }
 
@@ -378,12 +359,12 @@ static void drop_f32_overlapping(beatamd_ctx *ctx, const void *p, size_t bytes)
 {
     const char *a = (const char *)p, *b = a + bytes;
     for (size_t id = 0; id < ctx->seislibs.size(); id++) {
-        SeisLib *l = ctx->seislibs[id].get();
+        SeisStore *l = ctx->seislibs[id].get();
         if (!l || !l->g32 || !l->g) continue;
         const char *la = (const char *)l->g, *lb = la + (size_t)l->elems() * sizeof(double);
         if (b <= la || lb <= a) continue;
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(l->g32);
+        l->own32.reset();
         l->g32 = nullptr;
         for (auto &m : ctx->models) {
             if (!m) continue;
@@ -397,17 +378,13 @@ static void drop_f32_overlapping(beatamd_ctx *ctx, const void *p, size_t bytes)
 int beatamd_seis_gflib_round_to_f32(beatamd_ctx *ctx, int32_t lib_id)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
+    SeisStore *l = get_obj(ctx->seislibs, lib_id);
     BA_CHECK(l && l->g, BEATAMD_EINVAL, "gflib_round_to_f32: unknown or empty GF library %d", lib_id);
     if (!l->g32) {
-        hipError_t e = hipMalloc((void **)&l->g32, (size_t)l->elems() * sizeof(float));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            l->g32 = nullptr;
-            set_error("float copy of the GF library (%.2f GB) does not fit in HBM: %s", l->elems() * 4 / 1e9,
-                      hipGetErrorString(e));
-            return BEATAMD_ENOMEM;
-        }
+        const hipError_t e = l->own32.try_alloc((size_t)l->elems());
+        BA_CHECK(e == hipSuccess, BEATAMD_ENOMEM, "float copy of the GF library (%.2f GB) does not fit in HBM: %s",
+                 l->elems() * 4 / 1e9, hipGetErrorString(e));
+        l->g32 = l->own32.get();
     }
     BA_TRY(launch_round_to_f32(ctx, l->g, l->g32, l->elems()));
     return BEATAMD_OK;
@@ -435,12 +412,12 @@ int beatamd_seis_gflib_upload(beatamd_ctx *ctx, int32_t lib_id, const double *sr
                               int64_t count)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
+    SeisStore *l = get_obj(ctx->seislibs, lib_id);
     BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
     BA_CHECK(src && offset >= 0 && count >= 0 && offset + count <= l->elems(), BEATAMD_EINVAL,
              "gflib_upload: range [%lld, %lld) outside the library (%lld elements)",
              (long long)offset, (long long)(offset + count), (long long)l->elems());
-    BA_TRY(seis_ensure_storage(ctx, l));
+    BA_TRY(seis_ensure_storage(l));
     drop_f32_overlapping(ctx, l->g + offset, (size_t)count * 8);
     BA_HIP(hipMemcpyAsync(l->g + offset, src, (size_t)count * 8, hipMemcpyDefault, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
@@ -450,25 +427,25 @@ int beatamd_seis_gflib_upload(beatamd_ctx *ctx, int32_t lib_id, const double *sr
 int beatamd_seis_gflib_adopt(beatamd_ctx *ctx, int32_t lib_id, double *device_ptr)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
+    SeisStore *l = get_obj(ctx->seislibs, lib_id);
     BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
     BA_CHECK(device_ptr && is_device_ptr(device_ptr), BEATAMD_EINVAL,
              "gflib_adopt needs a device pointer");
     BA_CHECK(((uintptr_t)device_ptr & 15) == 0, BEATAMD_EINVAL,
              "gflib_adopt: pointer must be 16-byte aligned");
-    if (l->owned && l->g) BA_HIP(hipFree(l->g));
-    if (l->g32) { BA_HIP(hipFree(l->g32)); l->g32 = nullptr; }   // (a float copy belongs to the old storage)
+    l->own.reset();
+    l->own32.reset();   // (a float copy belongs to the old storage)
+    l->g32 = nullptr;
     l->g = device_ptr;
-    l->owned = false;
     return BEATAMD_OK;
 }
 
 int beatamd_seis_gflib_device_ptr(beatamd_ctx *ctx, int32_t lib_id, double **device_ptr)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
+    SeisStore *l = get_obj(ctx->seislibs, lib_id);
     BA_CHECK(l && device_ptr, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
-    BA_TRY(seis_ensure_storage(ctx, l));
+    BA_TRY(seis_ensure_storage(l));
     *device_ptr = l->g;
     return BEATAMD_OK;
 }
@@ -478,11 +455,7 @@ int beatamd_seis_gflib_destroy(beatamd_ctx *ctx, int32_t lib_id)
     ENTER(ctx);
     SeisLib *l = get_obj(ctx->seislibs, lib_id);
     BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    if (l->owned && l->g) BA_HIP(hipFree(l->g));
-    if (l->g32) BA_HIP(hipFree(l->g32));
-    ctx->seislibs[lib_id].reset();
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->seislibs, lib_id);
 }
 
 int beatamd_seis_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C,
@@ -498,25 +471,25 @@ int beatamd_seis_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C,
              BEATAMD_EINVAL, "Interpolation scheme %d not implemented!", interpolation);
     BA_CHECK(C >= 0, BEATAMD_EINVAL, "negative batch size");
     if (C == 0) return BEATAMD_OK;
-    const void *d_du, *d_st, *d_sl;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, durations, (size_t)C * l->P * 8, &d_du));
-    BA_TRY(stage_in(ctx, SL_IN1, starttimes, (size_t)C * l->T * l->P * 8, &d_st));
-    BA_TRY(stage_in(ctx, SL_IN2, slips, (size_t)C * l->P * 8, &d_sl));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)C * l->T * l->N * 8, &d_o, &rec));
+    Staging st(ctx);
+    const double *d_du, *d_st, *d_sl;
+    double *d_o;
+    BA_TRY(st.in(durations, (size_t)C * l->P, &d_du));
+    BA_TRY(st.in(starttimes, (size_t)C * l->T * l->P, &d_st));
+    BA_TRY(st.in(slips, (size_t)C * l->P, &d_sl));
+    BA_TRY(st.out(out, (size_t)C * l->T * l->N, &d_o));
     GfStackCall k;
     k.libs[0] = l;
     k.nvar = 1;
-    k.slips[0] = ChainVec{(const double *)d_sl, l->P, 0};
-    k.durations = ChainVec{(const double *)d_du, l->P, 0};
-    k.st.explicit_st = (const double *)d_st;
+    k.slips[0] = ChainVec{d_sl, l->P, 0};
+    k.durations = ChainVec{d_du, l->P, 0};
+    k.st.explicit_st = d_st;
     k.interp = interpolation;
     k.C = C;
     k.mode = GF_STORE_SYN;
-    k.out = (double *)d_o;
+    k.out = d_o;
     BA_TRY(launch_gfstack(ctx, k));
-    return finish_out(ctx, &rec, 1);
+    return st.finish();
 }
 
 int beatamd_geo_gflib_create(beatamd_ctx *ctx, int64_t P, int64_t Nobs, const double *G,
@@ -527,7 +500,7 @@ int beatamd_geo_gflib_create(beatamd_ctx *ctx, int64_t P, int64_t Nobs, const do
     std::unique_ptr<GeoLib> l(new GeoLib());
     l->P = P;
     l->Nobs = Nobs;
-    BA_TRY(dev_alloc_copy(ctx, G, (size_t)P * Nobs * 8, (void **)&l->g));
+    BA_TRY(l->g.alloc_copy(ctx, G, (size_t)P * Nobs));
     *lib_id = add_obj(ctx->geolibs, std::move(l));
     return BEATAMD_OK;
 }
@@ -537,10 +510,7 @@ int beatamd_geo_gflib_destroy(beatamd_ctx *ctx, int32_t lib_id)
     ENTER(ctx);
     GeoLib *l = get_obj(ctx->geolibs, lib_id);
     BA_CHECK(l, BEATAMD_EINVAL, "unknown geodetic GF library %d", lib_id);
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    if (l->g) BA_HIP(hipFree(l->g));
-    ctx->geolibs[lib_id].reset();
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->geolibs, lib_id);
 }
 
 int beatamd_geo_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C, const double *slips,
@@ -551,15 +521,15 @@ int beatamd_geo_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C, con
     BA_CHECK(l, BEATAMD_EINVAL, "unknown geodetic GF library %d", lib_id);
     BA_CHECK(slips && out && C >= 0, BEATAMD_EINVAL, "geo_stack_all: bad argument");
     if (C == 0) return BEATAMD_OK;
-    const void *d_sl;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, slips, (size_t)C * l->P * 8, &d_sl));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)C * l->Nobs * 8, &d_o, &rec, accumulate != 0));
+    Staging st(ctx);
+    const double *d_sl;
+    double *d_o;
+    BA_TRY(st.in(slips, (size_t)C * l->P, &d_sl));
+    BA_TRY(st.out(out, (size_t)C * l->Nobs, &d_o, accumulate != 0));
     const GeoLib *one[1] = {l};
-    const ChainVec sv[1] = {ChainVec{(const double *)d_sl, l->P, 0}};
-    BA_TRY(launch_geo_stack(ctx, one, 1, C, sv, accumulate, (double *)d_o));
-    return finish_out(ctx, &rec, 1);
+    const ChainVec sv[1] = {ChainVec{d_sl, l->P, 0}};
+    BA_TRY(launch_geo_stack(ctx, one, 1, C, sv, accumulate, d_o));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ likelihood
@@ -567,34 +537,36 @@ static int wset_fill(beatamd_ctx *ctx, WeightSet *w, const double *weights, cons
 {
     const size_t wbytes =
         (size_t)(w->kind == BEATAMD_W_SCALAR ? w->nd : w->nd * w->M * w->M) * sizeof(double);
-    BA_HIP(hipMemcpyAsync(w->w, weights, wbytes, hipMemcpyDefault, ctx->stream));
-    BA_HIP(hipMemcpyAsync(w->slog, slog, (size_t)w->nd * 8, hipMemcpyDefault, ctx->stream));
+    BA_HIP(hipMemcpyAsync(w->w.get(), weights, wbytes, hipMemcpyDefault, ctx->stream));
+    BA_HIP(hipMemcpyAsync(w->slog.get(), slog, (size_t)w->nd * 8, hipMemcpyDefault, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
     w->upper_tri = 0;
     if (w->kind == BEATAMD_W_DENSE) {
         void *p = nullptr;
         BA_TRY(ctx->get_scratch(SL_MISC, 64, &p));
-        BA_TRY(launch_check_upper_tri(ctx, w->w, w->nd, w->M, (int *)p));
+        BA_TRY(launch_check_upper_tri(ctx, w->w.get(), w->nd, w->M, (int *)p));
         int flag = 0;
         BA_HIP(hipMemcpyAsync(&flag, p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
         BA_HIP(hipStreamSynchronize(ctx->stream));
         w->upper_tri = flag;
         // banded?  (upper-triangular with nothing beyond a few columns right of the diagonal)
         w->band = -1;
-        if (w->wb) { BA_HIP(hipFree(w->wb)); w->wb = nullptr; }
+        w->wb.reset();
         if (flag && w->M > 2 * QF_BAND_LIMIT) {
             BA_TRY(ctx->get_scratch(SL_MISC, (size_t)w->nd * w->M * 8 + 64, &p));
             int64_t band = -1;
             w->dropped_rel = 0.0;
-            BA_TRY(launch_band_detect(ctx, w->w, w->nd, w->M, p, &band, &w->dropped_rel));
+            BA_TRY(launch_band_detect(ctx, w->w.get(), w->nd, w->M, p, &band, &w->dropped_rel));
             // the choice is visible: beatamd_weights_band_info, and one line under BEATAMD_VERBOSE
             if (getenv("BEATAMD_VERBOSE"))
                 fprintf(stderr, "beat_amd: weight set of %lld operators of %lld^2: %s (half bandwidth %lld, largest entry beyond it "
                                 "%.3g of its row's largest)\n", (long long)w->nd, (long long)w->M,
                         band <= QF_BAND_LIMIT ? "evaluated on its band" : "dense", (long long)band, w->dropped_rel);
             if (band >= 0 && band <= QF_BAND_LIMIT) {
-                BA_TRY(dev_alloc_copy(ctx, nullptr, (size_t)(w->nd * w->M * (band + 1)) * sizeof(double), (void **)&w->wb));
-                BA_TRY(launch_band_pack(ctx, w->w, w->nd, w->M, band, w->wb));
+                DevMem<double> wb;
+                BA_TRY(wb.alloc((size_t)(w->nd * w->M * (band + 1))));
+                BA_TRY(launch_band_pack(ctx, w->w.get(), w->nd, w->M, band, wb.get()));
+                w->wb = std::move(wb);
                 w->band = band;
             }
         }
@@ -614,9 +586,8 @@ int beatamd_weights_create(beatamd_ctx *ctx, int32_t kind, int64_t nd, int64_t M
     w->kind = kind;
     w->nd = nd;
     w->M = M;
-    const size_t wbytes = (size_t)(kind == BEATAMD_W_SCALAR ? nd : nd * M * M) * sizeof(double);
-    BA_TRY(dev_alloc_copy(ctx, nullptr, wbytes, (void **)&w->w));
-    BA_TRY(dev_alloc_copy(ctx, nullptr, (size_t)nd * 8, (void **)&w->slog));
+    BA_TRY(w->w.alloc((size_t)(kind == BEATAMD_W_SCALAR ? nd : nd * M * M)));
+    BA_TRY(w->slog.alloc((size_t)nd));
     BA_TRY(wset_fill(ctx, w.get(), weights, slog_pdet));
     *wset_id = add_obj(ctx->wsets, std::move(w));
     return BEATAMD_OK;
@@ -664,12 +635,7 @@ int beatamd_weights_destroy(beatamd_ctx *ctx, int32_t wset_id)
     ENTER(ctx);
     WeightSet *w = get_obj(ctx->wsets, wset_id);
     BA_CHECK(w, BEATAMD_EINVAL, "unknown weight set %d", wset_id);
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    if (w->w) BA_HIP(hipFree(w->w));
-    if (w->wb) BA_HIP(hipFree(w->wb));
-    if (w->slog) BA_HIP(hipFree(w->slog));
-    ctx->wsets[wset_id].reset();
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->wsets, wset_id);
 }
 
 int beatamd_mvn_chol_logp_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C,
@@ -680,17 +646,18 @@ int beatamd_mvn_chol_logp_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C,
     BA_CHECK(w, BEATAMD_EINVAL, "unknown weight set %d", wset_id);
     BA_CHECK(residuals && hp && logpts && C >= 0, BEATAMD_EINVAL, "mvn_chol_logp: bad argument");
     if (C == 0) return BEATAMD_OK;
-    const void *d_r, *d_h;
-    void *d_o, *p;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, residuals, (size_t)C * w->nd * w->M * 8, &d_r));
-    BA_TRY(stage_in(ctx, SL_IN1, hp, (size_t)C * w->nd * 8, &d_h));
-    BA_TRY(stage_out(ctx, SL_OUT0, logpts, (size_t)C * w->nd * 8, &d_o, &rec));
+    Staging st(ctx);
+    const double *d_r, *d_h;
+    double *d_o;
+    void *p;
+    BA_TRY(st.in(residuals, (size_t)C * w->nd * w->M, &d_r));
+    BA_TRY(st.in(hp, (size_t)C * w->nd, &d_h));
+    BA_TRY(st.out(logpts, (size_t)C * w->nd, &d_o));
     BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * w->nd * 8, &p));
-    BA_TRY(wset_quad(ctx, *w, C, (const double *)d_r, w->nd * w->M, w->M, (double *)p));
-    BA_TRY(launch_mvn_finish(ctx, C, w->nd, w->M, (const double *)p, w->slog,
-                             HpSrc{(const double *)d_h, w->nd, nullptr}, (double *)d_o, w->nd));
-    return finish_out(ctx, &rec, 1);
+    BA_TRY(wset_quad(ctx, *w, C, d_r, w->nd * w->M, w->M, (double *)p));
+    BA_TRY(launch_mvn_finish(ctx, C, w->nd, w->M, (const double *)p, w->slog.get(),
+                             HpSrc{d_h, w->nd, nullptr}, d_o, w->nd));
+    return st.finish();
 }
 
 int beatamd_laplacian_create(beatamd_ctx *ctx, int64_t P, const double *L, double logdet,
@@ -701,7 +668,7 @@ int beatamd_laplacian_create(beatamd_ctx *ctx, int64_t P, const double *L, doubl
     std::unique_ptr<Laplacian> l(new Laplacian());
     l->P = P;
     l->logdet = logdet;
-    BA_TRY(dev_alloc_copy(ctx, L, (size_t)P * P * 8, (void **)&l->L));
+    BA_TRY(l->L.alloc_copy(ctx, L, (size_t)P * P));
     *lap_id = add_obj(ctx->laps, std::move(l));
     return BEATAMD_OK;
 }
@@ -711,10 +678,7 @@ int beatamd_laplacian_destroy(beatamd_ctx *ctx, int32_t lap_id)
     ENTER(ctx);
     Laplacian *l = get_obj(ctx->laps, lap_id);
     BA_CHECK(l, BEATAMD_EINVAL, "unknown laplacian %d", lap_id);
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    if (l->L) BA_HIP(hipFree(l->L));
-    ctx->laps[lap_id].reset();
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->laps, lap_id);
 }
 
 int beatamd_laplacian_logp_batch(beatamd_ctx *ctx, int32_t lap_id, int64_t C, int64_t nvar,
@@ -725,21 +689,21 @@ int beatamd_laplacian_logp_batch(beatamd_ctx *ctx, int32_t lap_id, int64_t C, in
     BA_CHECK(l, BEATAMD_EINVAL, "unknown laplacian %d", lap_id);
     BA_CHECK(slips && hp && out && C >= 0 && nvar > 0, BEATAMD_EINVAL, "laplacian_logp: bad argument");
     if (C == 0) return BEATAMD_OK;
-    const void *d_s, *d_h;
-    void *d_o, *p;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, slips, (size_t)C * nvar * l->P * 8, &d_s));
-    BA_TRY(stage_in(ctx, SL_IN1, hp, (size_t)C * 8, &d_h));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)C * 8, &d_o, &rec));
+    Staging st(ctx);
+    const double *d_s, *d_h;
+    double *d_o;
+    void *p;
+    BA_TRY(st.in(slips, (size_t)C * nvar * l->P, &d_s));
+    BA_TRY(st.in(hp, (size_t)C, &d_h));
+    BA_TRY(st.out(out, (size_t)C, &d_o));
     BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * nvar * 8, &p));
     QuadformCall q;
-    q.A = l->L; q.a_stride = 0; q.M = l->P; q.nd = nvar; q.C = C;
-    q.X = (const double *)d_s; q.xs_c = nvar * l->P; q.xs_d = l->P;
+    q.A = l->L.get(); q.a_stride = 0; q.M = l->P; q.nd = nvar; q.C = C;
+    q.X = d_s; q.xs_c = nvar * l->P; q.xs_d = l->P;
     q.quad = (double *)p; q.q_stride = nvar;
     BA_TRY(launch_quadform(ctx, q));
-    BA_TRY(launch_laplacian_finish(ctx, C, nvar, l->P, l->logdet, (const double *)p,
-                                   HpSrc{(const double *)d_h, 1, nullptr}, (double *)d_o, 1));
-    return finish_out(ctx, &rec, 1);
+    BA_TRY(launch_laplacian_finish(ctx, C, nvar, l->P, l->logdet, (const double *)p, HpSrc{d_h, 1, nullptr}, d_o, 1));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ fused FFI model
@@ -768,10 +732,10 @@ int beatamd_ffi_model_create(beatamd_ctx *ctx, const beatamd_ffi_layout *layout,
     }
     m->P = P;
     if (nsub > 0) {
-        BA_TRY(dev_alloc_copy(ctx, m->ndip.data(), nsub * 4, (void **)&m->d_ndip));
-        BA_TRY(dev_alloc_copy(ctx, m->nstrike.data(), nsub * 4, (void **)&m->d_nstrike));
-        BA_TRY(dev_alloc_copy(ctx, m->patch_off.data(), nsub * 4, (void **)&m->d_patch_off));
-        BA_TRY(dev_alloc_copy(ctx, m->patch_size.data(), nsub * 8, (void **)&m->d_patch_size));
+        BA_TRY(m->d_ndip.alloc_copy(ctx, m->ndip.data(), (size_t)nsub));
+        BA_TRY(m->d_nstrike.alloc_copy(ctx, m->nstrike.data(), (size_t)nsub));
+        BA_TRY(m->d_patch_off.alloc_copy(ctx, m->patch_off.data(), (size_t)nsub));
+        BA_TRY(m->d_patch_size.alloc_copy(ctx, m->patch_size.data(), (size_t)nsub));
     }
     *model_id = add_obj(ctx->models, std::move(m));
     return BEATAMD_OK;
@@ -815,10 +779,10 @@ int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int3
             BA_CHECK(shift_off[t] >= 0 && shift_off[t] < np, BEATAMD_EINVAL,
                      "add_wavemap: shift_off[%lld] outside q", (long long)t);
     }
-    BA_TRY(dev_alloc_copy(ctx, data, (size_t)w.T * w.N * 8, (void **)&w.data));
-    BA_TRY(dev_alloc_copy(ctx, hp_off, (size_t)w.T * 8, (void **)&w.hp_off));
+    BA_TRY(w.data.alloc_copy(ctx, data, (size_t)w.T * w.N));
+    BA_TRY(w.hp_off.alloc_copy(ctx, hp_off, (size_t)w.T));
     if (shift_off) {
-        BA_TRY(dev_alloc_copy(ctx, shift_off, (size_t)w.T * 8, (void **)&w.shift_off));
+        BA_TRY(w.shift_off.alloc_copy(ctx, shift_off, (size_t)w.T));
         // slots in the order of first appearance
         std::vector<int32_t> tslot((size_t)w.T);
         std::vector<int64_t> slot_off;
@@ -830,11 +794,28 @@ int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int3
         }
         if ((int64_t)slot_off.size() < w.T) {
             w.nslot = (int32_t)slot_off.size();
-            BA_TRY(dev_alloc_copy(ctx, tslot.data(), tslot.size() * sizeof(int32_t), (void **)&w.tslot));
-            BA_TRY(dev_alloc_copy(ctx, slot_off.data(), slot_off.size() * sizeof(int64_t), (void **)&w.slot_shift_off));
+            BA_TRY(w.tslot.alloc_copy(ctx, tslot.data(), tslot.size()));
+            BA_TRY(w.slot_shift_off.alloc_copy(ctx, slot_off.data(), slot_off.size()));
         }
     }
     m->wavemaps.push_back(std::move(w));
+    return BEATAMD_OK;
+}
+
+// the datasets of a geodetic composite, checked (`fn`: the entry point, for the messages): g gets sizes, weight sets, Nobs
+static int geodetic_datasets(beatamd_ctx *ctx, const FfiModel &m, const char *fn, int32_t nd, const int64_t *sizes,
+                             const int32_t *wset_ids, const int64_t *hp_off, Geodetic &g)
+{
+    for (int d = 0; d < nd; d++) {
+        BA_CHECK(sizes[d] > 0, BEATAMD_EINVAL, "%s: empty dataset %d", fn, d);
+        BA_CHECK(hp_off[d] >= 0 && hp_off[d] < m.layout.nparams, BEATAMD_EINVAL, "%s: hp_off[%d] outside q", fn, d);
+        WeightSet *ws = get_obj(ctx->wsets, wset_ids[d]);
+        BA_CHECK(ws && ws->nd == 1 && ws->M == sizes[d], BEATAMD_EINVAL,
+                 "%s: weight set of dataset %d must be 1 x %lld", fn, d, (long long)sizes[d]);
+        g.sizes.push_back(sizes[d]);
+        g.wsets.push_back(wset_ids[d]);
+        g.Nobs += sizes[d];
+    }
     return BEATAMD_OK;
 }
 
@@ -850,32 +831,22 @@ int beatamd_ffi_model_add_geodetic(beatamd_ctx *ctx, int32_t model_id, const int
     BA_CHECK(geo_lib_ids && data && odws && sizes && wset_ids && hp_off && nd > 0, BEATAMD_EINVAL,
              "add_geodetic: bad argument");
     Geodetic g;
-    int64_t nobs = 0;
-    for (int d = 0; d < nd; d++) {
-        BA_CHECK(sizes[d] > 0, BEATAMD_EINVAL, "add_geodetic: empty dataset %d", d);
-        BA_CHECK(hp_off[d] >= 0 && hp_off[d] < m->layout.nparams, BEATAMD_EINVAL,
-                 "add_geodetic: hp_off[%d] outside q", d);
-        WeightSet *ws = get_obj(ctx->wsets, wset_ids[d]);
-        BA_CHECK(ws && ws->nd == 1 && ws->M == sizes[d], BEATAMD_EINVAL,
-                 "add_geodetic: weight set of dataset %d must be 1 x %lld", d, (long long)sizes[d]);
-        g.sizes.push_back(sizes[d]);
-        g.wsets.push_back(wset_ids[d]);
-        nobs += sizes[d];
-    }
+    BA_TRY(geodetic_datasets(ctx, *m, "add_geodetic", nd, sizes, wset_ids, hp_off, g));
+    int64_t P = m->P;
     for (int v = 0; v < m->layout.nvar; v++) {
         GeoLib *l = get_obj(ctx->geolibs, geo_lib_ids[v]);
-        BA_CHECK(l && l->Nobs == nobs, BEATAMD_EINVAL,
+        BA_CHECK(l && l->Nobs == g.Nobs, BEATAMD_EINVAL,
                  "add_geodetic: library %d missing or observation count mismatch", geo_lib_ids[v]);
         if (m->nsub > 0)
             BA_CHECK(l->P == m->P, BEATAMD_EINVAL, "add_geodetic: patch count mismatch");
         else
-            m->P = l->P;
+            P = l->P;
         g.libs.push_back(geo_lib_ids[v]);
     }
-    g.Nobs = nobs;
-    BA_TRY(dev_alloc_copy(ctx, data, (size_t)nobs * 8, (void **)&g.data));
-    BA_TRY(dev_alloc_copy(ctx, odws, (size_t)nobs * 8, (void **)&g.odws));
-    BA_TRY(dev_alloc_copy(ctx, hp_off, (size_t)nd * 8, (void **)&g.hp_off));
+    BA_TRY(g.data.alloc_copy(ctx, data, (size_t)g.Nobs));
+    BA_TRY(g.odws.alloc_copy(ctx, odws, (size_t)g.Nobs));
+    BA_TRY(g.hp_off.alloc_copy(ctx, hp_off, (size_t)nd));
+    m->P = P;
     m->geo = std::move(g);
     m->has_geo = true;
     return BEATAMD_OK;
@@ -898,40 +869,28 @@ int beatamd_ffi_model_add_geodetic_geometry(beatamd_ctx *ctx, int32_t model_id, 
              BEATAMD_EINVAL, "add_geodetic_geometry: bad argument");
     BA_CHECK(nu > -1.0 && nu < 0.5, BEATAMD_EINVAL, "Poisson ratio outside (-1, 0.5)");
     Geodetic g;
-    int64_t tot = 0;
-    for (int d = 0; d < nd; d++) {
-        BA_CHECK(sizes[d] > 0, BEATAMD_EINVAL, "add_geodetic_geometry: empty dataset %d", d);
-        BA_CHECK(hp_off[d] >= 0 && hp_off[d] < m->layout.nparams, BEATAMD_EINVAL,
-                 "add_geodetic_geometry: hp_off[%d] outside q", d);
-        WeightSet *ws = get_obj(ctx->wsets, wset_ids[d]);
-        BA_CHECK(ws && ws->nd == 1 && ws->M == sizes[d], BEATAMD_EINVAL,
-                 "add_geodetic_geometry: weight set of dataset %d must be 1 x %lld", d,
-                 (long long)sizes[d]);
-        g.sizes.push_back(sizes[d]);
-        g.wsets.push_back(wset_ids[d]);
-        tot += sizes[d];
-    }
-    BA_CHECK(tot == nobs, BEATAMD_EINVAL, "add_geodetic_geometry: dataset sizes sum to %lld, not %lld",
-             (long long)tot, (long long)nobs);
+    BA_TRY(geodetic_datasets(ctx, *m, "add_geodetic_geometry", nd, sizes, wset_ids, hp_off, g));
+    BA_CHECK(g.Nobs == nobs, BEATAMD_EINVAL, "add_geodetic_geometry: dataset sizes sum to %lld, not %lld",
+             (long long)g.Nobs, (long long)nobs);
     for (int i = 0; i < nsrc * 10; i++)
         BA_CHECK(param_off[i] < m->layout.nparams, BEATAMD_EINVAL,
                  "add_geodetic_geometry: parameter offset %d outside q", i);
     for (int i = 0; i < nsrc; i++)
         BA_CHECK(kind[i] == 0 || kind[i] == 1, BEATAMD_EINVAL, "unknown source kind %d", kind[i]);
-    g.Nobs = nobs;
-    BA_TRY(dev_alloc_copy(ctx, data, (size_t)nobs * 8, (void **)&g.data));
-    BA_TRY(dev_alloc_copy(ctx, odws, (size_t)nobs * 8, (void **)&g.odws));
-    BA_TRY(dev_alloc_copy(ctx, hp_off, (size_t)nd * 8, (void **)&g.hp_off));
-    GeomSources &gs = m->geom;
+    BA_TRY(g.data.alloc_copy(ctx, data, (size_t)nobs));
+    BA_TRY(g.odws.alloc_copy(ctx, odws, (size_t)nobs));
+    BA_TRY(g.hp_off.alloc_copy(ctx, hp_off, (size_t)nd));
+    GeomSources gs;
     gs.nsrc = nsrc;
     gs.Nobs = nobs;
     gs.nu = nu;
-    BA_TRY(dev_alloc_copy(ctx, kind, (size_t)nsrc * 4, (void **)&gs.kind));
-    BA_TRY(dev_alloc_copy(ctx, param_off, (size_t)nsrc * 10 * 8, (void **)&gs.poff));
-    BA_TRY(dev_alloc_copy(ctx, param_fixed, (size_t)nsrc * 10 * 8, (void **)&gs.pfix));
-    BA_TRY(dev_alloc_copy(ctx, east, (size_t)nobs * 8, (void **)&gs.east));
-    BA_TRY(dev_alloc_copy(ctx, north, (size_t)nobs * 8, (void **)&gs.north));
-    BA_TRY(dev_alloc_copy(ctx, los, (size_t)nobs * 3 * 8, (void **)&gs.los));
+    BA_TRY(gs.kind.alloc_copy(ctx, kind, (size_t)nsrc));
+    BA_TRY(gs.poff.alloc_copy(ctx, param_off, (size_t)nsrc * 10));
+    BA_TRY(gs.pfix.alloc_copy(ctx, param_fixed, (size_t)nsrc * 10));
+    BA_TRY(gs.east.alloc_copy(ctx, east, (size_t)nobs));
+    BA_TRY(gs.north.alloc_copy(ctx, north, (size_t)nobs));
+    BA_TRY(gs.los.alloc_copy(ctx, los, (size_t)nobs * 3));
+    m->geom = std::move(gs);
     m->geo = std::move(g);
     m->has_geo = true;
     m->geo_is_geometry = true;
@@ -990,15 +949,18 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
         }
         nbasis += t.n * t.K;
     }
-    BA_TRY(dev_alloc_copy(ctx, basis, (size_t)nbasis * 8, (void **)&g.corr_basis));
+    DevMem<double> d_basis;
+    BA_TRY(d_basis.alloc_copy(ctx, basis, (size_t)nbasis));
     int64_t bo = 0;
     for (int j = 0; j < nterm; j++) {
-        terms[(size_t)j].B = g.corr_basis + bo;
+        terms[(size_t)j].B = d_basis.get() + bo;
         bo += terms[(size_t)j].n * terms[(size_t)j].K;
     }
-    GeoCorrTerm *d_terms = nullptr;
-    BA_TRY(dev_alloc_copy(ctx, terms.data(), terms.size() * sizeof(GeoCorrTerm), (void **)&d_terms));
-    g.corr.terms = d_terms;
+    DevMem<GeoCorrTerm> d_terms;
+    BA_TRY(d_terms.alloc_copy(ctx, terms.data(), terms.size()));
+    g.corr_basis = std::move(d_basis);
+    g.corr_terms = std::move(d_terms);
+    g.corr.terms = g.corr_terms.get();
     g.corr.nterm = nterm;
     g.corr_set = true;
     return BEATAMD_OK;
@@ -1033,31 +995,7 @@ int beatamd_ffi_model_destroy(beatamd_ctx *ctx, int32_t model_id)
     ENTER(ctx);
     FfiModel *m = get_obj(ctx->models, model_id);
     BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    for (auto &w : m->wavemaps) {
-        if (w.data) (void)hipFree(w.data);
-        if (w.hp_off) (void)hipFree(w.hp_off);
-        if (w.shift_off) (void)hipFree(w.shift_off);
-        if (w.tslot) (void)hipFree(w.tslot);
-        if (w.slot_shift_off) (void)hipFree(w.slot_shift_off);
-    }
-    if (m->geo.data) (void)hipFree(m->geo.data);
-    if (m->geo.odws) (void)hipFree(m->geo.odws);
-    if (m->geo.hp_off) (void)hipFree(m->geo.hp_off);
-    if (m->geo.corr.terms) (void)hipFree((void *)m->geo.corr.terms);
-    if (m->geo.corr_basis) (void)hipFree(m->geo.corr_basis);
-    if (m->geom.kind) (void)hipFree(m->geom.kind);
-    if (m->geom.poff) (void)hipFree(m->geom.poff);
-    if (m->geom.pfix) (void)hipFree(m->geom.pfix);
-    if (m->geom.east) (void)hipFree(m->geom.east);
-    if (m->geom.north) (void)hipFree(m->geom.north);
-    if (m->geom.los) (void)hipFree(m->geom.los);
-    if (m->d_ndip) (void)hipFree(m->d_ndip);
-    if (m->d_nstrike) (void)hipFree(m->d_nstrike);
-    if (m->d_patch_off) (void)hipFree(m->d_patch_off);
-    if (m->d_patch_size) (void)hipFree(m->d_patch_size);
-    ctx->models[model_id].reset();
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->models, model_id);
 }
 
 static int model_check_layout(const FfiModel &m)
@@ -1095,12 +1033,13 @@ int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wav
     if (C == 0) return BEATAMD_OK;
     Wavemap &wm = m->wavemaps[wavemap_index];
     const int64_t np = m->layout.nparams;
-    const void *d_q;
-    void *d_o, *p;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, Q, (size_t)C * np * 8, &d_q));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)C * wm.T * wm.N * 8, &d_o, &rec));
-    const double *Qd = (const double *)d_q;
+    Staging st(ctx);
+    const double *d_q;
+    double *d_o;
+    void *p;
+    BA_TRY(st.in(Q, (size_t)C * np, &d_q));
+    BA_TRY(st.out(out, (size_t)C * wm.T * wm.N, &d_o));
+    const double *Qd = d_q;
     BA_TRY(ctx->get_scratch(SL_CHAINBAD, (size_t)C * sizeof(int32_t), &p));
     int32_t *chain_bad = (int32_t *)p;
     BA_HIP(hipMemsetAsync(chain_bad, 0, (size_t)C * sizeof(int32_t), ctx->stream));
@@ -1120,16 +1059,16 @@ int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wav
     k.st.nparams = np;
     k.order_key[0] = ChainVec{Qd, np, m->layout.nuc_strike_off};
     k.order_key[1] = ChainVec{Qd, np, m->layout.nuc_dip_off};
-    k.st.shift_off = wm.shift_off;
+    k.st.shift_off = wm.shift_off.get();
     k.st.chain_bad = chain_bad;
     k.interp = wm.interp;
     k.C = C;
-    k.data = wm.data;
+    k.data = wm.data.get();
     k.mode = residuals ? GF_RESID_STORE : GF_STORE_SYN;
-    k.out = (double *)d_o;
+    k.out = d_o;
     BA_TRY(launch_gfstack(ctx, k));
     BA_TRY(ctx->check_status());   // an index outside the library is the reference's IndexError
-    return finish_out(ctx, &rec, 1);
+    return st.finish();
 }
 
 int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q,
@@ -1141,13 +1080,13 @@ int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
     BA_CHECK(Q && LL && C >= 0, BEATAMD_EINVAL, "ffi_logp: bad argument");
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
-    const void *d_q;
-    void *d_l;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, Q, (size_t)C * m->layout.nparams * 8, &d_q));
-    BA_TRY(stage_out(ctx, SL_OUT0, LL, (size_t)C * m->nllk() * 8, &d_l, &rec));
-    BA_TRY(ffi_logp_device(ctx, *m, C, (const double *)d_q, (double *)d_l));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_q;
+    double *d_l;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.out(LL, (size_t)C * m->nllk(), &d_l));
+    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, d_l));
+    return st.finish();
 }
 
 int beatamd_ffi_model_nterm(beatamd_ctx *ctx, int32_t model_id, int64_t *nterm)
@@ -1167,13 +1106,13 @@ int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
     BA_CHECK(Q && llks && C >= 0, BEATAMD_EINVAL, "ffi_llks: bad argument");
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
-    const void *d_q;
-    void *d_l;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, Q, (size_t)C * m->layout.nparams * 8, &d_q));
-    BA_TRY(stage_out(ctx, SL_OUT0, llks, (size_t)C * model_nterm(*m) * 8, &d_l, &rec));
-    BA_TRY(ffi_logp_device(ctx, *m, C, (const double *)d_q, nullptr, nullptr, nullptr, (double *)d_l));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_q;
+    double *d_l;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.out(llks, (size_t)C * model_nterm(*m), &d_l));
+    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, nullptr, nullptr, d_l));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ the hyper-parameter model (hyper.hip)
@@ -1201,23 +1140,11 @@ int beatamd_hyper_model_create(beatamd_ctx *ctx, int64_t nterm, int64_t nh, cons
         h->group_end[g] = group_end[g];
     }
     BA_CHECK(group_end[ngroups - 1] == nterm, BEATAMD_EINVAL, "hyper_model_create: the last composite ends at nterm");
-    // registered first: whatever a failing upload leaves behind is freed by _destroy / with the context
-    HyperModel *hm = h.get();
-    const int32_t hid = add_obj(ctx->hypers, std::move(h));
-    void *p = nullptr;
-    int rc = dev_alloc_copy(ctx, Md.data(), (size_t)nterm * 8, &p);
-    if (rc == BEATAMD_OK) { hm->M = (double *)p; rc = dev_alloc_copy(ctx, slog, (size_t)nterm * 8, &p); }
-    if (rc == BEATAMD_OK) { hm->slog = (double *)p; rc = dev_alloc_copy(ctx, kind, (size_t)nterm * 4, &p); }
-    if (rc == BEATAMD_OK) { hm->kind = (int32_t *)p; rc = dev_alloc_copy(ctx, hp_index, (size_t)nterm * 4, &p); }
-    if (rc == BEATAMD_OK) hm->hp_index = (int32_t *)p;
-    if (rc != BEATAMD_OK) {
-        if (hm->M) (void)hipFree(hm->M);
-        if (hm->slog) (void)hipFree(hm->slog);
-        if (hm->kind) (void)hipFree(hm->kind);
-        ctx->hypers[hid].reset();
-        return rc;
-    }
-    *id = hid;
+    BA_TRY(h->M.alloc_copy(ctx, Md.data(), (size_t)nterm));
+    BA_TRY(h->slog.alloc_copy(ctx, slog, (size_t)nterm));
+    BA_TRY(h->kind.alloc_copy(ctx, kind, (size_t)nterm));
+    BA_TRY(h->hp_index.alloc_copy(ctx, hp_index, (size_t)nterm));
+    *id = add_obj(ctx->hypers, std::move(h));
     return BEATAMD_OK;
 }
 
@@ -1226,13 +1153,7 @@ int beatamd_hyper_model_destroy(beatamd_ctx *ctx, int32_t id)
     ENTER(ctx);
     HyperModel *h = get_obj(ctx->hypers, id);
     BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    if (h->M) (void)hipFree(h->M);
-    if (h->slog) (void)hipFree(h->slog);
-    if (h->kind) (void)hipFree(h->kind);
-    if (h->hp_index) (void)hipFree(h->hp_index);
-    ctx->hypers[id].reset();
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->hypers, id);
 }
 
 int beatamd_hyper_logp_batch(beatamd_ctx *ctx, int32_t id, int64_t C, const double *H, const double *llks, double *LL)
@@ -1242,14 +1163,14 @@ int beatamd_hyper_logp_batch(beatamd_ctx *ctx, int32_t id, int64_t C, const doub
     BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
     BA_CHECK(H && llks && LL && C >= 0, BEATAMD_EINVAL, "hyper_logp: bad argument");
     if (C == 0) return BEATAMD_OK;
-    const void *d_h, *d_l;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, H, (size_t)C * h->nh * 8, &d_h));
-    BA_TRY(stage_in(ctx, SL_IN1, llks, (size_t)C * h->nterm * 8, &d_l));
-    BA_TRY(stage_out(ctx, SL_OUT0, LL, (size_t)C * (h->nterm + 1) * 8, &d_o, &rec));
-    BA_TRY(launch_hyper_logp(ctx, *h, C, (const double *)d_h, (const double *)d_l, (double *)d_o));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_h, *d_l;
+    double *d_o;
+    BA_TRY(st.in(H, (size_t)C * h->nh, &d_h));
+    BA_TRY(st.in(llks, (size_t)C * h->nterm, &d_l));
+    BA_TRY(st.out(LL, (size_t)C * (h->nterm + 1), &d_o));
+    BA_TRY(launch_hyper_logp(ctx, *h, C, d_h, d_l, d_o));
+    return st.finish();
 }
 
 int beatamd_hyper_chain_batch(beatamd_ctx *ctx, int32_t id, int64_t C, int64_t n_steps, double *H, double *LL,
@@ -1305,16 +1226,18 @@ static int astep_impl(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0,
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
     const int64_t np = m->layout.nparams, nllk = m->nllk();
-    const void *d_de = nullptr, *d_sc, *d_lo, *d_up, *d_lu = nullptr, *d_be = nullptr, *d_f = nullptr;
-    void *d_q0, *d_l0, *d_acc, *p;
-    Arg recs[3];
-    BA_TRY(stage_out(ctx, SL_OUT0, Q0, (size_t)C * np * 8, &d_q0, &recs[0], true));
-    BA_TRY(stage_out(ctx, SL_OUT1, L0, (size_t)C * nllk * 8, &d_l0, &recs[1], true));
-    BA_TRY(stage_out(ctx, SL_OUT2, accepted, (size_t)C * 4, &d_acc, &recs[2]));
-    BA_TRY(stage_in(ctx, SL_IN2, scaling, (size_t)C * 8, &d_sc));
-    BA_TRY(stage_in(ctx, SL_IN3, lower, (size_t)np * 8, &d_lo));
-    BA_TRY(stage_in(ctx, SL_IN4, upper, (size_t)np * 8, &d_up));
-    if (betas) BA_TRY(stage_in(ctx, SL_IN6, betas, (size_t)C * 8, &d_be));
+    Staging st(ctx);
+    const double *d_de = nullptr, *d_sc, *d_lo, *d_up, *d_lu = nullptr, *d_be = nullptr, *d_f = nullptr;
+    double *d_q0, *d_l0;
+    int32_t *d_acc;
+    void *p;
+    BA_TRY(st.out(Q0, (size_t)C * np, &d_q0, true));
+    BA_TRY(st.out(L0, (size_t)C * nllk, &d_l0, true));
+    BA_TRY(st.out(accepted, (size_t)C, &d_acc));
+    BA_TRY(st.in(scaling, (size_t)C, &d_sc));
+    BA_TRY(st.in(lower, (size_t)np, &d_lo));
+    BA_TRY(st.in(upper, (size_t)np, &d_up));
+    if (betas) BA_TRY(st.in(betas, (size_t)C, &d_be));
     BA_TRY(ctx->get_scratch(SL_QPROP, (size_t)C * np * 8, &p));
     double *qprop = (double *)p;
     BA_TRY(ctx->get_scratch(SL_LPROP, (size_t)C * nllk * 8, &p));
@@ -1326,14 +1249,13 @@ static int astep_impl(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0,
         BA_CHECK(is_device_ptr(Q0) && (!acc_sum || is_device_ptr(acc_sum)) && (!n_acc || is_device_ptr(n_acc)),
                  BEATAMD_EINVAL, "ffi_mstep: chain states and counters live on the device");
         const int64_t K = draw->kind < 0 ? draw->K : np;
-        BA_TRY(stage_in(ctx, SL_IN0, draw->factor, (size_t)(draw->kind < 0 ? K * np : np) * 8, &d_f));
+        BA_TRY(st.in(draw->factor, (size_t)(draw->kind < 0 ? K * np : np), &d_f));
         BA_TRY(ctx->get_scratch(SL_LOGU, (size_t)C * 8, &p));
         double *lu = (double *)p;
         d_lu = lu;
         if (draw_propose_applicable(K, np)) {
-            BA_TRY(launch_draw_propose(ctx, C, K, np, draw->kind, (const double *)d_f, draw->df, draw->seed,
-                                       draw->step, draw->first_chain, (const double *)d_q0, (const double *)d_sc,
-                                       (const double *)d_lo, (const double *)d_up, qprop, lu, inb));
+            BA_TRY(launch_draw_propose(ctx, C, K, np, draw->kind, d_f, draw->df, draw->seed, draw->step, draw->first_chain,
+                                       d_q0, d_sc, d_lo, d_up, qprop, lu, inb));
         } else {
             BA_TRY(ctx->get_scratch(SL_DELTA, (size_t)C * np * 8, &p));
             double *de = (double *)p;
@@ -1348,27 +1270,24 @@ static int astep_impl(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0,
                 BA_TRY(launch_philox_chain(ctx, C, draw->seed, draw->step, draw->first_chain, draw->df, lu, rs));
                 GemmCall g;
                 g.A = z; g.lda = K;
-                g.B = (const double *)d_f; g.ldb = np; g.b_kn = 1;
+                g.B = d_f; g.ldb = np; g.b_kn = 1;
                 g.O = de; g.ldo = np;
                 g.M = C; g.N = np; g.K = K;
                 g.row_scale = rs;
                 g.timer = "proposal";
                 BA_TRY(launch_gemm_f64(ctx, g));
             } else {
-                BA_TRY(launch_philox_univariate(ctx, de, C, np, draw->kind, (const double *)d_f, draw->seed,
+                BA_TRY(launch_philox_univariate(ctx, de, C, np, draw->kind, d_f, draw->seed,
                                                 draw->step, draw->first_chain));
                 BA_TRY(launch_philox_chain(ctx, C, draw->seed, draw->step, draw->first_chain, 0, lu, nullptr));
             }
-            BA_TRY(launch_propose(ctx, C, np, (const double *)d_q0, de, (const double *)d_sc,
-                                  (const double *)d_lo, (const double *)d_up, qprop, inb));
+            BA_TRY(launch_propose(ctx, C, np, d_q0, de, d_sc, d_lo, d_up, qprop, inb));
         }
         advance = true;
     } else {
-        BA_TRY(stage_in(ctx, SL_IN1, delta, (size_t)C * np * 8, &d_de));
-        BA_TRY(stage_in(ctx, SL_IN5, log_u, (size_t)C * 8, &d_lu));
-        BA_TRY(launch_propose(ctx, C, np, (const double *)d_q0, (const double *)d_de,
-                              (const double *)d_sc, (const double *)d_lo, (const double *)d_up, qprop,
-                              inb));
+        BA_TRY(st.in(delta, (size_t)C * np, &d_de));
+        BA_TRY(st.in(log_u, (size_t)C, &d_lu));
+        BA_TRY(launch_propose(ctx, C, np, d_q0, d_de, d_sc, d_lo, d_up, qprop, inb));
     }
     // the `like` sum rides in the accept kernel (one launch fewer) while the row fits its LDS stage
     LikeTail tail;
@@ -1377,10 +1296,9 @@ static int astep_impl(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0,
     // never read (k_accept), so the stacking kernel may skip them (BEATAMD_SKIP_PARKED=0: evaluate every chain)
     const int32_t *active = GfKnobs::get(gf_knobs(ctx).skip_parked, 1) != 0 ? inb : nullptr;
     BA_TRY(ffi_logp_device(ctx, *m, C, qprop, lprop, fold ? &tail : nullptr, active));
-    BA_TRY(launch_accept(ctx, C, np, nllk, (double *)d_q0, (double *)d_l0, qprop, lprop, inb,
-                         (const double *)d_lu, beta, (const double *)d_be, (int32_t *)d_acc,
+    BA_TRY(launch_accept(ctx, C, np, nllk, d_q0, d_l0, qprop, lprop, inb, d_lu, beta, d_be, d_acc,
                          fold ? &tail.grp : nullptr, tail.chain_bad, acc_sum, n_acc, advance));
-    return finish_out(ctx, recs, 3);
+    return st.finish();
 }
 
 int beatamd_ffi_astep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0, double *L0,
@@ -1428,14 +1346,14 @@ int beatamd_autocovariance_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const 
     ENTER(ctx);
     BA_CHECK(data && out && nd >= 0 && n >= 0, BEATAMD_EINVAL, "autocovariance: bad argument");
     if (nd == 0 || n == 0) return BEATAMD_OK;
-    const void *d_d, *d_m;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, data, (size_t)nd * n * 8, &d_d));
-    BA_TRY(stage_in(ctx, SL_IN1, mean, (size_t)nd * 8, &d_m));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)nd * n * 8, &d_o, &rec));
-    BA_TRY(launch_autocovariance(ctx, nd, n, (const double *)d_d, (const double *)d_m, (double *)d_o));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_d, *d_m;
+    double *d_o;
+    BA_TRY(st.in(data, (size_t)nd * n, &d_d));
+    BA_TRY(st.in(mean, (size_t)nd, &d_m));
+    BA_TRY(st.out(out, (size_t)nd * n, &d_o));
+    BA_TRY(launch_autocovariance(ctx, nd, n, d_d, d_m, d_o));
+    return st.finish();
 }
 
 int beatamd_scaled_toeplitz_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *coeffs,
@@ -1444,14 +1362,14 @@ int beatamd_scaled_toeplitz_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const
     ENTER(ctx);
     BA_CHECK(coeffs && stds && out && nd >= 0 && n >= 0, BEATAMD_EINVAL, "scaled_toeplitz: bad argument");
     if (nd == 0 || n == 0) return BEATAMD_OK;
-    const void *d_c, *d_s;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, coeffs, (size_t)nd * n * 8, &d_c));
-    BA_TRY(stage_in(ctx, SL_IN1, stds, (size_t)nd * n * 8, &d_s));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)nd * n * n * 8, &d_o, &rec));
-    BA_TRY(launch_scaled_toeplitz(ctx, nd, n, (const double *)d_c, (const double *)d_s, (double *)d_o));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_c, *d_s;
+    double *d_o;
+    BA_TRY(st.in(coeffs, (size_t)nd * n, &d_c));
+    BA_TRY(st.in(stds, (size_t)nd * n, &d_s));
+    BA_TRY(st.out(out, (size_t)nd * n * n, &d_o));
+    BA_TRY(launch_scaled_toeplitz(ctx, nd, n, d_c, d_s, d_o));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ introspection
@@ -1547,17 +1465,17 @@ int beatamd_smc_calc_beta(beatamd_ctx *ctx, int64_t C, const double *likelihoods
     ENTER(ctx);
     BA_CHECK(likelihoods && beta_new && weights && C > 0 && stride > 0, BEATAMD_EINVAL,
              "smc_calc_beta: bad argument");
-    const void *d_l;
-    void *d_w, *p;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, likelihoods, (size_t)((C - 1) * stride + 1) * 8, &d_l));
-    BA_TRY(stage_out(ctx, SL_OUT0, weights, (size_t)C * 8, &d_w, &rec));
+    Staging st(ctx);
+    const double *d_l;
+    double *d_w;
+    void *p;
+    BA_TRY(st.in(likelihoods, (size_t)((C - 1) * stride + 1), &d_l));
+    BA_TRY(st.out(weights, (size_t)C, &d_w));
     BA_TRY(ctx->get_scratch(SL_STAGE2, 64, &p));
-    BA_TRY(launch_smc_calc_beta(ctx, C, (const double *)d_l, stride, beta, coef_variation, 0, 0.0,
-                                (double *)p, (double *)d_w));
+    BA_TRY(launch_smc_calc_beta(ctx, C, d_l, stride, beta, coef_variation, 0, 0.0, (double *)p, d_w));
     double out[2];
     BA_HIP(hipMemcpyAsync(out, p, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
-    BA_TRY(finish_out(ctx, &rec, 1));
+    BA_TRY(st.finish());
     BA_HIP(hipStreamSynchronize(ctx->stream));
     *beta_new = out[0];
     return BEATAMD_OK;
@@ -1568,15 +1486,15 @@ int beatamd_smc_stage_weights(beatamd_ctx *ctx, int64_t C, const double *likelih
 {
     ENTER(ctx);
     BA_CHECK(likelihoods && weights && C > 0 && stride > 0, BEATAMD_EINVAL, "smc_stage_weights: bad argument");
-    const void *d_l;
-    void *d_w, *p;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, likelihoods, (size_t)((C - 1) * stride + 1) * 8, &d_l));
-    BA_TRY(stage_out(ctx, SL_OUT0, weights, (size_t)C * 8, &d_w, &rec));
+    Staging st(ctx);
+    const double *d_l;
+    double *d_w;
+    void *p;
+    BA_TRY(st.in(likelihoods, (size_t)((C - 1) * stride + 1), &d_l));
+    BA_TRY(st.out(weights, (size_t)C, &d_w));
     BA_TRY(ctx->get_scratch(SL_STAGE2, 64, &p));
-    BA_TRY(launch_smc_calc_beta(ctx, C, (const double *)d_l, stride, 0.0, 0.0, 1, dbeta, (double *)p,
-                                (double *)d_w));
-    return finish_out(ctx, &rec, 1);
+    BA_TRY(launch_smc_calc_beta(ctx, C, d_l, stride, 0.0, 0.0, 1, dbeta, (double *)p, d_w));
+    return st.finish();
 }
 
 int beatamd_smc_resample(beatamd_ctx *ctx, int64_t C, const double *weights, double aux,
@@ -1585,14 +1503,15 @@ int beatamd_smc_resample(beatamd_ctx *ctx, int64_t C, const double *weights, dou
     ENTER(ctx);
     BA_CHECK(weights && indexes && C > 0, BEATAMD_EINVAL, "smc_resample: bad argument");
     BA_CHECK(C < (int64_t)0x7fffffff, BEATAMD_EINVAL, "smc_resample: too many chains");
-    const void *d_w;
-    void *d_i, *p;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, weights, (size_t)C * 8, &d_w));
-    BA_TRY(stage_out(ctx, SL_OUT0, indexes, (size_t)C * 4, &d_i, &rec));
+    Staging st(ctx);
+    const double *d_w;
+    int32_t *d_i;
+    void *p;
+    BA_TRY(st.in(weights, (size_t)C, &d_w));
+    BA_TRY(st.out(indexes, (size_t)C, &d_i));
     BA_TRY(ctx->get_scratch(SL_CUM, (size_t)C * 8, &p));
-    BA_TRY(launch_smc_resample(ctx, C, (const double *)d_w, aux, (double *)p, (int32_t *)d_i));
-    return finish_out(ctx, &rec, 1);
+    BA_TRY(launch_smc_resample(ctx, C, d_w, aux, (double *)p, d_i));
+    return st.finish();
 }
 
 int beatamd_smc_population_factor(beatamd_ctx *ctx, int64_t C, int64_t nparams,
@@ -1601,15 +1520,14 @@ int beatamd_smc_population_factor(beatamd_ctx *ctx, int64_t C, int64_t nparams,
     ENTER(ctx);
     BA_CHECK(population && weights && factor && C > 0 && nparams > 0, BEATAMD_EINVAL,
              "smc_population_factor: bad argument");
-    const void *d_x, *d_w;
-    void *d_f;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, population, (size_t)C * nparams * 8, &d_x));
-    BA_TRY(stage_in(ctx, SL_IN1, weights, (size_t)C * 8, &d_w));
-    BA_TRY(stage_out(ctx, SL_OUT0, factor, (size_t)C * nparams * 8, &d_f, &rec));
-    BA_TRY(launch_pop_factor(ctx, C, nparams, (const double *)d_x, nparams, (const double *)d_w,
-                             (double *)d_f));
-    return finish_out(ctx, &rec, 1);
+    Staging st(ctx);
+    const double *d_x, *d_w;
+    double *d_f;
+    BA_TRY(st.in(population, (size_t)C * nparams, &d_x));
+    BA_TRY(st.in(weights, (size_t)C, &d_w));
+    BA_TRY(st.out(factor, (size_t)C * nparams, &d_f));
+    BA_TRY(launch_pop_factor(ctx, C, nparams, d_x, nparams, d_w, d_f));
+    return st.finish();
 }
 
 int beatamd_proposal_draw(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t nparams,
@@ -1621,15 +1539,14 @@ int beatamd_proposal_draw(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t nparam
              BEATAMD_EINVAL, "proposal_draw: bad argument");
     BA_CHECK(df <= 64, BEATAMD_EINVAL, "proposal_draw: at most 64 degrees of freedom");
     if (C == 0) return BEATAMD_OK;
-    const void *d_f;
-    void *d_d, *d_u = nullptr, *p;
-    Arg recs[2];
-    int nrec = 1;
-    BA_TRY(stage_in(ctx, SL_IN0, factor, (size_t)K * nparams * 8, &d_f));
-    BA_TRY(stage_out(ctx, SL_OUT0, delta, (size_t)C * nparams * 8, &d_d, &recs[0]));
+    Staging st(ctx);
+    const double *d_f;
+    double *d_d, *d_u = nullptr;
+    void *p;
+    BA_TRY(st.in(factor, (size_t)K * nparams, &d_f));
+    BA_TRY(st.out(delta, (size_t)C * nparams, &d_d));
     if (log_u) {
-        BA_TRY(stage_out(ctx, SL_OUT1, log_u, (size_t)C * 8, &d_u, &recs[1]));
-        nrec = 2;
+        BA_TRY(st.out(log_u, (size_t)C, &d_u));
     }
     BA_TRY(ctx->get_scratch(SL_Z, (size_t)C * K * 8, &p));
     double *z = (double *)p;
@@ -1640,17 +1557,17 @@ int beatamd_proposal_draw(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t nparam
     }
     BA_TRY(launch_philox_normal(ctx, z, C, K, seed, step, (uint64_t)first_chain));
     if (d_u || rs)
-        BA_TRY(launch_philox_chain(ctx, C, seed, step, (uint64_t)first_chain, df, (double *)d_u, rs));
+        BA_TRY(launch_philox_chain(ctx, C, seed, step, (uint64_t)first_chain, df, d_u, rs));
     GemmCall g;
     g.A = z; g.lda = K;
-    g.B = (const double *)d_f; g.ldb = nparams; g.b_kn = 1;
-    g.O = (double *)d_d; g.ldo = nparams;
+    g.B = d_f; g.ldb = nparams; g.b_kn = 1;
+    g.O = d_d; g.ldo = nparams;
     g.M = C; g.N = nparams; g.K = K;
     g.row_scale = rs;
     g.timer = "proposal";
     BA_TRY(launch_gemm_f64(ctx, g));
     BA_TRY(launch_step_advance(ctx));
-    return finish_out(ctx, recs, nrec);
+    return st.finish();
 }
 
 int beatamd_proposal_draw_univariate(beatamd_ctx *ctx, int64_t C, int64_t nparams, int32_t kind,
@@ -1663,21 +1580,18 @@ int beatamd_proposal_draw_univariate(beatamd_ctx *ctx, int64_t C, int64_t nparam
     BA_CHECK(kind >= BEATAMD_PROPOSAL_NORMAL && kind <= BEATAMD_PROPOSAL_POISSON, BEATAMD_EINVAL,
              "proposal_draw_univariate: kind must be Normal (0), Cauchy (1), Laplace (2) or Poisson (3)");
     if (C == 0) return BEATAMD_OK;
-    const void *d_s;
-    void *d_d, *d_u = nullptr;
-    Arg recs[2];
-    int nrec = 1;
-    BA_TRY(stage_in(ctx, SL_IN0, scale, (size_t)nparams * 8, &d_s));
-    BA_TRY(stage_out(ctx, SL_OUT0, delta, (size_t)C * nparams * 8, &d_d, &recs[0]));
+    Staging st(ctx);
+    const double *d_s;
+    double *d_d, *d_u = nullptr;
+    BA_TRY(st.in(scale, (size_t)nparams, &d_s));
+    BA_TRY(st.out(delta, (size_t)C * nparams, &d_d));
     if (log_u) {
-        BA_TRY(stage_out(ctx, SL_OUT1, log_u, (size_t)C * 8, &d_u, &recs[1]));
-        nrec = 2;
+        BA_TRY(st.out(log_u, (size_t)C, &d_u));
     }
-    BA_TRY(launch_philox_univariate(ctx, (double *)d_d, C, nparams, kind, (const double *)d_s, seed, step,
-                                    (uint64_t)first_chain));
-    if (d_u) BA_TRY(launch_philox_chain(ctx, C, seed, step, (uint64_t)first_chain, 0, (double *)d_u, nullptr));
+    BA_TRY(launch_philox_univariate(ctx, d_d, C, nparams, kind, d_s, seed, step, (uint64_t)first_chain));
+    if (d_u) BA_TRY(launch_philox_chain(ctx, C, seed, step, (uint64_t)first_chain, 0, d_u, nullptr));
     BA_TRY(launch_step_advance(ctx));
-    return finish_out(ctx, recs, nrec);
+    return st.finish();
 }
 
 int beatamd_gather_rows(beatamd_ctx *ctx, int64_t nout, int64_t ncols, const double *src,
@@ -1687,16 +1601,16 @@ int beatamd_gather_rows(beatamd_ctx *ctx, int64_t nout, int64_t ncols, const dou
     BA_CHECK(src && indexes && out && nout >= 0 && ncols > 0 && nrows_src > 0, BEATAMD_EINVAL,
              "gather_rows: bad argument");
     if (nout == 0) return BEATAMD_OK;
-    const void *d_s, *d_i;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, src, (size_t)nrows_src * ncols * 8, &d_s));
-    BA_TRY(stage_in(ctx, SL_IN1, indexes, (size_t)nout * 4, &d_i));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)nout * ncols * 8, &d_o, &rec));
+    Staging st(ctx);
+    const double *d_s;
+    const int32_t *d_i;
+    double *d_o;
+    BA_TRY(st.in(src, (size_t)nrows_src * ncols, &d_s));
+    BA_TRY(st.in(indexes, (size_t)nout, &d_i));
+    BA_TRY(st.out(out, (size_t)nout * ncols, &d_o));
     BA_CHECK(d_o != d_s, BEATAMD_EINVAL, "gather_rows: out must not alias src");
-    BA_TRY(launch_gather_rows(ctx, nout, ncols, (const double *)d_s, ncols, nrows_src,
-                              (const int32_t *)d_i, (double *)d_o, ncols));
-    return finish_out(ctx, &rec, 1);
+    BA_TRY(launch_gather_rows(ctx, nout, ncols, d_s, ncols, nrows_src, d_i, d_o, ncols));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ a Metropolis step in pieces (target-sharded models)
@@ -1720,9 +1634,10 @@ int beatamd_like_assemble(beatamd_ctx *ctx, int64_t C, int64_t nllk, int64_t nsr
     for (int64_t r = 0; r < nsrc; r++)
         BA_CHECK(dst_col[r] >= -1 && dst_col[r] < nllk - 1, BEATAMD_EINVAL, "like_assemble: column %d of row %lld", dst_col[r], (long long)r);
     BA_CHECK(rest_dst0 >= 0 && rest_dst0 + n_rest <= nllk - 1, BEATAMD_EINVAL, "like_assemble: replicated columns outside the vector");
-    const void *d_dc;
-    BA_TRY(stage_in(ctx, SL_IN0, dst_col, (size_t)nsrc * 4, &d_dc));
-    BA_TRY(launch_like_assemble(ctx, C, nllk, nsrc, gathered, (const int32_t *)d_dc, local_ll, local_ld, local_col0, n_rest,
+    Staging st(ctx);
+    const int32_t *d_dc;
+    BA_TRY(st.in(dst_col, (size_t)nsrc, &d_dc));
+    BA_TRY(launch_like_assemble(ctx, C, nllk, nsrc, gathered, d_dc, local_ll, local_ld, local_col0, n_rest,
                                 rest_dst0, grp, LL, nullptr));
     return BEATAMD_OK;
 }
@@ -1760,12 +1675,13 @@ int beatamd_metropolis_tune(beatamd_ctx *ctx, int64_t C, double *scaling, int32_
     BA_CHECK(scaling && accepted && C >= 0 && tune_interval > 0, BEATAMD_EINVAL,
              "metropolis_tune: bad argument");
     if (C == 0) return BEATAMD_OK;
-    void *d_s, *d_a;
-    Arg recs[2];
-    BA_TRY(stage_out(ctx, SL_OUT0, scaling, (size_t)C * 8, &d_s, &recs[0], true));
-    BA_TRY(stage_out(ctx, SL_OUT1, accepted, (size_t)C * 4, &d_a, &recs[1], true));
-    BA_TRY(launch_tune_scaling(ctx, C, (double *)d_s, (int32_t *)d_a, (double)tune_interval));
-    return finish_out(ctx, recs, 2);
+    Staging st(ctx);
+    double *d_s;
+    int32_t *d_a;
+    BA_TRY(st.out(scaling, (size_t)C, &d_s, true));
+    BA_TRY(st.out(accepted, (size_t)C, &d_a, true));
+    BA_TRY(launch_tune_scaling(ctx, C, d_s, d_a, (double)tune_interval));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------ whitening operator
@@ -1775,15 +1691,15 @@ int beatamd_chol_inverse_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const do
     ENTER(ctx);
     BA_CHECK(covs && W && log_pdet && nd >= 0 && n > 0, BEATAMD_EINVAL, "chol_inverse_batch: bad argument");
     if (nd == 0) return BEATAMD_OK;
-    const void *d_c;
-    void *d_w, *d_l;
-    Arg recs[2];
-    BA_TRY(stage_in(ctx, SL_IN0, covs, (size_t)nd * n * n * 8, &d_c));
-    BA_TRY(stage_out(ctx, SL_OUT0, W, (size_t)nd * n * n * 8, &d_w, &recs[0]));
-    BA_TRY(stage_out(ctx, SL_OUT1, log_pdet, (size_t)nd * 8, &d_l, &recs[1]));
-    BA_TRY(launch_chol_inverse(ctx, nd, n, (const double *)d_c, (double *)d_w, (double *)d_l));
+    Staging st(ctx);
+    const double *d_c;
+    double *d_w, *d_l;
+    BA_TRY(st.in(covs, (size_t)nd * n * n, &d_c));
+    BA_TRY(st.out(W, (size_t)nd * n * n, &d_w));
+    BA_TRY(st.out(log_pdet, (size_t)nd, &d_l));
+    BA_TRY(launch_chol_inverse(ctx, nd, n, d_c, d_w, d_l));
     BA_TRY(ctx->check_status());
-    return finish_out(ctx, recs, 2);
+    return st.finish();
 }
 
 int beatamd_chol_inverse_batch_flags(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *covs, double *W,
@@ -1793,29 +1709,30 @@ int beatamd_chol_inverse_batch_flags(beatamd_ctx *ctx, int64_t nd, int64_t n, co
     BA_CHECK(covs && W && log_pdet && not_psd && nd >= 0 && n > 0, BEATAMD_EINVAL,
              "chol_inverse_batch_flags: bad argument");
     if (nd == 0) return BEATAMD_OK;
-    const void *d_c;
-    void *d_w, *d_l, *d_f;
-    Arg recs[3];
-    BA_TRY(stage_in(ctx, SL_IN0, covs, (size_t)nd * n * n * 8, &d_c));
-    BA_TRY(stage_out(ctx, SL_OUT0, W, (size_t)nd * n * n * 8, &d_w, &recs[0]));
-    BA_TRY(stage_out(ctx, SL_OUT1, log_pdet, (size_t)nd * 8, &d_l, &recs[1]));
-    BA_TRY(stage_out(ctx, SL_OUT2, not_psd, (size_t)nd * 4, &d_f, &recs[2]));
-    BA_TRY(launch_chol_inverse(ctx, nd, n, (const double *)d_c, (double *)d_w, (double *)d_l, (int32_t *)d_f));
-    return finish_out(ctx, recs, 3);
+    Staging st(ctx);
+    const double *d_c;
+    double *d_w, *d_l;
+    int32_t *d_f;
+    BA_TRY(st.in(covs, (size_t)nd * n * n, &d_c));
+    BA_TRY(st.out(W, (size_t)nd * n * n, &d_w));
+    BA_TRY(st.out(log_pdet, (size_t)nd, &d_l));
+    BA_TRY(st.out(not_psd, (size_t)nd, &d_f));
+    BA_TRY(launch_chol_inverse(ctx, nd, n, d_c, d_w, d_l, d_f));
+    return st.finish();
 }
 
 int beatamd_factor_compact(beatamd_ctx *ctx, int64_t K, int64_t n, const double *factor, double *R)
 {
     ENTER(ctx);
     BA_CHECK(factor && R && K > 0 && n > 0, BEATAMD_EINVAL, "factor_compact: bad argument");
-    const void *d_f;
-    void *d_r;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, factor, (size_t)K * n * 8, &d_f));
-    BA_TRY(stage_out(ctx, SL_OUT0, R, (size_t)n * n * 8, &d_r, &rec));
-    BA_TRY(launch_gram_cholesky(ctx, K, n, (const double *)d_f, (double *)d_r));
+    Staging st(ctx);
+    const double *d_f;
+    double *d_r;
+    BA_TRY(st.in(factor, (size_t)K * n, &d_f));
+    BA_TRY(st.out(R, (size_t)n * n, &d_r));
+    BA_TRY(launch_gram_cholesky(ctx, K, n, d_f, d_r));
     BA_TRY(ctx->check_status());
-    return finish_out(ctx, &rec, 1);
+    return st.finish();
 }
 
 int beatamd_whitening_ratio_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *W_new,
@@ -1824,15 +1741,15 @@ int beatamd_whitening_ratio_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const
     ENTER(ctx);
     BA_CHECK(W_new && W_old && M && nd >= 0 && n > 0, BEATAMD_EINVAL, "whitening_ratio_batch: bad argument");
     if (nd == 0) return BEATAMD_OK;
-    const void *d_n, *d_o;
-    void *d_m;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, W_new, (size_t)nd * n * n * 8, &d_n));
-    BA_TRY(stage_in(ctx, SL_IN1, W_old, (size_t)nd * n * n * 8, &d_o));
-    BA_TRY(stage_out(ctx, SL_OUT0, M, (size_t)nd * n * n * 8, &d_m, &rec));
-    BA_TRY(launch_triu_ratio(ctx, nd, n, (const double *)d_n, (const double *)d_o, (double *)d_m));
+    Staging st(ctx);
+    const double *d_n, *d_o;
+    double *d_m;
+    BA_TRY(st.in(W_new, (size_t)nd * n * n, &d_n));
+    BA_TRY(st.in(W_old, (size_t)nd * n * n, &d_o));
+    BA_TRY(st.out(M, (size_t)nd * n * n, &d_m));
+    BA_TRY(launch_triu_ratio(ctx, nd, n, d_n, d_o, d_m));
     BA_TRY(ctx->check_status());
-    return finish_out(ctx, &rec, 1);
+    return st.finish();
 }
 
 int beatamd_unwhiten_traces(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *W, double *X)
@@ -1840,14 +1757,14 @@ int beatamd_unwhiten_traces(beatamd_ctx *ctx, int64_t nd, int64_t n, const doubl
     ENTER(ctx);
     BA_CHECK(W && X && nd >= 0 && n > 0, BEATAMD_EINVAL, "unwhiten_traces: bad argument");
     if (nd == 0) return BEATAMD_OK;
-    const void *d_w;
-    void *d_o;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, W, (size_t)nd * n * n * 8, &d_w));
-    BA_TRY(stage_out(ctx, SL_OUT0, X, (size_t)nd * n * 8, &d_o, &rec, true));   // in place: host traces go up first
-    BA_TRY(launch_triu_solve_vec(ctx, nd, n, (const double *)d_w, (double *)d_o));
+    Staging st(ctx);
+    const double *d_w;
+    double *d_o;
+    BA_TRY(st.in(W, (size_t)nd * n * n, &d_w));
+    BA_TRY(st.out(X, (size_t)nd * n, &d_o, true));   // in place: host traces go up first
+    BA_TRY(launch_triu_solve_vec(ctx, nd, n, d_w, d_o));
     BA_TRY(ctx->check_status());
-    return finish_out(ctx, &rec, 1);
+    return st.finish();
 }
 
 int beatamd_ffi_model_update_data(beatamd_ctx *ctx, int32_t model_id, int32_t wavemap_index, const double *data)
@@ -1858,7 +1775,7 @@ int beatamd_ffi_model_update_data(beatamd_ctx *ctx, int32_t model_id, int32_t wa
     BA_CHECK(data && wavemap_index >= 0 && (size_t)wavemap_index < m->wavemaps.size(), BEATAMD_EINVAL,
              "model_update_data: bad argument");
     Wavemap &w = m->wavemaps[wavemap_index];
-    BA_HIP(hipMemcpyAsync(w.data, data, (size_t)w.T * w.N * 8, hipMemcpyDefault, ctx->stream));
+    BA_HIP(hipMemcpyAsync(w.data.get(), data, (size_t)w.T * w.N * 8, hipMemcpyDefault, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
     return BEATAMD_OK;
 }
@@ -1871,11 +1788,12 @@ int beatamd_whiten_rows(beatamd_ctx *ctx, double *rows, int64_t nrows, int64_t N
     BA_CHECK(is_device_ptr(rows), BEATAMD_EINVAL, "whiten_rows: rows must live in HBM");
     if (nrows == 0) return BEATAMD_OK;
     drop_f32_overlapping(ctx, rows, (size_t)nrows * N * 8);
-    const void *d_w;
+    Staging st(ctx);
+    const double *d_w;
     void *p;
-    BA_TRY(stage_in(ctx, SL_IN0, W, (size_t)N * N * 8, &d_w));
+    BA_TRY(st.in(W, (size_t)N * N, &d_w));
     BA_TRY(ctx->get_scratch(SL_MISC, 64, &p));
-    BA_TRY(launch_check_upper_tri(ctx, (const double *)d_w, 1, N, (int *)p));
+    BA_TRY(launch_check_upper_tri(ctx, d_w, 1, N, (int *)p));
     int upper = 0;
     BA_HIP(hipMemcpyAsync(&upper, p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
@@ -1888,7 +1806,7 @@ int beatamd_whiten_rows(beatamd_ctx *ctx, double *rows, int64_t nrows, int64_t N
         const int64_t nr = std::min(chunk, nrows - r0);
         GemmCall g;
         g.A = rows + r0 * N; g.lda = N;
-        g.B = (const double *)d_w; g.ldb = N; g.b_kn = 0; g.b_upper = upper;
+        g.B = d_w; g.ldb = N; g.b_kn = 0; g.b_upper = upper;
         g.O = tmp; g.ldo = N;
         g.M = nr; g.N = N; g.K = N;
         g.timer = "whiten";
@@ -1913,25 +1831,26 @@ int beatamd_whiten_rows_batch(beatamd_ctx *ctx, double *rows, int64_t nbatch, in
     BA_CHECK(nbatch <= 65535, BEATAMD_EINVAL, "whiten_rows_batch: at most 65535 datasets per call");
     if (nrows == 0 || nbatch == 0) return BEATAMD_OK;
     drop_f32_overlapping(ctx, rows, (size_t)nbatch * nrows * N * 8);
-    const void *d_w;
+    Staging st(ctx);
+    const double *d_w;
     void *p;
-    BA_TRY(stage_in(ctx, SL_IN1, W, (size_t)nbatch * N * N * 8, &d_w));
+    BA_TRY(st.in(W, (size_t)nbatch * N * N, &d_w));
     BA_TRY(ctx->get_scratch(SL_MISC, 64, &p));
-    BA_TRY(launch_check_upper_tri(ctx, (const double *)d_w, nbatch, N, (int *)p));
+    BA_TRY(launch_check_upper_tri(ctx, d_w, nbatch, N, (int *)p));
     int upper = 0;
     BA_HIP(hipMemcpyAsync(&upper, p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
     if (!upper) {
         // general operators (a QR-fallback chol_inverse, heart.py:234-237): dataset by dataset through a buffer
         for (int64_t b = 0; b < nbatch; b++)
-            BA_TRY(beatamd_whiten_rows(ctx, rows + b * nrows * N, nrows, N, (const double *)d_w + b * N * N));
+            BA_TRY(beatamd_whiten_rows(ctx, rows + b * nrows * N, nrows, N, d_w + b * N * N));
         return BEATAMD_OK;
     }
     const int ncb = (int)((N + 127) / 128);
     for (int cb = 0; cb < ncb; cb++) {
         GemmCall g;
         g.A = rows; g.lda = N; g.sA = nrows * N;
-        g.B = (const double *)d_w; g.ldb = N; g.sB = N * N; g.b_kn = 0; g.b_upper = 1;
+        g.B = d_w; g.ldb = N; g.sB = N * N; g.b_kn = 0; g.b_upper = 1;
         g.O = rows; g.ldo = N; g.sO = nrows * N;
         g.M = nrows; g.N = N; g.K = N;
         g.nbatch = (int)nbatch;
@@ -1958,18 +1877,19 @@ int beatamd_halfspace_displacements_batch(beatamd_ctx *ctx, int64_t C, int32_t n
     if (C == 0) return BEATAMD_OK;
     std::vector<int64_t> poff((size_t)nsrc * 10);
     for (size_t i = 0; i < poff.size(); i++) poff[i] = (int64_t)i;
-    const void *d_k, *d_o, *d_p, *d_e, *d_n;
-    void *d_out;
-    Arg rec;
-    BA_TRY(stage_in(ctx, SL_IN0, kind, (size_t)nsrc * 4, &d_k));
-    BA_TRY(stage_in(ctx, SL_IN1, poff.data(), poff.size() * 8, &d_o));
-    BA_TRY(stage_in(ctx, SL_IN2, params, (size_t)C * nsrc * 10 * 8, &d_p));
-    BA_TRY(stage_in(ctx, SL_IN3, east, (size_t)nobs * 8, &d_e));
-    BA_TRY(stage_in(ctx, SL_IN4, north, (size_t)nobs * 8, &d_n));
-    BA_TRY(stage_out(ctx, SL_OUT0, out, (size_t)C * nsrc * nobs * 3 * 8, &d_out, &rec));
-    BA_TRY(launch_geom_disp(ctx, nsrc, (const int32_t *)d_k, (const int64_t *)d_o, (const double *)d_p,
-                            C, nobs, (const double *)d_e, (const double *)d_n, nu, (double *)d_out));
-    BA_TRY(finish_out(ctx, &rec, 1));
+    Staging st(ctx);
+    const double *d_p, *d_e, *d_n;
+    const int32_t *d_k;
+    const int64_t *d_o;
+    double *d_out;
+    BA_TRY(st.in(kind, (size_t)nsrc, &d_k));
+    BA_TRY(st.in(poff.data(), poff.size(), &d_o));
+    BA_TRY(st.in(params, (size_t)C * nsrc * 10, &d_p));
+    BA_TRY(st.in(east, (size_t)nobs, &d_e));
+    BA_TRY(st.in(north, (size_t)nobs, &d_n));
+    BA_TRY(st.out(out, (size_t)C * nsrc * nobs * 3, &d_out));
+    BA_TRY(launch_geom_disp(ctx, nsrc, d_k, d_o, d_p, C, nobs, d_e, d_n, nu, d_out));
+    BA_TRY(st.finish());
     BA_HIP(hipStreamSynchronize(ctx->stream));   // `poff` is a stack temporary
     return BEATAMD_OK;
 }

@@ -61,16 +61,20 @@ bool is_device_ptr(const void *p)
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
-int stage_in(beatamd_ctx *ctx, int slot, const void *p, size_t bytes, const void **dev)
+int dev_copy_sync(beatamd_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
-    if (bytes == 0 || p == nullptr) {
-        *dev = p;
-        return BEATAMD_OK;
-    }
-    if (is_device_ptr(p)) {
-        *dev = p;
-        return BEATAMD_OK;
-    }
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    BA_CHECK(e == hipSuccess, BEATAMD_EHIP, "hipMemcpy(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+    return BEATAMD_OK;
+}
+
+int Staging::in_bytes(const void *p, size_t bytes, const void **dev)
+{
+    BA_CHECK(nin < SL_NIN, BEATAMD_EINVAL, "internal: more than %d staged inputs in one call", SL_NIN);
+    const int slot = SL_IN0 + nin++;
+    *dev = p;
+    if (bytes == 0 || p == nullptr || is_device_ptr(p)) return BEATAMD_OK;
     void *d = nullptr;
     BA_TRY(ctx->get_scratch(slot, bytes, &d));
     BA_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -78,39 +82,25 @@ int stage_in(beatamd_ctx *ctx, int slot, const void *p, size_t bytes, const void
     return BEATAMD_OK;
 }
 
-int stage_out(beatamd_ctx *ctx, int slot, void *p, size_t bytes, void **dev, Arg *rec,
-              bool preload)
+int Staging::out_bytes(void *p, size_t bytes, void **dev, bool preload)
 {
-    rec->ctx = ctx;
-    rec->bytes = bytes;
-    rec->out = true;
-    if (bytes == 0 || p == nullptr || is_device_ptr(p)) {
-        rec->host = nullptr;
-        rec->dev = p;
-        *dev = p;
-        return BEATAMD_OK;
-    }
+    BA_CHECK(nout < SL_NOUT, BEATAMD_EINVAL, "internal: more than %d staged outputs in one call", SL_NOUT);
+    const int slot = SL_OUT0 + nout++;
+    *dev = p;
+    if (bytes == 0 || p == nullptr || is_device_ptr(p)) return BEATAMD_OK;
     void *d = nullptr;
     BA_TRY(ctx->get_scratch(slot, bytes, &d));
     if (preload) BA_HIP(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-    rec->host = p;
-    rec->dev = d;
+    back[nback++] = {p, d, bytes};
     *dev = d;
     return BEATAMD_OK;
 }
 
-int finish_out(beatamd_ctx *ctx, Arg *recs, int n)
+int Staging::finish()
 {
-    bool any = false;
-    for (int i = 0; i < n; i++) {
-        if (recs[i].host) {
-            BA_HIP(hipMemcpyAsync(recs[i].host, recs[i].dev, recs[i].bytes, hipMemcpyDeviceToHost,
-                                  ctx->stream));
-            any = true;
-        }
-    }
-    if (any) return ctx->check_status();  // synchronises
-    return BEATAMD_OK;
+    for (int i = 0; i < nback; i++)
+        BA_HIP(hipMemcpyAsync(back[i].host, back[i].dev, back[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return nback ? ctx->check_status() : BEATAMD_OK;   // (synchronises)
 }
 
 int64_t FfiModel::nllk() const
@@ -268,49 +258,13 @@ int beatamd_ctx_destroy(beatamd_ctx *c)
     if (!c) return BEATAMD_OK;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (auto &l : c->seislibs)
-        if (l && l->owned && l->g) (void)hipFree(l->g);
-    for (auto &l : c->seislibs)
-        if (l && l->g32) (void)hipFree(l->g32);
-    for (auto &l : c->geolibs)
-        if (l && l->g) (void)hipFree(l->g);
-    for (auto &w : c->wsets)
-        if (w) {
-            if (w->w) (void)hipFree(w->w);
-            if (w->slog) (void)hipFree(w->slog);
-        }
-    for (auto &l : c->laps)
-        if (l && l->L) (void)hipFree(l->L);
-    for (auto &m : c->models)
-        if (m) {
-            for (auto &w : m->wavemaps) {
-                if (w.data) (void)hipFree(w.data);
-                if (w.hp_off) (void)hipFree(w.hp_off);
-                if (w.shift_off) (void)hipFree(w.shift_off);
-                if (w.tslot) (void)hipFree(w.tslot);
-                if (w.slot_shift_off) (void)hipFree(w.slot_shift_off);
-            }
-            if (m->geo.data) (void)hipFree(m->geo.data);
-            if (m->geo.odws) (void)hipFree(m->geo.odws);
-            if (m->geo.hp_off) (void)hipFree(m->geo.hp_off);
-            if (m->geom.kind) (void)hipFree(m->geom.kind);
-            if (m->geom.poff) (void)hipFree(m->geom.poff);
-            if (m->geom.pfix) (void)hipFree(m->geom.pfix);
-            if (m->geom.east) (void)hipFree(m->geom.east);
-            if (m->geom.north) (void)hipFree(m->geom.north);
-            if (m->geom.los) (void)hipFree(m->geom.los);
-            if (m->d_ndip) (void)hipFree(m->d_ndip);
-            if (m->d_nstrike) (void)hipFree(m->d_nstrike);
-            if (m->d_patch_off) (void)hipFree(m->d_patch_off);
-            if (m->d_patch_size) (void)hipFree(m->d_patch_size);
-        }
-    for (auto &h : c->hypers)
-        if (h) {
-            if (h->M) (void)hipFree(h->M);
-            if (h->slog) (void)hipFree(h->slog);
-            if (h->kind) (void)hipFree(h->kind);
-            if (h->hp_index) (void)hipFree(h->hp_index);
-        }
+    // the objects free their device arrays (before the stream and the status word go)
+    c->models.clear();
+    c->hypers.clear();
+    c->wsets.clear();
+    c->laps.clear();
+    c->geolibs.clear();
+    c->seislibs.clear();
     for (auto &s : c->scratch) s.release();
     for (auto &kv : c->timers)
         for (auto &pr : kv.second.pending) {

@@ -14,6 +14,8 @@
 
 #include "../../include/beat_amd.h"
 
+struct beatamd_ctx;
+
 namespace beatamd {
 
 void set_error(const char *fmt, ...);
@@ -52,54 +54,117 @@ struct DevBuf {
     void release();
 };
 
+// src -> dst on the context's stream (hipMemcpyDefault: either side may be host or device), synchronised
+int dev_copy_sync(beatamd_ctx *ctx, void *dst, const void *src, size_t bytes);
+
+// One hipMalloc'd array with an owner: freed when the owner goes (object destroyed, context closed, builder left early).
+// Move-only.  Kernels and call structs get the plain pointer (get()).
+template <class T>
+class DevMem {
+    T *p_ = nullptr;
+
+public:
+    DevMem() = default;
+    DevMem(DevMem &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevMem &operator=(DevMem &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevMem() { reset(); }
+    T *get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    // n elements, uninitialised (what was held is freed first); the caller words the error
+    hipError_t try_alloc(size_t n)
+    {
+        reset();
+        const hipError_t e = hipMalloc((void **)&p_, n ? n * sizeof(T) : 8);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            p_ = nullptr;
+        }
+        return e;
+    }
+    int alloc(size_t n)
+    {
+        const hipError_t e = try_alloc(n);
+        BA_CHECK(e == hipSuccess, BEATAMD_ENOMEM, "hipMalloc(%zu bytes) failed: %s", n * sizeof(T), hipGetErrorString(e));
+        return BEATAMD_OK;
+    }
+    // n elements holding a copy of src (host or device memory; nullptr: uninitialised)
+    int alloc_copy(beatamd_ctx *ctx, const T *src, size_t n)
+    {
+        BA_TRY(alloc(n));
+        if (!src || !n) return BEATAMD_OK;
+        const int rc = dev_copy_sync(ctx, p_, src, n * sizeof(T));
+        if (rc != BEATAMD_OK) reset();
+        return rc;
+    }
+};
+
 struct SeisLib {
     int64_t T = 0, P = 0, D = 0, S = 0, N = 0;
     // target count the patch-range rule sees (gf_patch_split): 0 = T; the whole wavemap's T for a rank's block of targets
     int64_t split_T = 0;
     double st_min = 0, st_dt = 1, du_min = 0, du_dt = 1;
     double *g = nullptr;  // HBM, (T,P,D,S,N) C-order, N fastest
-    float *g32 = nullptr; // optional float copy of g (beatamd_seis_gflib_store_f32; g then holds float-representable values)
-    bool owned = false;
+    float *g32 = nullptr; // optional float copy of g (beatamd_seis_gflib_round_to_f32; g then holds float-representable values)
     int64_t elems() const { return T * P * D * S * N; }
+};
+
+// a library as the context keeps it.  SeisLib itself stays a copyable view: the patch-range split stacks through
+// re-shaped copies of it (launch_gfstack_split)
+struct SeisStore : SeisLib {
+    DevMem<double> own;    // behind g; empty while the storage is the caller's (beatamd_seis_gflib_adopt)
+    DevMem<float> own32;   // behind g32
 };
 
 struct GeoLib {
     int64_t P = 0, Nobs = 0;
-    double *g = nullptr;  // (P, Nobs)
+    DevMem<double> g;  // (P, Nobs)
 };
 
 struct WeightSet {
     int kind = BEATAMD_W_SCALAR;
     int64_t nd = 0, M = 0;
-    double *w = nullptr;     // [nd] or [nd,M,M]
-    double *slog = nullptr;  // [nd]
+    DevMem<double> w;     // [nd] or [nd,M,M]
+    DevMem<double> slog;  // [nd]
     int upper_tri = 0;       // dense only: exact zeros below the diagonal in every W
     // dense only: every W is upper-triangular AND banded -- no entry further than `band` columns right of the diagonal
     // exceeds 2^-40 of the largest entry of its matrix (-1: not banded / band > QF_BAND_MAX).  The whitening operator of
     // the reference's "exponential" noise structure (covariance.py:24-51: C_ij = exp(-|i-j| dt / t0), a Markov kernel) is
     // bidiagonal: band = 1.  wb [nd, M, band + 1]: row i = W[i, i .. i+band] (k_quadform_banded)
     int64_t band = -1;
-    double *wb = nullptr;
+    DevMem<double> wb;
     double dropped_rel = 0.0;   // banded: the largest entry beyond the band, relative to the largest of its row (<= 2^-40)
 };
 
 struct Laplacian {
     int64_t P = 0;
-    double *L = nullptr;
+    DevMem<double> L;
     double logdet = 0;
 };
 
 struct Wavemap {
     std::vector<int32_t> libs;
-    double *data = nullptr;  // [T,N]
+    DevMem<double> data;  // [T,N]
     int32_t wset = -1;
-    int64_t *hp_off = nullptr;     // device [T]
-    int64_t *shift_off = nullptr;  // device [T] or nullptr
+    DevMem<int64_t> hp_off;     // device [T]
+    DevMem<int64_t> shift_off;  // device [T] or empty
     // targets that share a station correction (the channels of a station: heart.py:2941-2950 repeats the station
     // indices per channel) have the same start times -> the index tables are built per SLOT = distinct shift variable
     int32_t nslot = 0;             // 0: no shifts, or every target has its own (tables per target)
-    int32_t *tslot = nullptr;      // device [T]: slot of target t
-    int64_t *slot_shift_off = nullptr;   // device [nslot]: the shift variable of the slot
+    DevMem<int32_t> tslot;         // device [T]: slot of target t
+    DevMem<int64_t> slot_shift_off;      // device [nslot]: the shift variable of the slot
     int interp = 0;
     int64_t T = 0, N = 0;
     bool f32 = false;   // read the libraries' float copies where a kernel supports it
@@ -124,24 +189,25 @@ struct GeoCorr {
 
 struct Geodetic {
     std::vector<int32_t> libs;
-    double *data = nullptr, *odws = nullptr;  // [Nobs]
+    DevMem<double> data, odws;  // [Nobs]
     int64_t Nobs = 0;
     std::vector<int64_t> sizes;
     std::vector<int32_t> wsets;
-    int64_t *hp_off = nullptr;  // device [nd]
+    DevMem<int64_t> hp_off;  // device [nd]
     // dataset corrections (hierarchical parameters), in the order they are subtracted
     bool corr_set = false;
-    GeoCorr corr;
-    double *corr_basis = nullptr;    // device, the terms' basis columns concatenated
+    GeoCorr corr;                        // what the kernels get: a view of corr_terms
+    DevMem<GeoCorrTerm> corr_terms;      // device [corr.nterm]
+    DevMem<double> corr_basis;           // device, the terms' basis columns concatenated
 };
 
 // geometry-mode sources of the geodetic composite (analytic half space)
 struct GeomSources {
     int nsrc = 0;
-    int32_t *kind = nullptr;   // device [nsrc]
-    int64_t *poff = nullptr;   // device [nsrc*10]
-    double *pfix = nullptr;    // device [nsrc*10]
-    double *east = nullptr, *north = nullptr, *los = nullptr;  // device [Nobs], [Nobs], [Nobs,3]
+    DevMem<int32_t> kind;   // device [nsrc]
+    DevMem<int64_t> poff;   // device [nsrc*10]
+    DevMem<double> pfix;    // device [nsrc*10]
+    DevMem<double> east, north, los;  // device [Nobs], [Nobs], [Nobs,3]
     int64_t Nobs = 0;
     double nu = 0.25;
 };
@@ -152,8 +218,8 @@ struct FfiModel {
     std::vector<int32_t> ndip, nstrike, patch_off;
     std::vector<double> patch_size;
     int64_t P = 0;
-    int32_t *d_ndip = nullptr, *d_nstrike = nullptr, *d_patch_off = nullptr;
-    double *d_patch_size = nullptr;
+    DevMem<int32_t> d_ndip, d_nstrike, d_patch_off;
+    DevMem<double> d_patch_size;
     std::vector<Wavemap> wavemaps;
     bool has_geo = false;
     Geodetic geo;
@@ -166,8 +232,8 @@ struct FfiModel {
 // the hyper-parameter model (hyper.hip): term k = kind[k] formula on hyper-parameter hp_index[k] of the nh-vector
 struct HyperModel {
     int64_t nterm = 0, nh = 0;
-    double *M = nullptr, *slog = nullptr;          // device [nterm]
-    int32_t *kind = nullptr, *hp_index = nullptr;  // device [nterm]
+    DevMem<double> M, slog;          // device [nterm]
+    DevMem<int32_t> kind, hp_index;  // device [nterm]
     int32_t ngroups = 0, group_end[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // composites inside the term vector (exclusive ends)
 };
 
@@ -205,7 +271,7 @@ struct beatamd_ctx {
     std::vector<hipEvent_t> event_pool;
     int *d_status = nullptr;  // device status word
     std::vector<beatamd::DevBuf> scratch;
-    std::vector<std::unique_ptr<beatamd::SeisLib>> seislibs;
+    std::vector<std::unique_ptr<beatamd::SeisStore>> seislibs;
     std::vector<std::unique_ptr<beatamd::GeoLib>> geolibs;
     std::vector<std::unique_ptr<beatamd::WeightSet>> wsets;
     std::vector<std::unique_ptr<beatamd::Laplacian>> laps;
@@ -252,29 +318,6 @@ bool is_device_ptr(const void *p);
 // the knobs in force for a stacking call (re-read from the environment first in live mode)
 const GfKnobs &gf_knobs(beatamd_ctx *ctx);
 
-// RAII-ish staging of one array argument.  Host pointers are mirrored in a scratch slot.
-struct Arg {
-    beatamd_ctx *ctx;
-    void *host = nullptr;  // non-null => needs copy back (if out) after the launch
-    void *dev = nullptr;
-    size_t bytes = 0;
-    bool out = false;
-};
-
-// in: returns device pointer holding the data (copy if host)
-int stage_in(beatamd_ctx *ctx, int slot, const void *p, size_t bytes, const void **dev);
-// out: returns device pointer to write into; if host, remember for copy_back
-int stage_out(beatamd_ctx *ctx, int slot, void *p, size_t bytes, void **dev, Arg *rec,
-              bool preload = false);
-int finish_out(beatamd_ctx *ctx, Arg *recs, int n);  // D2H copies + sync if any host outs
-
-struct ScopedTimer {
-    beatamd_ctx *c;
-    const char *n;
-    ScopedTimer(beatamd_ctx *ctx, const char *name) : c(ctx), n(name) { c->time_begin(n); }
-    ~ScopedTimer() { c->time_end(n); }
-};
-
 // scratch slot map (one per logical temporary so slots never alias within a call)
 enum Slot : int {
     SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_IN6, SL_IN7,
@@ -284,6 +327,48 @@ enum Slot : int {
     SL_CHAINBAD, SL_Z, SL_ROWSCALE, SL_CUM, SL_STAGE2, SL_WHITEN,
     SL_CHOL_A, SL_CHOL_X, SL_CHOL_D, SL_CHOL_T, SL_CHOL_L,
     SL_GC_ORDER, SL_GS_ORDER, SL_GC_STREAM, SL_GC_HDR, SL_GC_META, SL_DELTA, SL_LOGU, SL_EDGES, SL_TSLOT, SL_SPLIT, SL_WS_PACK, SL_COUNT
+};
+constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
+
+// The array arguments of one entry point.  An argument may live on either side: NULL, an empty array and a device pointer
+// pass through; a host array is mirrored in a scratch slot (SL_IN* / SL_OUT*, handed out in call order) -- inputs go up
+// on the context's stream, outputs come back in finish().
+class Staging {
+    beatamd_ctx *ctx;
+    int nin = 0, nout = 0, nback = 0;
+    struct { void *host, *dev; size_t bytes; } back[SL_NOUT];   // host outputs: copied back by finish()
+    int in_bytes(const void *p, size_t bytes, const void **dev);
+    int out_bytes(void *p, size_t bytes, void **dev, bool preload);
+
+public:
+    explicit Staging(beatamd_ctx *c) : ctx(c) {}
+    // *dev: device pointer that holds the n elements of p
+    template <class T>
+    int in(const T *p, size_t n, const T **dev)
+    {
+        const void *d = nullptr;
+        BA_TRY(in_bytes(p, n * sizeof(T), &d));
+        *dev = static_cast<const T *>(d);
+        return BEATAMD_OK;
+    }
+    // *dev: device pointer to write the n elements into; preload: a host array's present content goes up first
+    template <class T>
+    int out(T *p, size_t n, T **dev, bool preload = false)
+    {
+        void *d = nullptr;
+        BA_TRY(out_bytes(p, n * sizeof(T), &d, preload));
+        *dev = static_cast<T *>(d);
+        return BEATAMD_OK;
+    }
+    // D2H copies; synchronises and reads the status word iff some output was a host array
+    int finish();
+};
+
+struct ScopedTimer {
+    beatamd_ctx *c;
+    const char *n;
+    ScopedTimer(beatamd_ctx *ctx, const char *name) : c(ctx), n(name) { c->time_begin(n); }
+    ~ScopedTimer() { c->time_end(n); }
 };
 
 }  // namespace beatamd

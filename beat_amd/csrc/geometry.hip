@@ -322,9 +322,9 @@ int launch_geom_los(beatamd_ctx *ctx, const GeomSources &g, const double *Q, int
     BA_CHECK(gc.nterm == 0 || (res && C <= 2147483647), BEATAMD_EINVAL,
              "geom_los: corrections act on the residual, of fewer than 2^31 chains");
     GeomSrcArgs a;
-    a.nsrc = g.nsrc; a.kind = g.kind; a.poff = g.poff; a.pfix = g.pfix;
+    a.nsrc = g.nsrc; a.kind = g.kind.get(); a.poff = g.poff.get(); a.pfix = g.pfix.get();
     a.Q = Q; a.nparams = nparams; a.C = C; a.Nobs = g.Nobs;
-    a.east = g.east; a.north = g.north; a.los = g.los; a.nu = g.nu; a.mu = mu;
+    a.east = g.east.get(); a.north = g.north.get(); a.los = g.los.get(); a.nu = g.nu; a.mu = mu;
     a.data = data; a.odw = odw; a.res = res; a.corr = gc;
     const int64_t n = C * g.Nobs;
     ScopedTimer tm(ctx, "geomlos");

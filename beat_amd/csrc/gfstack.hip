@@ -554,7 +554,6 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
     v.out = part;
     v.quad = nullptr; v.data = nullptr; v.wscalar = nullptr; v.band_w = nullptr;
     BA_TRY(launch_gfstack_impl(ctx, v));
-    for (int i = 0; i < call.nvar; i++) { views[i].g = nullptr; views[i].g32 = nullptr; }   // (views own nothing)
     {
         // (kernel name / plan of the stacking launch stay; the plan says that the library was split)
         const size_t n0 = strlen(ctx->gf_plan);

@@ -221,7 +221,7 @@ static HyperTables hyper_tables(const HyperModel &m)
 {
     HyperTables t;
     t.nterm = (int)m.nterm; t.nh = (int)m.nh;
-    t.M = m.M; t.slog = m.slog; t.kind = m.kind; t.hp_index = m.hp_index;
+    t.M = m.M.get(); t.slog = m.slog.get(); t.kind = m.kind.get(); t.hp_index = m.hp_index.get();
     t.grp.n = m.ngroups;
     for (int g = 0; g < m.ngroups; g++) t.grp.end[g] = m.group_end[g];
     return t;

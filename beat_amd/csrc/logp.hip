@@ -158,7 +158,7 @@ int launch_geo_stack(beatamd_ctx *ctx, const GeoLib *const *libs, int nvar, int6
     GeoStackArgs a;
     for (int v = 0; v < nvar; v++) {
         BA_CHECK(libs[v]->P == lib.P && libs[v]->Nobs == lib.Nobs, BEATAMD_EINVAL, "geo_stack: the libraries of the slip variables differ in shape");
-        a.G[v] = libs[v]->g;
+        a.G[v] = libs[v]->g.get();
         a.slips[v] = slips[v];
     }
     a.nvar = nvar; a.accumulate = accumulate;

@@ -324,10 +324,10 @@ int launch_sweep_model(beatamd_ctx *ctx, const FfiModel &m, const double *Q, int
     p.nuc_dip_off = m.layout.nuc_dip_off;
     p.time_off = m.layout.time_off;
     p.P = m.P;
-    p.sf_ndip = m.d_ndip;
-    p.sf_nstrike = m.d_nstrike;
-    p.sf_off = m.d_patch_off;
-    p.sf_h = m.d_patch_size;
+    p.sf_ndip = m.d_ndip.get();
+    p.sf_nstrike = m.d_nstrike.get();
+    p.sf_off = m.d_patch_off.get();
+    p.sf_h = m.d_patch_size.get();
     p.nsub = m.nsub;
     p.out = starttimes0;
     p.chain_bad = chain_bad;

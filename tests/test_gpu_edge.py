@@ -199,3 +199,59 @@ def test_release_frees_the_models_device_state(ctx):
     f.release()                                              # idempotent
     g = prob.compile(ctx)
     assert np.array_equal(g.batch(Q), a)
+
+
+def test_closing_a_context_frees_what_its_live_objects_hold():
+    """beatamd_ctx_destroy with live objects: every device array of every object goes with the context -- the banded copy
+    of a dense weight set, the correction basis and term table of a geodetic composite, a hyper model, a wavemap and the
+    libraries under them.  Three rounds on a context of their own, nothing destroyed by hand; the first warms the
+    runtime up, after the third the free device memory must be where it was after the second.
+
+    The arrays that scale with NOBS are sized on purpose: correction basis and geodetic library NOBS x 4 doubles (64 MiB
+    each), observations and their weights NOBS doubles (16 MiB each).  B = 16 MiB is the smallest of them; the margin is
+    B / 2, far above the allocator's granularity and below every one of them"""
+    import torch
+    from beat_amd import _lib
+    from beat_amd.engine import Context
+    from beat_amd.synthetic import SyntheticSpec, build_problem, draw_population
+
+    NOBS, NCOL, P = 1 << 21, 4, 4
+    B = NOBS * 8
+    spec = SyntheticSpec((4,), (4,), (1.0,), T=3, N=64, D=3, S=25, covariance="toeplitz")
+    rng = np.random.default_rng(5)
+    G = 1e-2 * rng.standard_normal((P, NOBS))
+    data, odw = 1e-2 * rng.standard_normal(NOBS), 0.5 + rng.random(NOBS)
+    basis = rng.standard_normal((NOBS, NCOL))
+    lay = _lib.FfiLayout()
+    lay.nparams, lay.nvar = P + 1 + NCOL, 1            # q = (slips, h_SAR, the term's coefficients)
+    for i in range(4):
+        lay.slip_off[i] = 0 if i == 0 else -1
+    lay.durations_off = lay.velocities_off = lay.nuc_strike_off = lay.nuc_dip_off = lay.time_off = -1
+    lay.h_laplacian_off = -1
+    q = rng.uniform(-1.0, 1.0, (2, lay.nparams))
+
+    def one_round():
+        c = Context(0)
+        # a wavemap under a dense weight set that the library evaluates on its band
+        prob, host = build_problem(spec)
+        f = prob.compile(c)
+        assert c.weights_band(f._wsets[0]) == 1
+        LL = f.batch(draw_population(spec, host["layout"], host["lower"], host["upper"], 4))
+        assert np.all(np.isfinite(LL))
+        # a geodetic composite with one correction term of NCOL basis columns
+        mid = c.ffi_model_create(lay, [], [], [])
+        ws = c.weights_create_scalar([1.0], [0.0], NOBS)
+        c.ffi_model_add_geodetic(mid, [c.geo_gflib_create(G)], data, odw, [NOBS], [ws], [P])
+        c.ffi_model_add_geodetic_corrections(mid, [0], [NCOL], [basis], [list(range(P + 1, P + 1 + NCOL))],
+                                             [[0.0] * NCOL])
+        assert np.all(np.isfinite(c.ffi_logp_batch(mid, q, c.ffi_model_nllk(mid))))
+        c.hyper_model_create(1, [NOBS], [0.0], [0], [0], [1])
+        c.close()                                            # nothing destroyed by hand
+        torch.cuda.synchronize(0)
+        return torch.cuda.mem_get_info(0)[0]
+
+    one_round()
+    free2 = one_round()
+    free3 = one_round()
+    print("free after round 2: %d, after round 3: %d, difference %d bytes (margin %d)" % (free2, free3, free2 - free3, B // 2))
+    assert abs(free3 - free2) <= B // 2
