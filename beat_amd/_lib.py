@@ -116,6 +116,13 @@ _PROTOS = {
     "beatamd_hyper_logp_batch": [_vp, _i32, _i64, _vp, _vp, _vp],
     "beatamd_hyper_chain_batch": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_uint64,
                                   C.c_uint32, _i64, _i32, _i32, _i32, _vp, _vp],
+    "beatamd_wset_quad_batch": [_vp, _i32, _i64, _vp, _vp],
+    "beatamd_ffi_obs_quads": [_vp, _i32, _vp],
+    "beatamd_ffi_variance_reductions_batch": [_vp, _i32, _i64, _vp, _vp],
+    "beatamd_ffi_geo_residuals_batch": [_vp, _i32, _i64, _vp, _i32, _vp],
+    "beatamd_standardize_batch": [_vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
+    "beatamd_ensemble_moments_update": [_vp, _i64, _i64, _vp, _vp, _i64],
+    "beatamd_ensemble_moments_finish": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "beatamd_like_assemble": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp],
     "beatamd_metropolis_propose": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "beatamd_metropolis_accept": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp],

@@ -88,6 +88,23 @@ int64_t model_nterm(const FfiModel &m)
     return n;
 }
 
+// datasets of the model: the first columns of the misfit vector (no Laplacian columns)
+int64_t model_ndata(const FfiModel &m)
+{
+    int64_t n = 0;
+    for (auto &w : m.wavemaps) n += w.T;
+    if (m.has_geo) n += (int64_t)m.geo.sizes.size();
+    return n;
+}
+
+// the cached |W d|^2 of every model go when weights, data, library rows or corrections change (a weight set or a
+// whitened library may serve several models: all are dropped, the next beatamd_ffi_obs_quads recomputes)
+void drop_obs_quads(beatamd_ctx *ctx)
+{
+    for (auto &m : ctx->models)
+        if (m) m->obs_quads_valid = false;
+}
+
 // what remains after the composites wrote their columns: the `like` sum.  A caller that passes a
 // LikeTail does that sum itself (the Metropolis step folds it into its accept kernel)
 struct LikeTail {
@@ -607,6 +624,7 @@ int beatamd_weights_update(beatamd_ctx *ctx, int32_t wset_id, int32_t kind, int6
     BA_CHECK(count == want, BEATAMD_EINVAL, "weights_update: %lld elements given, the set holds %lld",
              (long long)count, (long long)want);
     BA_HIP(hipStreamSynchronize(ctx->stream));
+    drop_obs_quads(ctx);
     return wset_fill(ctx, w, weights, slog_pdet);
 }
 
@@ -912,6 +930,7 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
              "add_geodetic_corrections: %d terms, the table holds %d", nterm, GEO_CORR_MAX);
     BA_CHECK(nterm == 0 || (dataset && ncol && basis && coef_off && coef_fixed), BEATAMD_EINVAL,
              "add_geodetic_corrections: bad argument");
+    m->obs_quads_valid = false;
     if (nterm == 0) {
         g.corr_set = true;
         return BEATAMD_OK;
@@ -1112,6 +1131,216 @@ int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
     BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
     BA_TRY(st.out(llks, (size_t)C * model_nterm(*m), &d_l));
     BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, nullptr, nullptr, d_l));
+    return st.finish();
+}
+
+// ------------------------------------------------------------------ posterior diagnostics (summary.hip)
+int beatamd_wset_quad_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C, const double *R, double *quad)
+{
+    ENTER(ctx);
+    WeightSet *w = get_obj(ctx->wsets, wset_id);
+    BA_CHECK(w, BEATAMD_EINVAL, "unknown weight set %d", wset_id);
+    BA_CHECK(R && quad && C >= 0, BEATAMD_EINVAL, "wset_quad: bad argument");
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_r;
+    double *d_q;
+    BA_TRY(st.in(R, (size_t)C * w->nd * w->M, &d_r));
+    BA_TRY(st.out(quad, (size_t)C * w->nd, &d_q));
+    BA_TRY(wset_quad(ctx, *w, C, d_r, w->nd * w->M, w->M, d_q));
+    return st.finish();
+}
+
+// |W_k d_k|^2 of every dataset of the model: wset_quad on the model's own data as a one-chain batch (the geodetic data
+// with its odw factor, as the residual carries it), kept on the model until something it depends on changes
+static int model_obs_quads(beatamd_ctx *ctx, FfiModel &m)
+{
+    const int64_t ndata = model_ndata(m);
+    if (m.obs_quads_valid && (int64_t)m.obs_quads.size() == ndata) return BEATAMD_OK;
+    BA_HIP(hipStreamSynchronize(ctx->stream));   // (a kernel in flight may still read the old copy)
+    DevMem<double> dq;
+    BA_TRY(dq.alloc((size_t)ndata));
+    int64_t col = 0;
+    void *p = nullptr;
+    for (auto &wm : m.wavemaps) {
+        WeightSet *ws = get_obj(ctx->wsets, wm.wset);
+        BA_CHECK(ws && ws->nd == wm.T && ws->M == wm.N, BEATAMD_EINVAL, "wavemap refers to a destroyed weight set");
+        BA_TRY(wset_quad(ctx, *ws, 1, wm.data.get(), wm.T * wm.N, wm.N, dq.get() + col));
+        col += wm.T;
+    }
+    if (m.has_geo) {
+        Geodetic &g = m.geo;
+        BA_TRY(ctx->get_scratch(SL_MU, (size_t)g.Nobs * 2 * sizeof(double), &p));
+        double *mu = (double *)p, *res = mu + g.Nobs;
+        BA_HIP(hipMemsetAsync(mu, 0, (size_t)g.Nobs * sizeof(double), ctx->stream));
+        BA_TRY(launch_geo_residual(ctx, 1, g.Nobs, g.data.get(), g.odws.get(), mu, res));   // (d - 0) * odw
+        int64_t o = 0;
+        for (size_t d = 0; d < g.sizes.size(); d++) {
+            WeightSet *ws = get_obj(ctx->wsets, g.wsets[d]);
+            BA_CHECK(ws && ws->nd == 1 && ws->M == g.sizes[d], BEATAMD_EINVAL,
+                     "geodetic dataset %zu: weight set missing or of the wrong size", d);
+            BA_TRY(wset_quad(ctx, *ws, 1, res + o, g.Nobs, 0, dq.get() + col + (int64_t)d));
+            o += g.sizes[d];
+        }
+        col += (int64_t)g.sizes.size();
+    }
+    BA_CHECK(col == ndata, BEATAMD_EINVAL, "internal: dataset layout mismatch");
+    m.obs_quads.resize((size_t)ndata);
+    if (ndata > 0) {
+        BA_HIP(hipMemcpyAsync(m.obs_quads.data(), dq.get(), (size_t)ndata * 8, hipMemcpyDeviceToHost, ctx->stream));
+        BA_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    m.d_obs_quads = std::move(dq);
+    m.obs_quads_valid = true;
+    return BEATAMD_OK;
+}
+
+int beatamd_ffi_obs_quads(beatamd_ctx *ctx, int32_t model_id, double *denom)
+{
+    ENTER(ctx);
+    FfiModel *m = get_obj(ctx->models, model_id);
+    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    BA_CHECK(denom, BEATAMD_EINVAL, "ffi_obs_quads: bad argument");
+    BA_TRY(model_check_layout(*m));
+    BA_TRY(model_obs_quads(ctx, *m));
+    const int64_t ndata = model_ndata(*m);
+    if (ndata == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    double *d_o;
+    BA_TRY(st.out(denom, (size_t)ndata, &d_o));
+    BA_HIP(hipMemcpyAsync(d_o, m->d_obs_quads.get(), (size_t)ndata * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return st.finish();
+}
+
+int beatamd_ffi_variance_reductions_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *VR)
+{
+    ENTER(ctx);
+    FfiModel *m = get_obj(ctx->models, model_id);
+    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    BA_CHECK(Q && VR && C >= 0, BEATAMD_EINVAL, "ffi_variance_reductions: bad argument");
+    BA_TRY(model_check_layout(*m));
+    const int64_t ndata = model_ndata(*m), nterm = model_nterm(*m);
+    if (C == 0 || ndata == 0) return BEATAMD_OK;
+    BA_TRY(model_obs_quads(ctx, *m));
+    Staging st(ctx);
+    const double *d_q;
+    double *d_v;
+    void *p;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.out(VR, (size_t)C * ndata, &d_v));
+    BA_TRY(ctx->get_scratch(SL_LPROP, (size_t)C * nterm * sizeof(double), &p));
+    double *llks = (double *)p;
+    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, nullptr, nullptr, llks));
+    BA_TRY(launch_variance_reduction(ctx, C, ndata, llks, nterm, m->d_obs_quads.get(), d_v));
+    return st.finish();
+}
+
+int beatamd_ffi_geo_residuals_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, int32_t residuals,
+                                    double *out)
+{
+    ENTER(ctx);
+    FfiModel *m = get_obj(ctx->models, model_id);
+    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    BA_CHECK(Q && out && C >= 0, BEATAMD_EINVAL, "ffi_geo_residuals: bad argument");
+    BA_CHECK(m->has_geo, BEATAMD_EINVAL, "ffi_geo_residuals: the model has no geodetic composite");
+    BA_TRY(model_check_layout(*m));
+    if (C == 0) return BEATAMD_OK;
+    Geodetic &g = m->geo;
+    const int64_t np = m->layout.nparams;
+    Staging st(ctx);
+    const double *d_q;
+    double *d_o;
+    void *p;
+    BA_TRY(st.in(Q, (size_t)C * np, &d_q));
+    BA_TRY(st.out(out, (size_t)C * g.Nobs, &d_o));
+    if (m->geo_is_geometry) {
+        if (residuals)
+            BA_TRY(launch_geom_los(ctx, m->geom, d_q, np, C, nullptr, g.data.get(), g.odws.get(), d_o, g.corr));
+        else
+            BA_TRY(launch_geom_los(ctx, m->geom, d_q, np, C, d_o));
+    } else {
+        const GeoLib *gls[4] = {nullptr, nullptr, nullptr, nullptr};
+        ChainVec slips[4];
+        BA_CHECK(m->layout.nvar <= 4, BEATAMD_EINVAL, "geodetic composite: more than 4 slip variables");
+        for (int v = 0; v < m->layout.nvar; v++) {
+            gls[v] = get_obj(ctx->geolibs, g.libs[v]);
+            BA_CHECK(gls[v], BEATAMD_EINVAL, "geodetic composite refers to a destroyed GF library");
+            slips[v] = ChainVec{d_q, np, m->layout.slip_off[v]};
+        }
+        double *mu = d_o;
+        if (residuals) {
+            BA_TRY(ctx->get_scratch(SL_MU, (size_t)C * g.Nobs * sizeof(double), &p));
+            mu = (double *)p;
+        }
+        BA_TRY(launch_geo_stack(ctx, gls, m->layout.nvar, C, slips, 0, mu));
+        if (residuals)
+            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data.get(), g.odws.get(), mu, d_o, d_q, np, g.corr));
+    }
+    return st.finish();
+}
+
+int beatamd_standardize_batch(beatamd_ctx *ctx, int32_t kind, const double *S, int64_t T, int64_t N, int64_t C,
+                              const double *R, const double *hp, double *out)
+{
+    ENTER(ctx);
+    BA_CHECK(kind == BEATAMD_W_SCALAR || kind == BEATAMD_W_DENSE, BEATAMD_EINVAL, "unknown operator kind %d", kind);
+    BA_CHECK(S && R && out && T > 0 && N > 0 && C >= 0, BEATAMD_EINVAL, "standardize: bad argument");
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_s, *d_r, *d_h;
+    double *d_o;
+    BA_TRY(st.in(S, (size_t)(kind == BEATAMD_W_SCALAR ? T : T * N * N), &d_s));
+    BA_TRY(st.in(R, (size_t)C * T * N, &d_r));
+    BA_TRY(st.in(hp, (size_t)C * T, &d_h));
+    BA_TRY(st.out(out, (size_t)C * T * N, &d_o));
+    if (kind == BEATAMD_W_SCALAR) {
+        BA_TRY(launch_standardize(ctx, C, T, N, d_s, d_h, d_r, d_o));
+        return st.finish();
+    }
+    BA_CHECK(d_o != d_r, BEATAMD_EINVAL, "standardize: a dense operator needs out apart from R");
+    // out[c, t, :] = S_t . R[c, t, :]: per dataset the chains' rows times S_t^T, the datasets as the batch of one launch
+    for (int64_t t0 = 0; t0 < T; t0 += 65535) {
+        GemmCall g;
+        g.A = d_r + t0 * N; g.lda = T * N; g.sA = N;
+        g.B = d_s + t0 * N * N; g.ldb = N; g.sB = N * N; g.b_kn = 0;
+        g.O = d_o + t0 * N; g.ldo = T * N; g.sO = N;
+        g.M = C; g.N = N; g.K = N;
+        g.nbatch = (int)std::min<int64_t>(65535, T - t0);
+        g.timer = "standardize";
+        BA_TRY(launch_gemm_f64(ctx, g));
+    }
+    if (d_h) BA_TRY(launch_standardize(ctx, C, T, N, nullptr, d_h, d_o, d_o));
+    return st.finish();
+}
+
+int beatamd_ensemble_moments_update(beatamd_ctx *ctx, int64_t C, int64_t M, const double *X, double *state, int64_t n_seen)
+{
+    ENTER(ctx);
+    BA_CHECK(X && state && C >= 0 && M > 0 && n_seen >= 0, BEATAMD_EINVAL, "ensemble_moments_update: bad argument");
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_x;
+    double *d_s;
+    BA_TRY(st.in(X, (size_t)C * M, &d_x));
+    BA_TRY(st.out(state, (size_t)5 * M, &d_s, n_seen > 0));
+    BA_TRY(launch_ensemble_moments(ctx, C, M, d_x, d_s, n_seen));
+    return st.finish();
+}
+
+int beatamd_ensemble_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int64_t n, double *mean, double *std,
+                                    double *min, double *max)
+{
+    ENTER(ctx);
+    BA_CHECK(state && mean && std && min && max && M > 0 && n > 0, BEATAMD_EINVAL, "ensemble_moments_finish: bad argument");
+    Staging st(ctx);
+    const double *d_s;
+    double *d_me, *d_sd, *d_mn, *d_mx;
+    BA_TRY(st.in(state, (size_t)5 * M, &d_s));
+    BA_TRY(st.out(mean, (size_t)M, &d_me));
+    BA_TRY(st.out(std, (size_t)M, &d_sd));
+    BA_TRY(st.out(min, (size_t)M, &d_mn));
+    BA_TRY(st.out(max, (size_t)M, &d_mx));
+    BA_TRY(launch_moments_finish(ctx, M, d_s, n, d_me, d_sd, d_mn, d_mx));
     return st.finish();
 }
 
@@ -1775,6 +2004,7 @@ int beatamd_ffi_model_update_data(beatamd_ctx *ctx, int32_t model_id, int32_t wa
     BA_CHECK(data && wavemap_index >= 0 && (size_t)wavemap_index < m->wavemaps.size(), BEATAMD_EINVAL,
              "model_update_data: bad argument");
     Wavemap &w = m->wavemaps[wavemap_index];
+    m->obs_quads_valid = false;
     BA_HIP(hipMemcpyAsync(w.data.get(), data, (size_t)w.T * w.N * 8, hipMemcpyDefault, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
     return BEATAMD_OK;
@@ -1788,6 +2018,7 @@ int beatamd_whiten_rows(beatamd_ctx *ctx, double *rows, int64_t nrows, int64_t N
     BA_CHECK(is_device_ptr(rows), BEATAMD_EINVAL, "whiten_rows: rows must live in HBM");
     if (nrows == 0) return BEATAMD_OK;
     drop_f32_overlapping(ctx, rows, (size_t)nrows * N * 8);
+    drop_obs_quads(ctx);
     Staging st(ctx);
     const double *d_w;
     void *p;
@@ -1831,6 +2062,7 @@ int beatamd_whiten_rows_batch(beatamd_ctx *ctx, double *rows, int64_t nbatch, in
     BA_CHECK(nbatch <= 65535, BEATAMD_EINVAL, "whiten_rows_batch: at most 65535 datasets per call");
     if (nrows == 0 || nbatch == 0) return BEATAMD_OK;
     drop_f32_overlapping(ctx, rows, (size_t)nbatch * nrows * N * 8);
+    drop_obs_quads(ctx);
     Staging st(ctx);
     const double *d_w;
     void *p;

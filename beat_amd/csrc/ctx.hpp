@@ -227,6 +227,11 @@ struct FfiModel {
     GeomSources geom;
     int32_t lap = -1;
     int64_t nllk() const;
+    // |W_k d_k|^2 of every dataset (beatamd_ffi_obs_quads), computed on first use and kept until the weights, the data
+    // or the corrections of the model change: host copy and the device copy the variance-reduction kernel reads
+    bool obs_quads_valid = false;
+    std::vector<double> obs_quads;
+    DevMem<double> d_obs_quads;
 };
 
 // the hyper-parameter model (hyper.hip): term k = kind[k] formula on hyper-parameter hp_index[k] of the nh-vector
@@ -321,7 +326,7 @@ const GfKnobs &gf_knobs(beatamd_ctx *ctx);
 // scratch slot map (one per logical temporary so slots never alias within a call)
 enum Slot : int {
     SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_IN6, SL_IN7,
-    SL_OUT0, SL_OUT1, SL_OUT2,
+    SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3,
     SL_ROWOFF, SL_WEIGHTS, SL_ST0, SL_RESID, SL_PARTIAL, SL_PARTIAL2, SL_QUAD, SL_MU, SL_SLIPS,
     SL_QPROP, SL_LPROP, SL_MISC, SL_GS_UROWS, SL_GS_UCOUNT, SL_GS_SLOT, SL_GS_W, SL_GS_UMAX, SL_GS_USLOT,
     SL_CHAINBAD, SL_Z, SL_ROWSCALE, SL_CUM, SL_STAGE2, SL_WHITEN,

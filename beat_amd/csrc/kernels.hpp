@@ -371,4 +371,17 @@ struct HyperChainCall {
 bool hyper_chain_applicable(int64_t nh, int64_t nterm);
 int launch_hyper_chain(beatamd_ctx *ctx, const HyperModel &m, const HyperChainCall &call);
 
+// ---- summary.hip: posterior diagnostics of a population
+// VR[c*n + k] = 1 - nom[c*ld + k] / denom[k]   (k_variance_reduction)
+int launch_variance_reduction(beatamd_ctx *ctx, int64_t C, int64_t n, const double *nom, int64_t ld, const double *denom,
+                              double *VR);
+// out[c,t,k] = exp(-hp[c,t]) * (S[t] * X[c,t,k]); S / hp nullable (k_standardize); X may be out
+int launch_standardize(beatamd_ctx *ctx, int64_t C, int64_t T, int64_t N, const double *S, const double *hp, const double *X,
+                       double *out);
+// Welford update of state [5, M] = (mean, M2, min, max, spare) with the rows of X [C, M] in row order, n_seen rows before
+// them (k_ensemble_moments); mean / sqrt(M2 / n) / min / max out of the state (k_moments_finish)
+int launch_ensemble_moments(beatamd_ctx *ctx, int64_t C, int64_t M, const double *X, double *state, int64_t n_seen);
+int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int64_t n, double *mean, double *std, double *mn,
+                          double *mx);
+
 }  // namespace beatamd

@@ -668,6 +668,103 @@ class Context(object):
             int(first_chain), int(tune_interval), int(steps_until_tune), int(buffer_thinning),
             None if trace is None else ptr(trace), None if n_accepted is None else ptr(n_accepted)))
 
+    # -- posterior diagnostics (csrc/summary.hip)
+    def wset_quad_batch(self, wset_id, residuals, out=None):
+        """residuals (C, nd, M) -> (C, nd): |W_d r|^2 per dataset of a weight set, the misfit kernels of
+        ``mvn_chol_logp_batch`` (seismic.py:610-616 nom / denom with W^T W = inv(C))"""
+        self._adopt_stream(residuals)
+        r = f64(residuals)
+        Cn, nd = int(r.shape[0]), int(r.shape[1])
+        if out is None:
+            out = _empty_like(r, (Cn, nd))
+        check(self._lib.beatamd_wset_quad_batch(self._h, wset_id, Cn, ptr(r), ptr(out)))
+        return out
+
+    def ffi_obs_quads(self, model_id, ndata, out=None):
+        """|W_k d_k|^2 of every dataset of the model -> (ndata,) numpy (or into the device tensor ``out``): the
+        denominators of the variance reduction (seismic.py:612-616, geodetic.py:497-501), cached on the model"""
+        if out is None:
+            out = np.empty(int(ndata))
+        else:
+            self._adopt_stream(out)
+        check(self._lib.beatamd_ffi_obs_quads(self._h, model_id, ptr(out)))
+        return out
+
+    def ffi_variance_reductions_batch(self, model_id, Q, ndata, out=None):
+        """Q (C, nparams) -> VR (C, ndata) = 1 - |W r|^2 / |W d|^2 per dataset and draw (get_variance_reductions,
+        seismic.py:564-634, geodetic.py:446-511)"""
+        self._adopt_stream(Q)
+        Q = f64(Q)
+        Cn = int(Q.shape[0])
+        if out is None:
+            out = _empty_like(Q, (Cn, int(ndata)))
+        check(self._lib.beatamd_ffi_variance_reductions_batch(self._h, model_id, Cn, ptr(Q), ptr(out)))
+        return out
+
+    def ffi_geo_residuals_batch(self, model_id, Q, nobs, residuals=True, out=None):
+        """Q (C, nparams) -> (C, nobs): the geodetic composite's residual (d - mu) * odw - corrections
+        (geodetic.py:1072-1077) or, residuals=False, its synthetics mu"""
+        self._adopt_stream(Q)
+        Q = f64(Q)
+        Cn = int(Q.shape[0])
+        if out is None:
+            out = _empty_like(Q, (Cn, int(nobs)))
+        check(self._lib.beatamd_ffi_geo_residuals_batch(self._h, model_id, Cn, ptr(Q), int(bool(residuals)), ptr(out)))
+        return out
+
+    def standardize_batch(self, S, residuals, hp=None, out=None):
+        """out[c, t] = exp(-hp[c, t]) * S_t . residuals[c, t]: the standardized residuals of
+        get_standardized_residuals (seismic.py:527-562) with S_t = inv(chol(C_t)).  S (T,) scalars or (T, N, N);
+        residuals (C, T, N); hp (C, T) or None"""
+        self._adopt_stream(residuals)
+        r = f64(residuals)
+        if r.ndim != 3:
+            raise ValueError("standardize_batch: residuals must be (C, T, N)")
+        Cn, T, N = [int(v) for v in r.shape]
+        Sc = f64(S)
+        if tuple(Sc.shape) == (T,):
+            kind = _lib.W_SCALAR
+        elif tuple(Sc.shape) == (T, N, N):
+            kind = _lib.W_DENSE
+        else:
+            raise ValueError("standardize_batch: S must be (%d,) or (%d, %d, %d)" % (T, T, N, N))
+        h = None
+        if hp is not None:
+            h = f64(hp)
+            if tuple(h.shape) != (Cn, T):
+                raise ValueError("standardize_batch: hp must be (%d, %d)" % (Cn, T))
+        if out is None:
+            out = _empty_like(r, (Cn, T, N))
+        check(self._lib.beatamd_standardize_batch(self._h, kind, ptr(Sc), T, N, Cn, ptr(r), ptr(h), ptr(out)))
+        return out
+
+    def ensemble_moments_update(self, X, state=None, n_seen=0):
+        """fold the rows of X (C, M) into the running column moments ``state`` (5, M) = (mean, M2, min, max, rows
+        seen), Welford in row order: the result does not depend on how the rows are cut into calls.  state None
+        (with n_seen 0) allocates one on X's side.  -> (state, n_seen + C)"""
+        self._adopt_stream(X)
+        x = f64(X)
+        if x.ndim != 2:
+            raise ValueError("ensemble_moments_update: X must be (C, M)")
+        Cn, M = int(x.shape[0]), int(x.shape[1])
+        if state is None:
+            if n_seen:
+                raise ValueError("ensemble_moments_update: %d rows seen but no state given" % n_seen)
+            state = _empty_like(x, (5, M))
+        if tuple(state.shape) != (5, M) or f64(state) is not state or _is_dev(state) != _is_dev(x):
+            raise ValueError("ensemble_moments_update: state must be a contiguous float64 (5, %d) array on X's side" % M)
+        check(self._lib.beatamd_ensemble_moments_update(self._h, Cn, M, ptr(x), ptr(state), int(n_seen)))
+        return state, int(n_seen) + Cn
+
+    def ensemble_moments_finish(self, state, n):
+        """-> (mean, std, min, max), each (M,): std = sqrt(M2 / n) as numpy.std (ddof = 0)"""
+        self._adopt_stream(state)
+        s = f64(state)
+        M = int(s.shape[1])
+        outs = [_empty_like(s, (M,)) for _ in range(4)]
+        check(self._lib.beatamd_ensemble_moments_finish(self._h, M, ptr(s), int(n), *[ptr(o) for o in outs]))
+        return tuple(outs)
+
     def halfspace_displacements_batch(self, kinds, params, east, north, nu=0.25):
         """params (C, nsrc, 10) -> (C, nsrc, nobs, 3) = (north, east, up) [m]"""
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)

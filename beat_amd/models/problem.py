@@ -480,6 +480,97 @@ class LogpForwFunc(object):
             raise RuntimeError("a weight update of this model did not complete: %s" % self._dirty)
         return self.ctx.ffi_llks_batch(self.model_id, Q, out)
 
+    # -- posterior diagnostics of a population (csrc/summary.hip)
+    def _ready(self, Q=None):
+        if self.model_id is None:
+            raise RuntimeError("this compiled model was released")
+        if Q is not None and Q.shape[-1] != self.nparams:
+            raise ValueError("expected %d parameters, got %d" % (self.nparams, Q.shape[-1]))
+        if self._dirty:
+            raise RuntimeError("a weight update of this model did not complete: %s" % self._dirty)
+
+    @property
+    def ndata(self):
+        """datasets of the model: the seismic datasets wavemap by wavemap, then the geodetic ones"""
+        g = self.problem.geodetic
+        return sum(wm.n_t for wm in self.problem.wavemaps) + (len(g.sizes) if g is not None else 0)
+
+    @property
+    def dataset_names(self):
+        """column labels of ``variance_reductions`` / ``obs_quads``"""
+        return list(self.problem.out_names[:self.ndata])
+
+    def obs_quads(self):
+        """|W_k d_k|^2 per dataset -> (ndata,) numpy: the denominators ``data.T.dot(icov).dot(data)`` of the variance
+        reduction (seismic.py:612-616, geodetic.py:497-501; geodetic data with its odw factor: DESIGN.md 3.9).  Cached
+        on the device model until weights, data or corrections change."""
+        self._ready()
+        return self.ctx.ffi_obs_quads(self.model_id, self.ndata)
+
+    def variance_reductions(self, Q, out=None):
+        """Q (C, nparams) -> (C, ndata): ``1 - nom / denom`` per dataset (columns: ``dataset_names``) and draw --
+        ``get_variance_reductions`` (seismic.py:564-634, geodetic.py:446-511) for a batch, as a fraction (the
+        reference's plots multiply by 100).  The hyper-parameter entries of Q are not read: ``inverse(exp(2h))``
+        scales numerator and denominator alike.  numpy in -> numpy out, torch-cuda in -> tensor on the same device."""
+        self._ready(Q)
+        return self.ctx.ffi_variance_reductions_batch(self.model_id, Q, self.ndata, out)
+
+    def geodetic_residuals(self, Q, residuals=True):
+        """Q (C, nparams) -> (C, nobs_total): the geodetic composite's residual ``(d - mu) * odw - corrections`` in the
+        order of geodetic.py:1072-1077 (residuals=False: its synthetics mu); FFI and geometry composites"""
+        self._ready(Q)
+        g = self.problem.geodetic
+        if g is None:
+            raise ValueError("the model has no geodetic composite")
+        return self.ctx.ffi_geo_residuals_batch(self.model_id, Q, int(sum(g.sizes)), residuals=residuals)
+
+    def _hp_columns(self, Q, hypers):
+        offs = [self.problem.layout.offset(n, i) for n, i in hypers]
+        if hasattr(Q, "data_ptr") and not isinstance(Q, np.ndarray):
+            import torch
+            return Q[:, torch.as_tensor(offs, device=Q.device)].contiguous()
+        return np.ascontiguousarray(np.asarray(Q)[:, offs])
+
+    def standardized_residuals(self, Q, covariances, wavemap_index=0):
+        """``get_standardized_residuals`` (seismic.py:527-562, geodetic.py:513-543) for a batch: per dataset
+        ``inv(cov.chol(exp(2 h))) . residual`` = ``exp(-h) * inv(cov.chol()) . residual``.
+
+        covariances: the datasets' ``beat_amd.heart.Covariance`` objects (or plain variances sigma^2); the operators
+        ``inv(cov.chol())`` are formed on the host once per call -- they are lower triangular and are NOT the
+        whitening operators ``chol_inverse`` the likelihood holds (same norm of the product, other elements).
+        h is read from Q as the model reads it (per dataset or shared).
+        wavemap_index: a wavemap -> (C, T, N); "geodetic" -> list of (C, n_k) per dataset (the sizes differ).
+        A pre-whitened wavemap is refused: its residuals are whitened by another operator already."""
+        self._ready(Q)
+        if wavemap_index == "geodetic":
+            g = self.problem.geodetic
+            if g is None:
+                raise ValueError("the model has no geodetic composite")
+            if len(covariances) != len(g.sizes):
+                raise ValueError("%d covariances for %d geodetic datasets" % (len(covariances), len(g.sizes)))
+            res = self.geodetic_residuals(Q)
+            hp = self._hp_columns(Q, g.hypers)
+            out, o = [], 0
+            for k, n in enumerate(g.sizes):
+                S = _standardizing_operators([covariances[k]], n)
+                r = res[:, o:o + n].reshape(-1, 1, n)
+                r = r.contiguous() if hasattr(r, "contiguous") else np.ascontiguousarray(r)
+                h = hp[:, k:k + 1]
+                h = h.contiguous() if hasattr(h, "contiguous") else np.ascontiguousarray(h)
+                out.append(self.ctx.standardize_batch(S, r, h).reshape(-1, n))
+                o += n
+            return out
+        wm = self.problem.wavemaps[wavemap_index]
+        if getattr(wm, "is_prewhitened", False):
+            raise ValueError("wavemap %s is pre-whitened: its residuals are W (d - s) already, the standardizing "
+                             "operator inv(chol(C)) does not apply to them" % wm.name)
+        T, N = wm.data.shape
+        if len(covariances) != T:
+            raise ValueError("%d covariances for %d datasets" % (len(covariances), T))
+        S = _standardizing_operators(covariances, N)
+        return self.ctx.standardize_batch(S, self.synthetics(Q, wavemap_index, residuals=True),
+                                          self._hp_columns(Q, wm.hypers))
+
     def update_weights(self, wavemap_index, weights, slog_pdet):
         """seismic.py:1509-1534 update_weights: new chol_inverse + slog_pdet per dataset.  Kind
         and size must match the uploaded set (checked by the library).  numpy arrays or torch-cuda
@@ -554,6 +645,23 @@ def _log_band(ctx, wset, what):
 
 def _host(a):
     return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+
+def _standardizing_operators(covariances, n):
+    """S_t = inv(cov_t.chol()) of datasets of n samples (seismic.py:560): (T,) = 1 / sigma_t when every covariance is a
+    plain variance sigma^2, else (T, n, n), lower triangular"""
+    if all(np.ndim(c) == 0 and not hasattr(c, "chol") for c in covariances):
+        return 1.0 / np.sqrt(np.asarray(covariances, dtype=np.float64))
+    S = np.empty((len(covariances), n, n))
+    for t, c in enumerate(covariances):
+        if hasattr(c, "chol"):
+            L = np.asarray(c.chol(), dtype=np.float64)
+            if L.shape != (n, n):
+                raise ValueError("covariance %d is %s, the dataset has %d samples" % (t, L.shape, n))
+            S[t] = np.linalg.inv(L)
+        else:
+            S[t] = np.eye(n) / np.sqrt(float(c))
+    return S
 
 
 def prior_logp_func(lower, upper):

@@ -199,6 +199,23 @@ class TargetShardedLogp(object):
                                   "all-gathered like the likelihood vector): estimate the hyper-parameters on the "
                                   "replicated model, or on self.local for this rank's targets")
 
+    def _no_diagnostics(self, what):
+        raise NotImplementedError("%s of a target-sharded model is not offered (the seismic columns would be all-gathered "
+                                  "like the likelihood vector): take the posterior diagnostics on the replicated model, or "
+                                  "on self.local for this rank's targets" % what)
+
+    def obs_quads(self):
+        self._no_diagnostics("obs_quads")
+
+    def variance_reductions(self, Q, out=None):
+        self._no_diagnostics("variance_reductions")
+
+    def geodetic_residuals(self, Q, residuals=True):
+        self._no_diagnostics("geodetic_residuals")
+
+    def standardized_residuals(self, Q, covariances, wavemap_index=0):
+        self._no_diagnostics("standardized_residuals")
+
     def synthetics(self, Q, wavemap_index=0, residuals=False):
         raise NotImplementedError("synthetics of a target-sharded model: evaluate the local model (self.local.synthetics) for "
                                   "this rank's targets %s" % (self.blocks[wavemap_index][self.rank],))

@@ -1,0 +1,120 @@
+"""
+Posterior diagnostics of a whole stage population on the device -- what the reference computes with one forward model
+per draw on one core:
+
+  beat/models/seismic.py:564-634, geodetic.py:446-511    get_variance_reductions(point)
+  beat/plotting/seismic.py:395-451                       form_result_ensemble: an ensemble of draws, their variance
+                                                         reductions and synthetics (also plotting/geodetic.py:194-227,
+                                                         580-610; station_variance_reductions, `beat summarize`)
+
+Here a batch of draws is one call of the compiled model (``LogpForwFunc.variance_reductions`` / ``.synthetics``), and
+the synthetics of an ensemble are reduced to mean / std / envelope where they are produced
+(``Context.ensemble_moments_update``): an ensemble of [E, T, N] doubles never travels to the host unless asked for.
+The functions take arrays (a population (n, nparams) in the order of the model's parameter vector), not stage
+directories.  There is no CPU fallback: without a GPU they raise.
+"""
+import numpy as np
+
+from .engine import get_context
+
+
+def ensemble_indices(n, nensemble):
+    """which of n draws make up an ensemble of ``nensemble``: the reference's
+    ``floor(arange(0, n, float(n) / nensemble)).astype("int32")`` (plotting/seismic.py:400-402).
+
+    DEVIATION: ``arange`` with a fractional step can come out one element longer than nensemble, the last one equal
+    to n (n = 530, nensemble = 7 gives a trailing 530), which the reference would then fail to look up in its trace.
+    Entries >= n are dropped here."""
+    n, nensemble = int(n), int(nensemble)
+    if n <= 0 or nensemble <= 0:
+        return np.zeros(0, dtype=np.int32)
+    raw = np.floor(np.arange(0, n, float(n) / nensemble)).astype("int32")
+    return raw[raw < n]
+
+
+def _ctx_of(f):
+    ctx = getattr(f, "ctx", None)
+    return ctx if ctx is not None else get_context()      # (raises without the library or a GPU)
+
+
+def _is_tensor(a):
+    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+
+def _to_device(ctx, a):
+    import torch
+    if _is_tensor(a):
+        return a
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:%d" % ctx.device)
+
+
+def posterior_variance_reductions(f, population, batch=512):
+    """variance reduction of every dataset at every draw: population (n, nparams) -> (n, ndata), columns
+    ``f.dataset_names``, as a fraction.  The draws go through the device in batches of ``batch``; numpy in -> numpy
+    out, torch-cuda in -> tensor."""
+    ctx = _ctx_of(f)
+    n = int(population.shape[0])
+    batch = max(int(batch), 1)
+    if _is_tensor(population):
+        import torch
+        out = torch.empty((n, f.ndata), dtype=torch.float64, device=population.device)
+        for a in range(0, n, batch):
+            f.variance_reductions(population[a:a + batch].contiguous(), out=out[a:a + batch])
+        return out
+    population = np.ascontiguousarray(population, dtype=np.float64)
+    out = np.empty((n, f.ndata))
+    for a in range(0, n, batch):
+        out[a:a + batch] = f.variance_reductions(_to_device(ctx, population[a:a + batch])).cpu().numpy()
+    return out
+
+
+def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, keep_synthetics=False):
+    """``form_result_ensemble`` (plotting/seismic.py:395-451) on arrays: ``nensemble`` draws of ``population``
+    (n, nparams) picked by ``ensemble_indices`` next to the point ``best`` (nparams,).  Returns
+
+      indices          (E,) int32
+      var_reductions   (E + 1, ndata) in percent, the best point first (the reference's ordering, :437-450)
+      moments          dict wavemap index -> dict(mean, std, min, max: (T, N) numpy) over the ENSEMBLE's synthetics of
+                       that wavemap (std as numpy.std, ddof = 0), accumulated on the device from the output of
+                       ``f.synthetics``; with ``keep_synthetics`` also ``synthetics`` (E, T, N) on the host.
+                       wavemap_index: an index, a list of them, or None for every wavemap of the model."""
+    ctx = _ctx_of(f)
+    idx = ensemble_indices(int(population.shape[0]), nensemble)
+    batch = max(int(batch), 1)
+    if _is_tensor(population):
+        import torch
+        ens = population[torch.as_tensor(idx.astype(np.int64), device=population.device)].contiguous()
+        best_d = _to_device(ctx, best).reshape(1, -1).to(ens.device)
+    else:
+        ens = _to_device(ctx, np.asarray(population, dtype=np.float64)[idx])
+        best_d = _to_device(ctx, np.asarray(best, dtype=np.float64).reshape(1, -1))
+    import torch
+    points = torch.cat([best_d, ens]).contiguous()
+    var_reductions = posterior_variance_reductions(f, points, batch).cpu().numpy() * 100.0
+
+    nwm = len(f.problem.wavemaps)
+    if wavemap_index is None:
+        which = list(range(nwm))
+    elif np.ndim(wavemap_index) == 0:
+        which = [int(wavemap_index)] if nwm else []
+    else:
+        which = [int(w) for w in wavemap_index]
+    moments = {}
+    E = int(ens.shape[0])
+    for wi in which:
+        T, N = f.problem.wavemaps[wi].data.shape
+        state, seen, kept = None, 0, []
+        for a in range(0, E, batch):
+            syn = f.synthetics(ens[a:a + batch], wi)                      # (e, T, N) on the device
+            state, seen = ctx.ensemble_moments_update(syn.view(-1, T * N), state, seen)
+            if keep_synthetics:
+                kept.append(syn.cpu().numpy())
+        entry = {}
+        if E:
+            mean, std, mn, mx = ctx.ensemble_moments_finish(state, seen)
+            entry = dict(mean=mean.cpu().numpy().reshape(T, N), std=std.cpu().numpy().reshape(T, N),
+                         min=mn.cpu().numpy().reshape(T, N), max=mx.cpu().numpy().reshape(T, N))
+        if keep_synthetics:
+            entry["synthetics"] = np.concatenate(kept) if kept else np.zeros((0, T, N))
+        moments[wi] = entry
+    return idx, var_reductions, moments

@@ -526,6 +526,61 @@ int beatamd_hyper_chain_batch(beatamd_ctx *ctx, int32_t id, int64_t C, int64_t n
                               int64_t first_chain, int32_t tune_interval, int32_t steps_until_tune, int32_t buffer_thinning,
                               double *trace, int64_t *n_accepted);
 
+/* ---------------------------------------------------------------- posterior diagnostics ----
+ * What a BEAT project asks of a finished stage -- variance reductions, standardized residuals, the synthetics of
+ * an ensemble of draws -- for whole populations at once (the reference runs one forward model per draw).
+ *
+ * replaces: the quadratic forms residual.T.dot(icov).dot(residual) / data.T.dot(icov).dot(data) of
+ *           get_variance_reductions           beat/models/seismic.py:610-616, beat/models/geodetic.py:494-501
+ *   quad[c,d] = |W_d R[c,d,:]|^2 for a weight set (W^T W = inv(C)), through the misfit kernels of
+ *   beatamd_mvn_chol_logp_batch: scalar, banded and dense.   R [C, nd, M] -> quad [C, nd] */
+int beatamd_wset_quad_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C, const double *R, double *quad);
+/* replaces: denom = data.T.dot(icov).dot(data) per dataset   seismic.py:612-616, geodetic.py:497-501
+ *   denom [ndata] = |W_k d_k|^2 of every dataset of the model, in the order of the first ndata columns of
+ *   beatamd_ffi_llks_batch (seismic datasets wavemap by wavemap, then the geodetic ones; no Laplacian columns):
+ *   beatamd_wset_quad_batch on the model's own data as a one-chain batch.  A pre-whitened wavemap holds whitened data:
+ *   |d'|^2.  Computed once and kept on the model until beatamd_weights_update, beatamd_ffi_model_update_data, a
+ *   (re-)whitening of library rows or beatamd_ffi_model_add_geodetic_corrections.
+ *   DEVIATION (as for beatamd_ffi_llks_batch): geodetic data carries the odw factor, d_k * odw_k, like the residual
+ *   of the likelihood; the reference's variance reduction leaves odw out (geodetic.py:221). */
+int beatamd_ffi_obs_quads(beatamd_ctx *ctx, int32_t model_id, double *denom);
+/* replaces: get_variance_reductions(point) per draw, as form_result_ensemble and `beat summarize` loop it
+ *           beat/models/seismic.py:564-634, beat/models/geodetic.py:446-511,
+ *           beat/plotting/seismic.py:395-451, beat/plotting/geodetic.py:194-227, 580-610
+ *   Q [C,nparams] -> VR [C,ndata] = 1 - nom / denom: nom = the misfits of beatamd_ffi_llks_batch, denom =
+ *   beatamd_ffi_obs_quads, plain IEEE arithmetic (a zero denominator gives what the division gives).  The
+ *   hyper-parameter entries of Q are not read: inverse(exp(2h)) scales numerator and denominator alike.  A chain
+ *   whose times leave the library grid gets a NaN row and raises the status word as beatamd_ffi_llks_batch does. */
+int beatamd_ffi_variance_reductions_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *VR);
+/* replaces: the geodetic residual / synthetics of a point     beat/models/geodetic.py:1065-1077 (FFI),
+ *           :605-659 (geometry), as get_standardized_residuals / get_variance_reductions need them (:446-543)
+ *   Q [C,nparams] -> out [C, nobs_total]: residuals != 0: the likelihood's own residual (d - mu) * odw - corrections
+ *   (geodetic.py:1072-1077); residuals == 0: mu.  The stacking and residual kernels of the likelihood. */
+int beatamd_ffi_geo_residuals_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, int32_t residuals,
+                                    double *out);
+/* replaces: choli = inv(covariance.chol(exp(hp * 2))); choli.dot(ydata)
+ *           get_standardized_residuals       beat/models/seismic.py:527-562, beat/models/geodetic.py:513-543
+ *   out[c,t,:] = exp(-hp[c,t]) * (S_t . R[c,t,:]) with S_t = inv(chol(C_t)) handed in (lower triangular in the
+ *   reference; any matrix is accepted -- this is NOT the whitening operator chol(inv(C)).T of a weight set):
+ *   kind BEATAMD_W_SCALAR: S [T] (1 / sigma_t), BEATAMD_W_DENSE: S [T,N,N] row-major.  R, out [C,T,N]; hp [C,T] or
+ *   NULL (no scale).  The dense product runs on the FP64 matrix cores (the GEMM of beatamd_whiten_rows), every
+ *   output element summed over k in a fixed order; out must not alias R for a dense operator. */
+int beatamd_standardize_batch(beatamd_ctx *ctx, int32_t kind, const double *S, int64_t T, int64_t N, int64_t C,
+                              const double *R, const double *hp, double *out);
+/* replaces: collecting processed_syn of every ensemble member and reducing them on the host
+ *           form_result_ensemble             beat/plotting/seismic.py:395-451
+ *   Running column moments of X [C,M] (a batch of synthetics [C, T*N] as it leaves beatamd_ffi_synthetics_batch):
+ *   state [5,M] = (mean, M2, min, max, rows seen); n_seen = rows folded in before this call (0: the state is
+ *   initialised, its content is not read).  Rows are taken in row order with exactly
+ *       d = x - m;  m = m + d / n;  M2 = M2 + d * (x - m)
+ *   so the result is bit for bit independent of how the rows are cut into calls.  A NaN makes its column's mean and
+ *   std NaN; min and max of such a column are unspecified.
+ *   finish: mean, std = sqrt(M2 / n) (numpy.std with ddof = 0), min, max [M] after n rows. */
+int beatamd_ensemble_moments_update(beatamd_ctx *ctx, int64_t C, int64_t M, const double *X, double *state,
+                                    int64_t n_seen);
+int beatamd_ensemble_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int64_t n, double *mean,
+                                    double *std, double *min, double *max);
+
 /* ---------------------------------------------------------------- library whitening ------
  * rows [nrows, N] (device, in place) <- rows . W^T, W [N,N] = chol_inverse of one dataset: the
  * dense W.r of multivariate_normal_chol (distributions.py:128) applied once to every library row
