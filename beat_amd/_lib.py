@@ -17,7 +17,7 @@ NEAREST_NEIGHBOR, MULTILINEAR = 0, 1
 W_SCALAR, W_DENSE = 0, 1
 INTERPOLATIONS = {"nearest_neighbor": NEAREST_NEIGHBOR, "multilinear": MULTILINEAR}
 
-OK, EINVAL, EHIP, EINDEX, ENOMEM, ENAN, ENOTPSD, EBADCOV = 0, -1, -2, -3, -4, -5, -6, -7
+OK, EINVAL, EHIP, EINDEX, ENOMEM, ENAN, ENOTPSD, EBADCOV, EOUTSIDE = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ABI_VERSION = 120   # include/beat_amd.h BEATAMD_VERSION this module was written against
 
 
@@ -123,6 +123,7 @@ _PROTOS = {
     "beatamd_standardize_batch": [_vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "beatamd_ensemble_moments_update": [_vp, _i64, _i64, _vp, _vp, _i64],
     "beatamd_ensemble_moments_finish": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "beatamd_trace_density_update": [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _i64, _i64, _f64, _vp],
     "beatamd_like_assemble": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp],
     "beatamd_metropolis_propose": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "beatamd_metropolis_accept": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp],
@@ -186,6 +187,8 @@ def check(rc):
         raise ValueError(msg)
     if rc == EINDEX:
         raise IndexError(msg)
+    if rc == EOUTSIDE:
+        raise TypeError(msg)
     if rc == ENOMEM:
         raise MemoryError(msg)
     if rc == ENOTPSD:

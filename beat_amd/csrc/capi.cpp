@@ -1344,6 +1344,24 @@ int beatamd_ensemble_moments_finish(beatamd_ctx *ctx, int64_t M, const double *s
     return st.finish();
 }
 
+int beatamd_trace_density_update(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin,
+                                 double deltat, const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid)
+{
+    ENTER(ctx);
+    BA_CHECK(Y && tmin && extent && grid && E >= 0 && T >= 0 && N > 0 && ny > 0 && nx > 0, BEATAMD_EINVAL,
+             "trace_density_update: bad argument");
+    Staging st(ctx);
+    const double *d_y, *d_t, *d_e;
+    double *d_g;
+    BA_TRY(st.in(Y, (size_t)E * T * N, &d_y));
+    BA_TRY(st.in(tmin, (size_t)T, &d_t));
+    BA_TRY(st.in(extent, (size_t)4 * T, &d_e));
+    BA_TRY(st.out(grid, (size_t)T * ny * nx, &d_g, true));
+    BA_TRY(launch_trace_density(ctx, E, T, N, d_y, d_t, deltat, d_e, ny, nx, linewidth, d_g));
+    BA_TRY(st.finish());
+    return ctx->check_status();   // (device arrays too: a line outside the grid is the caller's TypeError now, not later)
+}
+
 // ------------------------------------------------------------------ the hyper-parameter model (hyper.hip)
 int beatamd_hyper_model_create(beatamd_ctx *ctx, int64_t nterm, int64_t nh, const int64_t *M, const double *slog,
                                const int32_t *kind, const int32_t *hp_index, int32_t ngroups, const int32_t *group_end,

@@ -178,6 +178,15 @@ int beatamd_ctx::check_status()
             set_error("Matrix is not positive definite");   // numpy.linalg.LinAlgError's text
             return BEATAMD_ENOTPSD;
         }
+        if (st & ST_LINE_NONFINITE) {
+            set_error("trace_density: a sample or an extent that is not finite (or xmax <= xmin)");
+            return BEATAMD_EINVAL;
+        }
+        if (st & ST_LINE_OOB) {
+            // plotting/common.py:733-739 check_line_in_grid: the reference's TypeError
+            set_error("Line endpoint outside of given grid (an index above the last cell, or below -32768)");
+            return BEATAMD_EOUTSIDE;
+        }
         if (st & ST_BAD_SCALE) {
             set_error("PoissonProposal: a step width outside (0, 500] (or NaN): the draws of that parameter are NaN");
             return BEATAMD_EINVAL;
@@ -198,6 +207,7 @@ void GfKnobs::read_env()
     gc_global = rd("BEATAMD_GC_GLOBAL"); gc_sort = rd("BEATAMD_GC_SORT"); gc_keys = rd("BEATAMD_GC_KEYS"); gc_bands = rd("BEATAMD_GC_BANDS"); gr_cap = rd("BEATAMD_GR_CAP");
     gr_pass_alloc = rd("BEATAMD_GR_PASS_ALLOC"); gr_var = rd("BEATAMD_GR_VAR"); sweep_v1 = rd("BEATAMD_SWEEP_V1"); qf_band = rd("BEATAMD_QF_BAND"); qf_fuse = rd("BEATAMD_QF_FUSE"); gf_split = rd("BEATAMD_GF_SPLIT"); gm_wave = rd("BEATAMD_GM_WAVE");
     skip_parked = rd("BEATAMD_SKIP_PARKED");
+    td_strip = rd("BEATAMD_TD_STRIP");
 }
 
 const GfKnobs &gf_knobs(beatamd_ctx *ctx)

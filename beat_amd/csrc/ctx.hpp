@@ -45,7 +45,8 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 // device status bits set by kernels (checked at synchronisation points)
-enum : int { ST_INDEX_OOB = 1, ST_BAD_HYPO = 2, ST_NOT_PSD = 4, ST_BAD_COV = 8, ST_BAD_SCALE = 16 };
+enum : int { ST_INDEX_OOB = 1, ST_BAD_HYPO = 2, ST_NOT_PSD = 4, ST_BAD_COV = 8, ST_BAD_SCALE = 16, ST_LINE_OOB = 32,
+              ST_LINE_NONFINITE = 64 };
 
 struct DevBuf {
     void *p = nullptr;
@@ -253,7 +254,7 @@ struct GfKnobs {
         gs_win = KNOB_UNSET, gf_tinv = KNOB_UNSET, gs_tune = KNOB_UNSET, gf_order = KNOB_UNSET, gf_cgroup = KNOB_UNSET,
         gs_ml = KNOB_UNSET, gc_global = KNOB_UNSET, gc_sort = KNOB_UNSET, gc_keys = KNOB_UNSET, gc_bands = KNOB_UNSET, gr_cap = KNOB_UNSET,
         gr_pass_alloc = KNOB_UNSET, gr_var = KNOB_UNSET, sweep_v1 = KNOB_UNSET, qf_band = KNOB_UNSET, qf_fuse = KNOB_UNSET, gf_split = KNOB_UNSET, gm_wave = KNOB_UNSET,
-        skip_parked = KNOB_UNSET;
+        skip_parked = KNOB_UNSET, td_strip = KNOB_UNSET;
     void read_env();
     static int get(int v, int dflt) { return v == KNOB_UNSET ? dflt : v; }
     static bool is(int v, int x) { return v != KNOB_UNSET && v == x; }       // set and equal to x

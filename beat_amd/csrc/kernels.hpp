@@ -383,5 +383,9 @@ int launch_standardize(beatamd_ctx *ctx, int64_t C, int64_t T, int64_t N, const 
 int launch_ensemble_moments(beatamd_ctx *ctx, int64_t C, int64_t M, const double *X, double *state, int64_t n_seen);
 int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int64_t n, double *mean, double *std, double *mn,
                           double *mx);
+// grid [T,ny,nx] += the line images of the traces Y [E,T,N] in ensemble order (k_trace_density_check, k_trace_density);
+// an index outside the grid or a non-finite sample raises the status word
+int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
+                         const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid);
 
 }  // namespace beatamd

@@ -765,6 +765,49 @@ class Context(object):
         check(self._lib.beatamd_ensemble_moments_finish(self._h, M, ptr(s), int(n), *[ptr(o) for o in outs]))
         return tuple(outs)
 
+    def trace_density_update(self, Y, tmin, deltat, extent, grid_size=(500, 500), linewidth=7, grid=None):
+        """add the line images of the traces Y (E, T, N) to the density grids (T, ny, nx) of their targets -- the grid
+        ``fuzzy_waveforms`` builds with ``draw_line_on_array`` (plotting/seismic.py:255-316, plotting/common.py:619-801),
+        bit for bit.  Sample j of target t lies at tmin[t] + j * deltat; extent (T, 4) = (xmin, xmax, ymin, ymax) per
+        target (``summary.density_extent`` gives the reference's default); grid None allocates a zeroed one on Y's side,
+        a given one is added to and returned.  Traces are taken in ensemble order: cutting an ensemble into calls does
+        not change the result.  TypeError: a sample or time beyond the extent's upper side (below the lower side it is
+        clipped); ValueError: a non-finite sample, a bad shape."""
+        self._adopt_stream(Y)
+        y = f64(Y)
+        if y.ndim != 3:
+            raise ValueError("trace_density_update: Y must be (E, T, N)")
+        E, T, N = (int(v) for v in y.shape)
+        ny, nx = (int(v) for v in grid_size)
+        dev = _is_dev(y)
+
+        def side(a, shape, what):
+            if _is_dev(a) != dev and _is_dev(a):
+                a = a.cpu().numpy()
+            if not _is_dev(a):
+                a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))
+                if dev:
+                    import torch
+                    a = torch.from_numpy(a).to(y.device)
+            a = f64(a)
+            if tuple(a.shape) != shape:
+                raise ValueError("trace_density_update: %s must be %s" % (what, shape))
+            return a
+
+        tm, ext = side(tmin, (T,), "tmin"), side(extent, (T, 4), "extent")
+        if grid is None:
+            if dev:
+                import torch
+                grid = torch.zeros((T, ny, nx), dtype=torch.float64, device=y.device)
+            else:
+                grid = np.zeros((T, ny, nx))
+        if tuple(grid.shape) != (T, ny, nx) or f64(grid) is not grid or _is_dev(grid) != dev:
+            raise ValueError("trace_density_update: grid must be a contiguous float64 (%d, %d, %d) array on Y's side"
+                             % (T, ny, nx))
+        check(self._lib.beatamd_trace_density_update(self._h, E, T, N, ptr(y), ptr(tm), float(deltat), ptr(ext), ny, nx,
+                                                     float(linewidth), ptr(grid)))
+        return grid
+
     def halfspace_displacements_batch(self, kinds, params, east, north, nu=0.25):
         """params (C, nsrc, 10) -> (C, nsrc, nobs, 3) = (north, east, up) [m]"""
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)

@@ -68,7 +68,29 @@ def posterior_variance_reductions(f, population, batch=512):
     return out
 
 
-def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, keep_synthetics=False):
+def density_extent(mn, mx, tmin, deltat):
+    """the default extent of ``fuzzy_waveforms`` (plotting/seismic.py:282-291) per target, from the envelope (T, N) that
+    ``ensemble_moments_finish`` returns: [tmin, tmin + (N - 1) deltat, -a, a], a = max(|min|, |max|) over the target's
+    samples.  numpy or torch-cuda in -> numpy (T, 4)."""
+    if _is_tensor(mn):
+        mn = mn.cpu().numpy()
+    if _is_tensor(mx):
+        mx = mx.cpu().numpy()
+    mn, mx = np.asarray(mn, dtype=np.float64), np.asarray(mx, dtype=np.float64)
+    T, N = mn.shape
+    tmin = np.broadcast_to(np.asarray(tmin, dtype=np.float64), (T,))
+    a = np.maximum(np.abs(mn.min(axis=1)), np.abs(mx.max(axis=1)))
+    return np.stack([tmin, tmin + float(N - 1) * float(deltat), -a, a], axis=1)
+
+
+def trace_density(Y, tmin, deltat, extent, grid_size=(500, 500), linewidth=7, grid=None, ctx=None):
+    """density grid (T, ny, nx) of the traces Y (E, T, N): ``Context.trace_density_update`` on the default context"""
+    ctx = ctx if ctx is not None else get_context()
+    return ctx.trace_density_update(Y, tmin, deltat, extent, grid_size, linewidth, grid)
+
+
+def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, keep_synthetics=False, density=None,
+                    linewidth=7, tmin=0.0, deltat=1.0):
     """``form_result_ensemble`` (plotting/seismic.py:395-451) on arrays: ``nensemble`` draws of ``population``
     (n, nparams) picked by ``ensemble_indices`` next to the point ``best`` (nparams,).  Returns
 
@@ -77,7 +99,12 @@ def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, 
       moments          dict wavemap index -> dict(mean, std, min, max: (T, N) numpy) over the ENSEMBLE's synthetics of
                        that wavemap (std as numpy.std, ddof = 0), accumulated on the device from the output of
                        ``f.synthetics``; with ``keep_synthetics`` also ``synthetics`` (E, T, N) on the host.
-                       wavemap_index: an index, a list of them, or None for every wavemap of the model."""
+                       wavemap_index: an index, a list of them, or None for every wavemap of the model.
+                       density = (ny, nx): also ``density`` (T, ny, nx), the fuzzy-waveform grid of the ensemble at
+                       ``linewidth`` (``Context.trace_density_update``), and its ``extent`` (T, 4) =
+                       ``density_extent(min, max, tmin, deltat)``; tmin a scalar or (T,), the time of sample 0.  The
+                       extent needs the whole ensemble's envelope, so the batches go through ``f.synthetics`` a second
+                       time."""
     ctx = _ctx_of(f)
     idx = ensemble_indices(int(population.shape[0]), nensemble)
     batch = max(int(batch), 1)
@@ -114,6 +141,14 @@ def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, 
             mean, std, mn, mx = ctx.ensemble_moments_finish(state, seen)
             entry = dict(mean=mean.cpu().numpy().reshape(T, N), std=std.cpu().numpy().reshape(T, N),
                          min=mn.cpu().numpy().reshape(T, N), max=mx.cpu().numpy().reshape(T, N))
+            if density is not None:
+                extent = density_extent(entry["min"], entry["max"], tmin, deltat)
+                ext_d, tmin_d = _to_device(ctx, extent), _to_device(ctx, extent[:, 0])
+                grid = None
+                for a in range(0, E, batch):
+                    syn = f.synthetics(ens[a:a + batch], wi)
+                    grid = ctx.trace_density_update(syn, tmin_d, deltat, ext_d, density, linewidth, grid)
+                entry["density"], entry["extent"] = grid.cpu().numpy(), extent
         if keep_synthetics:
             entry["synthetics"] = np.concatenate(kept) if kept else np.zeros((0, T, N))
         moments[wi] = entry

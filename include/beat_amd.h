@@ -36,12 +36,14 @@ extern "C" {
 #define BEATAMD_ENOMEM (-4)
 #define BEATAMD_ENAN (-5)     /* non-finite likelihood at stage 0 (metropolis.py:279-284)  */
 #define BEATAMD_ENOTPSD (-6)  /* covariance not positive definite (numpy.linalg.LinAlgError) */
+#define BEATAMD_EOUTSIDE (-8) /* a line leaves the density grid (plotting/common.py:733-739: TypeError) */
 #define BEATAMD_EBADCOV (-7)  /* weighted sample covariance of the population contains Inf/NaN
                                * (reference: ValueError of SMC.calc_covariance, sampler/smc.py:167-186) */
 
 /* ABI revision: bumped whenever an entry point changes its signature or an error code is added
  * (1.1: beatamd_weights_update gained kind/count in round 2; BEATAMD_EBADCOV).  beat_amd/_lib.py
- * refuses a library whose revision differs from the header it was written against. */
+ * refuses a library whose revision differs from the header it was written against.  BEATAMD_EOUTSIDE came with
+ * beatamd_trace_density_update inside revision 120: only that entry returns it. */
 #define BEATAMD_VERSION 120
 
 #define BEATAMD_NEAREST_NEIGHBOR 0 /* interpolation="nearest_neighbor" */
@@ -580,6 +582,25 @@ int beatamd_ensemble_moments_update(beatamd_ctx *ctx, int64_t C, int64_t M, cons
                                     int64_t n_seen);
 int beatamd_ensemble_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int64_t n, double *mean,
                                     double *std, double *min, double *max);
+/* replaces: fuzzy_waveforms' loop of draw_line_on_array over the traces of an ensemble
+ *           beat/plotting/seismic.py:255-316 (used at :503 with linewidth=7, grid_size=(500, 500)),
+ *           draw_line_on_array / _weighted_line   beat/plotting/common.py:619-801,
+ *           positions2idxs                        beat/utility.py:1556
+ *   Y [E,T,N] (synthetics as they leave beatamd_ffi_synthetics_batch), sample j of target t at time tmin[t] + j * deltat,
+ *   extent [T,4] = (xmin, xmax, ymin, ymax) per target, grid [T,ny,nx] (rows = amplitude, columns = time): every trace is
+ *   drawn as N - 1 anti-aliased segments of width `linewidth` into an image of its own, a pixel keeping the value of
+ *   the last segment that writes it, and the image is ADDED to grid[t]; traces in ensemble order.  Cell indices are
+ *   round((pos - min - step / 2) / step), half to even, step = (max - min) / (n - 1); the last row and the last column
+ *   are never written (the reference's limits).  All arithmetic is the reference's, operation by operation: the grid
+ *   equals draw_line_on_array's bit for bit, however the ensemble is cut into calls.
+ *   BEATAMD_EOUTSIDE (TypeError, check_line_in_grid): an index above ny - 1 / nx - 1.  Negative indices are clipped.
+ *   DEVIATIONS: a sample or extent that is not finite (or xmax <= xmin) is BEATAMD_EINVAL -- the reference casts NaN to an
+ *   arbitrary int32; an index below -32768 is BEATAMD_EOUTSIDE -- the reference's int32 products overflow there.
+ *   BEATAMD_EINVAL also for ny, nx outside 2 ... 4096, linewidth outside (0, 64], N < 2, deltat <= 0.  The call
+ *   synchronises to report these; after an error the grid is unspecified. */
+int beatamd_trace_density_update(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin,
+                                 double deltat, const double *extent, int64_t ny, int64_t nx, double linewidth,
+                                 double *grid);
 
 /* ---------------------------------------------------------------- library whitening ------
  * rows [nrows, N] (device, in place) <- rows . W^T, W [N,N] = chol_inverse of one dataset: the

@@ -1,0 +1,222 @@
+"""GPU tests of the density grids (k_trace_density): every comparison is ``array_equal`` -- against the grids of the
+reference's own ``draw_line_on_array`` (tests/golden/trace_density.npz) and, at shapes too big for a fixture, against the
+numpy restatement that tests/test_density_host.py pins to those grids (tests/density_ref.py)."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import density_ref as dref  # noqa: E402
+from test_density_host import case_shape  # noqa: E402
+from test_gpu_hypers import _dev, _specs  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trace_density.npz"), allow_pickle=False)
+KEYS = [str(k) for k in GOLDEN["keys"]]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import beat_amd
+    return beat_amd.get_context(0)
+
+
+def _traces(rng, E, T, N, rough=0.15):
+    """(E, T, N): a few sinusoids and noise -- flat stretches, steep flanks, both signs"""
+    j = np.arange(N)
+    f = rng.uniform(0.5, 6.0, (E, T, 3, 1)) / N
+    ph = rng.uniform(0, 2 * np.pi, (E, T, 3, 1))
+    a = rng.uniform(0.2, 1.0, (E, T, 3, 1))
+    return (a * np.sin(2 * np.pi * f * j + ph)).sum(axis=2) + rough * rng.standard_normal((E, T, N))
+
+
+def _problem(seed, E, T, N, rough=0.15, deltat=0.5):
+    rng = np.random.default_rng(seed)
+    Y = _traces(rng, E, T, N, rough)
+    tmin = rng.uniform(-20.0, 20.0, T)
+    return Y, tmin, deltat, dref.density_extent(Y.min(axis=0), Y.max(axis=0), tmin, deltat)
+
+
+def _both_sides(ctx, Y, tmin, deltat, extent, size, lw, grid=None):
+    """the grid from host arrays and from device tensors"""
+    host = ctx.trace_density_update(Y, tmin, deltat, extent, size, lw, None if grid is None else grid.copy())
+    assert isinstance(host, np.ndarray)
+    dev = ctx.trace_density_update(_dev(Y, ctx), _dev(tmin, ctx), deltat, _dev(extent, ctx), size, lw,
+                                   None if grid is None else _dev(grid, ctx))
+    assert dev.is_cuda
+    return host, dev.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------- 1 the reference's grids
+@pytest.mark.parametrize("key", KEYS)
+def test_1_fixture_cases_bit_for_bit(ctx, key):
+    N, ny, nx, lw = case_shape(key)
+    ref = GOLDEN[key + "_grid"]
+    for got in _both_sides(ctx, GOLDEN[key + "_Y"], GOLDEN[key + "_tmin"], float(GOLDEN[key + "_deltat"]),
+                           GOLDEN[key + "_extent"], (ny, nx), lw):
+        assert got.shape == ref.shape and got.dtype == np.float64
+        assert np.array_equal(got, ref), "%s: %d pixels differ" % (key, (got != ref).sum())
+
+
+# ------------------------------------------------------------------------------------------------- 2 batching
+@pytest.fixture(scope="module")
+def batching():
+    Y, tmin, deltat, extent = _problem(2, 70, 3, 65)
+    return Y, tmin, deltat, extent, dref.trace_density(Y, tmin, deltat, extent, (40, 24), 7)
+
+
+def test_2_calls_of_1_4_65_traces_are_one_call_of_70(ctx, batching):
+    Y, tmin, deltat, extent, ref = batching
+    one_h, one_d = _both_sides(ctx, Y, tmin, deltat, extent, (40, 24), 7)
+    assert np.array_equal(one_h, ref) and np.array_equal(one_d, ref)
+    grid = None
+    Yd, td, ed = _dev(Y, ctx), _dev(tmin, ctx), _dev(extent, ctx)
+    for a, b in ((0, 1), (1, 5), (5, 70)):
+        out = ctx.trace_density_update(Yd[a:b].contiguous(), td, deltat, ed, (40, 24), 7, grid)
+        assert grid is None or out is grid
+        grid = out
+    assert np.array_equal(grid.cpu().numpy(), ref)
+
+
+def test_2_degenerate_shapes(ctx, batching):
+    Y, tmin, deltat, extent, ref = batching
+    for got in _both_sides(ctx, Y[:, 1:2], tmin[1:2], deltat, extent[1:2], (40, 24), 7):          # T = 1
+        assert np.array_equal(got, ref[1:2])
+    first = dref.trace_density(Y[:1], tmin, deltat, extent, (40, 24), 7)
+    for got in _both_sides(ctx, Y[:1], tmin, deltat, extent, (40, 24), 7):                        # E = 1
+        assert np.array_equal(got, first)
+    none = ctx.trace_density_update(Y[:0], tmin, deltat, extent, (40, 24), 7)                      # E = 0: zeros
+    assert none.shape == (3, 40, 24) and not none.any()
+
+
+def test_2_a_given_grid_is_added_to(ctx, batching):
+    Y, tmin, deltat, extent, ref = batching
+    start = np.random.default_rng(3).uniform(0.0, 5.0, ref.shape)
+    expect = dref.trace_density(Y[:9], tmin, deltat, extent, (40, 24), 7, grid=start)
+    assert not np.array_equal(expect, start)
+    for got in _both_sides(ctx, Y[:9], tmin, deltat, extent, (40, 24), 7, grid=start):
+        assert np.array_equal(got, expect)
+
+
+# ------------------------------------------------------------------------------------------------- 3 strips
+@pytest.fixture(scope="module")
+def default_grid():
+    """the reference's default grid and line width: 500 x 500, 7; N = 120 (several columns per segment) and N = 4096
+    (many segments per column, mostly steep)"""
+    out = {}
+    for N, rough in ((120, 0.15), (4096, 0.3)):
+        Y, tmin, deltat, extent = _problem(N, 3, 2, N, rough)
+        out[N] = (Y, tmin, deltat, extent, dref.trace_density(Y, tmin, deltat, extent, (500, 500), 7))
+    return out
+
+
+@pytest.mark.parametrize("N", [120, 4096])
+def test_3_default_grid_500_x_500(ctx, default_grid, N):
+    Y, tmin, deltat, extent, ref = default_grid[N]
+    assert ref.any()
+    for got in _both_sides(ctx, Y, tmin, deltat, extent, (500, 500), 7):
+        assert np.array_equal(got, ref), "%d pixels differ" % (got != ref).sum()
+        assert not got[:, -1, :].any() and not got[:, :, -1].any()                 # 4: last row and column
+
+
+@pytest.mark.parametrize("N", [120, 4096])
+def test_3_result_does_not_depend_on_the_strip_width(ctx, default_grid, N, monkeypatch):
+    """BEATAMD_TD_STRIP (a context of the test suite re-reads it at every call): 1, 7 and 31 columns per workgroup (at
+    31 and N = 4096 the segments of a strip take two chunks) against the default"""
+    Y, tmin, deltat, extent, ref = default_grid[N]
+    Yd, td, ed = _dev(Y, ctx), _dev(tmin, ctx), _dev(extent, ctx)
+    for strip in ("1", "7", "31"):
+        monkeypatch.setenv("BEATAMD_TD_STRIP", strip)
+        got = ctx.trace_density_update(Yd, td, deltat, ed, (500, 500), 7).cpu().numpy()
+        assert np.array_equal(got, ref), "strip %s: %d pixels differ" % (strip, (got != ref).sum())
+
+
+@pytest.mark.parametrize("ny,nx,lw", [(33, 47, 7), (40, 24, 3), (12, 10, 1), (61, 33, 64), (4096, 23, 2), (700, 45, 5),
+                                       (2, 2, 1), (17, 4096, 3)])
+def test_3_grid_widths_off_the_strip_width(ctx, ny, nx, lw):
+    """widths that are no multiple of the strip (47, 24, 10; 33 = one strip and one column), the widest line, the
+    tallest grid (a strip of 9 columns: the owner map takes what the LDS has), a map above 64 KiB, the smallest and the
+    widest grid"""
+    Y, tmin, deltat, extent = _problem(ny + nx, 3, 2, 130)
+    ref = dref.trace_density(Y, tmin, deltat, extent, (ny, nx), lw)
+    for got in _both_sides(ctx, Y, tmin, deltat, extent, (ny, nx), lw):
+        assert np.array_equal(got, ref), "%d pixels differ" % (got != ref).sum()
+        assert not got[:, -1, :].any() and not got[:, :, -1].any()
+
+
+# ------------------------------------------------------------------------------------------------- 5 clipping
+def test_5_extent_narrower_than_the_data_on_the_low_side_clips(ctx):
+    Y, tmin, deltat, extent = _problem(5, 6, 3, 65)
+    extent[:, 0] += 0.3 * (extent[:, 1] - extent[:, 0])
+    extent[:, 2] *= 0.4
+    assert (Y.min(axis=(0, 2)) < extent[:, 2]).all()
+    ref = dref.trace_density(Y, tmin, deltat, extent, (40, 24), 7)
+    for got in _both_sides(ctx, Y, tmin, deltat, extent, (40, 24), 7):
+        assert np.array_equal(got, ref)
+
+
+# ------------------------------------------------------------------------------------------------- 6 errors
+def test_6_errors_and_the_next_call(ctx):
+    N, ny, nx, lw = (int(v) for v in GOLDEN["err_shape"])
+    tmin, deltat, extent = GOLDEN["err_tmin"], float(GOLDEN["err_deltat"]), GOLDEN["err_extent"]
+    good = np.where(np.isnan(GOLDEN["err_nan_Y"]), 0.0, GOLDEN["err_nan_Y"])
+    ref = dref.trace_density(good, tmin, deltat, extent, (ny, nx), lw)
+    for conv in (lambda a: a, lambda a: _dev(a, ctx)):
+        with pytest.raises(TypeError, match="outside of given grid"):
+            ctx.trace_density_update(conv(GOLDEN["err_above_Y"]), conv(tmin), deltat, conv(extent), (ny, nx), lw)
+        got = ctx.trace_density_update(conv(good), conv(tmin), deltat, conv(extent), (ny, nx), lw)
+        assert np.array_equal(got if isinstance(got, np.ndarray) else got.cpu().numpy(), ref)
+        with pytest.raises(ValueError):
+            ctx.trace_density_update(conv(GOLDEN["err_nan_Y"]), conv(tmin), deltat, conv(extent), (ny, nx), lw)
+        got = ctx.trace_density_update(conv(good), conv(tmin), deltat, conv(extent), (ny, nx), lw)
+        assert np.array_equal(got if isinstance(got, np.ndarray) else got.cpu().numpy(), ref)
+    far = extent.copy()                      # an index below -32768
+    far[:, 2] = far[:, 3] - 1e-6 * (far[:, 3] - far[:, 2])
+    with pytest.raises(TypeError):
+        ctx.trace_density_update(good * 0.0 - 1.0, tmin, deltat, far, (ny, nx), lw)
+    for size, width, Y in (((1, 10), 1, good), ((10, 4097), 1, good), ((10, 10), 0, good), ((10, 10), 65, good),
+                           ((10, 10), 1, good[:, :, :1])):
+        with pytest.raises(ValueError):
+            ctx.trace_density_update(Y, tmin, deltat, extent, size, width)
+    ctx.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------- 7 result_ensemble
+def test_7_result_ensemble_density(ctx):
+    from beat_amd.summary import density_extent, result_ensemble
+    from beat_amd.synthetic import build_problem, draw_population
+    spec = _specs()["toeplitz_ml"]
+    prob, host = build_problem(spec)
+    f = prob.compile(ctx)
+    try:
+        n, E = 530, 7
+        pop = draw_population(spec, host["layout"], host["lower"], host["upper"], n)
+        best = pop[17]
+        tmin = np.linspace(-3.0, 4.0, spec.T)
+        idx, vr, moments = result_ensemble(f, pop, best, E, keep_synthetics=True, batch=3, density=(40, 24), linewidth=7,
+                                           tmin=tmin, deltat=0.5)
+        m = moments[0]
+        assert set(m) == {"mean", "std", "min", "max", "synthetics", "density", "extent"}
+        extent = density_extent(m["min"], m["max"], tmin, 0.5)
+        assert m["extent"].shape == (spec.T, 4) and np.array_equal(m["extent"], extent)
+        assert np.array_equal(extent, dref.density_extent(m["synthetics"].min(axis=0), m["synthetics"].max(axis=0), tmin, 0.5))
+        ref = dref.trace_density(m["synthetics"], tmin, 0.5, extent, (40, 24), 7)
+        assert isinstance(m["density"], np.ndarray) and m["density"].shape == (spec.T, 40, 24)
+        assert ref.any() and np.array_equal(m["density"], ref)
+        # density=None: the keys and the bits of a run without the keyword
+        idx0, vr0, plain = result_ensemble(f, pop, best, E, keep_synthetics=True, batch=3)
+        assert set(plain[0]) == {"mean", "std", "min", "max", "synthetics"}
+        assert np.array_equal(idx0, idx) and np.array_equal(vr0, vr)
+        syn = _dev(m["synthetics"], ctx)
+        state, seen = None, 0
+        for a in range(0, E, 3):
+            state, seen = ctx.ensemble_moments_update(syn[a:a + 3].reshape(-1, spec.T * spec.N), state, seen)
+        direct = [a.cpu().numpy().reshape(spec.T, spec.N) for a in ctx.ensemble_moments_finish(state, seen)]
+        for key, r in zip(("mean", "std", "min", "max"), direct):
+            assert np.array_equal(plain[0][key], r) and np.array_equal(m[key], r)
+        assert np.array_equal(plain[0]["synthetics"], m["synthetics"])
+    finally:
+        f.release()
