@@ -22,6 +22,7 @@ Reference entry points exercised (file:line under /root/reference):
   beat/sampler/pt.py:37-73                     tune
   beat/utility.py:1034-1138                    ensure_cov_psd
   data/examples/Laquila/geodetic_data.pkl      (arrays only)
+and, without the reference: oracle/okada_mp.py (mpmath) -> okada_mp.npz
 """
 import os
 import sys
@@ -342,6 +343,17 @@ def gen_laquila():
     save("laquila_geodetic", **out)
 
 
+# ---------------------------------------------------------------- multi-precision Okada / Mogi
+def gen_okada_mp():
+    """half-space displacements at 60 digits (oracle/okada_mp.py, mpmath; nothing of the reference is involved): the
+    rows of build_rows() -- inputs [es, ns, depth, strike, dip, rake, L, W, slip, f, nu, e, n], the source kind and
+    the group of each row -- and (ue, un, uz) rounded to float64"""
+    import okada_mp
+    groups, kinds, rows = okada_mp.build_rows()
+    save("okada_mp", group=groups, kind=kinds, inputs=rows, u=okada_mp.evaluate_rows(kinds, rows),
+         columns=np.array(okada_mp.COLUMNS), dps=np.array(okada_mp.DPS))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:          # regenerate selected fixtures only: gen_golden.py sweep_ties ...
         for what in sys.argv[1:]:
@@ -357,3 +369,4 @@ if __name__ == "__main__":
     gen_smc()
     gen_noise_cov()
     gen_laquila()
+    gen_okada_mp()

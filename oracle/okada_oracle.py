@@ -24,9 +24,21 @@ shear = slip*(1-|f|) split by rake into strike/dip components, opening = slip*f.
 import numpy as np
 
 
+# |cos(dip)| up to which I1..I5 take Okada's vertical expressions, as in geometry.hip: the general ones (in the form
+# of _I below) round like eps / |cos(dip)|, the vertical ones are off by ~5e-3 |cos(dip)| slip; they cross here at
+# ~5e-10 slip (5.7e-6 deg from vertical).  oracle/okada_mp.py is the reference without this switch.
+VERTICAL_COS = 1e-7
+
+
 def _chinnery(f, x, p, L, W, q, dip, nu):
-    return (f(x, p, q, dip, nu) - f(x, p - W, q, dip, nu)
-            - f(x - L, p, q, dip, nu) + f(x - L, p - W, q, dip, nu))
+    """f(x,p) - f(x,p-W) - f(x-L,p) + f(x-L,p-W); f -> (corner term, count of pi/2 in its I5 arc tangent): the
+    counts are summed as integers and enter once (_I)"""
+    tot, K = 0.0, 0.0
+    for sg, xi, eta in ((1.0, x, p), (-1.0, x, p - W), (-1.0, x - L, p), (1.0, x - L, p - W)):
+        u, s, coef = f(xi, eta, q, dip, nu)
+        tot = tot + sg * u
+        K = K + sg * s
+    return tot + np.multiply.outer(coef, K)
 
 
 def _common(xi, eta, q, dip):
@@ -38,25 +50,39 @@ def _common(xi, eta, q, dip):
 
 
 def _I(xi, eta, q, dip, nu, R, yt, dt):
-    """Okada (1985) eqs (28)-(29): I1..I5 with mu/(lambda+mu) = 1-2nu"""
+    """Okada (1985) eqs (28)-(29): I1..I5 with mu/(lambda+mu) = 1-2nu -> (I1, I2, I3, I4, I5, s, c5).
+
+    As printed, I1 and I3 are differences of terms ~ 1/cos^2(dip) and round like eps/cos^2(dip).  Two identities
+    take one power off (geometry.hip uses the same):
+      ln(R+d~) - sin ln(R+eta) = log1p(x) + cos t ln(R+eta),  x = -cos (eta t + q)/(R+eta),  t = cos/(1+sin)
+      atan(N/D) = s pi/2 - atan(D/N),  s = sgn(N) sgn(D)
+    I1 and I5 are returned WITHOUT their multiples of pi/2: I5 = (returned) + c5 s, I1 = (returned) - sin/cos c5 s;
+    _chinnery sums s over the corners exactly (it cancels wherever N keeps its sign)."""
     sd, cd = np.sin(dip), np.cos(dip)
     a = 1.0 - 2.0 * nu
     X = np.sqrt(xi ** 2 + q ** 2)
-    if np.abs(cd) > 1e-12:
+    lnRe = np.log(R + eta)
+    if np.abs(cd) > VERTICAL_COS:
+        N = eta * (X + q * cd) + X * (R + X) * sd
+        D = xi * (R + X) * cd
+        none = (np.abs(xi) < 1e-12) | (N == 0.0)
         with np.errstate(divide="ignore", invalid="ignore"):
-            I5 = a * 2.0 / cd * np.arctan((eta * (X + q * cd) + X * (R + X) * sd)
-                                          / (xi * (R + X) * cd))
-        I5 = np.where(np.abs(xi) < 1e-12, 0.0, I5)
-        I4 = a / cd * (np.log(R + dt) - sd * np.log(R + eta))
-        I3 = a * (yt / (cd * (R + dt)) - np.log(R + eta)) + sd / cd * I4
+            I5 = np.where(none, 0.0, a * 2.0 / cd * -np.arctan(D / N))
+        s = np.where(none, 0.0, np.sign(N) * np.sign(D))
+        c5 = a * 2.0 / cd * (np.pi / 2)
+        t = cd / (1.0 + sd)
+        lr = np.log1p(-cd * (eta * t + q) / (R + eta)) / cd
+        I4 = a * (lr + t * lnRe)
+        I3 = a * (yt / (cd * (R + dt)) + sd / cd * lr - lnRe / (1.0 + sd))
         I1 = a * (-xi / (cd * (R + dt))) - sd / cd * I5
     else:
         I5 = -a * xi * sd / (R + dt)
         I4 = -a * q / (R + dt)
-        I3 = a / 2.0 * (eta / (R + dt) + yt * q / (R + dt) ** 2 - np.log(R + eta))
+        I3 = a / 2.0 * (eta / (R + dt) + yt * q / (R + dt) ** 2 - lnRe)
         I1 = -a / 2.0 * xi * q / (R + dt) ** 2
-    I2 = a * (-np.log(R + eta)) - I3
-    return I1, I2, I3, I4, I5
+        s, c5 = np.zeros_like(I5), 0.0
+    I2 = a * (-lnRe) - I3
+    return I1, I2, I3, I4, I5, s, c5
 
 
 def _atan_term(xi, eta, q, R):
@@ -67,32 +93,35 @@ def _atan_term(xi, eta, q, R):
 
 def _ss(xi, eta, q, dip, nu):
     sd, cd, R, yt, dt = _common(xi, eta, q, dip)
-    I1, I2, I3, I4, I5 = _I(xi, eta, q, dip, nu, R, yt, dt)
+    I1, I2, I3, I4, I5, s, c5 = _I(xi, eta, q, dip, nu, R, yt, dt)
     at = _atan_term(xi, eta, q, R)
     ux = xi * q / (R * (R + eta)) + at + I1 * sd
     uy = yt * q / (R * (R + eta)) + q * cd / (R + eta) + I2 * sd
     uz = dt * q / (R * (R + eta)) + q * sd / (R + eta) + I4 * sd
-    return np.array([ux, uy, uz])
+    k1 = -sd / cd * c5 if c5 else 0.0                   # what one count of pi/2 adds to I1
+    return np.array([ux, uy, uz]), s, np.array([k1 * sd, 0.0, 0.0])
 
 
 def _ds(xi, eta, q, dip, nu):
     sd, cd, R, yt, dt = _common(xi, eta, q, dip)
-    I1, I2, I3, I4, I5 = _I(xi, eta, q, dip, nu, R, yt, dt)
+    I1, I2, I3, I4, I5, s, c5 = _I(xi, eta, q, dip, nu, R, yt, dt)
     at = _atan_term(xi, eta, q, R)
     ux = q / R - I3 * sd * cd
     uy = yt * q / (R * (R + xi)) + cd * at - I1 * sd * cd
     uz = dt * q / (R * (R + xi)) + sd * at - I5 * sd * cd
-    return np.array([ux, uy, uz])
+    k1 = -sd / cd * c5 if c5 else 0.0
+    return np.array([ux, uy, uz]), s, np.array([0.0, -k1 * sd * cd, -c5 * sd * cd])
 
 
 def _tf(xi, eta, q, dip, nu):
     sd, cd, R, yt, dt = _common(xi, eta, q, dip)
-    I1, I2, I3, I4, I5 = _I(xi, eta, q, dip, nu, R, yt, dt)
+    I1, I2, I3, I4, I5, s, c5 = _I(xi, eta, q, dip, nu, R, yt, dt)
     at = _atan_term(xi, eta, q, R)
     ux = q ** 2 / (R * (R + eta)) - I3 * sd ** 2
     uy = -dt * q / (R * (R + xi)) - sd * (xi * q / (R * (R + eta)) - at) - I1 * sd ** 2
     uz = yt * q / (R * (R + xi)) + cd * (xi * q / (R * (R + eta)) - at) - I5 * sd ** 2
-    return np.array([ux, uy, uz])
+    k1 = -sd / cd * c5 if c5 else 0.0
+    return np.array([ux, uy, uz]), s, np.array([0.0, -k1 * sd ** 2, -c5 * sd ** 2])
 
 
 def okada85_local(x, y, d, dip_deg, L, W, U1, U2, U3, nu=0.25):
