@@ -1,16 +1,9 @@
 // capi.cpp -- the extern "C" entry points of include/beat_amd.h (host side of the engine).
-#include "kernels.hpp"
+#include "model.hpp"
 
 using namespace beatamd;
 
 namespace {
-
-template <class T>
-T *get_obj(std::vector<std::unique_ptr<T>> &v, int32_t id)
-{
-    if (id < 0 || (size_t)id >= v.size()) return nullptr;
-    return v[id].get();
-}
 
 template <class T>
 int32_t add_obj(std::vector<std::unique_ptr<T>> &v, std::unique_ptr<T> o)
@@ -22,15 +15,6 @@ int32_t add_obj(std::vector<std::unique_ptr<T>> &v, std::unique_ptr<T> o)
         }
     v.push_back(std::move(o));
     return (int32_t)v.size() - 1;
-}
-
-// *_destroy: drain the stream, then the object goes and frees its device arrays
-template <class T>
-int destroy_obj(beatamd_ctx *ctx, std::vector<std::unique_ptr<T>> &v, int32_t id)
-{
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    v[id].reset();
-    return BEATAMD_OK;
 }
 
 // host copy of a small argument array that may live on either side
@@ -52,256 +36,55 @@ int host_copy(beatamd_ctx *ctx, const T *p, size_t n, std::vector<T> &out)
     BA_CHECK((ctx) != nullptr, BEATAMD_EINVAL, "ctx is NULL");        \
     BA_HIP(hipSetDevice((ctx)->device))
 
-// quad[c,d] = ||W_d x||^2 for one weight set, x(c,d,k) = X[c*xs_c + d*xs_d + k]
-int wset_quad(beatamd_ctx *ctx, const WeightSet &w, int64_t C, const double *X, int64_t xs_c,
-              int64_t xs_d, double *quad)
+// ---- object lookups: the id's object, or EINVAL with the message that callers match on
+template <class T>
+int find_obj(std::vector<std::unique_ptr<T>> &v, int32_t id, const char *what, T **out)
 {
-    if (w.kind == BEATAMD_W_SCALAR)
-        return launch_scalar_quad(ctx, C, w.nd, w.M, X, xs_c, xs_d, w.w.get(), quad);
-    // banded whitening operators (the reference's "exponential" noise structure gives bidiagonal ones): two products per
-    // sample instead of a row of the dense matrix
-    if (w.band >= 0 && w.wb && GfKnobs::get(gf_knobs(ctx).qf_band, 1) != 0)
-        return launch_quadform_banded(ctx, w.wb.get(), w.band, w.M, w.nd, C, X, xs_c, xs_d, quad, w.nd);
-    QuadformCall q;
-    q.A = w.w.get();
-    q.a_stride = w.M * w.M;
-    q.M = w.M;
-    q.nd = w.nd;
-    q.C = C;
-    q.X = X;
-    q.xs_c = xs_c;
-    q.xs_d = xs_d;
-    q.upper_tri = w.upper_tri;
-    q.quad = quad;
-    q.q_stride = w.nd;
-    return launch_quadform(ctx, q);
+    *out = get_obj(v, id);
+    BA_CHECK(*out, BEATAMD_EINVAL, "unknown %s %d", what, id);
+    return BEATAMD_OK;
+}
+// *_destroy: drain the stream, then the object goes and frees its device arrays
+template <class T>
+int destroy_obj(beatamd_ctx *ctx, std::vector<std::unique_ptr<T>> &v, int32_t id, const char *what)
+{
+    T *o;
+    BA_TRY(find_obj(v, id, what, &o));
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    v[id].reset();
+    return BEATAMD_OK;
+}
+int find_model(beatamd_ctx *ctx, int32_t id, FfiModel **m) { return find_obj(ctx->models, id, "model", m); }
+int find_wset(beatamd_ctx *ctx, int32_t id, WeightSet **w) { return find_obj(ctx->wsets, id, "weight set", w); }
+int find_seislib(beatamd_ctx *ctx, int32_t id, SeisStore **l) { return find_obj(ctx->seislibs, id, "GF library", l); }
+int find_geolib(beatamd_ctx *ctx, int32_t id, GeoLib **l) { return find_obj(ctx->geolibs, id, "geodetic GF library", l); }
+int find_lap(beatamd_ctx *ctx, int32_t id, Laplacian **l) { return find_obj(ctx->laps, id, "laplacian", l); }
+int find_hyper(beatamd_ctx *ctx, int32_t id, HyperModel **h) { return find_obj(ctx->hypers, id, "hyper model", h); }
+
+// *flag: every matrix of the stack W [nd, M, M] has exact zeros below its diagonal (one host synchronisation)
+int upper_tri_flag(beatamd_ctx *ctx, const double *W, int64_t nd, int64_t M, int *flag)
+{
+    int *d_flag;
+    BA_TRY(ctx->scratch(SL_MISC, 16, &d_flag));
+    BA_TRY(launch_check_upper_tri(ctx, W, nd, M, d_flag));
+    BA_HIP(hipMemcpyAsync(flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    return BEATAMD_OK;
 }
 
-// columns of the hyper model's misfit vector: one per seismic dataset, one per geodetic dataset, one per slip variable
-// of the Laplacian
-int64_t model_nterm(const FfiModel &m)
+// sum and maximum of the `which`-th per-(group, target, patch) counter array of the most recent chain-shared launch
+int gs_counters(beatamd_ctx *ctx, int which, int64_t *total, int64_t *max)
 {
-    int64_t n = 0;
-    for (auto &w : m.wavemaps) n += w.T;
-    if (m.has_geo) n += (int64_t)m.geo.sizes.size();
-    if (m.lap >= 0) n += m.layout.nvar;
-    return n;
-}
-
-// datasets of the model: the first columns of the misfit vector (no Laplacian columns)
-int64_t model_ndata(const FfiModel &m)
-{
-    int64_t n = 0;
-    for (auto &w : m.wavemaps) n += w.T;
-    if (m.has_geo) n += (int64_t)m.geo.sizes.size();
-    return n;
-}
-
-// the cached |W d|^2 of every model go when weights, data, library rows or corrections change (a weight set or a
-// whitened library may serve several models: all are dropped, the next beatamd_ffi_obs_quads recomputes)
-void drop_obs_quads(beatamd_ctx *ctx)
-{
-    for (auto &m : ctx->models)
-        if (m) m->obs_quads_valid = false;
-}
-
-// what remains after the composites wrote their columns: the `like` sum.  A caller that passes a
-// LikeTail does that sum itself (the Metropolis step folds it into its accept kernel)
-struct LikeTail {
-    LikeGroups grp;
-    const int32_t *chain_bad = nullptr;
-};
-
-// logp_forw_func on device pointers.  `active` (device [C], nullable): chains whose rows of LL the caller will not read;
-// kernels that honour it skip those chains and leave their rows unspecified (the fused Metropolis step passes the
-// in-box flags of its proposals)
-// `llks` (device [C, nterm], nullable): the hyper model's cached misfits instead of the likelihood -- every composite
-// stops in front of its epilogue and stores the quadratic form it would have handed to it (update_llks: seismic.py:510-525,
-// geodetic.py:429-444, laplacian.py:141-154); LL is then not written and the hyper-parameters are not read
-int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, double *LL,
-                    LikeTail *tail = nullptr, const int32_t *active = nullptr, double *llks = nullptr)
-{
-    const int64_t nllk = m.nllk();
-    const int64_t nterm = model_nterm(m);
-    int64_t tcol = 0;
-    const int64_t np = m.layout.nparams;
-    void *p = nullptr;
-    LikeGroups grp;
-    int64_t col = 0;
-
-    ChainVec slips[4];
-    for (int v = 0; v < m.layout.nvar; v++) slips[v] = ChainVec{Q, np, m.layout.slip_off[v]};
-
-    // chains whose indices leave the library grid / the patch grid: like = NaN (rejected by the
-    // Metropolis step) in addition to the status word that the next synchronisation raises
-    // (only the seismic index maps and the sweep flag chains: without wavemaps there is nothing to clear)
-    int32_t *chain_bad = nullptr;
-    if (!m.wavemaps.empty()) {
-        BA_TRY(ctx->get_scratch(SL_CHAINBAD, (size_t)C * sizeof(int32_t), &p));
-        chain_bad = (int32_t *)p;
-        BA_HIP(hipMemsetAsync(chain_bad, 0, (size_t)C * sizeof(int32_t), ctx->stream));
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<uint32_t> n((size_t)ctx->gs_ngtp);
+    BA_HIP(hipMemcpy(n.data(), (const uint32_t *)ctx->scratch_bufs[SL_GS_UCOUNT].p + which * ctx->gs_ngtp,
+                     n.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *total = *max = 0;
+    for (uint32_t u : n) {
+        *total += u;
+        *max = std::max<int64_t>(*max, u);
     }
-
-    if (!m.wavemaps.empty()) {
-        BA_TRY(ctx->get_scratch(SL_ST0, (size_t)C * m.P * sizeof(double), &p));
-        double *st0 = (double *)p;
-        BA_TRY(launch_sweep_model(ctx, m, Q, C, st0, chain_bad));
-        for (auto &wm : m.wavemaps) {
-            WeightSet *ws = get_obj(ctx->wsets, wm.wset);
-            BA_CHECK(ws, BEATAMD_EINVAL, "wavemap refers to a destroyed weight set");
-            GfStackCall k;
-            k.nvar = m.layout.nvar;
-            for (int v = 0; v < k.nvar; v++) {
-                k.libs[v] = get_obj(ctx->seislibs, wm.libs[v]);
-                BA_CHECK(k.libs[v] && k.libs[v]->g, BEATAMD_EINVAL,
-                         "wavemap refers to a destroyed / empty GF library");
-                k.slips[v] = slips[v];
-            }
-            k.durations = ChainVec{Q, np, m.layout.durations_off};
-            k.st.starttimes0 = st0;
-            k.st.Q = Q;
-            k.st.nparams = np;
-            k.order_key[0] = ChainVec{Q, np, m.layout.nuc_strike_off};   // (scheduling hint of k_gfstack_runs)
-            k.order_key[1] = ChainVec{Q, np, m.layout.nuc_dip_off};
-            k.st.shift_off = wm.shift_off.get();
-            k.st.nslot = wm.nslot; k.st.tslot = wm.tslot.get(); k.st.slot_shift_off = wm.slot_shift_off.get();
-            k.st.chain_bad = chain_bad;
-            k.active = active;
-            k.interp = wm.interp;
-            k.f32 = wm.f32;
-            k.C = C;
-            k.data = wm.data.get();
-            BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * wm.T * sizeof(double), &p));
-            double *quad = (double *)p;
-            if (ws->kind == BEATAMD_W_SCALAR) {
-                k.mode = GF_RESID_SCALAR;
-                k.wscalar = ws->w.get();
-                k.quad = quad;
-                BA_TRY(launch_gfstack(ctx, k));
-            } else if (ws->band == 1 && ws->wb && ws->M == wm.N && ws->nd == wm.T &&
-                       GfKnobs::get(gf_knobs(ctx).qf_band, 1) != 0) {
-                // bidiagonal whitening operators (the "exponential" noise structure): the misfit rides in the stacking
-                // kernel where it has the epilogue, else residual store + k_quadform_banded (launch_gfstack decides)
-                k.mode = GF_RESID_BAND1;
-                k.band_w = ws->wb.get();
-                k.quad = quad;
-                BA_TRY(ctx->get_scratch(SL_RESID, (size_t)C * wm.T * wm.N * sizeof(double), &p));
-                k.out = (double *)p;
-                BA_TRY(launch_gfstack(ctx, k));
-            } else {
-                k.mode = GF_RESID_STORE;
-                BA_TRY(ctx->get_scratch(SL_RESID, (size_t)C * wm.T * wm.N * sizeof(double), &p));
-                k.out = (double *)p;
-                BA_TRY(launch_gfstack(ctx, k));
-                BA_TRY(wset_quad(ctx, *ws, C, k.out, wm.T * wm.N, wm.N, quad));
-            }
-            if (llks)
-                BA_TRY(launch_store_misfits(ctx, C, wm.T, quad, llks + tcol, nterm));
-            else
-                BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.N, quad, ws->slog.get(), HpSrc{Q, np, wm.hp_off.get()},
-                                         LL + col, nllk));
-            col += wm.T;
-            tcol += wm.T;
-        }
-        grp.end[grp.n++] = (int32_t)col;
-    }
-    if (m.has_geo) {
-        Geodetic &g = m.geo;
-        BA_TRY(ctx->get_scratch(SL_MU, (size_t)C * g.Nobs * 2 * sizeof(double), &p));
-        double *mu = (double *)p, *res = mu + C * g.Nobs;
-        if (m.geo_is_geometry) {
-            // synthetics, line of sight and weighted residual in one kernel
-            BA_TRY(launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data.get(), g.odws.get(), res, g.corr));
-        } else {
-            // every slip variable's G.T . slips in one launch (geodetic.py:1065-1070 sums them)
-            const GeoLib *gls[4] = {nullptr, nullptr, nullptr, nullptr};
-            BA_CHECK(m.layout.nvar <= 4, BEATAMD_EINVAL, "geodetic composite: more than 4 slip variables");
-            for (int v = 0; v < m.layout.nvar; v++) {
-                gls[v] = get_obj(ctx->geolibs, g.libs[v]);
-                BA_CHECK(gls[v], BEATAMD_EINVAL, "geodetic composite refers to a destroyed GF library");
-            }
-            BA_TRY(launch_geo_stack(ctx, gls, m.layout.nvar, C, slips, 0, mu));
-            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data.get(), g.odws.get(), mu, res, Q, np, g.corr));
-        }
-        // small dense datasets (SAR scenes / GNSS of a few hundred points): every dataset's
-        // quadratic form and MVN epilogue in one launch; otherwise per dataset on the 64-row tiles
-        QuadformSmallCall qs;
-        bool small = g.sizes.size() <= 8;
-        int64_t o = 0;
-        for (size_t d = 0; d < g.sizes.size(); d++) {
-            WeightSet *ws = get_obj(ctx->wsets, g.wsets[d]);
-            BA_CHECK(ws && ws->nd == 1 && ws->M == g.sizes[d], BEATAMD_EINVAL,
-                     "geodetic dataset %zu: weight set missing or of the wrong size", d);
-            small = small && ws->kind != BEATAMD_W_SCALAR;
-            if (small) {
-                qs.A[d] = ws->w.get(); qs.M[d] = ws->M; qs.xoff[d] = o; qs.upper_tri[d] = ws->upper_tri;
-                qs.slog[d] = ws->slog.get(); qs.hp_off[d] = g.hp_off.get() + d;
-            }
-            o += g.sizes[d];
-        }
-        small = small && quadform_small_applicable((int)g.sizes.size(), qs.M);
-        if (small) {
-            qs.nd = (int)g.sizes.size();
-            qs.C = C; qs.X = res; qs.xs_c = g.Nobs; qs.Q = Q; qs.nparams = np;
-            qs.LL = LL + col; qs.ld = nllk;
-            if (llks) {
-                qs.LL = llks + tcol; qs.ld = nterm; qs.misfit_only = true;
-            }
-            BA_TRY(launch_quadform_small(ctx, qs));
-        } else {
-            BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * sizeof(double), &p));
-            double *quad = (double *)p;
-            o = 0;
-            for (size_t d = 0; d < g.sizes.size(); d++) {
-                WeightSet *ws = get_obj(ctx->wsets, g.wsets[d]);
-                BA_TRY(wset_quad(ctx, *ws, C, res + o, g.Nobs, 0, quad));
-                if (llks)
-                    BA_TRY(launch_store_misfits(ctx, C, 1, quad, llks + tcol + (int64_t)d, nterm));
-                else
-                    BA_TRY(launch_mvn_finish(ctx, C, 1, ws->M, quad, ws->slog.get(),
-                                             HpSrc{Q, np, g.hp_off.get() + d}, LL + col + (int64_t)d, nllk));
-                o += g.sizes[d];
-            }
-        }
-        col += (int64_t)g.sizes.size();
-        tcol += (int64_t)g.sizes.size();
-        grp.end[grp.n++] = (int32_t)col;
-    }
-    if (m.lap >= 0) {
-        Laplacian *lp = get_obj(ctx->laps, m.lap);
-        BA_CHECK(lp, BEATAMD_EINVAL, "model refers to a destroyed laplacian");
-        const int nvar = m.layout.nvar;
-        BA_TRY(ctx->get_scratch(SL_SLIPS, (size_t)C * nvar * lp->P * sizeof(double), &p));
-        double *sl = (double *)p;
-        BA_TRY(launch_gather_slips(ctx, C, nvar, lp->P, slips, sl));
-        BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * nvar * sizeof(double), &p));
-        double *quad = (double *)p;
-        QuadformCall q;
-        q.A = lp->L.get(); q.a_stride = 0; q.M = lp->P; q.nd = nvar; q.C = C;
-        q.X = sl; q.xs_c = nvar * lp->P; q.xs_d = lp->P;
-        q.quad = quad; q.q_stride = nvar;
-        BA_TRY(launch_quadform(ctx, q));
-        if (llks)   // one column per slip variable: the hyper model keeps them apart (laplacian.py:151-170)
-            BA_TRY(launch_store_misfits(ctx, C, nvar, quad, llks + tcol, nterm));
-        else
-            BA_TRY(launch_laplacian_finish(ctx, C, nvar, lp->P, lp->logdet, quad,
-                                           HpSrc{Q + m.layout.h_laplacian_off, np, nullptr}, LL + col,
-                                           nllk));
-        col += 1;
-        tcol += nvar;
-        grp.end[grp.n++] = (int32_t)col;
-    }
-    BA_CHECK(col == nllk - 1, BEATAMD_EINVAL, "internal: llk layout mismatch");
-    if (llks) {
-        BA_CHECK(tcol == nterm, BEATAMD_EINVAL, "internal: misfit layout mismatch");
-        return launch_misfits_mark_bad(ctx, C, nterm, llks, chain_bad);
-    }
-    if (tail) {
-        tail->grp = grp;
-        tail->chain_bad = chain_bad;
-        return BEATAMD_OK;
-    }
-    return launch_like_sum(ctx, C, nllk, grp, LL, chain_bad);
+    return BEATAMD_OK;
 }
 
 }  // namespace
@@ -351,8 +134,8 @@ int beatamd_seis_gflib_create(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t D,
 int beatamd_seis_gflib_set_split_targets(beatamd_ctx *ctx, int32_t lib_id, int64_t ntargets)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
+    SeisStore *l;
+    BA_TRY(find_seislib(ctx, lib_id, &l));
     BA_CHECK(ntargets >= 0, BEATAMD_EINVAL, "gflib_set_split_targets: negative target count");
     BA_CHECK(ntargets == 0 || ntargets >= l->T, BEATAMD_EINVAL,
              "gflib_set_split_targets: %lld targets, fewer than the library's %lld", (long long)ntargets, (long long)l->T);
@@ -429,8 +212,8 @@ int beatamd_seis_gflib_upload(beatamd_ctx *ctx, int32_t lib_id, const double *sr
                               int64_t count)
 {
     ENTER(ctx);
-    SeisStore *l = get_obj(ctx->seislibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
+    SeisStore *l;
+    BA_TRY(find_seislib(ctx, lib_id, &l));
     BA_CHECK(src && offset >= 0 && count >= 0 && offset + count <= l->elems(), BEATAMD_EINVAL,
              "gflib_upload: range [%lld, %lld) outside the library (%lld elements)",
              (long long)offset, (long long)(offset + count), (long long)l->elems());
@@ -444,8 +227,8 @@ int beatamd_seis_gflib_upload(beatamd_ctx *ctx, int32_t lib_id, const double *sr
 int beatamd_seis_gflib_adopt(beatamd_ctx *ctx, int32_t lib_id, double *device_ptr)
 {
     ENTER(ctx);
-    SeisStore *l = get_obj(ctx->seislibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
+    SeisStore *l;
+    BA_TRY(find_seislib(ctx, lib_id, &l));
     BA_CHECK(device_ptr && is_device_ptr(device_ptr), BEATAMD_EINVAL,
              "gflib_adopt needs a device pointer");
     BA_CHECK(((uintptr_t)device_ptr & 15) == 0, BEATAMD_EINVAL,
@@ -470,9 +253,7 @@ int beatamd_seis_gflib_device_ptr(beatamd_ctx *ctx, int32_t lib_id, double **dev
 int beatamd_seis_gflib_destroy(beatamd_ctx *ctx, int32_t lib_id)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
-    return destroy_obj(ctx, ctx->seislibs, lib_id);
+    return destroy_obj(ctx, ctx->seislibs, lib_id, "GF library");
 }
 
 int beatamd_seis_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C,
@@ -480,8 +261,8 @@ int beatamd_seis_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C,
                                  const double *slips, int32_t interpolation, double *out)
 {
     ENTER(ctx);
-    SeisLib *l = get_obj(ctx->seislibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown GF library %d", lib_id);
+    SeisStore *l;
+    BA_TRY(find_seislib(ctx, lib_id, &l));
     BA_CHECK(l->g, BEATAMD_EINVAL, "GF library %d holds no data (upload or adopt first)", lib_id);
     BA_CHECK(durations && starttimes && slips && out, BEATAMD_EINVAL, "stack_all: NULL array");
     BA_CHECK(interpolation == BEATAMD_NEAREST_NEIGHBOR || interpolation == BEATAMD_MULTILINEAR,
@@ -495,17 +276,7 @@ int beatamd_seis_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C,
     BA_TRY(st.in(starttimes, (size_t)C * l->T * l->P, &d_st));
     BA_TRY(st.in(slips, (size_t)C * l->P, &d_sl));
     BA_TRY(st.out(out, (size_t)C * l->T * l->N, &d_o));
-    GfStackCall k;
-    k.libs[0] = l;
-    k.nvar = 1;
-    k.slips[0] = ChainVec{d_sl, l->P, 0};
-    k.durations = ChainVec{d_du, l->P, 0};
-    k.st.explicit_st = d_st;
-    k.interp = interpolation;
-    k.C = C;
-    k.mode = GF_STORE_SYN;
-    k.out = d_o;
-    BA_TRY(launch_gfstack(ctx, k));
+    BA_TRY(stack_all(ctx, *l, C, d_du, d_st, d_sl, interpolation, d_o));
     return st.finish();
 }
 
@@ -525,17 +296,15 @@ int beatamd_geo_gflib_create(beatamd_ctx *ctx, int64_t P, int64_t Nobs, const do
 int beatamd_geo_gflib_destroy(beatamd_ctx *ctx, int32_t lib_id)
 {
     ENTER(ctx);
-    GeoLib *l = get_obj(ctx->geolibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown geodetic GF library %d", lib_id);
-    return destroy_obj(ctx, ctx->geolibs, lib_id);
+    return destroy_obj(ctx, ctx->geolibs, lib_id, "geodetic GF library");
 }
 
 int beatamd_geo_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C, const double *slips,
                                 int32_t accumulate, double *out)
 {
     ENTER(ctx);
-    GeoLib *l = get_obj(ctx->geolibs, lib_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown geodetic GF library %d", lib_id);
+    GeoLib *l;
+    BA_TRY(find_geolib(ctx, lib_id, &l));
     BA_CHECK(slips && out && C >= 0, BEATAMD_EINVAL, "geo_stack_all: bad argument");
     if (C == 0) return BEATAMD_OK;
     Staging st(ctx);
@@ -559,17 +328,14 @@ static int wset_fill(beatamd_ctx *ctx, WeightSet *w, const double *weights, cons
     BA_HIP(hipStreamSynchronize(ctx->stream));
     w->upper_tri = 0;
     if (w->kind == BEATAMD_W_DENSE) {
-        void *p = nullptr;
-        BA_TRY(ctx->get_scratch(SL_MISC, 64, &p));
-        BA_TRY(launch_check_upper_tri(ctx, w->w.get(), w->nd, w->M, (int *)p));
         int flag = 0;
-        BA_HIP(hipMemcpyAsync(&flag, p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        BA_HIP(hipStreamSynchronize(ctx->stream));
+        BA_TRY(upper_tri_flag(ctx, w->w.get(), w->nd, w->M, &flag));
         w->upper_tri = flag;
         // banded?  (upper-triangular with nothing beyond a few columns right of the diagonal)
         w->band = -1;
         w->wb.reset();
         if (flag && w->M > 2 * QF_BAND_LIMIT) {
+            void *p = nullptr;   // sized in bytes on purpose: launch_band_detect lays its scratch out itself
             BA_TRY(ctx->get_scratch(SL_MISC, (size_t)w->nd * w->M * 8 + 64, &p));
             int64_t band = -1;
             w->dropped_rel = 0.0;
@@ -633,7 +399,7 @@ int beatamd_weights_band_info(beatamd_ctx *ctx, int32_t wset_id, int64_t *band, 
     ENTER(ctx);
     WeightSet *w = get_obj(ctx->wsets, wset_id);
     BA_CHECK(w && band && max_dropped_rel, BEATAMD_EINVAL, "weights_band_info: bad argument");
-    const bool on = w->kind == BEATAMD_W_DENSE && w->wb && GfKnobs::get(gf_knobs(ctx).qf_band, 1) != 0;
+    const bool on = wset_banded(ctx, *w);
     *band = on ? w->band : -1;
     *max_dropped_rel = on ? w->dropped_rel : 0.0;
     return BEATAMD_OK;
@@ -642,39 +408,34 @@ int beatamd_weights_band_info(beatamd_ctx *ctx, int32_t wset_id, int64_t *band, 
 int beatamd_weights_band(beatamd_ctx *ctx, int32_t wset_id, int64_t *band)
 {
     ENTER(ctx);
-    WeightSet *w = get_obj(ctx->wsets, wset_id);
-    BA_CHECK(w && band, BEATAMD_EINVAL, "weights_band: unknown weight set %d", wset_id);
-    *band = (w->kind == BEATAMD_W_DENSE && w->wb && GfKnobs::get(gf_knobs(ctx).qf_band, 1) != 0) ? w->band : -1;
-    return BEATAMD_OK;
+    BA_CHECK(get_obj(ctx->wsets, wset_id) && band, BEATAMD_EINVAL, "weights_band: unknown weight set %d", wset_id);
+    double dropped_rel;
+    return beatamd_weights_band_info(ctx, wset_id, band, &dropped_rel);
 }
 
 int beatamd_weights_destroy(beatamd_ctx *ctx, int32_t wset_id)
 {
     ENTER(ctx);
-    WeightSet *w = get_obj(ctx->wsets, wset_id);
-    BA_CHECK(w, BEATAMD_EINVAL, "unknown weight set %d", wset_id);
-    return destroy_obj(ctx, ctx->wsets, wset_id);
+    return destroy_obj(ctx, ctx->wsets, wset_id, "weight set");
 }
 
 int beatamd_mvn_chol_logp_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C,
                                 const double *residuals, const double *hp, double *logpts)
 {
     ENTER(ctx);
-    WeightSet *w = get_obj(ctx->wsets, wset_id);
-    BA_CHECK(w, BEATAMD_EINVAL, "unknown weight set %d", wset_id);
+    WeightSet *w;
+    BA_TRY(find_wset(ctx, wset_id, &w));
     BA_CHECK(residuals && hp && logpts && C >= 0, BEATAMD_EINVAL, "mvn_chol_logp: bad argument");
     if (C == 0) return BEATAMD_OK;
     Staging st(ctx);
     const double *d_r, *d_h;
-    double *d_o;
-    void *p;
+    double *d_o, *quad;
     BA_TRY(st.in(residuals, (size_t)C * w->nd * w->M, &d_r));
     BA_TRY(st.in(hp, (size_t)C * w->nd, &d_h));
     BA_TRY(st.out(logpts, (size_t)C * w->nd, &d_o));
-    BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * w->nd * 8, &p));
-    BA_TRY(wset_quad(ctx, *w, C, d_r, w->nd * w->M, w->M, (double *)p));
-    BA_TRY(launch_mvn_finish(ctx, C, w->nd, w->M, (const double *)p, w->slog.get(),
-                             HpSrc{d_h, w->nd, nullptr}, d_o, w->nd));
+    BA_TRY(ctx->scratch(SL_QUAD, (size_t)C * w->nd, &quad));
+    BA_TRY(wset_quad(ctx, *w, C, d_r, w->nd * w->M, w->M, quad));
+    BA_TRY(launch_mvn_finish(ctx, C, w->nd, w->M, quad, w->slog.get(), HpSrc{d_h, w->nd, nullptr}, d_o, w->nd));
     return st.finish();
 }
 
@@ -694,33 +455,26 @@ int beatamd_laplacian_create(beatamd_ctx *ctx, int64_t P, const double *L, doubl
 int beatamd_laplacian_destroy(beatamd_ctx *ctx, int32_t lap_id)
 {
     ENTER(ctx);
-    Laplacian *l = get_obj(ctx->laps, lap_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown laplacian %d", lap_id);
-    return destroy_obj(ctx, ctx->laps, lap_id);
+    return destroy_obj(ctx, ctx->laps, lap_id, "laplacian");
 }
 
 int beatamd_laplacian_logp_batch(beatamd_ctx *ctx, int32_t lap_id, int64_t C, int64_t nvar,
                                  const double *slips, const double *hp, double *out)
 {
     ENTER(ctx);
-    Laplacian *l = get_obj(ctx->laps, lap_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown laplacian %d", lap_id);
+    Laplacian *l;
+    BA_TRY(find_lap(ctx, lap_id, &l));
     BA_CHECK(slips && hp && out && C >= 0 && nvar > 0, BEATAMD_EINVAL, "laplacian_logp: bad argument");
     if (C == 0) return BEATAMD_OK;
     Staging st(ctx);
     const double *d_s, *d_h;
-    double *d_o;
-    void *p;
+    double *d_o, *quad;
     BA_TRY(st.in(slips, (size_t)C * nvar * l->P, &d_s));
     BA_TRY(st.in(hp, (size_t)C, &d_h));
     BA_TRY(st.out(out, (size_t)C, &d_o));
-    BA_TRY(ctx->get_scratch(SL_QUAD, (size_t)C * nvar * 8, &p));
-    QuadformCall q;
-    q.A = l->L.get(); q.a_stride = 0; q.M = l->P; q.nd = nvar; q.C = C;
-    q.X = d_s; q.xs_c = nvar * l->P; q.xs_d = l->P;
-    q.quad = (double *)p; q.q_stride = nvar;
-    BA_TRY(launch_quadform(ctx, q));
-    BA_TRY(launch_laplacian_finish(ctx, C, nvar, l->P, l->logdet, (const double *)p, HpSrc{d_h, 1, nullptr}, d_o, 1));
+    BA_TRY(ctx->scratch(SL_QUAD, (size_t)C * nvar, &quad));
+    BA_TRY(laplacian_quad(ctx, *l, C, nvar, d_s, quad));
+    BA_TRY(launch_laplacian_finish(ctx, C, nvar, l->P, l->logdet, quad, HpSrc{d_h, 1, nullptr}, d_o, 1));
     return st.finish();
 }
 
@@ -764,8 +518,8 @@ int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int3
                                   const int64_t *shift_off, int32_t interpolation)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(lib_ids && data && hp_off, BEATAMD_EINVAL, "add_wavemap: NULL argument");
     BA_CHECK(m->nsub > 0, BEATAMD_EINVAL, "add_wavemap: model has no subfaults");
     BA_CHECK(interpolation == BEATAMD_NEAREST_NEIGHBOR || interpolation == BEATAMD_MULTILINEAR,
@@ -843,8 +597,8 @@ int beatamd_ffi_model_add_geodetic(beatamd_ctx *ctx, int32_t model_id, const int
                                    const int64_t *hp_off)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(!m->has_geo, BEATAMD_EINVAL, "model already has a geodetic composite");
     BA_CHECK(geo_lib_ids && data && odws && sizes && wset_ids && hp_off && nd > 0, BEATAMD_EINVAL,
              "add_geodetic: bad argument");
@@ -879,8 +633,8 @@ int beatamd_ffi_model_add_geodetic_geometry(beatamd_ctx *ctx, int32_t model_id, 
                                             const int32_t *wset_ids, const int64_t *hp_off)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(!m->has_geo, BEATAMD_EINVAL, "model already has a geodetic composite");
     BA_CHECK(nsrc > 0 && kind && param_off && param_fixed && east && north && los && data && odws &&
                  sizes && wset_ids && hp_off && nd > 0 && nobs > 0,
@@ -921,8 +675,8 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
                                                const double *coef_fixed)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(m->has_geo, BEATAMD_EINVAL, "add_geodetic_corrections: the model has no geodetic composite");
     Geodetic &g = m->geo;
     BA_CHECK(!g.corr_set, BEATAMD_EINVAL, "add_geodetic_corrections: the composite already has its corrections");
@@ -988,10 +742,10 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
 int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t lap_id)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
-    Laplacian *l = get_obj(ctx->laps, lap_id);
-    BA_CHECK(l, BEATAMD_EINVAL, "unknown laplacian %d", lap_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    Laplacian *l;
+    BA_TRY(find_lap(ctx, lap_id, &l));
     BA_CHECK(m->layout.h_laplacian_off >= 0 && m->layout.h_laplacian_off < m->layout.nparams,
              BEATAMD_EINVAL, "set_laplacian: layout has no h_laplacian offset");
     BA_CHECK(m->P == 0 || l->P == m->P, BEATAMD_EINVAL, "set_laplacian: patch count mismatch");
@@ -1003,8 +757,8 @@ int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t 
 int beatamd_ffi_model_nllk(beatamd_ctx *ctx, int32_t model_id, int64_t *nllk)
 {
     BA_CHECK(ctx && nllk, BEATAMD_EINVAL, "bad argument");
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     *nllk = m->nllk();
     return BEATAMD_OK;
 }
@@ -1012,77 +766,34 @@ int beatamd_ffi_model_nllk(beatamd_ctx *ctx, int32_t model_id, int64_t *nllk)
 int beatamd_ffi_model_destroy(beatamd_ctx *ctx, int32_t model_id)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
-    return destroy_obj(ctx, ctx->models, model_id);
-}
-
-static int model_check_layout(const FfiModel &m)
-{
-    const beatamd_ffi_layout &L = m.layout;
-    const int64_t np = L.nparams;
-    BA_CHECK(np > 0, BEATAMD_EINVAL, "layout: nparams must be positive");
-    for (int v = 0; v < L.nvar; v++)
-        BA_CHECK(L.slip_off[v] >= 0 && L.slip_off[v] + m.P <= np, BEATAMD_EINVAL,
-                 "layout: slip variable %d outside q", v);
-    if (!m.wavemaps.empty()) {
-        BA_CHECK(L.durations_off >= 0 && L.durations_off + m.P <= np, BEATAMD_EINVAL,
-                 "layout: durations outside q");
-        BA_CHECK(L.velocities_off >= 0 && L.velocities_off + m.P <= np, BEATAMD_EINVAL,
-                 "layout: velocities outside q");
-        BA_CHECK(L.nuc_strike_off >= 0 && L.nuc_strike_off + m.nsub <= np && L.nuc_dip_off >= 0 &&
-                     L.nuc_dip_off + m.nsub <= np && L.time_off >= 0 && L.time_off + m.nsub <= np,
-                 BEATAMD_EINVAL, "layout: hypocentre variables outside q");
-    }
-    BA_CHECK(!m.wavemaps.empty() || m.has_geo || m.lap >= 0, BEATAMD_EINVAL,
-             "model has no composite");
-    return BEATAMD_OK;
+    return destroy_obj(ctx, ctx->models, model_id, "model");
 }
 
 int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wavemap_index, int64_t C,
                                  const double *Q, int32_t residuals, double *out)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(Q && out && C >= 0, BEATAMD_EINVAL, "ffi_synthetics: bad argument");
     BA_CHECK(wavemap_index >= 0 && (size_t)wavemap_index < m->wavemaps.size(), BEATAMD_EINVAL,
              "ffi_synthetics: model has no wavemap %d", wavemap_index);
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
     Wavemap &wm = m->wavemaps[wavemap_index];
-    const int64_t np = m->layout.nparams;
     Staging st(ctx);
     const double *d_q;
-    double *d_o;
-    void *p;
-    BA_TRY(st.in(Q, (size_t)C * np, &d_q));
+    double *d_o, *st0;
+    int32_t *chain_bad;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
     BA_TRY(st.out(out, (size_t)C * wm.T * wm.N, &d_o));
-    const double *Qd = d_q;
-    BA_TRY(ctx->get_scratch(SL_CHAINBAD, (size_t)C * sizeof(int32_t), &p));
-    int32_t *chain_bad = (int32_t *)p;
-    BA_HIP(hipMemsetAsync(chain_bad, 0, (size_t)C * sizeof(int32_t), ctx->stream));
-    BA_TRY(ctx->get_scratch(SL_ST0, (size_t)C * m->P * sizeof(double), &p));
-    double *st0 = (double *)p;
-    BA_TRY(launch_sweep_model(ctx, *m, Qd, C, st0, chain_bad));
+    BA_TRY(model_start_times(ctx, *m, C, d_q, &st0, &chain_bad));
     GfStackCall k;
-    k.nvar = m->layout.nvar;
-    for (int v = 0; v < k.nvar; v++) {
-        k.libs[v] = get_obj(ctx->seislibs, wm.libs[v]);
-        BA_CHECK(k.libs[v] && k.libs[v]->g, BEATAMD_EINVAL, "wavemap refers to a destroyed / empty GF library");
-        k.slips[v] = ChainVec{Qd, np, m->layout.slip_off[v]};
-    }
-    k.durations = ChainVec{Qd, np, m->layout.durations_off};
-    k.st.starttimes0 = st0;
-    k.st.Q = Qd;
-    k.st.nparams = np;
-    k.order_key[0] = ChainVec{Qd, np, m->layout.nuc_strike_off};
-    k.order_key[1] = ChainVec{Qd, np, m->layout.nuc_dip_off};
-    k.st.shift_off = wm.shift_off.get();
-    k.st.chain_bad = chain_bad;
-    k.interp = wm.interp;
-    k.C = C;
-    k.data = wm.data.get();
+    BA_TRY(wavemap_call(ctx, *m, wm, C, d_q, st0, chain_bad, &k));
+    // Where this entry differs from the likelihood's call of the same wavemap, kept as found: index tables per target
+    // although targets share shift variables, the float64 rows although the wavemap is set to float copies, every chain
+    k.st.nslot = 0; k.st.tslot = nullptr; k.st.slot_shift_off = nullptr;
+    k.f32 = false; k.active = nullptr;
     k.mode = residuals ? GF_RESID_STORE : GF_STORE_SYN;
     k.out = d_o;
     BA_TRY(launch_gfstack(ctx, k));
@@ -1090,12 +801,11 @@ int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wav
     return st.finish();
 }
 
-int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q,
-                           double *LL)
+int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *LL)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(Q && LL && C >= 0, BEATAMD_EINVAL, "ffi_logp: bad argument");
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
@@ -1111,8 +821,8 @@ int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
 int beatamd_ffi_model_nterm(beatamd_ctx *ctx, int32_t model_id, int64_t *nterm)
 {
     BA_CHECK(ctx && nterm, BEATAMD_EINVAL, "bad argument");
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     *nterm = model_nterm(*m);
     return BEATAMD_OK;
 }
@@ -1120,8 +830,8 @@ int beatamd_ffi_model_nterm(beatamd_ctx *ctx, int32_t model_id, int64_t *nterm)
 int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *llks)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(Q && llks && C >= 0, BEATAMD_EINVAL, "ffi_llks: bad argument");
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
@@ -1130,7 +840,9 @@ int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
     double *d_l;
     BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
     BA_TRY(st.out(llks, (size_t)C * model_nterm(*m), &d_l));
-    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, nullptr, nullptr, d_l));
+    LogpOpts opt;
+    opt.llks = d_l;
+    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, opt));
     return st.finish();
 }
 
@@ -1138,8 +850,8 @@ int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
 int beatamd_wset_quad_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C, const double *R, double *quad)
 {
     ENTER(ctx);
-    WeightSet *w = get_obj(ctx->wsets, wset_id);
-    BA_CHECK(w, BEATAMD_EINVAL, "unknown weight set %d", wset_id);
+    WeightSet *w;
+    BA_TRY(find_wset(ctx, wset_id, &w));
     BA_CHECK(R && quad && C >= 0, BEATAMD_EINVAL, "wset_quad: bad argument");
     if (C == 0) return BEATAMD_OK;
     Staging st(ctx);
@@ -1151,55 +863,11 @@ int beatamd_wset_quad_batch(beatamd_ctx *ctx, int32_t wset_id, int64_t C, const 
     return st.finish();
 }
 
-// |W_k d_k|^2 of every dataset of the model: wset_quad on the model's own data as a one-chain batch (the geodetic data
-// with its odw factor, as the residual carries it), kept on the model until something it depends on changes
-static int model_obs_quads(beatamd_ctx *ctx, FfiModel &m)
-{
-    const int64_t ndata = model_ndata(m);
-    if (m.obs_quads_valid && (int64_t)m.obs_quads.size() == ndata) return BEATAMD_OK;
-    BA_HIP(hipStreamSynchronize(ctx->stream));   // (a kernel in flight may still read the old copy)
-    DevMem<double> dq;
-    BA_TRY(dq.alloc((size_t)ndata));
-    int64_t col = 0;
-    void *p = nullptr;
-    for (auto &wm : m.wavemaps) {
-        WeightSet *ws = get_obj(ctx->wsets, wm.wset);
-        BA_CHECK(ws && ws->nd == wm.T && ws->M == wm.N, BEATAMD_EINVAL, "wavemap refers to a destroyed weight set");
-        BA_TRY(wset_quad(ctx, *ws, 1, wm.data.get(), wm.T * wm.N, wm.N, dq.get() + col));
-        col += wm.T;
-    }
-    if (m.has_geo) {
-        Geodetic &g = m.geo;
-        BA_TRY(ctx->get_scratch(SL_MU, (size_t)g.Nobs * 2 * sizeof(double), &p));
-        double *mu = (double *)p, *res = mu + g.Nobs;
-        BA_HIP(hipMemsetAsync(mu, 0, (size_t)g.Nobs * sizeof(double), ctx->stream));
-        BA_TRY(launch_geo_residual(ctx, 1, g.Nobs, g.data.get(), g.odws.get(), mu, res));   // (d - 0) * odw
-        int64_t o = 0;
-        for (size_t d = 0; d < g.sizes.size(); d++) {
-            WeightSet *ws = get_obj(ctx->wsets, g.wsets[d]);
-            BA_CHECK(ws && ws->nd == 1 && ws->M == g.sizes[d], BEATAMD_EINVAL,
-                     "geodetic dataset %zu: weight set missing or of the wrong size", d);
-            BA_TRY(wset_quad(ctx, *ws, 1, res + o, g.Nobs, 0, dq.get() + col + (int64_t)d));
-            o += g.sizes[d];
-        }
-        col += (int64_t)g.sizes.size();
-    }
-    BA_CHECK(col == ndata, BEATAMD_EINVAL, "internal: dataset layout mismatch");
-    m.obs_quads.resize((size_t)ndata);
-    if (ndata > 0) {
-        BA_HIP(hipMemcpyAsync(m.obs_quads.data(), dq.get(), (size_t)ndata * 8, hipMemcpyDeviceToHost, ctx->stream));
-        BA_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    m.d_obs_quads = std::move(dq);
-    m.obs_quads_valid = true;
-    return BEATAMD_OK;
-}
-
 int beatamd_ffi_obs_quads(beatamd_ctx *ctx, int32_t model_id, double *denom)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(denom, BEATAMD_EINVAL, "ffi_obs_quads: bad argument");
     BA_TRY(model_check_layout(*m));
     BA_TRY(model_obs_quads(ctx, *m));
@@ -1215,8 +883,8 @@ int beatamd_ffi_obs_quads(beatamd_ctx *ctx, int32_t model_id, double *denom)
 int beatamd_ffi_variance_reductions_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *VR)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(Q && VR && C >= 0, BEATAMD_EINVAL, "ffi_variance_reductions: bad argument");
     BA_TRY(model_check_layout(*m));
     const int64_t ndata = model_ndata(*m), nterm = model_nterm(*m);
@@ -1225,13 +893,12 @@ int beatamd_ffi_variance_reductions_batch(beatamd_ctx *ctx, int32_t model_id, in
     Staging st(ctx);
     const double *d_q;
     double *d_v;
-    void *p;
+    LogpOpts opt;
     BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
     BA_TRY(st.out(VR, (size_t)C * ndata, &d_v));
-    BA_TRY(ctx->get_scratch(SL_LPROP, (size_t)C * nterm * sizeof(double), &p));
-    double *llks = (double *)p;
-    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, nullptr, nullptr, llks));
-    BA_TRY(launch_variance_reduction(ctx, C, ndata, llks, nterm, m->d_obs_quads.get(), d_v));
+    BA_TRY(ctx->scratch(SL_LPROP, (size_t)C * nterm, &opt.llks));
+    BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, opt));
+    BA_TRY(launch_variance_reduction(ctx, C, ndata, opt.llks, nterm, m->d_obs_quads.get(), d_v));
     return st.finish();
 }
 
@@ -1239,43 +906,21 @@ int beatamd_ffi_geo_residuals_batch(beatamd_ctx *ctx, int32_t model_id, int64_t 
                                     double *out)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(Q && out && C >= 0, BEATAMD_EINVAL, "ffi_geo_residuals: bad argument");
     BA_CHECK(m->has_geo, BEATAMD_EINVAL, "ffi_geo_residuals: the model has no geodetic composite");
     BA_TRY(model_check_layout(*m));
     if (C == 0) return BEATAMD_OK;
-    Geodetic &g = m->geo;
-    const int64_t np = m->layout.nparams;
+    const int64_t Nobs = m->geo.Nobs;
     Staging st(ctx);
     const double *d_q;
     double *d_o;
-    void *p;
-    BA_TRY(st.in(Q, (size_t)C * np, &d_q));
-    BA_TRY(st.out(out, (size_t)C * g.Nobs, &d_o));
-    if (m->geo_is_geometry) {
-        if (residuals)
-            BA_TRY(launch_geom_los(ctx, m->geom, d_q, np, C, nullptr, g.data.get(), g.odws.get(), d_o, g.corr));
-        else
-            BA_TRY(launch_geom_los(ctx, m->geom, d_q, np, C, d_o));
-    } else {
-        const GeoLib *gls[4] = {nullptr, nullptr, nullptr, nullptr};
-        ChainVec slips[4];
-        BA_CHECK(m->layout.nvar <= 4, BEATAMD_EINVAL, "geodetic composite: more than 4 slip variables");
-        for (int v = 0; v < m->layout.nvar; v++) {
-            gls[v] = get_obj(ctx->geolibs, g.libs[v]);
-            BA_CHECK(gls[v], BEATAMD_EINVAL, "geodetic composite refers to a destroyed GF library");
-            slips[v] = ChainVec{d_q, np, m->layout.slip_off[v]};
-        }
-        double *mu = d_o;
-        if (residuals) {
-            BA_TRY(ctx->get_scratch(SL_MU, (size_t)C * g.Nobs * sizeof(double), &p));
-            mu = (double *)p;
-        }
-        BA_TRY(launch_geo_stack(ctx, gls, m->layout.nvar, C, slips, 0, mu));
-        if (residuals)
-            BA_TRY(launch_geo_residual(ctx, C, g.Nobs, g.data.get(), g.odws.get(), mu, d_o, d_q, np, g.corr));
-    }
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.out(out, (size_t)C * Nobs, &d_o));
+    double *mu = d_o;   // (library mode keeps the synthetics apart from the residuals it makes of them)
+    if (residuals && !m->geo_is_geometry) BA_TRY(ctx->scratch(SL_MU, (size_t)C * Nobs, &mu));
+    BA_TRY(geodetic_residual(ctx, *m, C, d_q, mu, residuals ? d_o : nullptr));
     return st.finish();
 }
 
@@ -1398,16 +1043,14 @@ int beatamd_hyper_model_create(beatamd_ctx *ctx, int64_t nterm, int64_t nh, cons
 int beatamd_hyper_model_destroy(beatamd_ctx *ctx, int32_t id)
 {
     ENTER(ctx);
-    HyperModel *h = get_obj(ctx->hypers, id);
-    BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
-    return destroy_obj(ctx, ctx->hypers, id);
+    return destroy_obj(ctx, ctx->hypers, id, "hyper model");
 }
 
 int beatamd_hyper_logp_batch(beatamd_ctx *ctx, int32_t id, int64_t C, const double *H, const double *llks, double *LL)
 {
     ENTER(ctx);
-    HyperModel *h = get_obj(ctx->hypers, id);
-    BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
+    HyperModel *h;
+    BA_TRY(find_hyper(ctx, id, &h));
     BA_CHECK(H && llks && LL && C >= 0, BEATAMD_EINVAL, "hyper_logp: bad argument");
     if (C == 0) return BEATAMD_OK;
     Staging st(ctx);
@@ -1427,8 +1070,8 @@ int beatamd_hyper_chain_batch(beatamd_ctx *ctx, int32_t id, int64_t C, int64_t n
                               double *trace, int64_t *n_accepted)
 {
     ENTER(ctx);
-    HyperModel *h = get_obj(ctx->hypers, id);
-    BA_CHECK(h, BEATAMD_EINVAL, "unknown hyper model %d", id);
+    HyperModel *h;
+    BA_TRY(find_hyper(ctx, id, &h));
     BA_CHECK(H && LL && scaling && accepted_since_tune && llks && lower && upper && scales && C >= 0 && n_steps >= 0 &&
              first_chain >= 0 && tune_interval >= 0 && buffer_thinning >= 1, BEATAMD_EINVAL, "hyper_chain: bad argument");
     BA_CHECK(tune_interval == 0 || (steps_until_tune >= 0 && steps_until_tune <= tune_interval), BEATAMD_EINVAL,
@@ -1450,102 +1093,16 @@ int beatamd_hyper_chain_batch(beatamd_ctx *ctx, int32_t id, int64_t C, int64_t n
     return launch_hyper_chain(ctx, *h, k);
 }
 
-// proposal source of a step: rows handed in (delta, log_u) or drawn here (factor / scales + Philox key)
-struct StepDraw {
-    const double *factor = nullptr;   // [K, np] or the per-parameter scales [np]
-    int64_t K = 0;
-    int32_t kind = -1, df = 0;
-    uint64_t seed = 0, first_chain = 0;
-    uint32_t step = 0;
-};
-
-static int astep_impl(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0, double *L0,
-                      const double *delta, const double *scaling, const double *lower,
-                      const double *upper, const double *log_u, double beta, const double *betas,
-                      int32_t *accepted, const StepDraw *draw = nullptr, int32_t *acc_sum = nullptr,
-                      int64_t *n_acc = nullptr)
+// the three step entry points: the model of the id, then astep_impl (model.cpp)
+static int astep_entry(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0, double *L0, const double *delta,
+                       const double *scaling, const double *lower, const double *upper, const double *log_u, double beta,
+                       const double *betas, int32_t *accepted, const StepDraw *draw = nullptr, int32_t *acc_sum = nullptr,
+                       int64_t *n_acc = nullptr)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
-    BA_CHECK(Q0 && L0 && scaling && lower && upper && accepted && C >= 0 && (draw || (delta && log_u)),
-             BEATAMD_EINVAL, "ffi_astep: NULL argument");
-    BA_TRY(model_check_layout(*m));
-    if (C == 0) return BEATAMD_OK;
-    const int64_t np = m->layout.nparams, nllk = m->nllk();
-    Staging st(ctx);
-    const double *d_de = nullptr, *d_sc, *d_lo, *d_up, *d_lu = nullptr, *d_be = nullptr, *d_f = nullptr;
-    double *d_q0, *d_l0;
-    int32_t *d_acc;
-    void *p;
-    BA_TRY(st.out(Q0, (size_t)C * np, &d_q0, true));
-    BA_TRY(st.out(L0, (size_t)C * nllk, &d_l0, true));
-    BA_TRY(st.out(accepted, (size_t)C, &d_acc));
-    BA_TRY(st.in(scaling, (size_t)C, &d_sc));
-    BA_TRY(st.in(lower, (size_t)np, &d_lo));
-    BA_TRY(st.in(upper, (size_t)np, &d_up));
-    if (betas) BA_TRY(st.in(betas, (size_t)C, &d_be));
-    BA_TRY(ctx->get_scratch(SL_QPROP, (size_t)C * np * 8, &p));
-    double *qprop = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_LPROP, (size_t)C * nllk * 8, &p));
-    double *lprop = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_MISC, (size_t)C * 4 + 64, &p));
-    int32_t *inb = (int32_t *)p;
-    bool advance = false;
-    if (draw) {
-        BA_CHECK(is_device_ptr(Q0) && (!acc_sum || is_device_ptr(acc_sum)) && (!n_acc || is_device_ptr(n_acc)),
-                 BEATAMD_EINVAL, "ffi_mstep: chain states and counters live on the device");
-        const int64_t K = draw->kind < 0 ? draw->K : np;
-        BA_TRY(st.in(draw->factor, (size_t)(draw->kind < 0 ? K * np : np), &d_f));
-        BA_TRY(ctx->get_scratch(SL_LOGU, (size_t)C * 8, &p));
-        double *lu = (double *)p;
-        d_lu = lu;
-        if (draw_propose_applicable(K, np)) {
-            BA_TRY(launch_draw_propose(ctx, C, K, np, draw->kind, d_f, draw->df, draw->seed, draw->step, draw->first_chain,
-                                       d_q0, d_sc, d_lo, d_up, qprop, lu, inb));
-        } else {
-            BA_TRY(ctx->get_scratch(SL_DELTA, (size_t)C * np * 8, &p));
-            double *de = (double *)p;
-            if (draw->kind < 0) {
-                BA_TRY(ctx->get_scratch(SL_Z, (size_t)C * K * 8, &p));
-                double *z = (double *)p, *rs = nullptr;
-                if (draw->df > 0) {
-                    BA_TRY(ctx->get_scratch(SL_ROWSCALE, (size_t)C * 8, &p));
-                    rs = (double *)p;
-                }
-                BA_TRY(launch_philox_normal(ctx, z, C, K, draw->seed, draw->step, draw->first_chain));
-                BA_TRY(launch_philox_chain(ctx, C, draw->seed, draw->step, draw->first_chain, draw->df, lu, rs));
-                GemmCall g;
-                g.A = z; g.lda = K;
-                g.B = d_f; g.ldb = np; g.b_kn = 1;
-                g.O = de; g.ldo = np;
-                g.M = C; g.N = np; g.K = K;
-                g.row_scale = rs;
-                g.timer = "proposal";
-                BA_TRY(launch_gemm_f64(ctx, g));
-            } else {
-                BA_TRY(launch_philox_univariate(ctx, de, C, np, draw->kind, d_f, draw->seed,
-                                                draw->step, draw->first_chain));
-                BA_TRY(launch_philox_chain(ctx, C, draw->seed, draw->step, draw->first_chain, 0, lu, nullptr));
-            }
-            BA_TRY(launch_propose(ctx, C, np, d_q0, de, d_sc, d_lo, d_up, qprop, inb));
-        }
-        advance = true;
-    } else {
-        BA_TRY(st.in(delta, (size_t)C * np, &d_de));
-        BA_TRY(st.in(log_u, (size_t)C, &d_lu));
-        BA_TRY(launch_propose(ctx, C, np, d_q0, d_de, d_sc, d_lo, d_up, qprop, inb));
-    }
-    // the `like` sum rides in the accept kernel (one launch fewer) while the row fits its LDS stage
-    LikeTail tail;
-    const bool fold = nllk * 8 <= 48 * 1024;
-    // proposals outside the prior box are parked on their current point and always rejected: their likelihood rows are
-    // never read (k_accept), so the stacking kernel may skip them (BEATAMD_SKIP_PARKED=0: evaluate every chain)
-    const int32_t *active = GfKnobs::get(gf_knobs(ctx).skip_parked, 1) != 0 ? inb : nullptr;
-    BA_TRY(ffi_logp_device(ctx, *m, C, qprop, lprop, fold ? &tail : nullptr, active));
-    BA_TRY(launch_accept(ctx, C, np, nllk, d_q0, d_l0, qprop, lprop, inb, d_lu, beta, d_be, d_acc,
-                         fold ? &tail.grp : nullptr, tail.chain_bad, acc_sum, n_acc, advance));
-    return st.finish();
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    return astep_impl(ctx, *m, C, Q0, L0, delta, scaling, lower, upper, log_u, beta, betas, accepted, draw, acc_sum, n_acc);
 }
 
 int beatamd_ffi_astep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0, double *L0,
@@ -1553,9 +1110,7 @@ int beatamd_ffi_astep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, doubl
                             const double *upper, const double *log_u, double beta,
                             int32_t *accepted)
 {
-    BA_CHECK(ctx != nullptr, BEATAMD_EINVAL, "ctx is NULL");
-    return astep_impl(ctx, model_id, C, Q0, L0, delta, scaling, lower, upper, log_u, beta, nullptr,
-                      accepted);
+    return astep_entry(ctx, model_id, C, Q0, L0, delta, scaling, lower, upper, log_u, beta, nullptr, accepted);
 }
 
 int beatamd_ffi_astep_batch_betas(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0,
@@ -1564,8 +1119,7 @@ int beatamd_ffi_astep_batch_betas(beatamd_ctx *ctx, int32_t model_id, int64_t C,
                                   const double *betas, int32_t *accepted)
 {
     BA_CHECK(ctx != nullptr && betas != nullptr, BEATAMD_EINVAL, "ffi_astep_betas: NULL argument");
-    return astep_impl(ctx, model_id, C, Q0, L0, delta, scaling, lower, upper, log_u, 1.0, betas,
-                      accepted);
+    return astep_entry(ctx, model_id, C, Q0, L0, delta, scaling, lower, upper, log_u, 1.0, betas, accepted);
 }
 
 int beatamd_ffi_mstep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, double *Q0, double *L0,
@@ -1582,8 +1136,8 @@ int beatamd_ffi_mstep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, doubl
     StepDraw d;
     d.factor = factor; d.K = K; d.kind = kind; d.df = kind < 0 ? df : 0;
     d.seed = seed; d.step = step; d.first_chain = (uint64_t)first_chain;
-    return astep_impl(ctx, model_id, C, Q0, L0, nullptr, scaling, lower, upper, nullptr, betas ? 1.0 : beta,
-                      betas, accepted, &d, accepted_sum, n_accepted);
+    return astep_entry(ctx, model_id, C, Q0, L0, nullptr, scaling, lower, upper, nullptr, betas ? 1.0 : beta, betas, accepted,
+                       &d, accepted_sum, n_accepted);
 }
 
 // ------------------------------------------------------------------ noise covariance
@@ -1638,17 +1192,9 @@ int beatamd_ctx_gf_group_stats(beatamd_ctx *ctx, int64_t *chains_per_group, doub
     *max_rows = 0;
     *row_bytes = 0;
     if (ctx->gs_ngtp == 0) return BEATAMD_OK;  // the last launch was the streaming kernel
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> uc((size_t)ctx->gs_ngtp);
-    BA_HIP(hipMemcpy(uc.data(), ctx->scratch[SL_GS_UCOUNT].p, uc.size() * sizeof(uint32_t),
-                     hipMemcpyDeviceToHost));
-    int64_t tot = 0, mx = 0;
-    for (uint32_t u : uc) {
-        tot += u;
-        mx = std::max<int64_t>(mx, u);
-    }
-    *mean_rows = (double)tot / (double)uc.size();
-    *max_rows = mx;
+    int64_t tot = 0;
+    BA_TRY(gs_counters(ctx, 0, &tot, max_rows));
+    *mean_rows = (double)tot / (double)ctx->gs_ngtp;
     // every distinct row is staged once per (group, target) and slip variable
     *row_bytes = (int64_t)((double)tot * ctx->gs_trep) * ctx->gs_N * 8 * ctx->gs_nvar;
     return BEATAMD_OK;
@@ -1662,16 +1208,9 @@ int beatamd_ctx_gf_plan(beatamd_ctx *ctx, char *buf, int64_t buflen, double *mea
     if (mean_passes) *mean_passes = ctx->gs_ngtp ? 1.0 : 0.0;
     if (max_passes) *max_passes = ctx->gs_ngtp ? 1 : 0;
     if (!ctx->gs_has_passes || ctx->gs_ngtp == 0 || (!mean_passes && !max_passes)) return BEATAMD_OK;
-    BA_HIP(hipStreamSynchronize(ctx->stream));
-    std::vector<uint32_t> np((size_t)ctx->gs_ngtp);
-    BA_HIP(hipMemcpy(np.data(), (const uint32_t *)ctx->scratch[SL_GS_UCOUNT].p + ctx->gs_ngtp, np.size() * sizeof(uint32_t),
-                     hipMemcpyDeviceToHost));
     int64_t tot = 0, mx = 0;
-    for (uint32_t u : np) {
-        tot += u;
-        mx = std::max<int64_t>(mx, u);
-    }
-    if (mean_passes) *mean_passes = (double)tot / (double)np.size();
+    BA_TRY(gs_counters(ctx, 1, &tot, &mx));
+    if (mean_passes) *mean_passes = (double)tot / (double)ctx->gs_ngtp;
     if (max_passes) *max_passes = mx;
     return BEATAMD_OK;
 }
@@ -1714,14 +1253,13 @@ int beatamd_smc_calc_beta(beatamd_ctx *ctx, int64_t C, const double *likelihoods
              "smc_calc_beta: bad argument");
     Staging st(ctx);
     const double *d_l;
-    double *d_w;
-    void *p;
+    double *d_w, *d_out;
     BA_TRY(st.in(likelihoods, (size_t)((C - 1) * stride + 1), &d_l));
     BA_TRY(st.out(weights, (size_t)C, &d_w));
-    BA_TRY(ctx->get_scratch(SL_STAGE2, 64, &p));
-    BA_TRY(launch_smc_calc_beta(ctx, C, d_l, stride, beta, coef_variation, 0, 0.0, (double *)p, d_w));
+    BA_TRY(ctx->scratch(SL_STAGE2, 8, &d_out));
+    BA_TRY(launch_smc_calc_beta(ctx, C, d_l, stride, beta, coef_variation, 0, 0.0, d_out, d_w));
     double out[2];
-    BA_HIP(hipMemcpyAsync(out, p, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
+    BA_HIP(hipMemcpyAsync(out, d_out, sizeof(out), hipMemcpyDeviceToHost, ctx->stream));
     BA_TRY(st.finish());
     BA_HIP(hipStreamSynchronize(ctx->stream));
     *beta_new = out[0];
@@ -1735,12 +1273,11 @@ int beatamd_smc_stage_weights(beatamd_ctx *ctx, int64_t C, const double *likelih
     BA_CHECK(likelihoods && weights && C > 0 && stride > 0, BEATAMD_EINVAL, "smc_stage_weights: bad argument");
     Staging st(ctx);
     const double *d_l;
-    double *d_w;
-    void *p;
+    double *d_w, *d_out;
     BA_TRY(st.in(likelihoods, (size_t)((C - 1) * stride + 1), &d_l));
     BA_TRY(st.out(weights, (size_t)C, &d_w));
-    BA_TRY(ctx->get_scratch(SL_STAGE2, 64, &p));
-    BA_TRY(launch_smc_calc_beta(ctx, C, d_l, stride, 0.0, 0.0, 1, dbeta, (double *)p, d_w));
+    BA_TRY(ctx->scratch(SL_STAGE2, 8, &d_out));
+    BA_TRY(launch_smc_calc_beta(ctx, C, d_l, stride, 0.0, 0.0, 1, dbeta, d_out, d_w));
     return st.finish();
 }
 
@@ -1753,11 +1290,11 @@ int beatamd_smc_resample(beatamd_ctx *ctx, int64_t C, const double *weights, dou
     Staging st(ctx);
     const double *d_w;
     int32_t *d_i;
-    void *p;
+    double *cum;
     BA_TRY(st.in(weights, (size_t)C, &d_w));
     BA_TRY(st.out(indexes, (size_t)C, &d_i));
-    BA_TRY(ctx->get_scratch(SL_CUM, (size_t)C * 8, &p));
-    BA_TRY(launch_smc_resample(ctx, C, d_w, aux, (double *)p, d_i));
+    BA_TRY(ctx->scratch(SL_CUM, (size_t)C, &cum));
+    BA_TRY(launch_smc_resample(ctx, C, d_w, aux, cum, d_i));
     return st.finish();
 }
 
@@ -1789,30 +1326,12 @@ int beatamd_proposal_draw(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t nparam
     Staging st(ctx);
     const double *d_f;
     double *d_d, *d_u = nullptr;
-    void *p;
     BA_TRY(st.in(factor, (size_t)K * nparams, &d_f));
     BA_TRY(st.out(delta, (size_t)C * nparams, &d_d));
     if (log_u) {
         BA_TRY(st.out(log_u, (size_t)C, &d_u));
     }
-    BA_TRY(ctx->get_scratch(SL_Z, (size_t)C * K * 8, &p));
-    double *z = (double *)p;
-    double *rs = nullptr;
-    if (df > 0) {
-        BA_TRY(ctx->get_scratch(SL_ROWSCALE, (size_t)C * 8, &p));
-        rs = (double *)p;
-    }
-    BA_TRY(launch_philox_normal(ctx, z, C, K, seed, step, (uint64_t)first_chain));
-    if (d_u || rs)
-        BA_TRY(launch_philox_chain(ctx, C, seed, step, (uint64_t)first_chain, df, d_u, rs));
-    GemmCall g;
-    g.A = z; g.lda = K;
-    g.B = d_f; g.ldb = nparams; g.b_kn = 1;
-    g.O = d_d; g.ldo = nparams;
-    g.M = C; g.N = nparams; g.K = K;
-    g.row_scale = rs;
-    g.timer = "proposal";
-    BA_TRY(launch_gemm_f64(ctx, g));
+    BA_TRY(draw_multivariate(ctx, C, K, nparams, d_f, df, seed, step, (uint64_t)first_chain, d_d, d_u));
     BA_TRY(launch_step_advance(ctx));
     return st.finish();
 }
@@ -2017,8 +1536,8 @@ int beatamd_unwhiten_traces(beatamd_ctx *ctx, int64_t nd, int64_t n, const doubl
 int beatamd_ffi_model_update_data(beatamd_ctx *ctx, int32_t model_id, int32_t wavemap_index, const double *data)
 {
     ENTER(ctx);
-    FfiModel *m = get_obj(ctx->models, model_id);
-    BA_CHECK(m, BEATAMD_EINVAL, "unknown model %d", model_id);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(data && wavemap_index >= 0 && (size_t)wavemap_index < m->wavemaps.size(), BEATAMD_EINVAL,
              "model_update_data: bad argument");
     Wavemap &w = m->wavemaps[wavemap_index];
@@ -2039,18 +1558,14 @@ int beatamd_whiten_rows(beatamd_ctx *ctx, double *rows, int64_t nrows, int64_t N
     drop_obs_quads(ctx);
     Staging st(ctx);
     const double *d_w;
-    void *p;
-    BA_TRY(st.in(W, (size_t)N * N, &d_w));
-    BA_TRY(ctx->get_scratch(SL_MISC, 64, &p));
-    BA_TRY(launch_check_upper_tri(ctx, d_w, 1, N, (int *)p));
+    double *tmp;
     int upper = 0;
-    BA_HIP(hipMemcpyAsync(&upper, p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    BA_HIP(hipStreamSynchronize(ctx->stream));
+    BA_TRY(st.in(W, (size_t)N * N, &d_w));
+    BA_TRY(upper_tri_flag(ctx, d_w, 1, N, &upper));
     // out-of-place per chunk (every column block of a chunk reads all of its rows), then copied back
     int64_t chunk = std::max<int64_t>(64, ((int64_t)1 << 28) / (N * 8));
     chunk = std::min(chunk, nrows);
-    BA_TRY(ctx->get_scratch(SL_WHITEN, (size_t)chunk * N * 8, &p));
-    double *tmp = (double *)p;
+    BA_TRY(ctx->scratch(SL_WHITEN, (size_t)chunk * N, &tmp));
     for (int64_t r0 = 0; r0 < nrows; r0 += chunk) {
         const int64_t nr = std::min(chunk, nrows - r0);
         GemmCall g;
@@ -2083,13 +1598,9 @@ int beatamd_whiten_rows_batch(beatamd_ctx *ctx, double *rows, int64_t nbatch, in
     drop_obs_quads(ctx);
     Staging st(ctx);
     const double *d_w;
-    void *p;
-    BA_TRY(st.in(W, (size_t)nbatch * N * N, &d_w));
-    BA_TRY(ctx->get_scratch(SL_MISC, 64, &p));
-    BA_TRY(launch_check_upper_tri(ctx, d_w, nbatch, N, (int *)p));
     int upper = 0;
-    BA_HIP(hipMemcpyAsync(&upper, p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    BA_HIP(hipStreamSynchronize(ctx->stream));
+    BA_TRY(st.in(W, (size_t)nbatch * N * N, &d_w));
+    BA_TRY(upper_tri_flag(ctx, d_w, nbatch, N, &upper));
     if (!upper) {
         // general operators (a QR-fallback chol_inverse, heart.py:234-237): dataset by dataset through a buffer
         for (int64_t b = 0; b < nbatch; b++)

@@ -199,17 +199,12 @@ int launch_chol_inverse(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const doubl
              "chol_inverse: bad argument");
     const int64_t np = (n + CH_NB - 1) / CH_NB * CH_NB;
     const int nblk = (int)(np / CH_NB);
-    void *p = nullptr;
-    BA_TRY(ctx->get_scratch(SL_CHOL_A, (size_t)nbatch * np * np * 8, &p));
-    double *A = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_X, (size_t)nbatch * np * np * 8, &p));
-    double *X = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_D, (size_t)nbatch * nblk * CH_NB * CH_NB * 8, &p));
-    double *Dinv = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_T, (size_t)nbatch * ch_nbo() * np * 8, &p));
-    double *T = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_L, (size_t)nbatch * nblk * 8, &p));
-    double *logd = (double *)p;
+    double *A, *X, *Dinv, *T, *logd;
+    BA_TRY(ctx->scratch(SL_CHOL_A, (size_t)nbatch * np * np, &A));
+    BA_TRY(ctx->scratch(SL_CHOL_X, (size_t)nbatch * np * np, &X));
+    BA_TRY(ctx->scratch(SL_CHOL_D, (size_t)nbatch * nblk * CH_NB * CH_NB, &Dinv));
+    BA_TRY(ctx->scratch(SL_CHOL_T, (size_t)nbatch * ch_nbo() * np, &T));
+    BA_TRY(ctx->scratch(SL_CHOL_L, (size_t)nbatch * nblk, &logd));
     ScopedTimer tm(ctx, "chol_inverse");
     BA_HIP(hipMemsetAsync(X, 0, (size_t)nbatch * np * np * 8, ctx->stream));
     {
@@ -338,13 +333,10 @@ int launch_triu_ratio(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const double 
     BA_CHECK(Wn && Wo && M && nbatch > 0 && n > 0 && nbatch <= 65535, BEATAMD_EINVAL, "triu_ratio: bad argument");
     const int64_t np = (n + CH_NB - 1) / CH_NB * CH_NB;
     const int nblk = (int)(np / CH_NB);
-    void *p = nullptr;
-    BA_TRY(ctx->get_scratch(SL_CHOL_A, (size_t)nbatch * np * np * 8, &p));
-    double *A = (double *)p;      // padded Wo
-    BA_TRY(ctx->get_scratch(SL_CHOL_X, (size_t)nbatch * np * np * 8, &p));
-    double *X = (double *)p;      // padded Wn, overwritten by M block column by block column
-    BA_TRY(ctx->get_scratch(SL_CHOL_D, (size_t)nbatch * nblk * CH_NB * CH_NB * 8, &p));
-    double *Dinv = (double *)p;
+    double *A, *X, *Dinv;
+    BA_TRY(ctx->scratch(SL_CHOL_A, (size_t)nbatch * np * np, &A));   // padded Wo
+    BA_TRY(ctx->scratch(SL_CHOL_X, (size_t)nbatch * np * np, &X));   // padded Wn, overwritten by M block column by block column
+    BA_TRY(ctx->scratch(SL_CHOL_D, (size_t)nbatch * nblk * CH_NB * CH_NB, &Dinv));
     ScopedTimer tm(ctx, "triu_ratio");
     const dim3 gp((unsigned)((np * np + 255) / 256), (unsigned)nbatch);
     hipLaunchKernelGGL(k_pad_identity, gp, dim3(256), 0, ctx->stream, Wo, n, np, A);
@@ -510,17 +502,12 @@ int launch_gram_cholesky(beatamd_ctx *ctx, int64_t K, int64_t n, const double *F
     BA_CHECK(F && R && K > 0 && n > 0, BEATAMD_EINVAL, "gram_cholesky: bad argument");
     const int64_t np = (n + CH_NB - 1) / CH_NB * CH_NB;
     const int nblk = (int)(np / CH_NB);
-    void *p = nullptr;
-    BA_TRY(ctx->get_scratch(SL_CHOL_A, (size_t)np * np * 8, &p));
-    double *A = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_X, (size_t)np * np * 8, &p));
-    double *X = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_D, (size_t)nblk * CH_NB * CH_NB * 8, &p));
-    double *Dinv = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_T, (size_t)n * K * 8, &p));
-    double *Ft = (double *)p;
-    BA_TRY(ctx->get_scratch(SL_CHOL_L, (size_t)nblk * 8, &p));
-    double *logd = (double *)p;
+    double *A, *X, *Dinv, *Ft, *logd;
+    BA_TRY(ctx->scratch(SL_CHOL_A, (size_t)np * np, &A));
+    BA_TRY(ctx->scratch(SL_CHOL_X, (size_t)np * np, &X));
+    BA_TRY(ctx->scratch(SL_CHOL_D, (size_t)nblk * CH_NB * CH_NB, &Dinv));
+    BA_TRY(ctx->scratch(SL_CHOL_T, (size_t)n * K, &Ft));
+    BA_TRY(ctx->scratch(SL_CHOL_L, (size_t)nblk, &logd));
     ScopedTimer tm(ctx, "gram_cholesky");
     hipLaunchKernelGGL(k_transpose, dim3((unsigned)((K + 15) / 16), (unsigned)((n + 15) / 16)), dim3(256), 0,
                        ctx->stream, F, K, n, Ft);

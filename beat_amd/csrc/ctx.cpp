@@ -118,9 +118,9 @@ using namespace beatamd;
 
 int beatamd_ctx::get_scratch(int slot, size_t bytes, void **out)
 {
-    if ((size_t)slot >= scratch.size()) scratch.resize(slot + 1);
-    BA_TRY(scratch[slot].reserve(bytes));
-    *out = scratch[slot].p;
+    if ((size_t)slot >= scratch_bufs.size()) scratch_bufs.resize(slot + 1);
+    BA_TRY(scratch_bufs[slot].reserve(bytes));
+    *out = scratch_bufs[slot].p;
     return BEATAMD_OK;
 }
 
@@ -246,7 +246,7 @@ int beatamd_ctx_create(int device, beatamd_ctx **out)
     hipDeviceProp_t prop;
     BA_HIP(hipGetDeviceProperties(&prop, device));
     c->num_cu = prop.multiProcessorCount;
-    c->scratch.resize(SL_COUNT);
+    c->scratch_bufs.resize(SL_COUNT);
     c->knobs.read_env();
     {
         const char *live = getenv("BEATAMD_KNOBS_LIVE");
@@ -275,7 +275,7 @@ int beatamd_ctx_destroy(beatamd_ctx *c)
     c->laps.clear();
     c->geolibs.clear();
     c->seislibs.clear();
-    for (auto &s : c->scratch) s.release();
+    for (auto &s : c->scratch_bufs) s.release();
     for (auto &kv : c->timers)
         for (auto &pr : kv.second.pending) {
             (void)hipEventDestroy(pr.first);

@@ -276,7 +276,7 @@ struct beatamd_ctx {
     std::map<std::string, beatamd::KTimer> timers;
     std::vector<hipEvent_t> event_pool;
     int *d_status = nullptr;  // device status word
-    std::vector<beatamd::DevBuf> scratch;
+    std::vector<beatamd::DevBuf> scratch_bufs;
     std::vector<std::unique_ptr<beatamd::SeisStore>> seislibs;
     std::vector<std::unique_ptr<beatamd::GeoLib>> geolibs;
     std::vector<std::unique_ptr<beatamd::WeightSet>> wsets;
@@ -312,6 +312,15 @@ struct beatamd_ctx {
 
     // grow-only scratch slot
     int get_scratch(int slot, size_t bytes, void **out);
+    // the slot as n elements of T
+    template <class T>
+    int scratch(int slot, size_t n, T **out)
+    {
+        void *raw = nullptr;
+        const int rc = get_scratch(slot, n * sizeof(T), &raw);
+        *out = static_cast<T *>(raw);
+        return rc;
+    }
     hipEvent_t get_event();
     void time_begin(const char *name);
     void time_end(const char *name);

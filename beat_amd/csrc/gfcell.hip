@@ -323,7 +323,7 @@ int launch_chain_members(beatamd_ctx *ctx, int64_t C, const ChainVec key[2], int
 {
     *members = nullptr;
     if (!gc_cut_applicable(C, ngroups) || !key[0].base || !key[1].base) return BEATAMD_OK;
-    void *p = nullptr;
+    void *p = nullptr;   // sized in bytes on purpose: members, then the two key vectors on an 8-byte boundary (gc_cut_bytes)
     const int64_t padded = ngroups * cg;
     BA_TRY(ctx->get_scratch(SL_GS_ORDER, gc_cut_bytes(C, padded), &p));
     GcOrderArgs oa;
@@ -340,7 +340,7 @@ int launch_chain_members(beatamd_ctx *ctx, int64_t C, const ChainVec key[2], int
 // launches the chain order of a batch into oa.order (scratch for members / keys behind it)
 static int launch_gc_order(beatamd_ctx *ctx, GcOrderArgs &oa, int64_t ngroups, const GfKnobs &kn)
 {
-    void *p = nullptr;
+    void *p = nullptr;   // sized in bytes on purpose: the order, then (global) the cut's scratch of gc_cut_bytes behind it
     const size_t norder = (size_t)(ngroups * GC_CG + 64);
     const bool global = oa.sort && ngroups > 1 && gc_cut_applicable(oa.C, ngroups) && GfKnobs::get(kn.gc_global, 1) != 0;
     BA_TRY(ctx->get_scratch(SL_GC_ORDER, norder * sizeof(uint32_t) + (global ? gc_cut_bytes(oa.C, oa.C) + 64 : 0), &p));
@@ -1191,6 +1191,7 @@ int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *ro
     const int64_t DS = L.D * L.S, dense = L.D * (L.S + 1);
     const int64_t ngroups = (k.C + GC_CG - 1) / GC_CG;
     const int64_t GT = ngroups * Ttab, GTP = GT * L.P;
+    // sized in bytes on purpose: the four table slots below hold packed records of mixed types with byte slack behind them
     void *p = nullptr;
     *ovf_out = nullptr;
     // row passes: none when every dense slot of a patch (and the row requests they can take) fits a buffer; else the
@@ -1279,13 +1280,11 @@ int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *ro
     a.wtab = ta.wtab; a.ltab = ta.ltab; a.order = oa.order; a.dtab = ta.dtab;
     a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     if (k.mode == GF_RESID_SCALAR || k.mode == GF_RESID_BAND1) {
-        BA_TRY(ctx->get_scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile * sizeof(double), &p));
-        a.partial = (double *)p;
+        BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     }
     if (k.mode == GF_RESID_BAND1) {
         BA_CHECK(k.band_w && k.quad && k.data, BEATAMD_EINVAL, "gfstack: mode 3 needs band_w, quad, data");
-        BA_TRY(ctx->get_scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2 * sizeof(double), &p));
-        a.edges = (double *)p;
+        BA_TRY(ctx->scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2, &a.edges));
         a.band_w = k.band_w;
     }
     int64_t nblocks = ngroups * L.T * a.ntile;

@@ -2244,7 +2244,6 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     const int cap = bound <= 32 ? 32 : bound <= 64 ? 64 : WS_CAP_MAX;
     const int maxpass = (int)((bound + cap - 1) / cap);
     const int64_t vmax = L.P * maxpass;
-    void *p = nullptr;
 
     WsTabArgs ta;
     memset(&ta, 0, sizeof(ta));
@@ -2258,27 +2257,23 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     if (ngroups > 1 && k.order_key[0].base && k.order_key[1].base && GfKnobs::get(kn.gc_global, 1) != 0)
         BA_TRY(launch_chain_members(ctx, k.C, k.order_key, WS_CG, ngroups, &ta.order, GfKnobs::get(kn.gc_global, 1) == 2));
     // [utotal GTP][npass GTP][voff GTP][nv GT]
-    BA_TRY(ctx->get_scratch(SL_GS_UCOUNT, (size_t)(3 * GTP + GT) * sizeof(uint32_t), &p));
-    ta.utotal = (uint32_t *)p;
+    BA_TRY(ctx->scratch(SL_GS_UCOUNT, (size_t)(3 * GTP + GT), &ta.utotal));
     ta.npass = ta.utotal + GTP;
     uint32_t *voff = ta.npass + GTP, *nv = voff + GTP;
     // (+ 3 vsteps of padding behind the tables: the kernel runs its table pointers past the last step)
     const size_t nvs = (size_t)GT * vmax + 3;
-    BA_TRY(ctx->get_scratch(SL_GS_UROWS, nvs * sizeof(uint32_t), &p));
-    ta.ucount = (uint32_t *)p;
-    BA_TRY(ctx->get_scratch(SL_GS_USLOT, nvs * WS_USTRIDE * 2 * sizeof(uint32_t), &p));
-    ta.uent = (uint32_t *)p;
-    BA_TRY(ctx->get_scratch(SL_GS_SLOT, nvs * WS_CG * sizeof(uint16_t), &p));
-    ta.slot = (uint16_t *)p;
+    BA_TRY(ctx->scratch(SL_GS_UROWS, nvs, &ta.ucount));
+    BA_TRY(ctx->scratch(SL_GS_USLOT, nvs * WS_USTRIDE * 2, &ta.uent));
+    BA_TRY(ctx->scratch(SL_GS_SLOT, nvs * WS_CG, &ta.slot));
     ta.w_var_stride = (int64_t)GT * vmax * WS_CG;
-    BA_TRY(ctx->get_scratch(SL_GS_W, ((size_t)ta.w_var_stride * k.nvar + (size_t)3 * WS_CG) * sizeof(double), &p));
-    ta.w = (double *)p;
+    BA_TRY(ctx->scratch(SL_GS_W, (size_t)ta.w_var_stride * k.nvar + (size_t)3 * WS_CG, &ta.w));
     {
         ScopedTimer tm(ctx, "grouptables");
         if (k.active) {
-            BA_TRY(ctx->get_scratch(SL_WS_PACK, (size_t)ngroups * WS_CG * sizeof(uint32_t), &p));
-            hipLaunchKernelGGL(k_ws_pack, dim3((unsigned)ngroups), dim3(WS_CG), 0, ctx->stream, ta.order, k.active, k.C, (uint32_t *)p);
-            ta.order = (const uint32_t *)p;
+            uint32_t *packed;
+            BA_TRY(ctx->scratch(SL_WS_PACK, (size_t)ngroups * WS_CG, &packed));
+            hipLaunchKernelGGL(k_ws_pack, dim3((unsigned)ngroups), dim3(WS_CG), 0, ctx->stream, ta.order, k.active, k.C, packed);
+            ta.order = packed;
         }
         const bool map = ta.DS <= WS_MAP_MAX && !GfKnobs::is(kn.ws_map, 0);   // (BEATAMD_WS_MAP=0: tests of the ranking path)
         const size_t mlds = map ? (size_t)ta.DS * sizeof(uint16_t) : 0;
@@ -2317,12 +2312,10 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     a.w_var_stride = ta.w_var_stride;
     a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     if (k.mode == GF_RESID_SCALAR || k.mode == GF_RESID_BAND1) {
-        BA_TRY(ctx->get_scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile * sizeof(double), &p));
-        a.partial = (double *)p;
+        BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     }
     if (k.mode == GF_RESID_BAND1) {
-        BA_TRY(ctx->get_scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2 * sizeof(double), &p));
-        a.edges = (double *)p;
+        BA_TRY(ctx->scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2, &a.edges));
         a.band_w = k.band_w;
     }
     a.nthint = GfKnobs::set(kn.gs_nthint) ? (kn.gs_nthint != 0) : (GS_NTHINT_DEFAULT && ngroups == 1);
@@ -2385,7 +2378,6 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
     const int64_t ngroups = (k.C + CG - 1) / CG;
     const int64_t GTP = ngroups * Ttab * L.P;
-    void *p = nullptr;
 
     GroupTabArgs ga;
     memset(&ga, 0, sizeof(ga));
@@ -2395,23 +2387,17 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     for (int v = 0; v < k.nvar; v++) ga.slips[v] = k.slips[v];
     ga.ucap = ucap;
     ga.ustride = (ucap + 63) / 64 * 64;   // covers the unclamped first-pass ids of 8 waves
-    BA_TRY(ctx->get_scratch(SL_GS_UROWS, (size_t)GTP * ga.ustride * sizeof(uint32_t), &p));
-    ga.urows = (uint32_t *)p;
-    BA_TRY(ctx->get_scratch(SL_GS_USLOT, (size_t)GTP * ga.ustride * 2 * sizeof(uint32_t), &p));
-    ga.uent = (uint32_t *)p;
-    BA_TRY(ctx->get_scratch(SL_GS_UCOUNT, (size_t)GTP * sizeof(uint32_t), &p));
-    ga.ucount = (uint32_t *)p;
+    BA_TRY(ctx->scratch(SL_GS_UROWS, (size_t)GTP * ga.ustride, &ga.urows));
+    BA_TRY(ctx->scratch(SL_GS_USLOT, (size_t)GTP * ga.ustride * 2, &ga.uent));
+    BA_TRY(ctx->scratch(SL_GS_UCOUNT, (size_t)GTP, &ga.ucount));
     // (+ 3 steps of padding behind both tables: k_gfstack_ws runs its table pointers past the last step)
-    BA_TRY(ctx->get_scratch(SL_GS_SLOT, (size_t)(GTP + 3) * nrow * CG * sizeof(uint16_t), &p));
-    ga.slot = (uint16_t *)p;
+    BA_TRY(ctx->scratch(SL_GS_SLOT, (size_t)(GTP + 3) * nrow * CG, &ga.slot));
     ga.w_var_stride = (nrow == 1) ? ngroups * L.P * CG : GTP * 4 * CG;
-    BA_TRY(ctx->get_scratch(SL_GS_W, ((size_t)ga.w_var_stride * k.nvar + (size_t)3 * 4 * CG) * sizeof(double), &p));
-    ga.w = (double *)p;
+    BA_TRY(ctx->scratch(SL_GS_W, (size_t)ga.w_var_stride * k.nvar + (size_t)3 * 4 * CG, &ga.w));
     const bool fit_lds = CG <= 128 && !GfKnobs::is(kn.gs_fit, 0);
     ga.umax = nullptr;
     if (fit_lds) {
-        BA_TRY(ctx->get_scratch(SL_GS_UMAX, sizeof(uint32_t), &p));
-        ga.umax = (uint32_t *)p;
+        BA_TRY(ctx->scratch(SL_GS_UMAX, 1, &ga.umax));
         BA_HIP(hipMemsetAsync(ga.umax, 0, sizeof(uint32_t), ctx->stream));
     }
     ga.nissue = CG / 64;
@@ -2461,8 +2447,7 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     a.w_var_stride = ga.w_var_stride;
     a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     if (k.mode == GF_RESID_SCALAR) {
-        BA_TRY(ctx->get_scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile * sizeof(double), &p));
-        a.partial = (double *)p;
+        BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     }
     int64_t nblocks = ngroups * L.T * a.ntile;
     BA_CHECK(nblocks < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");

@@ -548,9 +548,8 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
     }
     v.patch_split = R;
     v.mode = GF_STORE_SYN;
-    void *p = nullptr;
-    BA_TRY(ctx->get_scratch(SL_SPLIT, (size_t)call.C * L.T * R * L.N * sizeof(double), &p));
-    double *part = (double *)p;
+    double *part;
+    BA_TRY(ctx->scratch(SL_SPLIT, (size_t)call.C * L.T * R * L.N, &part));
     v.out = part;
     v.quad = nullptr; v.data = nullptr; v.wscalar = nullptr; v.band_w = nullptr;
     BA_TRY(launch_gfstack_impl(ctx, v));
@@ -643,12 +642,12 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
     const int64_t R = k.patch_split;
     const int64_t Ttab = tinv ? R : slots ? (int64_t)k.st.nslot * R : L.T;
     k.tslot = slots ? k.st.tslot : nullptr;
-    void *p = nullptr;
     if (R > 1 && (tinv || slots)) {
-        BA_TRY(ctx->get_scratch(SL_TSLOT, (size_t)L.T * sizeof(int32_t), &p));
+        int32_t *vslot;
+        BA_TRY(ctx->scratch(SL_TSLOT, (size_t)L.T, &vslot));
         hipLaunchKernelGGL(k_split_tslot, dim3((unsigned)((L.T + 255) / 256)), dim3(256), 0, ctx->stream, L.T, (int)R,
-                           slots ? k.st.tslot : nullptr, (int32_t *)p);
-        k.tslot = (const int32_t *)p;
+                           slots ? k.st.tslot : nullptr, vslot);
+        k.tslot = vslot;
     }
     const int64_t CTP = k.C * Ttab * L.P;
     const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
@@ -662,12 +661,10 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
     ta.st = k.st;
     if (slots) ta.st.shift_off = k.st.slot_shift_off;
     ta.status = ctx->d_status;
-    BA_TRY(ctx->get_scratch(SL_ROWOFF, (size_t)CTP * nrow * sizeof(uint32_t), &p));
-    ta.rowoff = (uint32_t *)p;
+    BA_TRY(ctx->scratch(SL_ROWOFF, (size_t)CTP * nrow, &ta.rowoff));
     ta.fac = nullptr;
     if (nrow == 4) {
-        BA_TRY(ctx->get_scratch(SL_WEIGHTS, (size_t)CTP * 4 * sizeof(double), &p));
-        ta.fac = (double *)p;
+        BA_TRY(ctx->scratch(SL_WEIGHTS, (size_t)CTP * 4, &ta.fac));
     }
     {
         ScopedTimer tm(ctx, "tables");
@@ -789,8 +786,7 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
     a.ntile = (int)((L.N + tile_w - 1) / tile_w);
     if (k.mode == GF_RESID_SCALAR) {
         // (a stand-in keeps its tile sums apart from those of the kernel it stands in for)
-        BA_TRY(ctx->get_scratch(standin ? SL_PARTIAL2 : SL_PARTIAL, (size_t)k.C * L.T * a.ntile * sizeof(double), &p));
-        a.partial = (double *)p;
+        BA_TRY(ctx->scratch(standin ? SL_PARTIAL2 : SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     }
     const int64_t nblocks = k.C * L.T * a.ntile;
     BA_CHECK(nblocks < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large (%lld blocks)",

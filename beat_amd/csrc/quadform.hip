@@ -171,9 +171,7 @@ int launch_quadform(beatamd_ctx *ctx, const QuadformCall &k)
     a.nrb = (int)((k.M + QF_BM - 1) / QF_BM);
     a.vec_ok = (k.M % 2 == 0) && (k.a_stride % 2 == 0) && (k.xs_c % 2 == 0) && (k.xs_d % 2 == 0) &&
                (((uintptr_t)k.A | (uintptr_t)k.X) % 16 == 0);
-    void *p = nullptr;
-    BA_TRY(ctx->get_scratch(SL_PARTIAL, (size_t)k.nd * a.nrb * k.C * sizeof(double), &p));
-    a.partial = (double *)p;
+    BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.nd * a.nrb * k.C, &a.partial));
     const int BC = (k.C > 64) ? 128 : 64;
     a.ncb = (int)((k.C + BC - 1) / BC);
     const int64_t nwork = (int64_t)a.nrb * k.nd;

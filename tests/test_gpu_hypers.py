@@ -90,7 +90,7 @@ def test_g1_update_llks_vs_one_chain_composition(ctx, name, variant, C):
         host["weights"] = prob.wavemaps[0].weights = W
     f = prob.compile(ctx, prewhiten=(variant == "prewhitened"))
     try:
-        # the path the weight set takes is decided by its kind and its detected band (capi.cpp wset_quad / ffi_logp_device)
+        # the path the weight set takes is decided by its kind and its detected band (model.cpp wset_quad / ffi_logp_device)
         wm = prob.wavemaps[0]
         if variant == "plain":
             assert np.ndim(wm.weights) == 1 and not wm.is_prewhitened
