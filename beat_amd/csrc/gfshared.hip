@@ -20,6 +20,12 @@
 //   k_gfstack_dma     (groups of 64 .. 1024 chains, one or four rows per chain) rows by LDS-DMA into two LDS buffers one
 //                     step ahead, one barrier per step, hand-issued conflict-free ds_read_b64 (row pitch 65 doubles) or
 //                     ds_read_b128 (pitch 66); all global accesses of its loop are asm statements
+//   k_gfstack_dmaf    k_gfstack_dma on the float copies of rounded libraries (64-sample tiles, groups up to 512 chains): float
+//                     rows, float pairs gathered by ds_read_b64, widened in front of the f64 FMA
+//   k_gfstack_wsp     k_gfstack_ws with a pair gather: <1> on the float copies (reported as k_gfstack_ws32), <0> double pairs
+//                     by ds_read_b128 on the float64 rows (A/B, reported as k_gfstack_wsp64)
+// What the four do the same way (block decode, table cell, step iterator, row request, waits, gather operand lists, epilogue
+// arithmetic) stands once, in front of k_gfstack_dma.
 // (round 1's single-buffer k_gfstack_shared was retired in round 5: what does not fit two row buffers is stacked by the
 // row-pass kernels or by k_gfstack)
 //
@@ -225,10 +231,10 @@ struct GsArgs {
     int nvar, nrow;
     int64_t C, T, P, N;
     int CG, ucap, ustride, ntile, nt;
-    int dma;  // 1: k_gfstack_dma (two LDS row buffers filled by LDS-DMA)
-    int ws;            // k_gfstack_ws: 8 consumer + 4 loader wavefronts, three row buffers
-    int nthint;        // k_gfstack_ws / k_gfstack_dma: non-temporal row requests
-    int xcd_order;     // k_gfstack_dma: chain groups of a (target, tile) share an XCD
+    int dma;           // k_gfstack_dma: 2 ds_read_b64 gather at a row pitch of NT+1 (default), 1 ds_read_b128 at NT+2 (A/B)
+    int ws;            // k_gfstack_ws / _wsp: row buffers of the ring (8 consumer + 4 loader wavefronts); 0: k_gfstack_dma / _dmaf
+    int nthint;        // all four kernels: non-temporal row requests
+    int xcd_order;     // all four kernels: chain groups of a (target, tile) share an XCD (GS_BLOCK_DECODE)
     int64_t ngroups;
     // tables per (group, target, patch), or per (group, patch) when the start times do not depend
     // on the target (no station shifts): Ttab = T or 1; the row ids are then those of target 0 and
@@ -355,6 +361,431 @@ __device__ __forceinline__ void lds_wait8_b64(double (&x)[8])
 }
 
 // ---------------------------------------------------------------------------------------------
+// What the four lane-per-chain kernels (k_gfstack_dma, k_gfstack_dmaf, k_gfstack_ws, k_gfstack_wsp) do the same way.
+// The step loops react to single scalar instructions and to any control flow behind the gather, so a
+// shared piece has to leave every kernel's generated code as it was; tools/isa_compare.py compares two assembly listings
+// of this file.  That decides the form of each piece: force-inlined functions where they pass the comparison (those that
+// take values do; the epilogues did not while they took the argument struct), macros -- the same token stream as before,
+// so the same code by construction -- where no function did: the waits, whose immediates are pasted into the asm text,
+// the block decode (as a function its early return, a bool, survived as a flag tested in front of the step loop), the
+// loader-wavefront program of k_gfstack_ws / k_gfstack_wsp (a function moved scalar loads and compare / branch pairs
+// inside the loaders' and the consumers' loops, whether it took the argument struct, its fields as values or every
+// argument by reference) and what k_gfstack_dma / k_gfstack_dmaf share around their gathers (one body templated on the
+// element type changed branch polarity and scalar-load order inside the step loop).  A macro names the kernel's locals;
+// each says which.
+
+// Workgroup -> (chain group G, target T, sample tile TILE), which it declares; a block that only pads the grid returns.
+// xcd_order: workgroups b, b+8, b+16, ... run on the same XCD (round-robin dispatch).  The chain groups of one (target,
+// sample tile) are numbered b = 8*(ngroups*q + g) + x, so they run on one XCD at about the same time and walk the patches
+// in step: the library rows the groups have in common are fetched from HBM once and served from that XCD's L2 to the
+// others.  Scheduling only; results do not depend on it.
+#define GS_BLOCK_DECODE(A, G_, T_, TILE_)                                                                  \
+    int TILE_;                                                                                             \
+    int64_t T_, G_;                                                                                        \
+    if (A.xcd_order) {                                                                                     \
+        const int64_t b = blockIdx.x;                                                                      \
+        const int64_t x = b & 7, q = b >> 3;                                                               \
+        G_ = q % A.ngroups;                                                                                \
+        const int64_t tt = (q / A.ngroups) * 8 + x;   /* t * ntile + tile */                               \
+        if (tt >= A.T * A.ntile) return;              /* grid padded to a multiple of 8 per group */       \
+        TILE_ = (int)(tt % A.ntile);                                                                       \
+        T_ = tt / A.ntile;                                                                                 \
+    } else {                                                                                               \
+        TILE_ = blockIdx.x % A.ntile;                                                                      \
+        const int64_t gt0 = blockIdx.x / A.ntile;  /* g*T + t */                                           \
+        T_ = gt0 % A.T;                                                                                    \
+        G_ = gt0 / A.T;                                                                                    \
+    }
+
+// table cell gt of (group, target), and how far behind the rows the cell's ids name those of target t lie (elements)
+__device__ __forceinline__ void gs_table_cell(const GsArgs &a, int64_t g, int64_t t, int64_t &gt, int64_t &tbase)
+{
+    const int64_t slot = a.tslot ? (int64_t)a.tslot[t] : (a.Ttab == 1 ? 0 : t);
+    gt = g * a.Ttab + slot;
+    tbase = (t - slot) * a.rows_per_target * a.N;
+}
+
+// steps run patch-major over (patch, variable); (p, iv) of the steps ahead are advanced
+// incrementally (no integer divisions in the loop) and clamp at the last step
+__device__ __forceinline__ void gs_advance(int &p, int &iv, int P, int nvar)
+{
+    if (++iv == nvar) { iv = 0; ++p; }
+    if (p >= P) { p = P - 1; iv = nvar - 1; }
+}
+
+// One row request: LDS-DMA of this lane's share of a row segment (16 B of a float64 row, F32: 4 B of a float row) from
+// rowp + voff to the LDS byte address dst (through m0).  nt: non-temporal -- a row segment is read by this CU once and
+// by no other workgroup when the batch is a single chain group (several groups share rows through L2).
+// `dep` is an ordering token only (not named in the text): a request that lists the destination register of a load as
+// input cannot be placed in front of that load (any live VGPR, such as voff, where no ordering is needed).  `tk` chains
+// the requests of a step: every statement passes it through untouched (in/out operand, no instruction) and the caller
+// folds its final value into `keep` once per step -- the statements are not volatile (see k_gfstack_dma) and must not be
+// dropped.
+template <int F32>
+__device__ __forceinline__ void gs_row_request(uint32_t &tk, uint32_t voff, const char *rowp, uint32_t dst, uint32_t dep,
+                                               bool nt)
+{
+    if (F32 && nt)
+        asm("s_mov_b32 m0, %3\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dword %1, %2 nt"
+            : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
+    else if (F32)
+        asm("s_mov_b32 m0, %3\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dword %1, %2"
+            : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
+    else if (nt)
+        asm("s_mov_b32 m0, %3\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dwordx4 %1, %2 nt"
+            : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
+    else
+        asm("s_mov_b32 m0, %3\n\t"
+            "s_nop 0\n\t"
+            "global_load_lds_dwordx4 %1, %2"
+            : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
+}
+
+// k_gfstack_dma / _dmaf, top of a step: wait until at most NOUT vector-memory operations are outstanding, then copy the
+// landed slot / weight registers sl_n / wl_n into this step's sl / wl (the copy is part of the statement: hipcc would
+// otherwise place it in front of the wait and copy registers whose loads are still in flight)
+#define BA_WAIT_COPY(NOUT)                                                                      \
+        _Pragma("unroll") for (int k = 0; k < NROW; k++)                                        \
+            asm("s_waitcnt vmcnt(" #NOUT ")\n\t"                                                 \
+                "v_mov_b32 %0, %2\n\t"                                                          \
+                "v_mov_b64 %1, %3"                                                              \
+                : "=&v"(sl[k]), "=&v"(wl[k]) : "v"(sl_n[k]), "v"(wl_n[k]))
+
+// loader wavefronts of k_gfstack_ws / _wsp: wait until at most YOUNG (<= 32) of the wavefront's row requests stay in
+// flight (s_waitcnt takes an immediate; an over-wait is safe); TK, S: token and step, as in gs_row_request
+#define BA_LWAIT(NOUT, TK, S) asm("s_waitcnt vmcnt(" #NOUT ")" : "+s"(TK) : "s"(S))
+#define GS_LOADER_WAIT(YOUNG, TK, S)                                                                                       \
+    switch (YOUNG) {                                                                                                       \
+    case 0: BA_LWAIT(0, TK, S); break;   case 1: BA_LWAIT(1, TK, S); break;   case 2: BA_LWAIT(2, TK, S); break;           \
+    case 3: BA_LWAIT(3, TK, S); break;   case 4: BA_LWAIT(4, TK, S); break;   case 5: BA_LWAIT(5, TK, S); break;           \
+    case 6: BA_LWAIT(6, TK, S); break;   case 7: BA_LWAIT(7, TK, S); break;   case 8: BA_LWAIT(8, TK, S); break;           \
+    case 9: BA_LWAIT(9, TK, S); break;   case 10: BA_LWAIT(10, TK, S); break; case 11: BA_LWAIT(11, TK, S); break;         \
+    case 12: BA_LWAIT(12, TK, S); break; case 13: BA_LWAIT(13, TK, S); break; case 14: BA_LWAIT(14, TK, S); break;         \
+    case 15: BA_LWAIT(15, TK, S); break; case 16: BA_LWAIT(16, TK, S); break; case 17: BA_LWAIT(17, TK, S); break;         \
+    case 18: BA_LWAIT(18, TK, S); break; case 19: BA_LWAIT(19, TK, S); break; case 20: BA_LWAIT(20, TK, S); break;         \
+    case 21: BA_LWAIT(21, TK, S); break; case 22: BA_LWAIT(22, TK, S); break; case 23: BA_LWAIT(23, TK, S); break;         \
+    case 24: BA_LWAIT(24, TK, S); break; case 25: BA_LWAIT(25, TK, S); break; case 26: BA_LWAIT(26, TK, S); break;         \
+    case 27: BA_LWAIT(27, TK, S); break; case 28: BA_LWAIT(28, TK, S); break; case 29: BA_LWAIT(29, TK, S); break;         \
+    case 30: BA_LWAIT(30, TK, S); break; case 31: BA_LWAIT(31, TK, S); break; default: BA_LWAIT(32, TK, S); break;         \
+    }
+
+// The loader-wavefront program of k_gfstack_ws / k_gfstack_wsp (see k_gfstack_ws), expanded inside `if (wave >= CW)`.
+// Loader lw of LW issues rows lw, lw + LW, ... of every step's list NB-1 steps ahead into the ring of NB row buffers and
+// keeps the workgroup's barrier count.  F32_ / ES_ / ELEM_T_: float rows (a 64-sample segment is one full-wave request of
+// 4 B per lane) or float64 rows (32 lanes x 16 B); GLIB_: the statement that sets G_a to the library of variable iv.
+// It names the kernel's a, wave, lane, CW, LW, KPRE, GS_PITCH, NB, NTH, MODE, N, n0, lds0, bufsz, gt, tbase, P, nvar and
+// nsteps.  A macro because every form of a function changed loop bodies (see above).
+// fetch_ids reads through the constant address space: the tables are written by k_ws_tables before this launch, never
+// here, and must come in through scalar loads -- a vector load would be counted in this wavefront's vmcnt together with
+// its row requests.
+#define GS_LOADER_PROGRAM(F32_, ES_, ELEM_T_, GLIB_)                                                                           \
+    const int lw = wave - CW;                                                                                                  \
+    const bool dma_lane = F32_ ? (n0 + lane < N) : ((lane < 32) && (n0 + lane * 2 < N));   /* N even (launcher) */             \
+    const uint32_t voff = F32_ ? (uint32_t)((n0 + lane) * 4) : (uint32_t)((n0 + lane * 2) * 8);   /* byte offset inside a row */ \
+    const uint32_t rowbytes = (uint32_t)(N * ES_);                                                                             \
+    uint32_t keep = 0;                                                                                                         \
+    auto dma_row = [&](const ELEM_T_ *Gv, uint32_t r, uint32_t slotidx, int boff, uint32_t &tk) {                              \
+        const uint64_t off = (uint64_t)r * (uint64_t)rowbytes;                                                                 \
+        const char *rowp = reinterpret_cast<const char *>(Gv) + off;                                                           \
+        const uint32_t dst = lds0 + (uint32_t)(boff * ES_) + slotidx * (uint32_t)(GS_PITCH * ES_);                             \
+        gs_row_request<F32_>(tk, voff, rowp, dst, voff, NTH != 0);                                                             \
+    };                                                                                                                         \
+    const int kstr = a.ustride / LW;                                                                                           \
+    const char *const cnt_base = reinterpret_cast<const char *>(a.ucount + gt * a.vmax);                                       \
+    const char *const ent_base = reinterpret_cast<const char *>(a.uent + ((gt * a.vmax) * LW + lw) * kstr * 2);                \
+    const uint32_t ent_step = (uint32_t)(a.ustride * 8);                                                                       \
+    int U_a;                                                                                                                   \
+    uint32_t rid[KPRE], rsl[KPRE];                                                                                             \
+    const ELEM_T_ *G_a = nullptr;                                                                                              \
+    auto fetch_ids = [&](int p, int iv) {                                                                                      \
+        typedef const __attribute__((address_space(4))) uint32_t *cu32;                                                        \
+        typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));                                                          \
+        typedef const __attribute__((address_space(4))) u32x16 *cent;                                                          \
+        U_a = (int)*(cu32)(uintptr_t)(cnt_base + (uint32_t)p * 4u);                                                            \
+        const char *e = ent_base + (uint32_t)p * ent_step;                                                                     \
+        const u32x16 e0 = *(cent)(uintptr_t)e;                                                                                 \
+        const u32x16 e1 = *(cent)(uintptr_t)(e + 64);                                                                          \
+    _Pragma("unroll")                                                                                                          \
+        for (int k = 0; k < 8; k++) {                                                                                          \
+            rid[k] = e0[2 * k];      rsl[k] = e0[2 * k + 1];                                                                   \
+            rid[8 + k] = e1[2 * k];  rsl[8 + k] = e1[2 * k + 1];                                                               \
+        }                                                                                                                      \
+        GLIB_;                                                                                                                 \
+    };                                                                                                                         \
+    auto dma_count = [&](int U) { return U > lw ? (U - lw + LW - 1) / LW : 0; };                                               \
+    /* rows lw, lw + LW, ... of the list whose entries are in rid / rsl -> buffer at boff */                                   \
+    auto issue_rows = [&](int p, int boff) {                                                                                   \
+        if (dma_lane) {                                                                                                        \
+            uint32_t tk = 0;                                                                                                   \
+    _Pragma("unroll")                                                                                                          \
+            for (int k = 0; k < KPRE; k++)                                                                                     \
+                if (lw + k * LW < U_a) dma_row(G_a, rid[k], rsl[k], boff, tk);                                                 \
+            if (U_a > KPRE * LW) {   /* rare: more than 64 distinct rows */                                                    \
+                typedef const __attribute__((address_space(4))) uint32_t *cu32;                                                \
+                cu32 ue = (cu32)(uintptr_t)(ent_base + (uint32_t)p * ent_step);                                                \
+                for (int k = KPRE; lw + k * LW < U_a; k++) dma_row(G_a, ue[2 * k], ue[2 * k + 1], boff, tk);                   \
+            }                                                                                                                  \
+            keep |= tk;                                                                                                        \
+        }                                                                                                                      \
+    };                                                                                                                         \
+    /* steps 0 .. NB-2 go out before the loop, then step s+NB-1 behind the barrier of step s */                                \
+    int boff[NB];                                                                                                              \
+    _Pragma("unroll")                                                                                                          \
+    for (int j = 0; j < NB; j++) boff[j] = j * bufsz;   /* boff[j]: buffer of step s+j */                                      \
+    int cnt[NB];                                          /* cnt[j]: this loader's requests of step s+j */                     \
+    _Pragma("unroll")                                                                                                          \
+    for (int j = 0; j < NB; j++) cnt[j] = 0;                                                                                   \
+    int pn = 0, ivn = 0;                                  /* next step to fetch ids for */                                     \
+    fetch_ids(pn, ivn);                                                                                                        \
+    _Pragma("unroll")                                                                                                          \
+    for (int j = 0; j < NB - 1; j++) {                                                                                         \
+        if (j < nsteps) {                                                                                                      \
+            issue_rows(pn, boff[j]);                                                                                           \
+            cnt[j] = dma_count(U_a);                                                                                           \
+        }                                                                                                                      \
+        gs_advance(pn, ivn, P, nvar);                                                                                          \
+        fetch_ids(pn, ivn);                               /* ids of step j+1 */                                                \
+    }                                                                                                                          \
+    int p_i = pn;                                         /* step whose ids are in rid / rsl (s+NB-1) */                       \
+    for (int s = 0; s < nsteps; s++) {                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        /* its rows of step s have landed: at most the requests of the NB-2 younger steps stay in flight */                    \
+        {                                                                                                                      \
+            int young = 0;                                                                                                     \
+    _Pragma("unroll")                                                                                                          \
+            for (int j = 1; j < NB - 1; j++) young += cnt[j];                                                                  \
+            uint32_t tk = 0;                                                                                                   \
+            GS_LOADER_WAIT(young, tk, s)                                                                                       \
+            keep |= tk;                                                                                                        \
+        }                                                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        __builtin_amdgcn_s_barrier();   /* rows of step s published; buffer of step s-1 is free */                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        int k_new = 0;                                                                                                         \
+        if (s + NB - 1 < nsteps) {                                                                                             \
+            issue_rows(p_i, boff[NB - 1]);                                                                                     \
+            k_new = dma_count(U_a);                                                                                            \
+        }                                                                                                                      \
+        gs_advance(pn, ivn, P, nvar);                                                                                          \
+        p_i = pn;                                                                                                              \
+        fetch_ids(pn, ivn);                                                                                                    \
+        const int b0 = boff[0];                                                                                                \
+    _Pragma("unroll")                                                                                                          \
+        for (int j = 0; j < NB - 1; j++) { boff[j] = boff[j + 1]; cnt[j] = cnt[j + 1]; }                                       \
+        boff[NB - 1] = b0;                                                                                                     \
+        cnt[NB - 1] = 0;                                                                                                       \
+        cnt[NB - 2] = k_new;                                                                                                   \
+    }                                                                                                                          \
+    __builtin_amdgcn_s_barrier();   /* the consumers' barrier "of step nsteps" (their pipelined loop) */                       \
+    /* the consumers' epilogue passes the data tile through LDS behind two barriers */                                         \
+    if (MODE != GF_STORE_SYN) {                                                                                                \
+        __builtin_amdgcn_s_barrier();                                                                                          \
+        __builtin_amdgcn_s_barrier();                                                                                          \
+    }                                                                                                                          \
+    if (keep != 0) a.out[0] = 0.0;   /* never true: keeps the request statements alive */
+
+// ---- k_gfstack_dma and k_gfstack_dmaf share everything but their gather: the three macros below are the kernels' text
+// in front of the step loop, at the top of a step and behind the loop (macros because one body templated on the element
+// type changed the step loop, see above).  They name the kernels' a, tid, lane, wave, c, g, t, tile, gt, tbase, N, n0,
+// xbuf and the constants WAVES, NROW, MODE, CG, KPRE, GS_NT, GS_PITCH.
+//
+// GS_DMA_SETUP declares dma_lane, voff, lds0, bufsz, acc[], keep, P, nvar, nsteps, the step positions p1 / iv1 (s+1) and
+// p2 / iv2 (s+2), U_a / rid_a / rsl_a / G_a (list of the step whose rows go out next), sl_n[] / wl_n[] (the lane's slot and
+// weight of the next step, in flight) and the lambdas dma_row, fetch_ids, issue_rows, fetch_tabs, and issues the requests
+// of step 0.  F32_ / ES_ / ELEM_T_ / GFIELD_: float rows from a.G32 (a 64-sample segment is one full-wave request of 4 B
+// per lane) or float64 rows from a.G (GS_NT / 2 lanes x 16 B).
+//   * row j of a step lands at buf*bufsz + j*GS_PITCH (scalar address arithmetic kept short: 32 x 32 -> 64 bit products,
+//     one exec region per step); `dep`, `tk`: gs_row_request
+//   * (row id, LDS slot) of this wavefront's first KPRE list entries are contiguous in memory: one scalar load instruction
+//     (the gather's lgkmcnt waits count scalar loads too)
+//   * table addresses: the (group, target) part is loop invariant and hoisted as 64-bit bases; the per-step part is a
+//     32 x 32 bit product added as an unsigned byte offset (scalar loads take it as their offset operand).  Written out by
+//     hand: hipcc kept whole 64 x 64 bit index products inside the loop (about 60 scalar instructions per step)
+//   * G_a, the library base pointer of a step: a scalar load from the kernel arguments, issued with the list entries one
+//     step before it is needed (selecting among four register pairs by a run-time index costs a branch maze of ~25 scalar
+//     instructions per step)
+//   * fetch_tabs: asm loads (hipcc must not count them, see k_gfstack_dma); valid after the step-top wait, which names them
+#define GS_DMA_SETUP(F32_, ES_, ELEM_T_, GFIELD_)                                                                              \
+    const bool dma_lane = F32_ ? (n0 + lane < N) : ((lane < GS_NT / 2) && (n0 + lane * 2 < N));   /* N even (launcher) */      \
+    const uint32_t voff = F32_ ? (uint32_t)((n0 + lane) * 4) : (uint32_t)((n0 + lane * 2) * 8);   /* byte offset inside a row */ \
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)xbuf;                                 \
+    const int bufsz = a.ucap * GS_PITCH;                          /* elements per buffer */                                    \
+    double acc[GS_NT];                                                                                                         \
+    _Pragma("unroll")                                                                                                          \
+    for (int i = 0; i < GS_NT; i++) acc[i] = 0.0;                                                                              \
+    uint32_t keep = 0;  /* results of the DMA statements (always 0): keeps them alive */                                       \
+    const int P = (int)a.P, nvar = a.nvar;                                                                                     \
+    const int nsteps = P * nvar;                                                                                               \
+    const uint32_t rowbytes = (uint32_t)(N * ES_);                                                                             \
+    auto dma_row = [&](const ELEM_T_ *Gv, uint32_t r, uint32_t slotidx, int boff, uint32_t dep, uint32_t &tk) {                \
+        const uint64_t off = (uint64_t)r * (uint64_t)rowbytes;                                                                 \
+        const char *rowp = reinterpret_cast<const char *>(Gv) + off;                                                           \
+        const uint32_t dst = lds0 + (uint32_t)(boff * ES_) + slotidx * (uint32_t)(GS_PITCH * ES_);                             \
+        gs_row_request<F32_>(tk, voff, rowp, dst, dep, a.nthint != 0);                                                         \
+    };                                                                                                                         \
+    struct alignas(KPRE * 8) EntBlock { uint32_t v[2 * KPRE]; };                                                               \
+    const int kstr = a.ustride / WAVES;                                                                                        \
+    const char *const cnt_base = reinterpret_cast<const char *>(a.ucount + gt * a.P);                                          \
+    const char *const ent_base = reinterpret_cast<const char *>(a.uent + ((gt * a.P) * WAVES + wave) * kstr * 2);              \
+    const uint32_t ent_step = (uint32_t)(a.ustride * 8);   /* bytes per patch: WAVES * kstr entries of 8 B */                  \
+    const ELEM_T_ *G_a = nullptr;   /* library of the step whose list entries are in rid_a / rsl_a */                          \
+    auto fetch_ids = [&](int p, int iv, int &U, uint32_t (&rid)[KPRE], uint32_t (&rsl)[KPRE]) {                                \
+        U = __builtin_amdgcn_readfirstlane(                                                                                    \
+            (int)*reinterpret_cast<const uint32_t *>(cnt_base + (uint32_t)p * 4u));                                            \
+        const EntBlock eb = *reinterpret_cast<const EntBlock *>(ent_base + (uint32_t)p * ent_step);                            \
+    _Pragma("unroll")                                                                                                          \
+        for (int k = 0; k < KPRE; k++) {   /* padded: always in bounds */                                                      \
+            rid[k] = eb.v[2 * k];                                                                                              \
+            rsl[k] = eb.v[2 * k + 1];                                                                                          \
+        }                                                                                                                      \
+        G_a = a.GFIELD_[iv] + tbase;                                                                                           \
+    };                                                                                                                         \
+    auto issue_rows_dep = [&](int p, int iv, int boff, int U, const uint32_t (&rid)[KPRE],                                     \
+                              const uint32_t (&rsl)[KPRE], uint32_t dep) {                                                     \
+        const ELEM_T_ *Gv = G_a;                                                                                               \
+        if (dma_lane) {                                                                                                        \
+            uint32_t tk = 0;                                                                                                   \
+    _Pragma("unroll")                                                                                                          \
+            for (int k = 0; k < KPRE; k++)                                                                                     \
+                if (wave + k * WAVES < U) dma_row(Gv, rid[k], rsl[k], boff, dep, tk);                                          \
+            if (U > KPRE * WAVES) {   /* rare: more distinct rows than the prefetched ids cover */                             \
+                const uint32_t *ue = reinterpret_cast<const uint32_t *>(ent_base + (uint32_t)p * ent_step);                    \
+                for (int k = KPRE; wave + k * WAVES < U; k++) dma_row(Gv, ue[2 * k], ue[2 * k + 1], boff, dep, tk);            \
+            }                                                                                                                  \
+            keep |= tk;                                                                                                        \
+        }                                                                                                                      \
+    };                                                                                                                         \
+    auto issue_rows = [&](int p, int iv, int buf, int U, const uint32_t (&rid)[KPRE],                                          \
+                          const uint32_t (&rsl)[KPRE]) {                                                                       \
+        issue_rows_dep(p, iv, buf * bufsz, U, rid, rsl, voff);   /* (any live VGPR: no ordering needed here) */                \
+    };                                                                                                                         \
+    uint32_t sl_n[NROW];                                                                                                       \
+    double wl_n[NROW];                                                                                                         \
+    const char *const slot_base = reinterpret_cast<const char *>(a.slot + (gt * a.P * NROW) * CG + tid);                       \
+    const char *const w_base = reinterpret_cast<const char *>(                                                                 \
+        (NROW == 1) ? a.w + (g * a.P) * CG + tid : a.w + (gt * a.P * 4) * CG + tid);                                           \
+    const uint32_t slot_step = (uint32_t)(NROW * CG * 2);                    /* bytes per patch */                             \
+    const uint32_t w_step = (uint32_t)((NROW == 1 ? 1 : 4) * CG * 8);                                                          \
+    const int64_t w_var_bytes = a.w_var_stride * 8;                                                                            \
+    auto fetch_tabs = [&](int p, int iv) {                                                                                     \
+        const char *sp = slot_base + (uint32_t)p * slot_step;                                                                  \
+        const char *wp = w_base + (uint32_t)p * w_step + (nvar == 1 ? (int64_t)0 : (int64_t)iv * w_var_bytes);                 \
+    _Pragma("unroll")                                                                                                          \
+        for (int k = 0; k < NROW; k++) {                                                                                       \
+            const uint16_t *ps = reinterpret_cast<const uint16_t *>(sp) + k * CG;                                              \
+            const double *pw = reinterpret_cast<const double *>(wp) + k * CG;                                                  \
+            asm("global_load_ushort %0, %1, off" : "=v"(sl_n[k]) : "v"(ps));                                                   \
+            asm("global_load_dwordx2 %0, %1, off" : "=v"(wl_n[k]) : "v"(pw));                                                  \
+        }                                                                                                                      \
+    };                                                                                                                         \
+    int p1 = 0, iv1 = 0;          /* step s+1 */                                                                               \
+    gs_advance(p1, iv1, P, nvar);                                                                                              \
+    int p2 = p1, iv2 = iv1;       /* step s+2 */                                                                               \
+    gs_advance(p2, iv2, P, nvar);                                                                                              \
+    int U_a;                                                                                                                   \
+    uint32_t rid_a[KPRE], rsl_a[KPRE];                                                                                         \
+    fetch_ids(0, 0, U_a, rid_a, rsl_a);                                                                                        \
+    issue_rows(0, 0, 0, U_a, rid_a, rsl_a);                                                                                    \
+    fetch_tabs(0, 0);                                                                                                          \
+    fetch_ids(p1, iv1, U_a, rid_a, rsl_a);
+
+// top of step s: wait for the step's slot / weight (BA_WAIT_COPY declares them as sl[] / wl[]), the barrier, the requests of
+// step s+1 into the other buffer; declares gbuf, the buffer of step s (elements)
+#define GS_DMA_STEP_TOP()                                                                                                      \
+    /* the tables of this step and (older) the DMA of this step's rows have landed */                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                                                         \
+    uint32_t sl[NROW];                                                                                                         \
+    double wl[NROW];                                                                                                           \
+    BA_WAIT_COPY(0);                                                                                                           \
+    __builtin_amdgcn_sched_barrier(0);                                                                                         \
+    __syncthreads();  /* rows of step s visible; everyone has left the FMA phase of step s-1 */                                \
+    __builtin_amdgcn_sched_barrier(0);                                                                                         \
+    /* rows of step s+1 -> the other buffer, then that step's slot/weight and the ids of step s+2 */                           \
+    if (s + 1 < nsteps) issue_rows(p1, iv1, (s + 1) & 1, U_a, rid_a, rsl_a);                                                   \
+    fetch_tabs(p1, iv1);                                                                                                       \
+    fetch_ids(p2, iv2, U_a, rid_a, rsl_a);                                                                                     \
+    p1 = p2; iv1 = iv2;                                                                                                        \
+    gs_advance(p2, iv2, P, nvar);                                                                                              \
+    __builtin_amdgcn_sched_barrier(0);                                                                                         \
+    const int gbuf = (s & 1) * bufsz;   /* elements: the buffer of step s */
+
+// Behind the loop.  The slot/weight loads issued in the last step (for the step after the last) are still in flight: wait
+// for them before their registers can be given to anything else.  Without this the epilogue's store addresses were built
+// in those registers and overwritten by the late data (observed as a memory fault with RESID_STORE and >= 29 groups;
+// tools/audit_hidden_loads.py follows the loop's exit paths as well).  Then the epilogue.
+#define GS_DMA_FINISH()                                                                                                        \
+    _Pragma("unroll")                                                                                                          \
+    for (int k = 0; k < NROW; k++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(sl_n[k]), "+v"(wl_n[k]));                          \
+    __builtin_amdgcn_sched_barrier(0);                                                                                         \
+    /* ---- epilogue: lane = chain c, acc[i] = synthetics[c, t, n0 + i] */                                                     \
+    const bool live = (c < a.C) && (keep == 0);                                                                                \
+    const int nvalid = (int)min((int64_t)GS_NT, N - n0);                                                                       \
+    if (MODE == GF_STORE_SYN) {                                                                                                \
+        if (live) {                                                                                                            \
+            gs_store_syn<GS_NT>(a.out + (c * a.T + t) * N + n0, acc, nvalid);                                                  \
+        }                                                                                                                      \
+        return;                                                                                                                \
+    }                                                                                                                          \
+    __syncthreads();                                                                                                           \
+    if (tid < GS_NT) xbuf[tid] = (tid < nvalid) ? a.data[t * N + n0 + tid] : 0.0;                                              \
+    __syncthreads();                                                                                                           \
+    if (MODE == GF_RESID_STORE) {                                                                                              \
+        gs_resid_store<GS_NT>(a.out + (c * a.T + t) * N + n0, acc, xbuf, live, nvalid);                                        \
+    } else {                                                                                                                   \
+        const double q = gs_misfit_scalar<GS_NT>(a.wscalar[t], acc, xbuf, nvalid);                                             \
+        if (live) a.partial[(c * a.T + t) * a.ntile + tile] = q;                                                               \
+    }
+
+// ---- epilogue arithmetic: lane <-> chain, acc[i] = the chain's synthetics at sample i of the tile, of which nvalid lie
+// inside the trace; xbuf[0 .. NT) = the tile's data, staged through LDS by the kernel (k_gfstack_ws / _wsp count their
+// barriers by hand, the others use __syncthreads).  k_gfstack_ws has two epilogues of its own besides: the bidiagonal band
+// and the residual store through per-wavefront transpose tiles.
+template <int NT>
+__device__ __forceinline__ void gs_store_syn(double *o, const double (&acc)[NT], int nvalid)
+{
+#pragma unroll
+    for (int i = 0; i < NT; i++)
+        if (i < nvalid) o[i] = acc[i];
+}
+
+// the tile's share of the scalar-weight misfit sum_i (w (data_i - syn_i))^2
+template <int NT>
+__device__ __forceinline__ double gs_misfit_scalar(const double w, const double (&acc)[NT], const double *xbuf, int nvalid)
+{
+    double q = 0.0;
+#pragma unroll
+    for (int i0 = 0; i0 < NT; i0 += 8) {
+#pragma unroll
+        for (int i = i0; i < i0 + 8; i++)
+            if (i < nvalid) {
+                const double tt = w * (xbuf[i] - acc[i]);
+                q = fma(tt, tt, q);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return q;
+}
+
+// residuals data - synthetics, every lane storing its own chain's samples
+template <int NT>
+__device__ __forceinline__ void gs_resid_store(double *o, const double (&acc)[NT], const double *xbuf, bool live, int nvalid)
+{
+#pragma unroll
+    for (int i0 = 0; i0 < NT; i0 += 8) {
+#pragma unroll
+        for (int i = i0; i < i0 + 8; i++)
+            if (live && i < nvalid) o[i] = xbuf[i] - acc[i];  // seismic.py:1332
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_gfstack_dma: the same mapping (lane <-> chain, 64 static accumulators, distinct rows staged
 // once per workgroup) with the row staging taken off the waves' critical path:
 //   * two LDS row buffers; the rows of step s+1 are written by LDS-DMA
@@ -384,7 +815,6 @@ k_gfstack_dma(GsArgs a)
 {
     constexpr int GS_NT = NT;
     constexpr int GS_PITCH = B64 ? NT + 1 : NT + 2;
-    constexpr int LPR = NT / 2;         // lanes moving one row segment (16 B each)
     // row ids per wavefront fetched ahead (scalar registers): 32 rows per workgroup and step are
     // covered by the unrolled DMA slots, more (rare) go through a loop
     constexpr int KPRE = WAVES >= 4 ? 64 / WAVES : 8;
@@ -393,177 +823,15 @@ k_gfstack_dma(GsArgs a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (a.guard_mode && ((a.guard_mode == 1) == (*a.guard_umax > (uint32_t)a.guard_fit))) return;
-    int tile;
-    int64_t t, g;
-    if (a.xcd_order) {
-        // Workgroups b, b+8, b+16, ... run on the same XCD (round-robin dispatch).  The chain
-        // groups of one (target, sample tile) are numbered b = 8*(ngroups*q + g) + x, so they
-        // run on one XCD at about the same time and walk the patches in step: the library rows the
-        // groups have in common are fetched from HBM once and served from that XCD's L2 to the
-        // others.  Scheduling only; results do not depend on it.
-        const int64_t b = blockIdx.x;
-        const int64_t x = b & 7, q = b >> 3;
-        g = q % a.ngroups;
-        const int64_t tt = (q / a.ngroups) * 8 + x;   // t * ntile + tile
-        if (tt >= a.T * a.ntile) return;              // grid padded to a multiple of 8 per group
-        tile = (int)(tt % a.ntile);
-        t = tt / a.ntile;
-    } else {
-        tile = blockIdx.x % a.ntile;
-        const int64_t gt0 = blockIdx.x / a.ntile;  // g*T + t
-        t = gt0 % a.T;
-        g = gt0 / a.T;
-    }
-    const int64_t slot = a.tslot ? (int64_t)a.tslot[t] : (a.Ttab == 1 ? 0 : t);
-    const int64_t gt = g * a.Ttab + slot;                                        // table cell
-    const int64_t tbase = (t - slot) * a.rows_per_target * a.N;                  // doubles
+    GS_BLOCK_DECODE(a, g, t, tile)
+    int64_t gt, tbase;
+    gs_table_cell(a, g, t, gt, tbase);
     const int64_t c = g * CG + tid;
     const int64_t N = a.N;
     const int64_t n0 = (int64_t)tile * GS_NT;
-    const bool dma_lane = (lane < LPR) && (n0 + lane * 2 < N);   // N even (launcher)
-    const uint32_t voff = (uint32_t)((n0 + lane * 2) * 8);      // byte offset inside a row
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)xbuf;
-    const int bufsz = a.ucap * GS_PITCH;                          // doubles per buffer
-
-    double acc[GS_NT];
-#pragma unroll
-    for (int i = 0; i < GS_NT; i++) acc[i] = 0.0;
-    uint32_t keep = 0;  // results of the DMA statements (always 0): keeps them alive
-
-    const int P = (int)a.P, nvar = a.nvar;
-    const int nsteps = P * nvar;
-    // steps run patch-major over (patch, variable); (p, iv) of the steps ahead are advanced
-    // incrementally (no integer divisions in the loop) and clamp at the last step
-    auto advance = [&](int &p, int &iv) {
-        if (++iv == nvar) { iv = 0; ++p; }
-        if (p >= P) { p = P - 1; iv = nvar - 1; }
-    };
-    // row j of the step lands at buf*bufsz + j*PITCH; lanes 0..LPR-1 move its NT samples.
-    // (scalar address arithmetic kept short: 32 x 32 -> 64 bit products, one exec region per step)
-    const uint32_t rowbytes = (uint32_t)(N * 8);
-    // `dep` is an ordering token only (not named in the text): a request that lists the destination
-    // register of the step's slot load as input cannot be placed in front of that load
-    // `tk` chains the requests of a step: every statement passes it through untouched (in/out
-    // operand, no instruction), its final value is folded into `keep` once per step -- the
-    // statements are not volatile (see above) and must not be dropped.
-    auto dma_row = [&](const double *Gv, uint32_t r, uint32_t slotidx, int boff, uint32_t dep, uint32_t &tk) {
-        const uint64_t off = (uint64_t)r * (uint64_t)rowbytes;
-        const char *rowp = reinterpret_cast<const char *>(Gv) + off;
-        const uint32_t dst = lds0 + (uint32_t)(boff * 8) + slotidx * (uint32_t)(GS_PITCH * 8);
-        if (a.nthint)   // non-temporal: single-group batches read every row segment exactly once
-            asm("s_mov_b32 m0, %3\n\t"
-                "s_nop 0\n\t"
-                "global_load_lds_dwordx4 %1, %2 nt"
-                : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
-        else
-            asm("s_mov_b32 m0, %3\n\t"
-                "s_nop 0\n\t"
-                "global_load_lds_dwordx4 %1, %2"
-                : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
-    };
-    // (row id, LDS slot) of this wavefront's first KPRE list entries: contiguous in memory, one
-    // scalar load instruction (the gather's lgkmcnt waits count scalar loads too)
-    struct alignas(KPRE * 8) EntBlock { uint32_t v[2 * KPRE]; };
-    const int kstr = a.ustride / WAVES;
-    // Table addresses: the (group, target) part is loop invariant and hoisted as 64-bit bases; the
-    // per-step part is a 32 x 32 bit product added as an unsigned byte offset (scalar loads take it
-    // as their offset operand).  Written out by hand: hipcc kept whole 64 x 64 bit index products
-    // inside the loop (about 60 scalar instructions per step).
-    const char *const cnt_base = reinterpret_cast<const char *>(a.ucount + gt * a.P);
-    const char *const ent_base = reinterpret_cast<const char *>(a.uent + ((gt * a.P) * WAVES + wave) * kstr * 2);
-    const uint32_t ent_step = (uint32_t)(a.ustride * 8);   // bytes per patch: WAVES * kstr entries of 8 B
-    const double *G_a = nullptr;   // library of the step whose list entries are in rid_a / rsl_a
-    auto fetch_ids = [&](int p, int iv, int &U, uint32_t (&rid)[KPRE], uint32_t (&rsl)[KPRE]) {
-        U = __builtin_amdgcn_readfirstlane(
-            (int)*reinterpret_cast<const uint32_t *>(cnt_base + (uint32_t)p * 4u));
-        const EntBlock eb = *reinterpret_cast<const EntBlock *>(ent_base + (uint32_t)p * ent_step);
-#pragma unroll
-        for (int k = 0; k < KPRE; k++) {   // padded: always in bounds
-            rid[k] = eb.v[2 * k];
-            rsl[k] = eb.v[2 * k + 1];
-        }
-        // library base pointer of that step: a scalar load from the kernel arguments, issued with
-        // the list entries one step before it is needed (selecting among four register pairs by a
-        // run-time index costs a branch maze of ~25 scalar instructions per step)
-        G_a = a.G[iv] + tbase;
-    };
-    auto issue_rows_dep = [&](int p, int iv, int boff, int U, const uint32_t (&rid)[KPRE],
-                              const uint32_t (&rsl)[KPRE], uint32_t dep) {
-        const double *Gv = G_a;
-        if (dma_lane) {
-            uint32_t tk = 0;
-#pragma unroll
-            for (int k = 0; k < KPRE; k++)
-                if (wave + k * WAVES < U) dma_row(Gv, rid[k], rsl[k], boff, dep, tk);
-            if (U > KPRE * WAVES) {   // rare: more distinct rows than the prefetched ids cover
-                const uint32_t *ue = reinterpret_cast<const uint32_t *>(ent_base + (uint32_t)p * ent_step);
-                for (int k = KPRE; wave + k * WAVES < U; k++) dma_row(Gv, ue[2 * k], ue[2 * k + 1], boff, dep, tk);
-            }
-            keep |= tk;
-        }
-    };
-    auto issue_rows = [&](int p, int iv, int buf, int U, const uint32_t (&rid)[KPRE],
-                          const uint32_t (&rsl)[KPRE]) {
-        issue_rows_dep(p, iv, buf * bufsz, U, rid, rsl, voff);   // (any live VGPR: no ordering needed here)
-    };
-    // the lane's slot and weight of step s: asm loads (hipcc must not count them, see above);
-    // valid after the step-top wait statement, which names them
-    uint32_t sl_n[NROW];
-    double wl_n[NROW];
-    const char *const slot_base = reinterpret_cast<const char *>(a.slot + (gt * a.P * NROW) * CG + tid);
-    const char *const w_base = reinterpret_cast<const char *>(
-        (NROW == 1) ? a.w + (g * a.P) * CG + tid : a.w + (gt * a.P * 4) * CG + tid);
-    const uint32_t slot_step = (uint32_t)(NROW * CG * 2);                    // bytes per patch
-    const uint32_t w_step = (uint32_t)((NROW == 1 ? 1 : 4) * CG * 8);
-    const int64_t w_var_bytes = a.w_var_stride * 8;
-    auto fetch_tabs = [&](int p, int iv) {
-        const char *sp = slot_base + (uint32_t)p * slot_step;
-        const char *wp = w_base + (uint32_t)p * w_step + (nvar == 1 ? (int64_t)0 : (int64_t)iv * w_var_bytes);
-#pragma unroll
-        for (int k = 0; k < NROW; k++) {
-            const uint16_t *ps = reinterpret_cast<const uint16_t *>(sp) + k * CG;
-            const double *pw = reinterpret_cast<const double *>(wp) + k * CG;
-            asm("global_load_ushort %0, %1, off" : "=v"(sl_n[k]) : "v"(ps));
-            asm("global_load_dwordx2 %0, %1, off" : "=v"(wl_n[k]) : "v"(pw));
-        }
-    };
-
-    int p1 = 0, iv1 = 0;          // step s+1
-    advance(p1, iv1);
-    int p2 = p1, iv2 = iv1;       // step s+2
-    advance(p2, iv2);
-    int U_a;
-    uint32_t rid_a[KPRE], rsl_a[KPRE];
-    fetch_ids(0, 0, U_a, rid_a, rsl_a);
-    issue_rows(0, 0, 0, U_a, rid_a, rsl_a);
-    fetch_tabs(0, 0);
-    fetch_ids(p1, iv1, U_a, rid_a, rsl_a);
+    GS_DMA_SETUP(0, 8, double, G)
     for (int s = 0; s < nsteps; s++) {
-        // the tables of this step and (older) the DMA of this step's rows have landed
-        __builtin_amdgcn_sched_barrier(0);
-        // (the copy into this step's registers is part of the statement: hipcc would otherwise
-        // place it in front of the wait and copy registers whose loads are still in flight)
-        uint32_t sl[NROW];
-        double wl[NROW];
-#define BA_WAIT_COPY(NOUT)                                                                      \
-        _Pragma("unroll") for (int k = 0; k < NROW; k++)                                        \
-            asm("s_waitcnt vmcnt(" #NOUT ")\n\t"                                                 \
-                "v_mov_b32 %0, %2\n\t"                                                          \
-                "v_mov_b64 %1, %3"                                                              \
-                : "=&v"(sl[k]), "=&v"(wl[k]) : "v"(sl_n[k]), "v"(wl_n[k]))
-        BA_WAIT_COPY(0);
-#undef BA_WAIT_COPY
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();  // rows of step s visible; everyone has left the FMA phase of step s-1
-        __builtin_amdgcn_sched_barrier(0);
-        // rows of step s+1 -> the other buffer, then that step's slot/weight and the ids of step s+2
-        if (s + 1 < nsteps) issue_rows(p1, iv1, (s + 1) & 1, U_a, rid_a, rsl_a);
-        fetch_tabs(p1, iv1);
-        fetch_ids(p2, iv2, U_a, rid_a, rsl_a);
-        p1 = p2; iv1 = iv2;
-        advance(p2, iv2);
-        __builtin_amdgcn_sched_barrier(0);
-        const int gbuf = (s & 1) * bufsz;   // doubles: the buffer of step s
+        GS_DMA_STEP_TOP()
         // ---- every lane applies ITS rows with ITS weights.  The 2*NT/4 ds_read_b128 of a row
         // are issued by hand in groups of 8, two groups in flight (hipcc keeps 3-4 reads in
         // flight, which leaves the phase bound by LDS latency instead of LDS throughput); the
@@ -623,58 +891,11 @@ k_gfstack_dma(GsArgs a)
             }
         }
     }
-    // The slot/weight loads issued in the last step (for the step after the last) are still in
-    // flight: wait for them before their registers can be given to anything else.  Without this the
-    // epilogue's store addresses were built in those registers and overwritten by the late data
-    // (observed as a memory fault with RESID_STORE and >= 29 groups; tools/audit_hidden_loads.py
-    // now follows the loop's exit paths as well).
-#pragma unroll
-    for (int k = 0; k < NROW; k++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(sl_n[k]), "+v"(wl_n[k]));
-    __builtin_amdgcn_sched_barrier(0);
-
-    // ---- epilogue: lane = chain c, acc[i] = synthetics[c, t, n0 + i]
-    const bool live = (c < a.C) && (keep == 0);
-    const int nvalid = (int)min((int64_t)GS_NT, N - n0);
-    if (MODE == GF_STORE_SYN) {
-        if (live) {
-            double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-            for (int i = 0; i < GS_NT; i++)
-                if (i < nvalid) o[i] = acc[i];
-        }
-        return;
-    }
-    __syncthreads();
-    if (tid < GS_NT) xbuf[tid] = (tid < nvalid) ? a.data[t * N + n0 + tid] : 0.0;
-    __syncthreads();
-    if (MODE == GF_RESID_STORE) {
-        double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (live && i < nvalid) o[i] = xbuf[i] - acc[i];  // seismic.py:1332
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    } else {
-        const double w = a.wscalar[t];
-        double q = 0.0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (i < nvalid) {
-                    const double tt = w * (xbuf[i] - acc[i]);
-                    q = fma(tt, tt, q);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (live) a.partial[(c * a.T + t) * a.ntile + tile] = q;
-    }
+    GS_DMA_FINISH()
 }
 
 
-// k_gfstack_dmaf: k_gfstack_dma on the float copies of the libraries (beatamd_seis_gflib_store_f32), 64-sample
+// k_gfstack_dmaf: k_gfstack_dma on the float copies of the libraries (beatamd_seis_gflib_round_to_f32), 64-sample
 // tiles: 256-byte row segments by full-wave global_load_lds_dword, float rows at a pitch of 33 pairs, float
 // PAIRS gathered by ds_read_b64 (half the LDS instructions of the f64 kernel -- the multilinear instance of
 // which is bound by exactly those), operands widened in front of the f64 FMA.  Same values, same order:
@@ -693,177 +914,15 @@ k_gfstack_dmaf(GsArgs a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (a.guard_mode && ((a.guard_mode == 1) == (*a.guard_umax > (uint32_t)a.guard_fit))) return;
-    int tile;
-    int64_t t, g;
-    if (a.xcd_order) {
-        // Workgroups b, b+8, b+16, ... run on the same XCD (round-robin dispatch).  The chain
-        // groups of one (target, sample tile) are numbered b = 8*(ngroups*q + g) + x, so they
-        // run on one XCD at about the same time and walk the patches in step: the library rows the
-        // groups have in common are fetched from HBM once and served from that XCD's L2 to the
-        // others.  Scheduling only; results do not depend on it.
-        const int64_t b = blockIdx.x;
-        const int64_t x = b & 7, q = b >> 3;
-        g = q % a.ngroups;
-        const int64_t tt = (q / a.ngroups) * 8 + x;   // t * ntile + tile
-        if (tt >= a.T * a.ntile) return;              // grid padded to a multiple of 8 per group
-        tile = (int)(tt % a.ntile);
-        t = tt / a.ntile;
-    } else {
-        tile = blockIdx.x % a.ntile;
-        const int64_t gt0 = blockIdx.x / a.ntile;  // g*T + t
-        t = gt0 % a.T;
-        g = gt0 / a.T;
-    }
-    const int64_t slot = a.tslot ? (int64_t)a.tslot[t] : (a.Ttab == 1 ? 0 : t);
-    const int64_t gt = g * a.Ttab + slot;                                        // table cell
-    const int64_t tbase = (t - slot) * a.rows_per_target * a.N;                  // doubles
+    GS_BLOCK_DECODE(a, g, t, tile)
+    int64_t gt, tbase;
+    gs_table_cell(a, g, t, gt, tbase);
     const int64_t c = g * CG + tid;
     const int64_t N = a.N;
     const int64_t n0 = (int64_t)tile * GS_NT;
-    const bool dma_lane = (n0 + lane < N);
-    const uint32_t voff = (uint32_t)((n0 + lane) * 4);          // byte offset inside a row
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)xbuf;
-    const int bufsz = a.ucap * GS_PITCH;                          // floats per buffer
-
-    double acc[GS_NT];
-#pragma unroll
-    for (int i = 0; i < GS_NT; i++) acc[i] = 0.0;
-    uint32_t keep = 0;  // results of the DMA statements (always 0): keeps them alive
-
-    const int P = (int)a.P, nvar = a.nvar;
-    const int nsteps = P * nvar;
-    // steps run patch-major over (patch, variable); (p, iv) of the steps ahead are advanced
-    // incrementally (no integer divisions in the loop) and clamp at the last step
-    auto advance = [&](int &p, int &iv) {
-        if (++iv == nvar) { iv = 0; ++p; }
-        if (p >= P) { p = P - 1; iv = nvar - 1; }
-    };
-    // row j of the step lands at buf*bufsz + j*PITCH; lanes 0..LPR-1 move its NT samples.
-    // (scalar address arithmetic kept short: 32 x 32 -> 64 bit products, one exec region per step)
-    const uint32_t rowbytes = (uint32_t)(N * 4);
-    // `dep` is an ordering token only (not named in the text): a request that lists the destination
-    // register of the step's slot load as input cannot be placed in front of that load
-    // `tk` chains the requests of a step: every statement passes it through untouched (in/out
-    // operand, no instruction), its final value is folded into `keep` once per step -- the
-    // statements are not volatile (see above) and must not be dropped.
-    auto dma_row = [&](const float *Gv, uint32_t r, uint32_t slotidx, int boff, uint32_t dep, uint32_t &tk) {
-        const uint64_t off = (uint64_t)r * (uint64_t)rowbytes;
-        const char *rowp = reinterpret_cast<const char *>(Gv) + off;
-        const uint32_t dst = lds0 + (uint32_t)(boff * 4) + slotidx * (uint32_t)(GS_PITCH * 4);
-        if (a.nthint)   // non-temporal: single-group batches read every row segment exactly once
-            asm("s_mov_b32 m0, %3\n\t"
-                "s_nop 0\n\t"
-                "global_load_lds_dword %1, %2 nt"
-                : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
-        else
-            asm("s_mov_b32 m0, %3\n\t"
-                "s_nop 0\n\t"
-                "global_load_lds_dword %1, %2"
-                : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst), "v"(dep));
-    };
-    // (row id, LDS slot) of this wavefront's first KPRE list entries: contiguous in memory, one
-    // scalar load instruction (the gather's lgkmcnt waits count scalar loads too)
-    struct alignas(KPRE * 8) EntBlock { uint32_t v[2 * KPRE]; };
-    const int kstr = a.ustride / WAVES;
-    // Table addresses: the (group, target) part is loop invariant and hoisted as 64-bit bases; the
-    // per-step part is a 32 x 32 bit product added as an unsigned byte offset (scalar loads take it
-    // as their offset operand).  Written out by hand: hipcc kept whole 64 x 64 bit index products
-    // inside the loop (about 60 scalar instructions per step).
-    const char *const cnt_base = reinterpret_cast<const char *>(a.ucount + gt * a.P);
-    const char *const ent_base = reinterpret_cast<const char *>(a.uent + ((gt * a.P) * WAVES + wave) * kstr * 2);
-    const uint32_t ent_step = (uint32_t)(a.ustride * 8);   // bytes per patch: WAVES * kstr entries of 8 B
-    const float *G_a = nullptr;   // library of the step whose list entries are in rid_a / rsl_a
-    auto fetch_ids = [&](int p, int iv, int &U, uint32_t (&rid)[KPRE], uint32_t (&rsl)[KPRE]) {
-        U = __builtin_amdgcn_readfirstlane(
-            (int)*reinterpret_cast<const uint32_t *>(cnt_base + (uint32_t)p * 4u));
-        const EntBlock eb = *reinterpret_cast<const EntBlock *>(ent_base + (uint32_t)p * ent_step);
-#pragma unroll
-        for (int k = 0; k < KPRE; k++) {   // padded: always in bounds
-            rid[k] = eb.v[2 * k];
-            rsl[k] = eb.v[2 * k + 1];
-        }
-        // library base pointer of that step: a scalar load from the kernel arguments, issued with
-        // the list entries one step before it is needed (selecting among four register pairs by a
-        // run-time index costs a branch maze of ~25 scalar instructions per step)
-        G_a = a.G32[iv] + tbase;
-    };
-    auto issue_rows_dep = [&](int p, int iv, int boff, int U, const uint32_t (&rid)[KPRE],
-                              const uint32_t (&rsl)[KPRE], uint32_t dep) {
-        const float *Gv = G_a;
-        if (dma_lane) {
-            uint32_t tk = 0;
-#pragma unroll
-            for (int k = 0; k < KPRE; k++)
-                if (wave + k * WAVES < U) dma_row(Gv, rid[k], rsl[k], boff, dep, tk);
-            if (U > KPRE * WAVES) {   // rare: more distinct rows than the prefetched ids cover
-                const uint32_t *ue = reinterpret_cast<const uint32_t *>(ent_base + (uint32_t)p * ent_step);
-                for (int k = KPRE; wave + k * WAVES < U; k++) dma_row(Gv, ue[2 * k], ue[2 * k + 1], boff, dep, tk);
-            }
-            keep |= tk;
-        }
-    };
-    auto issue_rows = [&](int p, int iv, int buf, int U, const uint32_t (&rid)[KPRE],
-                          const uint32_t (&rsl)[KPRE]) {
-        issue_rows_dep(p, iv, buf * bufsz, U, rid, rsl, voff);   // (any live VGPR: no ordering needed here)
-    };
-    // the lane's slot and weight of step s: asm loads (hipcc must not count them, see above);
-    // valid after the step-top wait statement, which names them
-    uint32_t sl_n[NROW];
-    double wl_n[NROW];
-    const char *const slot_base = reinterpret_cast<const char *>(a.slot + (gt * a.P * NROW) * CG + tid);
-    const char *const w_base = reinterpret_cast<const char *>(
-        (NROW == 1) ? a.w + (g * a.P) * CG + tid : a.w + (gt * a.P * 4) * CG + tid);
-    const uint32_t slot_step = (uint32_t)(NROW * CG * 2);                    // bytes per patch
-    const uint32_t w_step = (uint32_t)((NROW == 1 ? 1 : 4) * CG * 8);
-    const int64_t w_var_bytes = a.w_var_stride * 8;
-    auto fetch_tabs = [&](int p, int iv) {
-        const char *sp = slot_base + (uint32_t)p * slot_step;
-        const char *wp = w_base + (uint32_t)p * w_step + (nvar == 1 ? (int64_t)0 : (int64_t)iv * w_var_bytes);
-#pragma unroll
-        for (int k = 0; k < NROW; k++) {
-            const uint16_t *ps = reinterpret_cast<const uint16_t *>(sp) + k * CG;
-            const double *pw = reinterpret_cast<const double *>(wp) + k * CG;
-            asm("global_load_ushort %0, %1, off" : "=v"(sl_n[k]) : "v"(ps));
-            asm("global_load_dwordx2 %0, %1, off" : "=v"(wl_n[k]) : "v"(pw));
-        }
-    };
-
-    int p1 = 0, iv1 = 0;          // step s+1
-    advance(p1, iv1);
-    int p2 = p1, iv2 = iv1;       // step s+2
-    advance(p2, iv2);
-    int U_a;
-    uint32_t rid_a[KPRE], rsl_a[KPRE];
-    fetch_ids(0, 0, U_a, rid_a, rsl_a);
-    issue_rows(0, 0, 0, U_a, rid_a, rsl_a);
-    fetch_tabs(0, 0);
-    fetch_ids(p1, iv1, U_a, rid_a, rsl_a);
+    GS_DMA_SETUP(1, 4, float, G32)
     for (int s = 0; s < nsteps; s++) {
-        // the tables of this step and (older) the DMA of this step's rows have landed
-        __builtin_amdgcn_sched_barrier(0);
-        // (the copy into this step's registers is part of the statement: hipcc would otherwise
-        // place it in front of the wait and copy registers whose loads are still in flight)
-        uint32_t sl[NROW];
-        double wl[NROW];
-#define BA_WAIT_COPY(NOUT)                                                                      \
-        _Pragma("unroll") for (int k = 0; k < NROW; k++)                                        \
-            asm("s_waitcnt vmcnt(" #NOUT ")\n\t"                                                 \
-                "v_mov_b32 %0, %2\n\t"                                                          \
-                "v_mov_b64 %1, %3"                                                              \
-                : "=&v"(sl[k]), "=&v"(wl[k]) : "v"(sl_n[k]), "v"(wl_n[k]))
-        BA_WAIT_COPY(0);
-#undef BA_WAIT_COPY
-        __builtin_amdgcn_sched_barrier(0);
-        __syncthreads();  // rows of step s visible; everyone has left the FMA phase of step s-1
-        __builtin_amdgcn_sched_barrier(0);
-        // rows of step s+1 -> the other buffer, then that step's slot/weight and the ids of step s+2
-        if (s + 1 < nsteps) issue_rows(p1, iv1, (s + 1) & 1, U_a, rid_a, rsl_a);
-        fetch_tabs(p1, iv1);
-        fetch_ids(p2, iv2, U_a, rid_a, rsl_a);
-        p1 = p2; iv1 = iv2;
-        advance(p2, iv2);
-        __builtin_amdgcn_sched_barrier(0);
-        const int gbuf = (s & 1) * bufsz;   // doubles: the buffer of step s
+        GS_DMA_STEP_TOP()
         // ---- every lane applies ITS rows with ITS weights.  The 2*NT/4 ds_read_b128 of a row
         // are issued by hand in groups of 8, two groups in flight (hipcc keeps 3-4 reads in
         // flight, which leaves the phase bound by LDS latency instead of LDS throughput); the
@@ -901,57 +960,41 @@ k_gfstack_dmaf(GsArgs a)
             }
         }
     }
-    // The slot/weight loads issued in the last step (for the step after the last) are still in
-    // flight: wait for them before their registers can be given to anything else.  Without this the
-    // epilogue's store addresses were built in those registers and overwritten by the late data
-    // (observed as a memory fault with RESID_STORE and >= 29 groups; tools/audit_hidden_loads.py
-    // now follows the loop's exit paths as well).
-#pragma unroll
-    for (int k = 0; k < NROW; k++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(sl_n[k]), "+v"(wl_n[k]));
-    __builtin_amdgcn_sched_barrier(0);
-
-    // ---- epilogue: lane = chain c, acc[i] = synthetics[c, t, n0 + i]
-    const bool live = (c < a.C) && (keep == 0);
-    const int nvalid = (int)min((int64_t)GS_NT, N - n0);
-    if (MODE == GF_STORE_SYN) {
-        if (live) {
-            double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-            for (int i = 0; i < GS_NT; i++)
-                if (i < nvalid) o[i] = acc[i];
-        }
-        return;
-    }
-    __syncthreads();
-    if (tid < GS_NT) xbuf[tid] = (tid < nvalid) ? a.data[t * N + n0 + tid] : 0.0;
-    __syncthreads();
-    if (MODE == GF_RESID_STORE) {
-        double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (live && i < nvalid) o[i] = xbuf[i] - acc[i];  // seismic.py:1332
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    } else {
-        const double w = a.wscalar[t];
-        double q = 0.0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (i < nvalid) {
-                    const double tt = w * (xbuf[i] - acc[i]);
-                    q = fma(tt, tt, q);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (live) a.partial[(c * a.T + t) * a.ntile + tile] = q;
-    }
+    GS_DMA_FINISH()
 }
 
 
+
+// The gather of k_gfstack_ws as asm-operand lists.  One asm statement per gather group: wait for the group's reads, its
+// 8 FMAs, and the reads of the group after next into the registers just consumed (v_fmac_f64 d, x, w = fma(x, w, d)).
+// BA_ACC8 / BA_GROUP name the kernel's acc[], w and xs.
+#define BA_FMA8 \
+    "v_fmac_f64 %0, %8, %16\n\tv_fmac_f64 %1, %9, %16\n\tv_fmac_f64 %2, %10, %16\n\tv_fmac_f64 %3, %11, %16\n\t" \
+    "v_fmac_f64 %4, %12, %16\n\tv_fmac_f64 %5, %13, %16\n\tv_fmac_f64 %6, %14, %16\n\tv_fmac_f64 %7, %15, %16\n\t"
+#define BA_RD8(OFF) \
+    "ds_read_b64 %8, %17 offset:" #OFF "\n\tds_read_b64 %9, %17 offset:" #OFF "+8\n\t" \
+    "ds_read_b64 %10, %17 offset:" #OFF "+16\n\tds_read_b64 %11, %17 offset:" #OFF "+24\n\t" \
+    "ds_read_b64 %12, %17 offset:" #OFF "+32\n\tds_read_b64 %13, %17 offset:" #OFF "+40\n\t" \
+    "ds_read_b64 %14, %17 offset:" #OFF "+48\n\tds_read_b64 %15, %17 offset:" #OFF "+56"
+#define BA_ACC8(G) \
+    "+v"(acc[G * 8]), "+v"(acc[G * 8 + 1]), "+v"(acc[G * 8 + 2]), "+v"(acc[G * 8 + 3]), "+v"(acc[G * 8 + 4]), \
+        "+v"(acc[G * 8 + 5]), "+v"(acc[G * 8 + 6]), "+v"(acc[G * 8 + 7])
+#define BA_Y8(Y) "+v"(Y[0]), "+v"(Y[1]), "+v"(Y[2]), "+v"(Y[3]), "+v"(Y[4]), "+v"(Y[5]), "+v"(Y[6]), "+v"(Y[7])
+#define BA_FMA4A \
+    "v_fmac_f64 %0, %8, %16\n\tv_fmac_f64 %1, %9, %16\n\tv_fmac_f64 %2, %10, %16\n\tv_fmac_f64 %3, %11, %16\n\t"
+#define BA_FMA4B \
+    "v_fmac_f64 %4, %12, %16\n\tv_fmac_f64 %5, %13, %16\n\tv_fmac_f64 %6, %14, %16\n\tv_fmac_f64 %7, %15, %16\n\t"
+#define BA_RD4A(OFF) \
+    "ds_read_b64 %8, %17 offset:" #OFF "\n\tds_read_b64 %9, %17 offset:" #OFF "+8\n\t" \
+    "ds_read_b64 %10, %17 offset:" #OFF "+16\n\tds_read_b64 %11, %17 offset:" #OFF "+24\n\t"
+#define BA_RD4B(OFF) \
+    "ds_read_b64 %12, %17 offset:" #OFF "+32\n\tds_read_b64 %13, %17 offset:" #OFF "+40\n\t" \
+    "ds_read_b64 %14, %17 offset:" #OFF "+48\n\tds_read_b64 %15, %17 offset:" #OFF "+56"
+// in half groups of 4 (LDS operations return in order): 12..16 reads stay in flight instead of
+// 8..16 -- measured 0.5 % (39 rows per step) to 1.3 % (21 rows) per launch
+#define BA_GROUP(G, Y, OFFNEXT) \
+    asm("s_waitcnt lgkmcnt(12)\n\t" BA_FMA4A BA_RD4A(OFFNEXT) "s_waitcnt lgkmcnt(12)\n\t" BA_FMA4B BA_RD4B(OFFNEXT) \
+        : BA_ACC8(G), BA_Y8(Y) : "v"(w), "v"(xs))
 
 // ---------------------------------------------------------------------------------------------
 // k_gfstack_ws: wave-specialised form of k_gfstack_dma (512-chain groups).  Ablations of
@@ -977,31 +1020,14 @@ k_gfstack_ws(GsArgs a)
     constexpr int CW = 8, LW = 4;
     constexpr int GS_NT = 64;
     constexpr int GS_PITCH = GS_NT + 1;   // ds_read_b64 layout
-    constexpr int LPR = GS_NT / 2;        // lanes moving one row segment (16 B each)
     constexpr int KPRE = 16;              // list entries per loader fetched ahead (64 rows per step)
     extern __shared__ __attribute__((aligned(16))) double xbuf[];  // [3][slots][GS_PITCH]
     constexpr int CG = CW * 64;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile;
-    int64_t t, g;
-    if (a.xcd_order) {
-        const int64_t b = blockIdx.x;
-        const int64_t x = b & 7, q = b >> 3;
-        g = q % a.ngroups;
-        const int64_t tt = (q / a.ngroups) * 8 + x;
-        if (tt >= a.T * a.ntile) return;
-        tile = (int)(tt % a.ntile);
-        t = tt / a.ntile;
-    } else {
-        tile = blockIdx.x % a.ntile;
-        const int64_t gt0 = blockIdx.x / a.ntile;
-        t = gt0 % a.T;
-        g = gt0 / a.T;
-    }
-    const int64_t slot = a.tslot ? (int64_t)a.tslot[t] : (a.Ttab == 1 ? 0 : t);
-    const int64_t gt = g * a.Ttab + slot;                                        // table cell
-    const int64_t tbase = (t - slot) * a.rows_per_target * a.N;                  // doubles
+    GS_BLOCK_DECODE(a, g, t, tile)
+    int64_t gt, tbase;
+    gs_table_cell(a, g, t, gt, tbase);
     const int64_t N = a.N;
     const int64_t n0 = (int64_t)tile * GS_NT;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)xbuf;
@@ -1011,146 +1037,9 @@ k_gfstack_ws(GsArgs a)
     const int P = a.nv ? (int)__builtin_amdgcn_readfirstlane((int)a.nv[gt]) : (int)a.P;
     const int nvar = a.nvar;
     const int nsteps = P * nvar;
-    auto advance = [&](int &p, int &iv) {
-        if (++iv == nvar) { iv = 0; ++p; }
-        if (p >= P) { p = P - 1; iv = nvar - 1; }
-    };
 
     if (wave >= CW) {
-        // ==================================== loader ====================================
-        const int lw = wave - CW;
-        const bool dma_lane = (lane < LPR) && (n0 + lane * 2 < N);   // N even (launcher)
-        const uint32_t voff = (uint32_t)((n0 + lane * 2) * 8);      // byte offset inside a row
-        const uint32_t rowbytes = (uint32_t)(N * 8);
-        uint32_t keep = 0;
-        auto dma_row = [&](const double *Gv, uint32_t r, uint32_t slotidx, int boff, uint32_t &tk) {
-            const uint64_t off = (uint64_t)r * (uint64_t)rowbytes;
-            const char *rowp = reinterpret_cast<const char *>(Gv) + off;
-            const uint32_t dst = lds0 + (uint32_t)(boff * 8) + slotidx * (uint32_t)(GS_PITCH * 8);
-            // NTH: non-temporal requests -- a row segment is read by this CU once and by no other
-            // workgroup when the batch is a single chain group (several groups share rows through L2)
-            if (NTH)
-                asm("s_mov_b32 m0, %3\n\t"
-                    "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %1, %2 nt"
-                    : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst));
-            else
-                asm("s_mov_b32 m0, %3\n\t"
-                    "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %1, %2"
-                    : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst));
-        };
-        const int kstr = a.ustride / LW;
-        const char *const cnt_base = reinterpret_cast<const char *>(a.ucount + gt * a.vmax);
-        const char *const ent_base = reinterpret_cast<const char *>(a.uent + ((gt * a.vmax) * LW + lw) * kstr * 2);
-        const uint32_t ent_step = (uint32_t)(a.ustride * 8);
-        int U_a;
-        uint32_t rid[KPRE], rsl[KPRE];
-        const double *G_a = nullptr;
-        auto fetch_ids = [&](int p, int iv) {
-            // constant address space: the tables are written by k_gf_group_tables before this
-            // launch, never here, and must come in through scalar loads -- a vector load would be
-            // counted in this wavefront's vmcnt together with its row requests
-            typedef const __attribute__((address_space(4))) uint32_t *cu32;
-            typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-            typedef const __attribute__((address_space(4))) u32x16 *cent;
-            U_a = (int)*(cu32)(uintptr_t)(cnt_base + (uint32_t)p * 4u);
-            const char *e = ent_base + (uint32_t)p * ent_step;
-            const u32x16 e0 = *(cent)(uintptr_t)e;
-            const u32x16 e1 = *(cent)(uintptr_t)(e + 64);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                rid[k] = e0[2 * k];      rsl[k] = e0[2 * k + 1];
-                rid[8 + k] = e1[2 * k];  rsl[8 + k] = e1[2 * k + 1];
-            }
-            G_a = a.G[iv] + tbase;
-        };
-        auto dma_count = [&](int U) { return U > lw ? (U - lw + LW - 1) / LW : 0; };
-        // rows lw, lw + LW, ... of the list whose entries are in rid / rsl -> buffer at boff
-        auto issue_rows = [&](int p, int boff) {
-            if (dma_lane) {
-                uint32_t tk = 0;
-#pragma unroll
-                for (int k = 0; k < KPRE; k++)
-                    if (lw + k * LW < U_a) dma_row(G_a, rid[k], rsl[k], boff, tk);
-                if (U_a > KPRE * LW) {   // rare: more than 64 distinct rows
-                    typedef const __attribute__((address_space(4))) uint32_t *cu32;
-                    cu32 ue = (cu32)(uintptr_t)(ent_base + (uint32_t)p * ent_step);
-                    for (int k = KPRE; lw + k * LW < U_a; k++) dma_row(G_a, ue[2 * k], ue[2 * k + 1], boff, tk);
-                }
-                keep |= tk;
-            }
-        };
-        // steps 0 .. NB-2 go out before the loop, then step s+NB-1 behind the barrier of step s
-        int boff[NB];
-#pragma unroll
-        for (int j = 0; j < NB; j++) boff[j] = j * bufsz;   // boff[j]: buffer of step s+j
-        int cnt[NB];                                          // cnt[j]: this loader's requests of step s+j
-#pragma unroll
-        for (int j = 0; j < NB; j++) cnt[j] = 0;
-        int pn = 0, ivn = 0;                                  // next step to fetch ids for
-        fetch_ids(pn, ivn);
-#pragma unroll
-        for (int j = 0; j < NB - 1; j++) {
-            if (j < nsteps) {
-                issue_rows(pn, boff[j]);
-                cnt[j] = dma_count(U_a);
-            }
-            advance(pn, ivn);
-            fetch_ids(pn, ivn);                               // ids of step j+1
-        }
-        int p_i = pn;                                         // step whose ids are in rid / rsl (s+NB-1)
-        for (int s = 0; s < nsteps; s++) {
-            __builtin_amdgcn_sched_barrier(0);
-            // this loader's rows of step s have landed when at most its requests of the NB-2
-            // younger steps stay in flight (s_waitcnt takes an immediate; an over-wait is safe)
-            {
-                int young = 0;
-#pragma unroll
-                for (int j = 1; j < NB - 1; j++) young += cnt[j];
-                uint32_t tk = 0;
-#define BA_LWAIT(NOUT) asm("s_waitcnt vmcnt(" #NOUT ")" : "+s"(tk) : "s"(s))
-                switch (young) {
-                case 0: BA_LWAIT(0); break;   case 1: BA_LWAIT(1); break;   case 2: BA_LWAIT(2); break;
-                case 3: BA_LWAIT(3); break;   case 4: BA_LWAIT(4); break;   case 5: BA_LWAIT(5); break;
-                case 6: BA_LWAIT(6); break;   case 7: BA_LWAIT(7); break;   case 8: BA_LWAIT(8); break;
-                case 9: BA_LWAIT(9); break;   case 10: BA_LWAIT(10); break; case 11: BA_LWAIT(11); break;
-                case 12: BA_LWAIT(12); break; case 13: BA_LWAIT(13); break; case 14: BA_LWAIT(14); break;
-                case 15: BA_LWAIT(15); break; case 16: BA_LWAIT(16); break; case 17: BA_LWAIT(17); break;
-                case 18: BA_LWAIT(18); break; case 19: BA_LWAIT(19); break; case 20: BA_LWAIT(20); break;
-                case 21: BA_LWAIT(21); break; case 22: BA_LWAIT(22); break; case 23: BA_LWAIT(23); break;
-                case 24: BA_LWAIT(24); break; case 25: BA_LWAIT(25); break; case 26: BA_LWAIT(26); break;
-                case 27: BA_LWAIT(27); break; case 28: BA_LWAIT(28); break; case 29: BA_LWAIT(29); break;
-                case 30: BA_LWAIT(30); break; case 31: BA_LWAIT(31); break; default: BA_LWAIT(32); break;
-                }
-#undef BA_LWAIT
-                keep |= tk;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();   // rows of step s published; buffer of step s-1 is free
-            __builtin_amdgcn_sched_barrier(0);
-            int k_new = 0;
-            if (s + NB - 1 < nsteps) {
-                issue_rows(p_i, boff[NB - 1]);
-                k_new = dma_count(U_a);
-            }
-            advance(pn, ivn);
-            p_i = pn;
-            fetch_ids(pn, ivn);
-            const int b0 = boff[0];
-#pragma unroll
-            for (int j = 0; j < NB - 1; j++) { boff[j] = boff[j + 1]; cnt[j] = cnt[j + 1]; }
-            boff[NB - 1] = b0;
-            cnt[NB - 1] = 0;
-            cnt[NB - 2] = k_new;
-        }
-        __builtin_amdgcn_s_barrier();   // the consumers' barrier "of step nsteps" (their pipelined loop)
-        // the consumers' epilogue passes the data tile through LDS behind two barriers
-        if (MODE != GF_STORE_SYN) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_s_barrier();
-        }
-        if (keep != 0) a.out[0] = 0.0;   // never true: keeps the request statements alive
+        GS_LOADER_PROGRAM(0, 8, double, G_a = a.G[iv] + tbase)
         return;
     }
 
@@ -1205,7 +1094,7 @@ k_gfstack_ws(GsArgs a)
     static_assert(NG8 == 8, "the read schedule below is written for 64-sample tiles");
     double ya[8], yb[8];
     int p1 = 0, iv1 = 0;          // position of the step whose slot/weight are fetched next
-    advance(p1, iv1);
+    gs_advance(p1, iv1, P, nvar);
     int gbuf = 0;                 // row buffer of the step being gathered
     const int ring = NB * bufsz;
     // The gather of a step is 8 groups of 8 ds_read_b64 + 8 FMA, two groups in flight.  It is
@@ -1230,7 +1119,7 @@ k_gfstack_ws(GsArgs a)
     lds_rd8_b64<64>(yb, xs, -1);
     __builtin_amdgcn_sched_barrier(0);
     fetch_tabs(tab_slot(p1), tab_w(p1, iv1));
-    advance(p1, iv1);
+    gs_advance(p1, iv1, P, nvar);
     // The tables of step s+2 as RUNNING pointers (round 4).  The loop is sensitive to every scalar instruction -- 28
     // dummy s_add_u32 per step cost 5 % -- and rebuilding both pointers from (patch, variable) with the clamp at the last
     // step took ~25 of them.  Now: five scalar instructions pick the increments (hand-written: hipcc turns the same
@@ -1247,35 +1136,6 @@ k_gfstack_ws(GsArgs a)
         int gnext = gbuf + bufsz;
         if (gnext == ring) gnext = 0;
         __builtin_amdgcn_sched_barrier(0);
-        // One asm statement per gather group: wait for the group's reads, its 8 FMAs, and the reads
-        // of the group after next into the registers just consumed (v_fmac_f64 d, x, w = fma(x, w, d)).
-#define BA_FMA8 \
-    "v_fmac_f64 %0, %8, %16\n\tv_fmac_f64 %1, %9, %16\n\tv_fmac_f64 %2, %10, %16\n\tv_fmac_f64 %3, %11, %16\n\t" \
-    "v_fmac_f64 %4, %12, %16\n\tv_fmac_f64 %5, %13, %16\n\tv_fmac_f64 %6, %14, %16\n\tv_fmac_f64 %7, %15, %16\n\t"
-#define BA_RD8(OFF) \
-    "ds_read_b64 %8, %17 offset:" #OFF "\n\tds_read_b64 %9, %17 offset:" #OFF "+8\n\t" \
-    "ds_read_b64 %10, %17 offset:" #OFF "+16\n\tds_read_b64 %11, %17 offset:" #OFF "+24\n\t" \
-    "ds_read_b64 %12, %17 offset:" #OFF "+32\n\tds_read_b64 %13, %17 offset:" #OFF "+40\n\t" \
-    "ds_read_b64 %14, %17 offset:" #OFF "+48\n\tds_read_b64 %15, %17 offset:" #OFF "+56"
-#define BA_ACC8(G) \
-    "+v"(acc[G * 8]), "+v"(acc[G * 8 + 1]), "+v"(acc[G * 8 + 2]), "+v"(acc[G * 8 + 3]), "+v"(acc[G * 8 + 4]), \
-        "+v"(acc[G * 8 + 5]), "+v"(acc[G * 8 + 6]), "+v"(acc[G * 8 + 7])
-#define BA_Y8(Y) "+v"(Y[0]), "+v"(Y[1]), "+v"(Y[2]), "+v"(Y[3]), "+v"(Y[4]), "+v"(Y[5]), "+v"(Y[6]), "+v"(Y[7])
-#define BA_FMA4A \
-    "v_fmac_f64 %0, %8, %16\n\tv_fmac_f64 %1, %9, %16\n\tv_fmac_f64 %2, %10, %16\n\tv_fmac_f64 %3, %11, %16\n\t"
-#define BA_FMA4B \
-    "v_fmac_f64 %4, %12, %16\n\tv_fmac_f64 %5, %13, %16\n\tv_fmac_f64 %6, %14, %16\n\tv_fmac_f64 %7, %15, %16\n\t"
-#define BA_RD4A(OFF) \
-    "ds_read_b64 %8, %17 offset:" #OFF "\n\tds_read_b64 %9, %17 offset:" #OFF "+8\n\t" \
-    "ds_read_b64 %10, %17 offset:" #OFF "+16\n\tds_read_b64 %11, %17 offset:" #OFF "+24\n\t"
-#define BA_RD4B(OFF) \
-    "ds_read_b64 %12, %17 offset:" #OFF "+32\n\tds_read_b64 %13, %17 offset:" #OFF "+40\n\t" \
-    "ds_read_b64 %14, %17 offset:" #OFF "+48\n\tds_read_b64 %15, %17 offset:" #OFF "+56"
-// in half groups of 4 (LDS operations return in order): 12..16 reads stay in flight instead of
-// 8..16 -- measured 0.5 % (39 rows per step) to 1.3 % (21 rows) per launch
-#define BA_GROUP(G, Y, OFFNEXT) \
-    asm("s_waitcnt lgkmcnt(12)\n\t" BA_FMA4A BA_RD4A(OFFNEXT) "s_waitcnt lgkmcnt(12)\n\t" BA_FMA4B BA_RD4B(OFFNEXT) \
-        : BA_ACC8(G), BA_Y8(Y) : "v"(w), "v"(xs))
         BA_GROUP(0, ya, 128);
         BA_GROUP(1, yb, 192);
         BA_GROUP(2, ya, 256);
@@ -1302,15 +1162,6 @@ k_gfstack_ws(GsArgs a)
             : BA_ACC8(7), BA_Y8(yb), "+v"(w) : "v"(xs_n), "v"(wl_n));
         xs = xs_n;
         __builtin_amdgcn_sched_barrier(0);
-#undef BA_GROUP
-#undef BA_RD4B
-#undef BA_RD4A
-#undef BA_FMA4B
-#undef BA_FMA4A
-#undef BA_Y8
-#undef BA_ACC8
-#undef BA_RD8
-#undef BA_FMA8
         fetch_tabs(ps_run, pw_run);     // slot / weight of step s+2
         {
             // patch-major over (patch, variable): the slot table moves on with the patch, the weight table every step
@@ -1339,10 +1190,7 @@ k_gfstack_ws(GsArgs a)
     const int nvalid = (int)min((int64_t)GS_NT, N - n0);
     if (MODE == GF_STORE_SYN) {
         if (live) {
-            double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-            for (int i = 0; i < GS_NT; i++)
-                if (i < nvalid) o[i] = acc[i];
+            gs_store_syn<GS_NT>(a.out + (c * a.T + t) * N + n0, acc, nvalid);
         }
         return;
     }
@@ -1411,30 +1259,30 @@ k_gfstack_ws(GsArgs a)
             __builtin_amdgcn_wave_barrier();
         }
     } else {
-        const double w = a.wscalar[t];
-        double q = 0.0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (i < nvalid) {
-                    const double tt = w * (xbuf[i] - acc[i]);
-                    q = fma(tt, tt, q);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        const double q = gs_misfit_scalar<GS_NT>(a.wscalar[t], acc, xbuf, nvalid);
         if (live) a.partial[(c * a.T + t) * a.ntile + tile] = q;
     }
 }
 
 
-// k_gfstack_ws32: k_gfstack_ws on the float copy of the library (beatamd_seis_gflib_store_f32): a row
-// segment of a 64-sample tile is 256 bytes -- one full-wave global_load_lds_dword --, the LDS rows hold
-// floats (pitch 66 dwords = 33 qwords: conflict-free ds_read_b64 gather of float PAIRS, half the LDS
-// instructions of the f64 kernel), every operand is widened by v_cvt_f64_f32 in front of its FMA; accumulation, weights and epilogues stay f64.  The f64 library holds the same
-// (float-representable) values, so the result is bit for bit what the f64 kernels give.
-// F32 = 0: the same pair gather on the float64 library (A/B: BEATAMD_GS_PAIR=1): double PAIRS by
-// ds_read_b128 at a pitch of 66 doubles = 33 x 16 bytes.
+#undef BA_GROUP
+#undef BA_RD4B
+#undef BA_RD4A
+#undef BA_FMA4B
+#undef BA_FMA4A
+#undef BA_Y8
+#undef BA_ACC8
+#undef BA_RD8
+#undef BA_FMA8
+
+// k_gfstack_wsp<1> (reported as k_gfstack_ws32): k_gfstack_ws on the float copy of the library
+// (beatamd_seis_gflib_round_to_f32): a row segment of a 64-sample tile is 256 bytes -- one full-wave global_load_lds_dword --,
+// the LDS rows hold floats (pitch 66 dwords = 33 qwords: conflict-free ds_read_b64 gather of float PAIRS, half the LDS
+// instructions of the f64 kernel), every operand is widened by v_cvt_f64_f32 in front of its FMA; accumulation, weights
+// and epilogues stay f64.  The f64 library holds the same (float-representable) values, so the result is bit for bit what
+// the f64 kernels give.
+// F32 = 0 (reported as k_gfstack_wsp64): the same pair gather on the float64 library (A/B: BEATAMD_GS_PAIR=1): double
+// PAIRS by ds_read_b128 at a pitch of 66 doubles = 33 x 16 bytes.
 template <int F32, int MODE, int NB, int NTH>
 __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3)))
 k_gfstack_wsp(GsArgs a)
@@ -1450,25 +1298,9 @@ k_gfstack_wsp(GsArgs a)
     constexpr int CG = CW * 64;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int tile;
-    int64_t t, g;
-    if (a.xcd_order) {
-        const int64_t b = blockIdx.x;
-        const int64_t x = b & 7, q = b >> 3;
-        g = q % a.ngroups;
-        const int64_t tt = (q / a.ngroups) * 8 + x;
-        if (tt >= a.T * a.ntile) return;
-        tile = (int)(tt % a.ntile);
-        t = tt / a.ntile;
-    } else {
-        tile = blockIdx.x % a.ntile;
-        const int64_t gt0 = blockIdx.x / a.ntile;
-        t = gt0 % a.T;
-        g = gt0 / a.T;
-    }
-    const int64_t slot = a.tslot ? (int64_t)a.tslot[t] : (a.Ttab == 1 ? 0 : t);
-    const int64_t gt = g * a.Ttab + slot;                                        // table cell
-    const int64_t tbase = (t - slot) * a.rows_per_target * a.N;                  // doubles
+    GS_BLOCK_DECODE(a, g, t, tile)
+    int64_t gt, tbase;
+    gs_table_cell(a, g, t, gt, tbase);
     const int64_t N = a.N;
     const int64_t n0 = (int64_t)tile * GS_NT;
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)xbuf;
@@ -1478,156 +1310,9 @@ k_gfstack_wsp(GsArgs a)
     const int P = a.nv ? (int)__builtin_amdgcn_readfirstlane((int)a.nv[gt]) : (int)a.P;
     const int nvar = a.nvar;
     const int nsteps = P * nvar;
-    auto advance = [&](int &p, int &iv) {
-        if (++iv == nvar) { iv = 0; ++p; }
-        if (p >= P) { p = P - 1; iv = nvar - 1; }
-    };
 
     if (wave >= CW) {
-        // ==================================== loader ====================================
-        const int lw = wave - CW;
-        const bool dma_lane = F32 ? (n0 + lane < N) : ((lane < 32) && (n0 + lane * 2 < N));
-        const uint32_t voff = F32 ? (uint32_t)((n0 + lane) * 4) : (uint32_t)((n0 + lane * 2) * 8);   // byte offset inside a row
-        const uint32_t rowbytes = (uint32_t)(N * ES);
-        uint32_t keep = 0;
-        auto dma_row = [&](const elem_t *Gv, uint32_t r, uint32_t slotidx, int boff, uint32_t &tk) {
-            const uint64_t off = (uint64_t)r * (uint64_t)rowbytes;
-            const char *rowp = reinterpret_cast<const char *>(Gv) + off;
-            const uint32_t dst = lds0 + (uint32_t)(boff * ES) + slotidx * (uint32_t)(GS_PITCH * ES);
-            // NTH: non-temporal requests -- a row segment is read by this CU once and by no other
-            // workgroup when the batch is a single chain group (several groups share rows through L2)
-            if (F32 && NTH)
-                asm("s_mov_b32 m0, %3\n\t"
-                    "s_nop 0\n\t"
-                    "global_load_lds_dword %1, %2 nt"
-                    : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst));
-            else if (F32)
-                asm("s_mov_b32 m0, %3\n\t"
-                    "s_nop 0\n\t"
-                    "global_load_lds_dword %1, %2"
-                    : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst));
-            else if (NTH)
-                asm("s_mov_b32 m0, %3\n\t"
-                    "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %1, %2 nt"
-                    : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst));
-            else
-                asm("s_mov_b32 m0, %3\n\t"
-                    "s_nop 0\n\t"
-                    "global_load_lds_dwordx4 %1, %2"
-                    : "+s"(tk) : "v"(voff), "s"(rowp), "s"(dst));
-        };
-        const int kstr = a.ustride / LW;
-        const char *const cnt_base = reinterpret_cast<const char *>(a.ucount + gt * a.vmax);
-        const char *const ent_base = reinterpret_cast<const char *>(a.uent + ((gt * a.vmax) * LW + lw) * kstr * 2);
-        const uint32_t ent_step = (uint32_t)(a.ustride * 8);
-        int U_a;
-        uint32_t rid[KPRE], rsl[KPRE];
-        const elem_t *G_a = nullptr;
-        auto fetch_ids = [&](int p, int iv) {
-            // constant address space: the tables are written by k_gf_group_tables before this
-            // launch, never here, and must come in through scalar loads -- a vector load would be
-            // counted in this wavefront's vmcnt together with its row requests
-            typedef const __attribute__((address_space(4))) uint32_t *cu32;
-            typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-            typedef const __attribute__((address_space(4))) u32x16 *cent;
-            U_a = (int)*(cu32)(uintptr_t)(cnt_base + (uint32_t)p * 4u);
-            const char *e = ent_base + (uint32_t)p * ent_step;
-            const u32x16 e0 = *(cent)(uintptr_t)e;
-            const u32x16 e1 = *(cent)(uintptr_t)(e + 64);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                rid[k] = e0[2 * k];      rsl[k] = e0[2 * k + 1];
-                rid[8 + k] = e1[2 * k];  rsl[8 + k] = e1[2 * k + 1];
-            }
-            if constexpr (F32 != 0) G_a = a.G32[iv] + tbase; else G_a = a.G[iv] + tbase;
-        };
-        auto dma_count = [&](int U) { return U > lw ? (U - lw + LW - 1) / LW : 0; };
-        // rows lw, lw + LW, ... of the list whose entries are in rid / rsl -> buffer at boff
-        auto issue_rows = [&](int p, int boff) {
-            if (dma_lane) {
-                uint32_t tk = 0;
-#pragma unroll
-                for (int k = 0; k < KPRE; k++)
-                    if (lw + k * LW < U_a) dma_row(G_a, rid[k], rsl[k], boff, tk);
-                if (U_a > KPRE * LW) {   // rare: more than 64 distinct rows
-                    typedef const __attribute__((address_space(4))) uint32_t *cu32;
-                    cu32 ue = (cu32)(uintptr_t)(ent_base + (uint32_t)p * ent_step);
-                    for (int k = KPRE; lw + k * LW < U_a; k++) dma_row(G_a, ue[2 * k], ue[2 * k + 1], boff, tk);
-                }
-                keep |= tk;
-            }
-        };
-        // steps 0 .. NB-2 go out before the loop, then step s+NB-1 behind the barrier of step s
-        int boff[NB];
-#pragma unroll
-        for (int j = 0; j < NB; j++) boff[j] = j * bufsz;   // boff[j]: buffer of step s+j
-        int cnt[NB];                                          // cnt[j]: this loader's requests of step s+j
-#pragma unroll
-        for (int j = 0; j < NB; j++) cnt[j] = 0;
-        int pn = 0, ivn = 0;                                  // next step to fetch ids for
-        fetch_ids(pn, ivn);
-#pragma unroll
-        for (int j = 0; j < NB - 1; j++) {
-            if (j < nsteps) {
-                issue_rows(pn, boff[j]);
-                cnt[j] = dma_count(U_a);
-            }
-            advance(pn, ivn);
-            fetch_ids(pn, ivn);                               // ids of step j+1
-        }
-        int p_i = pn;                                         // step whose ids are in rid / rsl (s+NB-1)
-        for (int s = 0; s < nsteps; s++) {
-            __builtin_amdgcn_sched_barrier(0);
-            // this loader's rows of step s have landed when at most its requests of the NB-2
-            // younger steps stay in flight (s_waitcnt takes an immediate; an over-wait is safe)
-            {
-                int young = 0;
-#pragma unroll
-                for (int j = 1; j < NB - 1; j++) young += cnt[j];
-                uint32_t tk = 0;
-#define BA_LWAIT(NOUT) asm("s_waitcnt vmcnt(" #NOUT ")" : "+s"(tk) : "s"(s))
-                switch (young) {
-                case 0: BA_LWAIT(0); break;   case 1: BA_LWAIT(1); break;   case 2: BA_LWAIT(2); break;
-                case 3: BA_LWAIT(3); break;   case 4: BA_LWAIT(4); break;   case 5: BA_LWAIT(5); break;
-                case 6: BA_LWAIT(6); break;   case 7: BA_LWAIT(7); break;   case 8: BA_LWAIT(8); break;
-                case 9: BA_LWAIT(9); break;   case 10: BA_LWAIT(10); break; case 11: BA_LWAIT(11); break;
-                case 12: BA_LWAIT(12); break; case 13: BA_LWAIT(13); break; case 14: BA_LWAIT(14); break;
-                case 15: BA_LWAIT(15); break; case 16: BA_LWAIT(16); break; case 17: BA_LWAIT(17); break;
-                case 18: BA_LWAIT(18); break; case 19: BA_LWAIT(19); break; case 20: BA_LWAIT(20); break;
-                case 21: BA_LWAIT(21); break; case 22: BA_LWAIT(22); break; case 23: BA_LWAIT(23); break;
-                case 24: BA_LWAIT(24); break; case 25: BA_LWAIT(25); break; case 26: BA_LWAIT(26); break;
-                case 27: BA_LWAIT(27); break; case 28: BA_LWAIT(28); break; case 29: BA_LWAIT(29); break;
-                case 30: BA_LWAIT(30); break; case 31: BA_LWAIT(31); break; default: BA_LWAIT(32); break;
-                }
-#undef BA_LWAIT
-                keep |= tk;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();   // rows of step s published; buffer of step s-1 is free
-            __builtin_amdgcn_sched_barrier(0);
-            int k_new = 0;
-            if (s + NB - 1 < nsteps) {
-                issue_rows(p_i, boff[NB - 1]);
-                k_new = dma_count(U_a);
-            }
-            advance(pn, ivn);
-            p_i = pn;
-            fetch_ids(pn, ivn);
-            const int b0 = boff[0];
-#pragma unroll
-            for (int j = 0; j < NB - 1; j++) { boff[j] = boff[j + 1]; cnt[j] = cnt[j + 1]; }
-            boff[NB - 1] = b0;
-            cnt[NB - 1] = 0;
-            cnt[NB - 2] = k_new;
-        }
-        __builtin_amdgcn_s_barrier();   // the consumers' barrier "of step nsteps" (their pipelined loop)
-        // the consumers' epilogue passes the data tile through LDS behind two barriers
-        if (MODE != GF_STORE_SYN) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_s_barrier();
-        }
-        if (keep != 0) a.out[0] = 0.0;   // never true: keeps the request statements alive
+        GS_LOADER_PROGRAM(F32, ES, elem_t, if constexpr (F32 != 0) G_a = a.G32[iv] + tbase; else G_a = a.G[iv] + tbase)
         return;
     }
 
@@ -1681,7 +1366,7 @@ k_gfstack_wsp(GsArgs a)
     // statements that name the landing registers.
     pair_t ya[4], yb[4];
     int p1 = 0, iv1 = 0;          // position of the step whose slot/weight are fetched next
-    advance(p1, iv1);
+    gs_advance(p1, iv1, P, nvar);
     int gbuf = 0;                 // row buffer of the step being gathered
     const int ring = NB * bufsz;
     double w;
@@ -1696,7 +1381,7 @@ k_gfstack_wsp(GsArgs a)
     lds_rd4_pair<F32 ? 1 : 2, 32>(yb, xs, -1);
     __builtin_amdgcn_sched_barrier(0);
     fetch_tabs(tab_slot(p1), tab_w(p1, iv1));
-    advance(p1, iv1);
+    gs_advance(p1, iv1, P, nvar);
 #define F2_FMA(G, Y)                                                          \
     _Pragma("unroll") for (int q = 0; q < 4; q++) {                           \
         acc[(G) * 8 + 2 * q] = fma((double)Y[q].x, w, acc[(G) * 8 + 2 * q]);   \
@@ -1714,7 +1399,7 @@ k_gfstack_wsp(GsArgs a)
         int gnext = gbuf + bufsz;
         if (gnext == ring) gnext = 0;
         const char *const ps2 = tab_slot(p1), *const pw2 = tab_w(p1, iv1);   // tables of step s+2
-        advance(p1, iv1);
+        gs_advance(p1, iv1, P, nvar);
         __builtin_amdgcn_sched_barrier(0);
         F2_GROUP(0, ya, 64)
         F2_GROUP(1, yb, 96)
@@ -1757,10 +1442,7 @@ k_gfstack_wsp(GsArgs a)
     const int nvalid = (int)min((int64_t)GS_NT, N - n0);
     if (MODE == GF_STORE_SYN) {
         if (live) {
-            double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-            for (int i = 0; i < GS_NT; i++)
-                if (i < nvalid) o[i] = acc[i];
+            gs_store_syn<GS_NT>(a.out + (c * a.T + t) * N + n0, acc, nvalid);
         }
         return;
     }
@@ -1770,27 +1452,9 @@ k_gfstack_wsp(GsArgs a)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (MODE == GF_RESID_STORE) {
-        double *o = a.out + (c * a.T + t) * N + n0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (live && i < nvalid) o[i] = xbuf[i] - acc[i];  // seismic.py:1332
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        gs_resid_store<GS_NT>(a.out + (c * a.T + t) * N + n0, acc, xbuf, live, nvalid);
     } else {
-        const double w = a.wscalar[t];
-        double q = 0.0;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++)
-                if (i < nvalid) {
-                    const double tt = w * (xbuf[i] - acc[i]);
-                    q = fma(tt, tt, q);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        const double q = gs_misfit_scalar<GS_NT>(a.wscalar[t], acc, xbuf, nvalid);
         if (live) a.partial[(c * a.T + t) * a.ntile + tile] = q;
     }
 }
@@ -2146,19 +1810,17 @@ static int pick_group(int64_t C)
 }
 
 // the distinct-row bound of chain groups of `cg`, or false when their row buffers or the table
-// kernel's maps do not fit LDS
-static bool shared_fit(const GfStackCall &k, int cg, int *ucap_out)
+// kernel's maps do not fit LDS (row_passes: the loader / consumer kernel takes any library)
+static bool shared_fit(const GfStackCall &k, int cg, bool row_passes, int *ucap_out)
 {
     const SeisLib &L = *k.libs[0];
     const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
     const int64_t DS = L.D * L.S;
     const int64_t ucap = std::min<int64_t>((int64_t)cg * nrow, DS);
-    if (ws_wanted(k, cg)) {   // row passes: any library
-        *ucap_out = (int)std::max<int64_t>(ucap, 2);
-        return true;
+    if (!row_passes) {
+        if (2 * ucap * (GS_NT_MAX + 2) * 8 > 158 * 1024) return false;   // two row buffers of the bound
+        if (2 * DS * 4 + cg * 4 + 2048 > 60 * 1024) return false;         // presence map + group masks of k_gf_group_tables
     }
-    if (2 * ucap * (GS_NT_MAX + 2) * 8 > 158 * 1024) return false;   // two row buffers of the bound
-    if (2 * DS * 4 + cg * 4 + 2048 > 60 * 1024) return false;         // presence map + group masks of k_gf_group_tables
     *ucap_out = (int)std::max<int64_t>(ucap, 2);
     return true;
 }
@@ -2180,7 +1842,7 @@ int gfstack_shared_candidates(const GfStackCall &k, int *cgs, int *ucaps)
         if (k.C >= 1024 && cand[i] < 256) continue;
         if (k.C >= 384 && cand[i] < 128) continue;
         int u = 0;
-        if (shared_fit(k, cand[i], &u)) { cgs[n] = cand[i]; ucaps[n] = u; n++; }
+        if (shared_fit(k, cand[i], ws_wanted(k, cand[i]), &u)) { cgs[n] = cand[i]; ucaps[n] = u; n++; }
     }
     return n;
 }
@@ -2201,24 +1863,12 @@ bool gfstack_shared_applicable(const GfStackCall &k, int *cg_out, int *ucap_out)
         if (!ws_wanted(k, WS_CG)) return false;
         cg = WS_CG;
     }
-    const int64_t DS = L.D * L.S;
-    int64_t ucap = std::min<int64_t>((int64_t)cg * nrow, DS);
-    if (ws_wanted(k, cg)) {
-        *cg_out = cg;
-        *ucap_out = (int)std::max<int64_t>(ucap, 2);
-        return true;
-    }
+    const bool ws = ws_wanted(k, cg);   // (of the size asked for: a 1024-chain request halved to 512 stays a small-group launch here)
     // two row buffers of the group's distinct-row bound must fit LDS (prefer >= 2 workgroups per CU): halve the group
     // until they do
-    const int GS_PITCH = GS_NT_MAX + 2;
-    while (ucap * GS_PITCH * 8 > 72 * 1024 && cg > 64) {
-        cg /= 2;
-        ucap = std::min<int64_t>((int64_t)cg * nrow, DS);
-    }
-    if (2 * ucap * GS_PITCH * 8 > 158 * 1024) return false;
-    if (2 * DS * 4 + cg * 4 + 2048 > 60 * 1024) return false;  // presence map + group masks of k_gf_group_tables
+    while (!ws && std::min<int64_t>((int64_t)cg * nrow, L.D * L.S) * (GS_NT_MAX + 2) * 8 > 72 * 1024 && cg > 64) cg /= 2;
+    if (!shared_fit(k, cg, ws, ucap_out)) return false;
     *cg_out = cg;
-    *ucap_out = (int)std::max<int64_t>(ucap, 2);
     return true;
 }
 
@@ -2230,6 +1880,49 @@ static bool ws_wanted(const GfStackCall &k, int CG)
     const bool want = GfKnobs::get(kn.gs_ws, GS_WS_DEFAULT) != 0;
     return want && CG == WS_CG && k.interp != BEATAMD_MULTILINEAR && k.libs[0]->N % 2 == 0 &&
            !(GfKnobs::set(kn.gs_dma) && kn.gs_dma != 2) && !(GfKnobs::set(kn.gs_nt) && kn.gs_nt != 64);
+}
+
+// ---- what launch_gfstack_ws and launch_gfstack_shared do the same way
+// the kernel arguments that do not depend on the kernel chosen; *f32: the call asks for the float copies and every
+// library has one
+static void gs_common_args(GsArgs &a, const GfStackCall &k, int64_t Ttab, int64_t ngroups, bool *f32)
+{
+    const GfKnobs &kn = *k.knobs;
+    const SeisLib &L = *k.libs[0];
+    memset(&a, 0, sizeof(a));
+    *f32 = k.f32;
+    for (int v = 0; v < k.nvar; v++) {
+        a.G[v] = k.libs[v]->g;
+        a.G32[v] = k.libs[v]->g32;
+        *f32 = *f32 && a.G32[v] != nullptr;
+    }
+    a.nvar = k.nvar;
+    a.C = k.C; a.T = L.T; a.P = L.P; a.N = L.N;
+    a.Ttab = Ttab; a.rows_per_target = L.P * L.D * L.S;
+    a.tslot = k.tslot;
+    a.ngroups = ngroups;
+    a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
+    a.nthint = GfKnobs::set(kn.gs_nthint) ? (kn.gs_nthint != 0) : (GS_NTHINT_DEFAULT && ngroups == 1);
+}
+
+// chain groups of one (target, tile) on one XCD (several groups only; BEATAMD_GS_ORDER) -> workgroups of the grid, padded
+// to a multiple of 8 per group in that order.  Requires a.T, a.ngroups and a.ntile (the tile count of the launch itself)
+static int64_t gs_grid(GsArgs &a, const GfKnobs &kn)
+{
+    a.xcd_order = (a.ngroups > 1 && !GfKnobs::is(kn.gs_order, 0)) ? 1 : 0;
+    if (GfKnobs::is(kn.gs_order, 1)) a.xcd_order = 1;
+    return a.xcd_order ? ((a.T * a.ntile + 7) / 8) * 8 * a.ngroups : a.ngroups * a.T * a.ntile;
+}
+
+// what beatamd_ctx_gf_group_stats reports of the launch
+static void gs_record_stats(beatamd_ctx *ctx, const GfStackCall &k, int64_t GTP, int64_t Ttab, int cg, bool has_passes)
+{
+    ctx->gs_ngtp = GTP;
+    ctx->gs_trep = (double)k.libs[0]->T / (double)Ttab;
+    ctx->gs_N = k.libs[0]->N;
+    ctx->gs_cg = cg;
+    ctx->gs_nvar = k.nvar;
+    ctx->gs_has_passes = has_passes;
 }
 
 static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *rowoff, int64_t Ttab)
@@ -2289,28 +1982,18 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     BA_HIP(hipGetLastError());
 
     GsArgs a;
-    memset(&a, 0, sizeof(a));
-    bool f32 = k.f32;   // float copies: the pair gather of k_gfstack_wsp<1>
+    bool f32;   // float copies: the pair gather of k_gfstack_wsp<1>
+    gs_common_args(a, k, Ttab, ngroups, &f32);
     const bool pair64 = GfKnobs::is(kn.gs_pair, 1);   // A/B: ds_read_b128 pairs
-    for (int v = 0; v < k.nvar; v++) {
-        a.G[v] = k.libs[v]->g;
-        a.G32[v] = k.libs[v]->g32;
-        f32 = f32 && a.G32[v] != nullptr;
-    }
-    a.nvar = k.nvar; a.nrow = 1;
-    a.C = k.C; a.T = L.T; a.P = L.P; a.N = L.N;
-    a.Ttab = Ttab; a.rows_per_target = L.P * L.D * L.S;
-    a.tslot = k.tslot;
+    a.nrow = 1;
     a.CG = WS_CG; a.ucap = cap; a.ustride = WS_USTRIDE;
     a.nt = 64; a.dma = 2; a.ws = 3;
-    a.ngroups = ngroups;
     a.ntile = (int)((L.N + 63) / 64);
     a.nv = maxpass > 1 ? nv : nullptr;
     a.vmax = vmax;
     a.order = ta.order;
     a.uent = ta.uent; a.ucount = ta.ucount; a.slot = ta.slot; a.w = ta.w;
     a.w_var_stride = ta.w_var_stride;
-    a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     if (k.mode == GF_RESID_SCALAR || k.mode == GF_RESID_BAND1) {
         BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     }
@@ -2318,14 +2001,7 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
         BA_TRY(ctx->scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2, &a.edges));
         a.band_w = k.band_w;
     }
-    a.nthint = GfKnobs::set(kn.gs_nthint) ? (kn.gs_nthint != 0) : (GS_NTHINT_DEFAULT && ngroups == 1);
-    int64_t nblocks = ngroups * L.T * a.ntile;
-    {
-        // chain groups of one (target, tile) on one XCD (several groups only)
-        a.xcd_order = (ngroups > 1 && !GfKnobs::is(kn.gs_order, 0)) ? 1 : 0;
-        if (GfKnobs::is(kn.gs_order, 1)) a.xcd_order = 1;
-        if (a.xcd_order) nblocks = ((L.T * a.ntile + 7) / 8) * 8 * ngroups;
-    }
+    const int64_t nblocks = gs_grid(a, kn);
     BA_CHECK(nblocks < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");
     // three row buffers of cap slots + the zero row each
     size_t lds = f32 ? (size_t)(cap + 1) * (64 + 2) * sizeof(float) * 3
@@ -2341,12 +2017,7 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
              "loader/consumer kernel: 512-chain groups, nearest neighbour; %d row slots per LDS buffer (a patch can touch min(512, "
              "D*S = %lld) rows), %s", cap, (long long)(L.D * L.S),
              maxpass > 1 ? "patches that touch more are staged in passes of equal size" : "one pass per patch");
-    ctx->gs_ngtp = GTP;
-    ctx->gs_trep = (double)L.T / (double)Ttab;
-    ctx->gs_N = L.N;
-    ctx->gs_cg = WS_CG;
-    ctx->gs_nvar = k.nvar;
-    ctx->gs_has_passes = maxpass > 1;
+    gs_record_stats(ctx, k, GTP, Ttab, WS_CG, maxpass > 1);
     {
         ScopedTimer tm(ctx, "gfstack");
         BA_TRY(launch_ws(k.mode, dim3((unsigned)nblocks), lds, ctx->stream, a, f32 ? 1 : (pair64 ? 2 : 0)));
@@ -2424,33 +2095,22 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     BA_HIP(hipGetLastError());
 
     GsArgs a;
-    memset(&a, 0, sizeof(a));
-    bool f32 = k.f32;   // float copies: k_gfstack_dmaf (LDS-DMA kernel, 64-sample tiles, groups up to 512 chains)
-    for (int v = 0; v < k.nvar; v++) {
-        a.G[v] = k.libs[v]->g;
-        a.G32[v] = k.libs[v]->g32;
-        f32 = f32 && a.G32[v] != nullptr;
-    }
-    a.nvar = k.nvar; a.nrow = nrow;
-    a.C = k.C; a.T = L.T; a.P = L.P; a.N = L.N;
-    a.Ttab = Ttab; a.rows_per_target = L.P * L.D * L.S;
-    a.tslot = k.tslot;
+    bool f32;   // float copies: k_gfstack_dmaf (LDS-DMA kernel, 64-sample tiles, groups up to 512 chains)
+    gs_common_args(a, k, Ttab, ngroups, &f32);
+    a.nrow = nrow;
     a.CG = CG; a.ucap = ucap; a.ustride = ga.ustride;
     a.nt = 64;
     {
         if (GfKnobs::is(kn.gs_nt, 32)) a.nt = 32;
         if (CG == 1024) a.nt = 32;
     }
-    a.ngroups = ngroups;
     a.ntile = (int)((L.N + a.nt - 1) / a.nt);
     a.urows = ga.urows; a.uent = ga.uent; a.ucount = ga.ucount; a.slot = ga.slot; a.w = ga.w;
     a.w_var_stride = ga.w_var_stride;
-    a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     if (k.mode == GF_RESID_SCALAR) {
         BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     }
-    int64_t nblocks = ngroups * L.T * a.ntile;
-    BA_CHECK(nblocks < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");
+    BA_CHECK(ngroups * L.T * a.ntile < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");
     // Small chain groups (1-2 wavefronts per workgroup) reach the 2 waves/SIMD the kernels are
     // built for only if several workgroups fit a CU's LDS: their row buffers are sized by the
     // largest distinct-row count that actually occurs instead of the bound min(chains*rows, D*S).
@@ -2485,12 +2145,10 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     }
     // (fitted twin first, then the full-size twin; a single unguarded launch otherwise)
     const int full_ucap = ucap;
-    const int64_t nblocks0 = nblocks;
     const int nt0 = a.nt, ntile0 = a.ntile;
     ScopedTimer tm(ctx, "gfstack");   // (both twins: one timing)
     for (int twin = (ucap_fit ? 1 : 0); twin <= (ucap_fit ? 2 : 0); twin++) {
     ucap = (twin == 1) ? ucap_fit : full_ucap;
-    nblocks = nblocks0;
     a.nt = nt0; a.ntile = ntile0;
     a.ucap = ucap;
     a.guard_mode = twin;
@@ -2501,12 +2159,10 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
         // two row buffers (the candidates were chosen so that they fit); BEATAMD_GS_DMA=1: the ds_read_b128 layout (A/B)
         BA_CHECK(2 * lds <= 158 * 1024, BEATAMD_EINVAL, "internal: k_gfstack_dma row buffers exceed LDS");
         a.dma = GfKnobs::is(kn.gs_dma, 1) ? 1 : 2;   // 2: ds_read_b64 / pitch NT+1 (default); 1: b128 / pitch NT+2
-        if (a.nt == 32 && a.dma != 2) { a.nt = 64; a.ntile = (int)((L.N + 63) / 64); nblocks = ngroups * L.T * a.ntile;
-                                        lds = (size_t)ucap * (a.nt + 2) * sizeof(double); }
+        if (a.nt == 32 && a.dma != 2) { a.nt = 64; a.ntile = (int)((L.N + 63) / 64); lds = (size_t)ucap * (a.nt + 2) * sizeof(double); }
         BA_CHECK(CG != 1024 || a.dma == 2, BEATAMD_EINVAL, "gfstack: 1024-chain groups need the LDS-DMA kernel");
         BA_CHECK(!ga.windowed || a.dma == 2, BEATAMD_EINVAL, "internal: window slots need the ds_read_b64 kernel");
         a.ws = 0;
-        a.nthint = GfKnobs::set(kn.gs_nthint) ? (kn.gs_nthint != 0) : (GS_NTHINT_DEFAULT && ngroups == 1);
         a.f32pair = 0;
         if (a.dma == 2 && a.nt == 64 && CG <= 512 && f32) {
             a.f32pair = 1;
@@ -2515,23 +2171,13 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
             lds *= 2;
         }
     }
-    {
-        // chain groups of one (target, tile) on one XCD (several groups only)
-        a.xcd_order = (ngroups > 1 && !GfKnobs::is(kn.gs_order, 0)) ? 1 : 0;
-        if (GfKnobs::is(kn.gs_order, 1)) a.xcd_order = 1;
-        if (a.xcd_order) nblocks = ((L.T * a.ntile + 7) / 8) * 8 * ngroups;
-    }
+    const int64_t nblocks = gs_grid(a, kn);
     if (a.f32pair)
         snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_dmaf<%d,%d,%d>", CG / 64, nrow, k.mode);
     else
         snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "%s<%d,%d,%d,%d,%d>",
                  "k_gfstack_dma", CG / 64, nrow, k.mode, a.nt, a.dma == 2 ? 1 : 0);
-    ctx->gs_ngtp = GTP;
-    ctx->gs_trep = (double)L.T / (double)Ttab;
-    ctx->gs_N = L.N;
-    ctx->gs_cg = CG;
-    ctx->gs_nvar = k.nvar;
-    ctx->gs_has_passes = false;
+    gs_record_stats(ctx, k, GTP, Ttab, CG, false);
     snprintf(ctx->gf_plan, sizeof(ctx->gf_plan),
              "lane <-> chain kernel with %d-chain groups (%s): row buffers of %d slots%s", CG,
              k.C < 384 ? "small batch" : nrow == 4 ? "multilinear below 192 chains or an odd sample count" : "group size measured fastest",
