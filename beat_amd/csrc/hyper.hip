@@ -12,14 +12,14 @@
 // k_hyper_logp, accept, now and then tune) is bound by its launches.  The chains never talk to each other, hence
 // k_hyper_chain runs ALL steps of a chain inside one kernel: one wavefront per chain, lanes over hyper-parameters and
 // terms, the chain's state in LDS, no barrier between wavefronts after the tables are staged, no atomics but the final
-// acceptance count.  Draws, box test, term formula, `like` order, accept rule and tuning table are the device
-// functions the step-by-step kernels use (philox.hpp, hyper_term, hyper_like below), so both paths agree bit for bit.
+// acceptance count.  Both paths call the same device functions, so they agree bit for bit: the draws
+// (philox_univariate_pair, philox_log_u: philox.hpp), the proposal with its box test, the accept rule and the tuning
+// table (propose_component, metropolis_accept, tune_factor: metropolis.hpp), the term formula and `like` (hyper_term,
+// hyper_like below, shared with k_hyper_logp).
 #include "kernels.hpp"
-#include "philox.hpp"
+#include "metropolis.hpp"
 
 namespace beatamd {
-
-#define LOG_2PI 1.8378770664093453  // log(2*pi), distributions.py:13
 
 // kind 0 (dataset, distributions.py:212-219; M = data.samples uncast, no M log 2pi):
 //     -0.5 * (slog_pdet + (M * 2 * hp) + (1 / exp(hp * 2)) * llk)
@@ -35,6 +35,7 @@ __device__ __forceinline__ double hyper_term(int kind, double M, double slog, do
 // `like` of one chain by its wavefront (all 64 lanes call; every lane returns the same bits): per composite, lane l
 // sums the terms l, l + 64, ... in ascending order, the 64 partial sums meet in a butterfly (xor 32, 16, ... 1), and the
 // composite sums are added in composite order (problems.py:286-296).  The order depends on (nterm, group ends) only.
+// (Not like_serial's order, on purpose: that one is a single thread walking the row.)
 __device__ __forceinline__ double hyper_like(const double *terms, const LikeGroups &grp, int lane)
 {
 #pragma clang fp contract(off)
@@ -158,24 +159,14 @@ __global__ void __launch_bounds__(64 * HY_WAVES) k_hyper_chain(HyperChainArgs a)
             sut = a.tune_interval;
         }
         const uint32_t step = a.step0 + (uint32_t)s;
-        // k_philox_univariate + k_propose: delta = draw * scale; q = q0 + delta * scaling; box test
+        // k_philox_univariate + k_propose: delta = draw * scale, then propose_component
         bool ok = true;
         for (int j = lane; j < npair; j += 64) {
             double x, y;
             philox_univariate_pair(a.kind, (uint32_t)j, gc, step, k0, k1, x, y);
             const int k = 2 * j;
-            {
-                const double d = (x * ssc[k]) * sc;
-                const double q = h[k] + d;
-                hp[k] = q;
-                if (!(q >= slo[k] && q <= sup[k])) ok = false;
-            }
-            if (k + 1 < nh) {
-                const double d = (y * ssc[k + 1]) * sc;
-                const double q = h[k + 1] + d;
-                hp[k + 1] = q;
-                if (!(q >= slo[k + 1] && q <= sup[k + 1])) ok = false;
-            }
+            if (!propose_component(h[k], x * ssc[k], sc, slo[k], sup[k], hp[k])) ok = false;
+            if (k + 1 < nh && !propose_component(h[k + 1], y * ssc[k + 1], sc, slo[k + 1], sup[k + 1], hp[k + 1])) ok = false;
         }
         const double log_u = philox_log_u(gc, step, k0, k1);
         // outside the box: rejected without evaluation (metropolis.py:341-343, 383-385)
@@ -184,8 +175,7 @@ __global__ void __launch_bounds__(64 * HY_WAVES) k_hyper_chain(HyperChainArgs a)
             for (int k = lane; k < nterm; k += 64) prop[k] = hyper_term(skind[k], sM[k], sslog[k], hp[shp[k]], llk[k]);
             wave_lds_sync();
             const double lp = hyper_like(prop, a.t.grp, lane);
-            const double mr = 1.0 * (lp - lcur);      // k_accept with beta = 1
-            if (isfinite(mr) && (log_u < mr)) {
+            if (metropolis_accept(1.0, lp, lcur, log_u)) {      // k_accept with beta = 1
                 for (int j = lane; j < npair; j += 64) {      // (the lane that draws a pair owns its h)
                     h[2 * j] = hp[2 * j];
                     if (2 * j + 1 < nh) h[2 * j + 1] = hp[2 * j + 1];

@@ -166,7 +166,7 @@ bool quadform_small_applicable(int nd, const int64_t *M);
 int launch_quadform_small(beatamd_ctx *ctx, const QuadformSmallCall &call);
 int launch_check_upper_tri(beatamd_ctx *ctx, const double *A, int64_t nd, int64_t M, int *flag_dev);
 
-// ---- logp.hip (small kernels) ------------------------------------------------------
+// ---- logp.hip (small kernels: likelihood epilogues, geodetic stacking) -------------
 struct HpSrc {  // hp(c,d) = base[c*stride + (offs ? offs[d] : d)]
     const double *base = nullptr;
     int64_t stride = 0;
@@ -266,18 +266,6 @@ int launch_like_assemble(beatamd_ctx *ctx, int64_t C, int64_t nllk, int64_t nsrc
 // gather slips of all variables into a dense [C, nvar, P] buffer
 int launch_gather_slips(beatamd_ctx *ctx, int64_t C, int nvar, int64_t P, const ChainVec *slips,
                         double *out);
-// metropolis.py:276-422 pieces
-int launch_propose(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q0,
-                   const double *delta, const double *scaling, const double *lower,
-                   const double *upper, double *Qprop, int32_t *inbounds);
-// grp (nullable): sum the `like` column of Lprop here instead of a launch_like_sum before; acc_sum /
-// n_acc (nullable): per-chain and population acceptance counters; advance_step: bump ctx->step_dev
-int launch_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int64_t nllk, double *Q0,
-                  double *L0, const double *Qprop, double *Lprop, const int32_t *inbounds,
-                  const double *log_u, double beta, const double *betas, int32_t *accepted,
-                  const LikeGroups *grp = nullptr, const int32_t *chain_bad = nullptr,
-                  int32_t *acc_sum = nullptr, int64_t *n_acc = nullptr, bool advance_step = false);
-
 // geometry.hip: line-of-sight synthetics of rectangular / Mogi sources, mu [C, Nobs]
 // with res (and data, odw [Nobs]): res = (data - mu) * odw is stored instead of mu, minus the correction terms gc
 int launch_geom_los(beatamd_ctx *ctx, const GeomSources &g, const double *Q, int64_t nparams,
@@ -324,7 +312,7 @@ int launch_triu_ratio(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const double 
 // X[b, :] = inv(W[b]) . X[b, :] for upper-triangular W (one vector per matrix, back substitution)
 int launch_triu_solve_vec(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const double *W, double *X);
 
-// ---- smc.hip: sampler steps on the device
+// ---- smc.hip: sampler steps on the device (stage transition, draws, propose / accept, tuning)
 int launch_smc_calc_beta(beatamd_ctx *ctx, int64_t n, const double *lik, int64_t stride, double beta,
                          double cv, int mode, double dbeta, double *out2, double *weights);
 int launch_smc_resample(beatamd_ctx *ctx, int64_t n, const double *weights, double aux, double *cum,
@@ -341,7 +329,7 @@ int launch_philox_univariate(beatamd_ctx *ctx, double *delta, int64_t C, int64_t
                              const double *scale, uint64_t seed, uint32_t step, uint64_t first_chain);
 int launch_step_advance(beatamd_ctx *ctx);
 // small parameter vectors (K, np <= 64): draws + factor product + propose in one launch; kind -1
-// multivariate (factor [K, np]), 0/1/2 the per-parameter families (factor = scales [np], K == np)
+// multivariate (factor [K, np]), 0..3 the per-parameter families (factor = scales [np], K == np)
 bool draw_propose_applicable(int64_t K, int64_t np);
 int launch_draw_propose(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, int kind, const double *factor,
                         int df, uint64_t seed, uint32_t step, uint64_t first_chain, const double *Q0,
@@ -349,6 +337,17 @@ int launch_draw_propose(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, int 
                         double *log_u, int32_t *inbounds);
 int launch_philox_chain(beatamd_ctx *ctx, int64_t C, uint64_t seed, uint32_t step, uint64_t first_chain,
                         int df, double *log_u, double *row_scale);
+// the step around the forward model (metropolis.py:276-422 pieces): propose before it, accept behind it
+int launch_propose(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q0,
+                   const double *delta, const double *scaling, const double *lower,
+                   const double *upper, double *Qprop, int32_t *inbounds);
+// grp (nullable): sum the `like` column of Lprop here instead of a launch_like_sum before; acc_sum /
+// n_acc (nullable): per-chain and population acceptance counters; advance_step: bump ctx->step_dev
+int launch_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int64_t nllk, double *Q0,
+                  double *L0, const double *Qprop, double *Lprop, const int32_t *inbounds,
+                  const double *log_u, double beta, const double *betas, int32_t *accepted,
+                  const LikeGroups *grp = nullptr, const int32_t *chain_bad = nullptr,
+                  int32_t *acc_sum = nullptr, int64_t *n_acc = nullptr, bool advance_step = false);
 
 
 // ---- hyper.hip: the hyper-parameter model on cached misfits

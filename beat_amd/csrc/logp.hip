@@ -1,10 +1,9 @@
-// logp.hip -- the small kernels around the two heavy ones: likelihood epilogues, the
-// geodetic static stacking, the Metropolis propose/accept step.  All O(C * small).
+// logp.hip -- the small kernels around the two heavy ones: likelihood epilogues (`like` of a row and
+// LOG_2PI: metropolis.hpp), the geodetic static stacking, noise covariance estimation.  All O(C * small).
 #include "kernels.hpp"
+#include "metropolis.hpp"
 
 namespace beatamd {
-
-#define LOG_2PI 1.8378770664093453  // log(2*pi), distributions.py:13
 
 __device__ __forceinline__ double hp_value(const HpSrc &h, int64_t c, int64_t d)
 {
@@ -263,24 +262,14 @@ int launch_misfits_mark_bad(beatamd_ctx *ctx, int64_t C, int64_t n, double *llks
     return BEATAMD_OK;
 }
 
-// problems.py:227-247: like = sum over composites of (composite llk vector).sum()
+// problems.py:227-247: like = sum over composites of (composite llk vector).sum()  (like_serial, metropolis.hpp)
 __global__ void __launch_bounds__(256) k_like_sum(int64_t C, int64_t nllk, LikeGroups grp,
                                                  double *LL, const int32_t *chain_bad)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
     double *l = LL + c * nllk;
-    double total = 0.0;
-    int k = 0;
-    for (int g = 0; g < grp.n; g++) {
-        double s = 0.0;
-        for (; k < grp.end[g]; k++) s += l[k];
-        total += s;
-    }
-    // a chain whose start times / durations left the library grid (the reference raises
-    // IndexError there) carries NaN: metrop_select rejects it (isfinite test in k_accept)
-    if (chain_bad && chain_bad[c]) total = __builtin_nan("");
-    l[nllk - 1] = total;
+    l[nllk - 1] = like_serial(l, grp, chain_bad && chain_bad[c]);
 }
 
 int launch_like_sum(beatamd_ctx *ctx, int64_t C, int64_t nllk, const LikeGroups &grp, double *LL,
@@ -298,8 +287,7 @@ int launch_like_sum(beatamd_ctx *ctx, int64_t C, int64_t nllk, const LikeGroups 
 // rank by rank, the rows a rank contributes -- the logpts of its datasets (dst_col[r] = their column in the full vector)
 // and one flag row per rank (dst_col[r] = -1: NaN marks a chain whose times left the library grid on one of THAT rank's
 // targets).  Thread <-> chain: scatter the rows into LL [C, nllk], copy the replicated columns (geodetic, Laplacian) from
-// this rank's local vector, then `like` in k_like_sum's order (per composite, then over composites; problems.py:227-247)
-// -- from the same gathered bits on every rank.
+// this rank's local vector, then `like` as k_like_sum takes it (like_serial) -- from the same gathered bits on every rank.
 __global__ void __launch_bounds__(256) k_like_assemble(int64_t C, int64_t nllk, int64_t nsrc, const double *src,
                                                       const int32_t *dst_col, const double *rest, int64_t rest_ld,
                                                       int64_t rest_col0, int64_t n_rest, int64_t rest_dst0, LikeGroups grp,
@@ -316,15 +304,7 @@ __global__ void __launch_bounds__(256) k_like_assemble(int64_t C, int64_t nllk, 
         else bad = bad || (v != v);
     }
     for (int64_t k = 0; k < n_rest; k++) l[rest_dst0 + k] = rest[c * rest_ld + rest_col0 + k];
-    double total = 0.0;
-    int k = 0;
-    for (int g = 0; g < grp.n; g++) {
-        double s = 0.0;
-        for (; k < grp.end[g]; k++) s += l[k];
-        total += s;
-    }
-    if (bad) total = __builtin_nan("");
-    l[nllk - 1] = total;
+    l[nllk - 1] = like_serial(l, grp, bad);
     if (chain_bad) chain_bad[c] = bad ? 1 : 0;
 }
 
@@ -364,132 +344,6 @@ int launch_gather_slips(beatamd_ctx *ctx, int64_t C, int nvar, int64_t P, const 
     if (n == 0) return BEATAMD_OK;
     hipLaunchKernelGGL(k_gather_slips, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        C, nvar, P, g, out);
-    BA_HIP(hipGetLastError());
-    return BEATAMD_OK;
-}
-
-// metropolis.py:313-343: q = q0 + delta * scaling ; prior_logp finite <=> inside the box
-__global__ void __launch_bounds__(256) k_propose(int64_t C, int64_t nparams, const double *Q0,
-                                                const double *delta, const double *scaling,
-                                                const double *lower, const double *upper,
-                                                double *Qprop, int32_t *inbounds)
-{
-    const int64_t c = blockIdx.x;
-    __shared__ int s_ok;
-    if (threadIdx.x == 0) s_ok = 1;
-    __syncthreads();
-    const double sc = scaling[c];
-    int ok = 1;
-    for (int64_t k = threadIdx.x; k < nparams; k += 256) {
-        const double d = delta[c * nparams + k] * sc;
-        const double q = Q0[c * nparams + k] + d;
-        Qprop[c * nparams + k] = q;
-        if (!(q >= lower[k] && q <= upper[k])) ok = 0;
-    }
-    if (!ok) s_ok = 0;
-    __syncthreads();
-    // metropolis.py:341-343,383-385: outside the prior box the forward model is NOT evaluated
-    // and the chain stays.  The batch evaluates every chain, so park the rejected chain on its
-    // current point (keeps durations/start times inside the library grid).
-    if (!s_ok)
-        for (int64_t k = threadIdx.x; k < nparams; k += 256)
-            Qprop[c * nparams + k] = Q0[c * nparams + k];
-    if (threadIdx.x == 0) inbounds[c] = s_ok;
-}
-
-int launch_propose(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q0,
-                   const double *delta, const double *scaling, const double *lower,
-                   const double *upper, double *Qprop, int32_t *inbounds)
-{
-    if (C == 0) return BEATAMD_OK;
-    hipLaunchKernelGGL(k_propose, dim3((unsigned)C), dim3(256), 0, ctx->stream, C, nparams, Q0,
-                       delta, scaling, lower, upper, Qprop, inbounds);
-    BA_HIP(hipGetLastError());
-    return BEATAMD_OK;
-}
-
-// metropolis.py:344-385 + pymc metrop_select: accept iff in bounds, isfinite(mr), log u < mr.
-// One workgroup per chain.  Optional tail work of the step, so that a step needs no further launch:
-//   grp.n > 0   the `like` column of the proposal is summed here (k_like_sum's order: per composite,
-//               then over composites; chain_bad -> NaN) from an LDS copy of the row
-//   acc_sum     per-chain acceptance counter (+= flag), n_acc the population total (+= flags)
-//   step_dev    the device-resident Philox step counter moves on (read only by the draw kernels, which
-//               precede this launch in stream order)
-__global__ void __launch_bounds__(256) k_accept(int64_t C, int64_t nparams, int64_t nllk,
-                                               double *Q0, double *L0, const double *Qprop,
-                                               double *Lprop, const int32_t *inbounds,
-                                               const double *log_u, double beta,
-                                               const double *betas, int32_t *accepted, LikeGroups grp,
-                                               const int32_t *chain_bad, int32_t *acc_sum,
-                                               unsigned long long *n_acc, uint32_t *step_dev)
-{
-    extern __shared__ __attribute__((aligned(16))) double s_l[];
-    const int64_t c = blockIdx.x;
-    // a proposal outside the box is rejected without a look at its likelihood row: the forward model may have skipped it
-    // (ffi_logp_device's `active`), the row then holds whatever an earlier step left there
-    if (!inbounds[c]) {
-        if (threadIdx.x == 0) {
-            accepted[c] = 0;
-            if (step_dev && c == 0) *step_dev += 1u;
-        }
-        return;
-    }
-    double lp;
-    if (grp.n > 0) {
-        for (int64_t k = threadIdx.x; k < nllk - 1; k += 256) s_l[k] = Lprop[c * nllk + k];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double total = 0.0;
-            int k = 0;
-            for (int g = 0; g < grp.n; g++) {
-                double s = 0.0;
-                for (; k < grp.end[g]; k++) s += s_l[k];
-                total += s;
-            }
-            if (chain_bad && chain_bad[c]) total = __builtin_nan("");
-            s_l[nllk - 1] = total;
-            Lprop[c * nllk + nllk - 1] = total;
-        }
-        __syncthreads();
-        lp = s_l[nllk - 1];
-    } else {
-        lp = Lprop[c * nllk + nllk - 1];
-    }
-    const double b = betas ? betas[c] : beta;  // per-replica beta for parallel tempering
-    const double mr = b * (lp - L0[c * nllk + nllk - 1]);
-    const bool acc = isfinite(mr) && (log_u[c] < mr);
-    if (acc) {
-        for (int64_t k = threadIdx.x; k < nparams; k += 256) Q0[c * nparams + k] = Qprop[c * nparams + k];
-        __syncthreads();  // all lanes have read L0[like] before it is overwritten
-        if (grp.n > 0) {
-            for (int64_t k = threadIdx.x; k < nllk; k += 256) L0[c * nllk + k] = s_l[k];
-        } else {
-            for (int64_t k = threadIdx.x; k < nllk; k += 256) L0[c * nllk + k] = Lprop[c * nllk + k];
-        }
-    }
-    if (threadIdx.x == 0) {
-        accepted[c] = acc ? 1 : 0;
-        if (acc_sum && acc) acc_sum[c] += 1;
-        if (n_acc && acc) atomicAdd(n_acc, 1ull);
-        if (step_dev && c == 0) *step_dev += 1u;
-    }
-}
-
-int launch_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int64_t nllk, double *Q0,
-                  double *L0, const double *Qprop, double *Lprop, const int32_t *inbounds,
-                  const double *log_u, double beta, const double *betas, int32_t *accepted,
-                  const LikeGroups *grp, const int32_t *chain_bad, int32_t *acc_sum, int64_t *n_acc,
-                  bool advance_step)
-{
-    if (C == 0) return BEATAMD_OK;
-    LikeGroups g;
-    if (grp) g = *grp;
-    const size_t lds = grp ? (size_t)nllk * sizeof(double) : 0;
-    BA_CHECK(lds <= 48 * 1024, BEATAMD_EINVAL, "accept: likelihood vector of %lld entries", (long long)nllk);
-    ScopedTimer tm(ctx, "astep");
-    hipLaunchKernelGGL(k_accept, dim3((unsigned)C), dim3(256), lds, ctx->stream, C, nparams, nllk,
-                       Q0, L0, Qprop, Lprop, inbounds, log_u, beta, betas, accepted, g, chain_bad, acc_sum,
-                       (unsigned long long *)n_acc, advance_step ? ctx->step_dev : nullptr);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

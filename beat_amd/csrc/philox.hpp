@@ -1,8 +1,12 @@
-// philox.hpp -- device functions shared by the sampler kernels (smc.hip, hyper.hip): the counter-based generator,
-// the transforms of the per-parameter proposal families and the step-size table.  One definition each, so that a
-// kernel that fuses a whole chain draws and tunes bit for bit what the step-by-step kernels do.
+// philox.hpp -- the random draws of the sampler kernels (smc.hip, hyper.hip) as device functions: the counter-based
+// generator and, per stream, the one function that turns its blocks into a draw.  Every kernel that draws calls
+// these -- the step-by-step kernels (k_philox_normal, k_philox_chain, k_philox_univariate) and the fused ones
+// (k_draw_propose, k_hyper_chain) alike -- so the same counters give the same bits on every path.  What a step does
+// with a draw (propose, box test, accept, tune) is metropolis.hpp.
 #pragma once
 #include <cstdint>
+
+#include "ctx.hpp"
 
 #ifdef __HIPCC__
 namespace beatamd {
@@ -34,6 +38,7 @@ __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo)
     return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6) + 0.5) * (1.0 / 9007199254740992.0);
 }
 
+// a pair of standard normals from one block: (cos, sin) of the same radius and angle
 __device__ __forceinline__ void box_muller(const uint32_t (&r)[4], double &a, double &b)
 {
     const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
@@ -44,6 +49,23 @@ __device__ __forceinline__ void box_muller(const uint32_t (&r)[4], double &a, do
 }
 
 // counter layout: (pair index inside the row, global chain id, step, stream); key = seed
+//   stream 0: proposal normals z[c, 2j], z[c, 2j+1] from pair j of chain c (box_muller; the callers draw the block)
+//   stream 1: the row scale 1 / sqrt(chi2(df) / df) of a multivariate-t proposal with df degrees of freedom
+//             (base.py:35-71): chi2 as the sum of df squared normals, two per block
+__device__ __forceinline__ double philox_t_row_scale(uint32_t gc, uint32_t step, int df, uint32_t k0, uint32_t k1)
+{
+    double x = 0.0;
+    for (int m = 0; m < df; m += 2) {
+        uint32_t r[4];
+        philox4x32_10((uint32_t)(m / 2), gc, step, 1u, k0, k1, r);
+        double g0, g1;
+        box_muller(r, g0, g1);
+        x += g0 * g0;
+        if (m + 1 < df) x += g1 * g1;
+    }
+    return 1.0 / sqrt(x / (double)df);
+}
+
 //   stream 2: Metropolis uniforms -- log u of chain gc at `step`
 __device__ __forceinline__ double philox_log_u(uint32_t gc, uint32_t step, uint32_t k0, uint32_t k1)
 {
@@ -77,18 +99,50 @@ __device__ __forceinline__ void philox_univariate_pair(int kind, uint32_t j, uin
     }
 }
 
-// metropolis.py:294-306 with pymc's tune table (restated from its documentation):
-//   acc < 0.001 x0.1 | < 0.05 x0.5 | < 0.2 x0.9 | > 0.95 x10 | > 0.75 x2 | > 0.5 x1.1
-__device__ __forceinline__ double tune_factor(double acc)
+// Poisson variate from ONE uniform by inversion (sequential search from k = 0, pmf recurrence p_k = p_{k-1} lam / k).
+// Exact in law while exp(-lam) is a normal double; step widths lam <= 500 only: a wider one (or NaN) raises
+// ST_BAD_SCALE -> BEATAMD_EINVAL at the next synchronisation (the host side refuses it beforehand,
+// beat_amd/sampler/metropolis.py) and the draw is NaN.  The search stops where the cumulative sum stops growing (a
+// uniform above the rounded sum, ~1e-13 of the draws at lam near 500, lands on that far-tail k instead of the search cap).
+__device__ __forceinline__ double poisson_from_uniform(double u, double lam, int *status)
 {
-    double f = 1.0;
-    if (acc < 0.001) f = 0.1;
-    else if (acc < 0.05) f = 0.5;
-    else if (acc < 0.2) f = 0.9;
-    else if (acc > 0.95) f = 10.0;
-    else if (acc > 0.75) f = 2.0;
-    else if (acc > 0.5) f = 1.1;
-    return f;
+    if (lam == 0.0) return 0.0;
+    if (!(lam > 0.0 && lam <= 500.0)) {
+        atomicOr(status, ST_BAD_SCALE);
+        return __builtin_nan("");
+    }
+    double p = exp(-lam), F = p;
+    int k = 0;
+    while (u > F && k < 4096) {
+        k++;
+        p *= lam / (double)k;
+        const double Fn = F + p;
+        if (Fn == F && (double)k > lam) break;
+        F = Fn;
+    }
+    return (double)k;
+}
+
+// the scaled steps (2j, 2j + 1) of a row of any per-parameter family (base.py:129-160: every component is an
+// independent draw times the parameter's scale):
+//   kind 0..2  philox_univariate_pair times the scales sa, sb
+//   kind 3     PoissonProposal  poisson(lam = scale) - scale, both uniforms from the stream-3 block (base.py:150-155;
+//              integer steps around zero mean)
+// A row of odd length has no component 2j + 1 in its last pair: the caller passes sb = 0.0 there and drops b.
+__device__ __forceinline__ void philox_scaled_pair(int kind, uint32_t j, uint32_t gc, uint32_t step, uint32_t k0,
+                                                   uint32_t k1, double sa, double sb, int *status, double &a, double &b)
+{
+    if (kind == 3) {
+        uint32_t r[4];
+        philox4x32_10(j, gc, step, 3u, k0, k1, r);
+        const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
+        a = poisson_from_uniform(u1, sa, status) - sa;
+        b = poisson_from_uniform(u2, sb, status) - sb;
+        return;
+    }
+    philox_univariate_pair(kind, j, gc, step, k0, k1, a, b);
+    a = a * sa;
+    b = b * sb;
 }
 
 }  // namespace beatamd

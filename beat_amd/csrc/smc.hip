@@ -1,8 +1,9 @@
 // smc.hip -- the sampler steps around the forward model, on the device: SMC stage transition
-// (tempering step, importance weights, systematic resampling, proposal factor), proposal rows
-// from an own counter-based generator, per-chain step-size tuning, row gathers for the
-// population / replica exchange.  The population never leaves HBM between stages; only the
-// new beta (and acceptance counts) go back to the host.
+// (tempering step, importance weights, systematic resampling, proposal factor), row gathers for the
+// population / replica exchange, and the Metropolis step: proposal rows from an own counter-based
+// generator, propose, accept, per-chain step-size tuning (its rules: philox.hpp, metropolis.hpp).
+// The population never leaves HBM between stages; only the new beta (and acceptance counts) go
+// back to the host.
 //
 // Reference arithmetic (hvasbath/beat):
 //   SMC.calc_beta        beat/sampler/smc.py:133-165   bisection on the coefficient of variation
@@ -15,7 +16,7 @@
 // width), so every rank of a multi-GPU run computes bit-identical stage decisions from the same
 // gathered arrays.
 #include "kernels.hpp"
-#include "philox.hpp"
+#include "metropolis.hpp"
 
 namespace beatamd {
 
@@ -234,7 +235,7 @@ int launch_gather_rows(beatamd_ctx *ctx, int64_t nout, int64_t ncol, const doubl
     return BEATAMD_OK;
 }
 
-// metropolis.py:294-306 with pymc's tune table (tune_factor, philox.hpp)
+// metropolis.py:294-306 with pymc's tune table (tune_factor, metropolis.hpp)
 __global__ void __launch_bounds__(256) k_tune_scaling(int64_t C, double *scaling, int32_t *accepted,
                                                      double interval)
 {
@@ -271,11 +272,8 @@ int launch_accumulate_i32(beatamd_ctx *ctx, int64_t C, const int32_t *a, int32_t
 }
 
 // ---------------------------------------------------------------------------------------------
-// Philox4x32-10 draws (generator, uniforms and the proposal families' transforms: philox.hpp)
-// counter layout: (pair index inside the row, global chain id, step, stream); key = seed
-//   stream 0: proposal normals z[c, 2j], z[c, 2j+1] from pair j of chain c (Box-Muller cos / sin)
-//   stream 1: chi-square normals of the multivariate-t divisor (base.py:35-71)
-//   stream 2: Metropolis uniforms
+// Philox4x32-10 draws (generator, counter layout, streams and every transform: philox.hpp)
+//   stream 0: proposal normals z[c, 2j], z[c, 2j+1] from pair j of chain c
 __global__ void __launch_bounds__(256) k_philox_normal(double *z, int64_t C, int64_t K, uint64_t seed,
                                                       uint32_t step, uint64_t first_chain, const uint32_t *step_dev)
 {
@@ -287,11 +285,10 @@ __global__ void __launch_bounds__(256) k_philox_normal(double *z, int64_t C, int
     const uint64_t gc = first_chain + (uint64_t)c;
     uint32_t r[4];
     philox4x32_10((uint32_t)j, (uint32_t)gc, step, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-    const double rad = sqrt(-2.0 * log(u1));
-    const double th = 6.283185307179586476925286766559 * u2;
-    z[c * K + 2 * j] = rad * cos(th);
-    if (2 * j + 1 < K) z[c * K + 2 * j + 1] = rad * sin(th);
+    double a, b;
+    box_muller(r, a, b);
+    z[c * K + 2 * j] = a;
+    if (2 * j + 1 < K) z[c * K + 2 * j + 1] = b;
 }
 
 // per chain: log of the Metropolis uniform (metrop_select) and, for a multivariate-t proposal with
@@ -303,58 +300,13 @@ __global__ void __launch_bounds__(256) k_philox_chain(int64_t C, uint64_t seed, 
     if (step_dev) step = *step_dev;
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= C) return;
-    const uint64_t gc = first_chain + (uint64_t)c;
-    uint32_t r[4];
-    if (log_u) {
-        log_u[c] = philox_log_u((uint32_t)gc, step, (uint32_t)seed, (uint32_t)(seed >> 32));
-    }
-    if (row_scale) {
-        double x = 0.0;
-        for (int m = 0; m < df; m += 2) {
-            philox4x32_10((uint32_t)(m / 2), (uint32_t)gc, step, 1u, (uint32_t)seed,
-                          (uint32_t)(seed >> 32), r);
-            const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-            const double rad = sqrt(-2.0 * log(u1));
-            const double th = 6.283185307179586476925286766559 * u2;
-            const double g0 = rad * cos(th), g1 = rad * sin(th);
-            x += g0 * g0;
-            if (m + 1 < df) x += g1 * g1;
-        }
-        row_scale[c] = 1.0 / sqrt(x / (double)df);
-    }
+    const uint32_t gc = (uint32_t)(first_chain + (uint64_t)c), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    if (log_u) log_u[c] = philox_log_u(gc, step, k0, k1);
+    if (row_scale) row_scale[c] = philox_t_row_scale(gc, step, df, k0, k1);
 }
 
-// per-parameter proposal families (reference beat/sampler/base.py:129-160): every component of a row is an
-// independent draw times the parameter's scale.  Streams 3 / 4 of the same counter layout; one thread
-// per (chain, pair of parameters).
-//   kind 0  NormalProposal   normal(scale)                                  (Box-Muller pair)
-//   kind 1  CauchyProposal   standard_cauchy() * scale = tan(pi (u - 1/2)) * scale
-//   kind 2  LaplaceProposal  (standard_exponential() - standard_exponential()) * scale
-//   kind 3  PoissonProposal  poisson(lam = scale) - scale        (base.py:150-155; integer steps around zero mean)
-// Poisson variate from ONE uniform by inversion (sequential search from k = 0, pmf recurrence p_k = p_{k-1} lam / k).
-// Exact in law while exp(-lam) is a normal double; step widths lam <= 500 only: a wider one (or NaN) raises
-// ST_BAD_SCALE -> BEATAMD_EINVAL at the next synchronisation (the host side refuses it beforehand,
-// beat_amd/sampler/metropolis.py) and the draw is NaN.  The search stops where the cumulative sum stops growing (a
-// uniform above the rounded sum, ~1e-13 of the draws at lam near 500, lands on that far-tail k instead of the search cap).
-__device__ __forceinline__ double poisson_from_uniform(double u, double lam, int *status)
-{
-    if (lam == 0.0) return 0.0;
-    if (!(lam > 0.0 && lam <= 500.0)) {
-        atomicOr(status, ST_BAD_SCALE);
-        return __builtin_nan("");
-    }
-    double p = exp(-lam), F = p;
-    int k = 0;
-    while (u > F && k < 4096) {
-        k++;
-        p *= lam / (double)k;
-        const double Fn = F + p;
-        if (Fn == F && (double)k > lam) break;
-        F = Fn;
-    }
-    return (double)k;
-}
-
+// per-parameter proposal families (reference beat/sampler/base.py:129-160; kinds 0..3: philox_scaled_pair): every
+// component of a row is an independent draw times the parameter's scale.  One thread per (chain, pair of parameters).
 __global__ void __launch_bounds__(256) k_philox_univariate(double *delta, int64_t C, int64_t np, int kind,
                                                           const double *scale, uint64_t seed, uint32_t step,
                                                           uint64_t first_chain, const uint32_t *step_dev, int *status)
@@ -365,21 +317,12 @@ __global__ void __launch_bounds__(256) k_philox_univariate(double *delta, int64_
     if (i >= C * npair) return;
     const int64_t c = i / npair, j = i - c * npair;
     const uint64_t gc = first_chain + (uint64_t)c;
-    // (the entries admit kind 0..3 only; before the families moved to philox.hpp any other value fell into this
-    // Poisson branch, now it would take the Laplace one)
-    if (kind == 3) {
-        uint32_t r[4];
-        philox4x32_10((uint32_t)j, (uint32_t)gc, step, 3u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-        const double u1 = u53(r[0], r[1]), u2 = u53(r[2], r[3]);
-        const double la = scale[2 * j], lb = (2 * j + 1 < np) ? scale[2 * j + 1] : 0.0;
-        delta[c * np + 2 * j] = poisson_from_uniform(u1, la, status) - la;
-        if (2 * j + 1 < np) delta[c * np + 2 * j + 1] = poisson_from_uniform(u2, lb, status) - lb;
-        return;
-    }
+    const bool second = 2 * j + 1 < np;   // (a row of odd length has no second component in its last pair)
     double a, b;
-    philox_univariate_pair(kind, (uint32_t)j, (uint32_t)gc, step, (uint32_t)seed, (uint32_t)(seed >> 32), a, b);
-    delta[c * np + 2 * j] = a * scale[2 * j];
-    if (2 * j + 1 < np) delta[c * np + 2 * j + 1] = b * scale[2 * j + 1];
+    philox_scaled_pair(kind, (uint32_t)j, (uint32_t)gc, step, (uint32_t)seed, (uint32_t)(seed >> 32), scale[2 * j],
+                       second ? scale[2 * j + 1] : 0.0, status, a, b);
+    delta[c * np + 2 * j] = a;
+    if (second) delta[c * np + 2 * j + 1] = b;
 }
 
 int launch_philox_univariate(beatamd_ctx *ctx, double *delta, int64_t C, int64_t np, int kind,
@@ -416,10 +359,11 @@ int launch_philox_chain(beatamd_ctx *ctx, int64_t C, uint64_t seed, uint32_t ste
 }
 
 // ---- small parameter vectors (geometry mode: ~10 parameters, ~1000 chains): the whole proposal of a
-// step in ONE launch -- the draws of k_philox_normal / k_philox_chain / k_philox_univariate (same counters,
-// so the same numbers), the factor product of the proposal GEMM (k ascending, one FMA chain per component)
-// and k_propose (q = q0 + delta * scaling, prior-box test, parked on q0 outside the box).  A workgroup
-// serves DP_CB chains; factor, normals and flags sit in LDS.
+// step in ONE launch -- the draws of k_philox_normal / k_philox_chain / k_philox_univariate (the same
+// philox.hpp functions on the same counters, so the same numbers), the factor product of the proposal GEMM
+// (k ascending, one FMA chain per component: the one piece k_draw_propose states itself) and k_propose's
+// propose_component with a chain parked on q0 outside the box.  A workgroup serves DP_CB chains; factor,
+// normals and flags sit in LDS.
 constexpr int DP_CB = 16, DP_MAX = 64;
 
 struct DrawProposeArgs {
@@ -454,54 +398,22 @@ __global__ void __launch_bounds__(256) k_draw_propose(DrawProposeArgs a)
     for (int i = tid; i < nc * npair; i += 256) {
         const int c = i / npair, j = i - c * npair;
         const uint32_t gc = (uint32_t)(a.first_chain + (uint64_t)(c0 + c));
-        uint32_t r[4];
         double x, y;
         if (a.kind < 0) {
+            uint32_t r[4];
             philox4x32_10((uint32_t)j, gc, step, 0u, k0, k1, r);
             box_muller(r, x, y);
         } else {
-            philox4x32_10((uint32_t)j, gc, step, 3u, k0, k1, r);
-            if (a.kind == 0) {
-                box_muller(r, x, y);
-            } else if (a.kind == 1) {
-                x = tan(3.14159265358979323846 * (u53(r[0], r[1]) - 0.5));
-                y = tan(3.14159265358979323846 * (u53(r[2], r[3]) - 0.5));
-            } else if (a.kind == 2) {
-                uint32_t q[4];
-                philox4x32_10((uint32_t)j, gc, step, 4u, k0, k1, q);
-                x = log(u53(q[0], q[1])) - log(u53(r[0], r[1]));
-                y = log(u53(q[2], q[3])) - log(u53(r[2], r[3]));
-            }
-            if (a.kind == 3) {
-                const double la = a.factor[2 * j], lb = (2 * j + 1 < K) ? a.factor[2 * j + 1] : 0.0;
-                x = poisson_from_uniform(u53(r[0], r[1]), la, a.status) - la;
-                y = poisson_from_uniform(u53(r[2], r[3]), lb, a.status) - lb;
-            } else {
-                x *= a.factor[2 * j];
-                if (2 * j + 1 < K) y *= a.factor[2 * j + 1];
-            }
+            philox_scaled_pair(a.kind, (uint32_t)j, gc, step, k0, k1, a.factor[2 * j],
+                               (2 * j + 1 < K) ? a.factor[2 * j + 1] : 0.0, a.status, x, y);
         }
         zs[c][2 * j] = x;
         if (2 * j + 1 < K) zs[c][2 * j + 1] = y;
     }
     if (tid < nc) {
         const uint32_t gc = (uint32_t)(a.first_chain + (uint64_t)(c0 + tid));
-        uint32_t r[4];
-        philox4x32_10(0u, gc, step, 2u, k0, k1, r);
-        a.log_u[c0 + tid] = log(u53(r[0], r[1]));
-        double scale = 1.0;
-        if (a.kind < 0 && a.df > 0) {
-            double x = 0.0;
-            for (int m = 0; m < a.df; m += 2) {
-                philox4x32_10((uint32_t)(m / 2), gc, step, 1u, k0, k1, r);
-                double g0, g1;
-                box_muller(r, g0, g1);
-                x += g0 * g0;
-                if (m + 1 < a.df) x += g1 * g1;
-            }
-            scale = 1.0 / sqrt(x / (double)a.df);
-        }
-        rs[tid] = scale;
+        a.log_u[c0 + tid] = philox_log_u(gc, step, k0, k1);
+        rs[tid] = (a.kind < 0 && a.df > 0) ? philox_t_row_scale(gc, step, a.df, k0, k1) : 1.0;
         ok[tid] = 1;
     }
     __syncthreads();
@@ -516,9 +428,10 @@ __global__ void __launch_bounds__(256) k_draw_propose(DrawProposeArgs a)
             o = zs[c][n];
         }
         const int64_t g = (c0 + c) * a.np + n;
-        const double q = a.Q0[g] + o * a.scaling[c0 + c];
+        double q;
+        const bool inside = propose_component(a.Q0[g], o, a.scaling[c0 + c], a.lower[n], a.upper[n], q);
         a.Qprop[g] = q;
-        if (!(q >= a.lower[n] && q <= a.upper[n])) ok[c] = 0;
+        if (!inside) ok[c] = 0;
     }
     __syncthreads();
     for (int i = tid; i < nc * np; i += 256) {
@@ -547,6 +460,125 @@ int launch_draw_propose(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, int 
     a.Qprop = Qprop; a.log_u = log_u; a.inbounds = inbounds;
     ScopedTimer tm(ctx, "proposal");
     hipLaunchKernelGGL(k_draw_propose, dim3((unsigned)((C + DP_CB - 1) / DP_CB)), dim3(256), 0, ctx->stream, a);
+    BA_HIP(hipGetLastError());
+    return BEATAMD_OK;
+}
+
+// ---- the step around the forward model: propose before it, accept behind it
+// metropolis.py:313-343: propose_component for every parameter of a chain; one workgroup per chain
+__global__ void __launch_bounds__(256) k_propose(int64_t C, int64_t nparams, const double *Q0,
+                                                const double *delta, const double *scaling,
+                                                const double *lower, const double *upper,
+                                                double *Qprop, int32_t *inbounds)
+{
+    const int64_t c = blockIdx.x;
+    __shared__ int s_ok;
+    if (threadIdx.x == 0) s_ok = 1;
+    __syncthreads();
+    const double sc = scaling[c];
+    int ok = 1;
+    for (int64_t k = threadIdx.x; k < nparams; k += 256) {
+        double q;
+        const bool inside = propose_component(Q0[c * nparams + k], delta[c * nparams + k], sc, lower[k], upper[k], q);
+        Qprop[c * nparams + k] = q;
+        if (!inside) ok = 0;
+    }
+    if (!ok) s_ok = 0;
+    __syncthreads();
+    // metropolis.py:341-343,383-385: outside the prior box the forward model is NOT evaluated
+    // and the chain stays.  The batch evaluates every chain, so park the rejected chain on its
+    // current point (keeps durations/start times inside the library grid).
+    if (!s_ok)
+        for (int64_t k = threadIdx.x; k < nparams; k += 256)
+            Qprop[c * nparams + k] = Q0[c * nparams + k];
+    if (threadIdx.x == 0) inbounds[c] = s_ok;
+}
+
+int launch_propose(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q0,
+                   const double *delta, const double *scaling, const double *lower,
+                   const double *upper, double *Qprop, int32_t *inbounds)
+{
+    if (C == 0) return BEATAMD_OK;
+    hipLaunchKernelGGL(k_propose, dim3((unsigned)C), dim3(256), 0, ctx->stream, C, nparams, Q0,
+                       delta, scaling, lower, upper, Qprop, inbounds);
+    BA_HIP(hipGetLastError());
+    return BEATAMD_OK;
+}
+
+// metropolis.py:344-385 + pymc metrop_select: accept iff in bounds and metropolis_accept.
+// One workgroup per chain.  Optional tail work of the step, so that a step needs no further launch:
+//   grp.n > 0   the `like` column of the proposal is summed here (like_serial, as k_like_sum) from an
+//               LDS copy of the row
+//   acc_sum     per-chain acceptance counter (+= flag), n_acc the population total (+= flags)
+//   step_dev    the device-resident Philox step counter moves on (read only by the draw kernels, which
+//               precede this launch in stream order)
+__global__ void __launch_bounds__(256) k_accept(int64_t C, int64_t nparams, int64_t nllk,
+                                               double *Q0, double *L0, const double *Qprop,
+                                               double *Lprop, const int32_t *inbounds,
+                                               const double *log_u, double beta,
+                                               const double *betas, int32_t *accepted, LikeGroups grp,
+                                               const int32_t *chain_bad, int32_t *acc_sum,
+                                               unsigned long long *n_acc, uint32_t *step_dev)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_l[];
+    const int64_t c = blockIdx.x;
+    // a proposal outside the box is rejected without a look at its likelihood row: the forward model may have skipped it
+    // (ffi_logp_device's `active`), the row then holds whatever an earlier step left there
+    if (!inbounds[c]) {
+        if (threadIdx.x == 0) {
+            accepted[c] = 0;
+            if (step_dev && c == 0) *step_dev += 1u;
+        }
+        return;
+    }
+    double lp;
+    if (grp.n > 0) {
+        for (int64_t k = threadIdx.x; k < nllk - 1; k += 256) s_l[k] = Lprop[c * nllk + k];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double total = like_serial(s_l, grp, chain_bad && chain_bad[c]);
+            s_l[nllk - 1] = total;
+            Lprop[c * nllk + nllk - 1] = total;
+        }
+        __syncthreads();
+        lp = s_l[nllk - 1];
+    } else {
+        lp = Lprop[c * nllk + nllk - 1];
+    }
+    const double b = betas ? betas[c] : beta;  // per-replica beta for parallel tempering
+    const bool acc = metropolis_accept(b, lp, L0[c * nllk + nllk - 1], log_u[c]);
+    if (acc) {
+        for (int64_t k = threadIdx.x; k < nparams; k += 256) Q0[c * nparams + k] = Qprop[c * nparams + k];
+        __syncthreads();  // all lanes have read L0[like] before it is overwritten
+        if (grp.n > 0) {
+            for (int64_t k = threadIdx.x; k < nllk; k += 256) L0[c * nllk + k] = s_l[k];
+        } else {
+            for (int64_t k = threadIdx.x; k < nllk; k += 256) L0[c * nllk + k] = Lprop[c * nllk + k];
+        }
+    }
+    if (threadIdx.x == 0) {
+        accepted[c] = acc ? 1 : 0;
+        if (acc_sum && acc) acc_sum[c] += 1;
+        if (n_acc && acc) atomicAdd(n_acc, 1ull);
+        if (step_dev && c == 0) *step_dev += 1u;
+    }
+}
+
+int launch_accept(beatamd_ctx *ctx, int64_t C, int64_t nparams, int64_t nllk, double *Q0,
+                  double *L0, const double *Qprop, double *Lprop, const int32_t *inbounds,
+                  const double *log_u, double beta, const double *betas, int32_t *accepted,
+                  const LikeGroups *grp, const int32_t *chain_bad, int32_t *acc_sum, int64_t *n_acc,
+                  bool advance_step)
+{
+    if (C == 0) return BEATAMD_OK;
+    LikeGroups g;
+    if (grp) g = *grp;
+    const size_t lds = grp ? (size_t)nllk * sizeof(double) : 0;
+    BA_CHECK(lds <= 48 * 1024, BEATAMD_EINVAL, "accept: likelihood vector of %lld entries", (long long)nllk);
+    ScopedTimer tm(ctx, "astep");
+    hipLaunchKernelGGL(k_accept, dim3((unsigned)C), dim3(256), lds, ctx->stream, C, nparams, nllk,
+                       Q0, L0, Qprop, Lprop, inbounds, log_u, beta, betas, accepted, g, chain_bad, acc_sum,
+                       (unsigned long long *)n_acc, advance_step ? ctx->step_dev : nullptr);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

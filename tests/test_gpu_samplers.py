@@ -766,13 +766,24 @@ def test_covariance_update_of_a_prewhitened_model(ctx):
 
 
 @pytest.mark.parametrize("ndip,kind,df,per_chain_beta", [(4, -1, 0, False), (4, -1, 3, True), (4, 1, 0, False),
-                                                         (6, -1, 0, True), (6, -1, 4, False), (6, 2, 0, False)])
+                                                         (6, -1, 0, True), (6, -1, 4, False), (6, 2, 0, False),
+                                                         (4, 0, 0, False), (4, 3, 0, True)])
 def test_fused_step_equals_draw_plus_astep(ctx, ndip, kind, df, per_chain_beta):
     """beatamd_ffi_mstep_batch (draws + proposal + forward model + accept + counters in one call) against
     the two calls it replaces, beatamd_proposal_draw[_univariate] + beatamd_ffi_astep_batch[_betas]: the
-    same Philox counters, so the same chains.  More than 64 parameters: the same kernels run -> bitwise;
-    up to 64 the draws, the factor product and the box test are one kernel (FMA chain instead of the
-    matrix-core GEMM: last-bit differences in the proposal)."""
+    same Philox counters, so the same chains.  More than 64 parameters: the same kernels run -> bitwise.
+    Up to 64 the draws, the factor product and the box test are one kernel (k_draw_propose).  A per-parameter
+    family (kind >= 0) has no product in it: the same device functions draw, scale, propose and accept in the
+    same order on both paths and contraction is off -> bitwise too, Q, L and the flags after every step.  The
+    multivariate proposal (kind < 0) goes through an FMA chain there instead of the matrix-core GEMM: last-bit
+    differences in the proposal, compared to a tolerance and the chains re-joined after every step.
+    The fixture has 52 parameters at ndip = 4, an even count: the odd tail of a row (second scale 0.0, second
+    draw dropped) is covered by k_philox_univariate's npar = 7 test only.  70 chains leave the last workgroup
+    of k_draw_propose with 6 of its 16 chains.
+    Poisson (kind 3): integer steps of a parameter's span would leave the box every time, so every width is
+    1e-3: 95 % of the rows draw k = 0 everywhere and move by -lam * scaling, the others jump by one in some
+    parameter.  Measured on the build before the draws became shared device functions: 27 of the 4 x 70
+    proposals accepted (8, 5, 7, 7 per step), 9.6 %; widths of 2e-3 / 5e-3 / 1e-2 gave 7.1 / 4.3 / 2.9 %."""
     import torch
     from beat_amd.synthetic import SyntheticSpec, build_problem, draw_population
     spec = SyntheticSpec((ndip,), (ndip,), (1.0,), T=3, N=32, D=3, S=25)
@@ -791,6 +802,8 @@ def test_fused_step_equals_draw_plus_astep(ctx, ndip, kind, df, per_chain_beta):
     span = np.where(up_h > lo_h, up_h - lo_h, 1.0)
     if kind < 0:
         factor = torch.from_numpy(rng.standard_normal((npar, npar)) * 2e-3 * span[None, :] / np.sqrt(npar)).to(dev)
+    elif kind == 3:
+        factor = torch.full((npar,), 1e-3, dtype=torch.float64, device=dev)
     else:
         factor = torch.from_numpy(2e-3 * span).to(dev)
     scaling = torch.from_numpy(0.5 + rng.random(C)).to(dev)
@@ -811,12 +824,14 @@ def test_fused_step_equals_draw_plus_astep(ctx, ndip, kind, df, per_chain_beta):
                       acc_sum, n_acc)
         assert torch.equal(accA, accB), "step %d" % step
         total += accA.cpu().numpy()
-        if npar > 64:
-            assert torch.equal(QA, QB) and torch.equal(LA, LB)
+        if npar > 64 or kind >= 0:
+            assert torch.equal(QA, QB) and torch.equal(LA, LB), "step %d" % step
         else:
             np.testing.assert_allclose(QB.cpu().numpy(), QA.cpu().numpy(), rtol=1e-13, atol=1e-15)
             np.testing.assert_allclose(LB.cpu().numpy(), LA.cpu().numpy(), rtol=1e-9)
             QB.copy_(QA)
             LB.copy_(LA)
     assert 0 < total.sum() < 4 * C
+    if kind == 3:
+        assert 0.05 * 4 * C <= total.sum() <= 0.95 * 4 * C
     assert np.array_equal(acc_sum.cpu().numpy(), total) and int(n_acc.item()) == total.sum()
