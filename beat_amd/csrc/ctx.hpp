@@ -293,7 +293,6 @@ struct beatamd_ctx {
     bool gs_has_passes = false;     // the statistics slot holds [rows per patch][passes per patch]
     // what the selection chose for the most recent stacking launch and why (beatamd_ctx_gf_plan)
     char gf_plan[384] = "";
-    bool gf_band_fused = false;     // mode 3: the stacking kernel of the launch in hand evaluated the bidiagonal misfit itself
     char gf_tune_log[512] = "";   // the most recent group-size measurement (launch_gfstack), in words
     // largest distinct-row count of the previous small-group launch, read back asynchronously
     // (pinned mailbox + event; never waited for): sizes the next launch's row buffers

@@ -1340,9 +1340,8 @@ int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *ro
         hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream, a);
     }
     BA_HIP(hipGetLastError());
-    if (k.mode == GF_RESID_SCALAR) BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad, a.ovf, 0));
-    if (k.mode == GF_RESID_BAND1)
-        BA_TRY(launch_sum_tiles_band1(ctx, a.partial, a.edges, k.band_w, k.C, L.T, L.N, a.ntile, 64, k.quad, a.ovf, 0));
+    if (a.partial)   // (modes 1 and 3; mode 3 has edges)
+        BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad, a.ovf, 0, a.edges, k.band_w, L.T, L.N));
     *ovf_out = a.ovf;
     return BEATAMD_OK;
 }

@@ -35,6 +35,7 @@
 // the same fma() as in k_gfstack: for one slip variable all kernels produce bitwise identical
 // synthetics (tests/test_gpu_parity.py).
 #include "kernels.hpp"
+#include "misfit.hpp"
 
 namespace beatamd {
 
@@ -754,22 +755,11 @@ __device__ __forceinline__ void gs_store_syn(double *o, const double (&acc)[NT],
         if (i < nvalid) o[i] = acc[i];
 }
 
-// the tile's share of the scalar-weight misfit sum_i (w (data_i - syn_i))^2
+// the tile's share q_k of the scalar-weight misfit sum_i (w (data_i - syn_i))^2 (misfit.hpp)
 template <int NT>
 __device__ __forceinline__ double gs_misfit_scalar(const double w, const double (&acc)[NT], const double *xbuf, int nvalid)
 {
-    double q = 0.0;
-#pragma unroll
-    for (int i0 = 0; i0 < NT; i0 += 8) {
-#pragma unroll
-        for (int i = i0; i < i0 + 8; i++)
-            if (i < nvalid) {
-                const double tt = w * (xbuf[i] - acc[i]);
-                q = fma(tt, tt, q);
-            }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return q;
+    return scalar_tile<true, NT>([&](int i) { return scalar_t(w, xbuf[i], acc[i]); }, nvalid);
 }
 
 // residuals data - synthetics, every lane storing its own chain's samples
@@ -1202,36 +1192,18 @@ k_gfstack_ws(GsArgs a)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     if (MODE == GF_RESID_BAND1) {
-        // distributions.py:119-138 with a bidiagonal W: y_i = W[i,i] r_i + W[i,i+1] r_{i+1} -- the two products of
-        // k_quadform_banded<1> in its order -- for the samples whose neighbour this lane holds; the tile's LAST sample needs
-        // the next tile's first residual: both go to `edges`, k_sum_tiles_band1 adds that term (the trace's very last
-        // sample has no neighbour and is finished here)
+        // q_k of the bidiagonal misfit (misfit.hpp) for the samples whose neighbour this lane holds; the tile's LAST sample
+        // needs the next tile's first residual: both go to `edges`, k_sum_tiles adds that term (the trace's very last sample
+        // has no neighbour and is finished here)
         const double *wbt = xbuf + GS_NT;
-        const bool trace_end = n0 + nvalid == N;
-        double q = 0.0, ri = xbuf[0] - acc[0];
-        const double rfirst = ri;
-#pragma unroll
-        for (int i0 = 0; i0 < GS_NT; i0 += 8) {
-#pragma unroll
-            for (int i = i0; i < i0 + 8; i++) {
-                if (i + 1 < nvalid) {
-                    const double rn = xbuf[i + 1] - acc[i + 1];     // seismic.py:1332
-                    double y = fma(wbt[2 * i], ri, 0.0);
-                    y = fma(wbt[2 * i + 1], rn, y);
-                    q = fma(y, y, q);
-                    ri = rn;
-                } else if (i + 1 == nvalid && trace_end) {
-                    const double y = fma(wbt[2 * i], ri, 0.0);
-                    q = fma(y, y, q);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        const auto resid = [&](int i) { return xbuf[i] - acc[i]; };     // seismic.py:1332
+        const double rfirst = resid(0);
+        const Band1Tile tl = band1_tile<true, GS_NT>(resid, [&](int i, int b) { return wbt[2 * i + b]; }, nvalid, n0 + nvalid == N);
         if (live) {
             const int64_t e = (c * a.T + t) * a.ntile + tile;
-            a.partial[e] = q;
+            a.partial[e] = tl.q;
             a.edges[2 * e] = rfirst;
-            a.edges[2 * e + 1] = ri;        // residual of the tile's last valid sample
+            a.edges[2 * e + 1] = tl.r_last;
         }
     } else if (MODE == GF_RESID_STORE) {
         // A lane holds 64 consecutive samples of ITS chain: stored directly, every store instruction scatters 64 x 8 bytes
@@ -2023,25 +1995,23 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
         BA_TRY(launch_ws(k.mode, dim3((unsigned)nblocks), lds, ctx->stream, a, f32 ? 1 : (pair64 ? 2 : 0)));
     }
     BA_HIP(hipGetLastError());
-    if (k.mode == GF_RESID_SCALAR) BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad));
-    if (k.mode == GF_RESID_BAND1)
-        BA_TRY(launch_sum_tiles_band1(ctx, a.partial, a.edges, k.band_w, k.C, L.T, L.N, a.ntile, 64, k.quad));
+    if (a.partial)   // (modes 1 and 3; mode 3 has edges)
+        BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad, nullptr, 0, a.edges, k.band_w, L.T, L.N));
     return BEATAMD_OK;
 }
 
 int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint32_t *rowoff,
-                          const double *fac, int CG, int ucap, int64_t Ttab)
+                          const double *fac, int CG, int ucap, int64_t Ttab, bool *band1_done)
 {
     GfStackCall k = k_in;
     if (k.mode == GF_RESID_BAND1) {
-        // the bidiagonal epilogue exists in k_gfstack_ws (float64 rows); every other kernel stores the residuals and
-        // launch_gfstack runs k_quadform_banded behind it (BEATAMD_QF_FUSE=0: always -- A/B, tests)
-        const GfKnobs &kn0 = *k.knobs;
+        // of the kernels launched here k_gfstack_ws on float64 rows has the bidiagonal epilogue (not its pair-gather twin);
+        // every other one stores the residuals and launch_gfstack runs k_quadform_band1 behind it
         bool f32 = k.f32;
         for (int v = 0; v < k.nvar; v++) f32 = f32 && k.libs[v]->g32 != nullptr;
-        const bool fuse = ws_wanted(k, CG) && !f32 && !GfKnobs::is(kn0.gs_pair, 1) && !GfKnobs::is(kn0.qf_fuse, 0);
-        if (!fuse) k.mode = GF_RESID_STORE;
-        ctx->gf_band_fused = fuse;
+        const bool ws64 = ws_wanted(k, CG) && !f32 && !GfKnobs::is(k.knobs->gs_pair, 1);
+        *band1_done = gf_carries_band1(*k.knobs, ws64 ? GF_BY_WS : GF_BY_OTHER);
+        if (!*band1_done) k.mode = GF_RESID_STORE;
     }
     if (ws_wanted(k, CG)) return launch_gfstack_ws(ctx, k, rowoff, Ttab);
     const GfKnobs &kn = *k.knobs;

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "kernels.hpp"
+#include "misfit.hpp"
 
 namespace beatamd {
 
@@ -326,58 +327,35 @@ int launch_round_to_f32(beatamd_ctx *ctx, double *g, float *g32, int64_t n)
     return BEATAMD_OK;
 }
 
-// guard (nullable): the launch works only when (*guard != 0) == (want != 0) -- the two producers of a misfit, the runs
-// kernel and its stand-in, each bring their own tile sums
-__global__ void __launch_bounds__(256) k_sum_tiles(const double *partial, int64_t n, int ntile,
-                                                  double *quad, const int *guard, int want)
+// quad[i] = the tiles of (chain, target) i joined in ascending order (misfit.hpp) -- fixed order: deterministic, the same on
+// every rank.  edges == nullptr: the plain sum (scalar weight); mode 3 (bidiagonal operator): behind every tile but the last
+// its boundary term from edges [n, ntile, 2] = (first, last residual of the 64-sample tile) and the band row of the tile's
+// last sample.  guard: guard_skips
+__global__ void __launch_bounds__(256) k_sum_tiles(const double *partial, int64_t n, int ntile, double *quad, const int *guard,
+                                                  int want, const double *edges, const double *band_w, int64_t T, int64_t N)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if (guard && (*guard != 0) != (want != 0)) return;
-    double s = 0.0;
-    for (int k = 0; k < ntile; k++) s += partial[i * ntile + k];  // fixed order: deterministic
-    quad[i] = s;
-}
-
-int launch_sum_tiles(beatamd_ctx *ctx, const double *partial, int64_t n, int ntile, double *quad, const int *guard, int want)
-{
-    hipLaunchKernelGGL(k_sum_tiles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       partial, n, ntile, quad, guard, want);
-    BA_HIP(hipGetLastError());
-    return BEATAMD_OK;
-}
-
-// mode 3 (bidiagonal whitening operator): the tiles of a (chain, target) in ascending order, behind each tile's inner
-// samples its last one -- y = W[i,i] r_last(tile) + W[i,i+1] r_first(tile + 1), the two products of k_quadform_banded<1> --
-// fixed order: deterministic, the same on every rank
-__global__ void __launch_bounds__(256) k_sum_tiles_band1(const double *partial, const double *edges, const double *band_w,
-                                                        int64_t n, int64_t T, int64_t N, int ntile, int NT, double *quad,
-                                                        const int *guard, int want)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    if (guard && (*guard != 0) != (want != 0)) return;
-    const int64_t t = i % T;
+    if (guard_skips(guard, want)) return;
+    const int64_t t = edges ? i % T : 0;
     double s = 0.0;
     for (int k = 0; k < ntile; k++) {
-        s += partial[i * ntile + k];
-        if (k + 1 < ntile) {
-            const int64_t smp = (int64_t)k * NT + NT - 1;
-            const double *w = band_w + (t * N + smp) * 2;
-            double y = fma(w[0], edges[(i * ntile + k) * 2 + 1], 0.0);
-            y = fma(w[1], edges[(i * ntile + k + 1) * 2], y);
-            s = fma(y, y, s);
+        if (edges && k + 1 < ntile) {
+            const double *w = band_w + (t * N + (int64_t)k * 64 + 63) * 2;
+            const double *e = edges + (i * ntile + k) * 2;
+            s = band1_join(s, partial[i * ntile + k], true, w[0], w[1], e[1], e[2]);
+        } else {
+            s = tile_join(s, partial[i * ntile + k]);
         }
     }
     quad[i] = s;
 }
 
-int launch_sum_tiles_band1(beatamd_ctx *ctx, const double *partial, const double *edges, const double *band_w, int64_t C,
-                           int64_t T, int64_t N, int ntile, int NT, double *quad, const int *guard, int want)
+int launch_sum_tiles(beatamd_ctx *ctx, const double *partial, int64_t n, int ntile, double *quad, const int *guard, int want,
+                     const double *edges, const double *band_w, int64_t T, int64_t N)
 {
-    const int64_t n = C * T;
-    hipLaunchKernelGGL(k_sum_tiles_band1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, partial, edges, band_w,
-                       n, T, N, ntile, NT, quad, guard, want);
+    hipLaunchKernelGGL(k_sum_tiles, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, partial, n, ntile, quad,
+                       guard, want, edges, band_w, T, N);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }
@@ -401,7 +379,7 @@ static void launch_nvar(int nvar, int mode, dim3 grid, hipStream_t s, const GfAr
     else launch_mode<INTERP, 3, VEC, W>(mode, grid, s, a);
 }
 
-static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call);
+static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, bool *band1_done);
 
 // ---- patch split of small-N libraries --------------------------------------------------------------------------------
 // A (target, 64-sample tile) walk over P patches is a SERIAL path of P (x slip variables) steps per workgroup; a library
@@ -451,8 +429,8 @@ __global__ void __launch_bounds__(256) k_split_tslot(int64_t Tv, int R, const in
 }
 
 // syn[c,t,n] = sum over the ranges r ascending of part[c, t*R + r, n], then the epilogue of `mode`:
-//   0 out = syn   2 / 3 out = d - syn (seismic.py:1332)   1 quad[c,t] = sum_n (w_t (d - syn))^2 -- per 64-sample tile
-//   ascending, then the tiles ascending (the order of the lane <-> chain kernels)
+//   0 out = syn   2 out = d - syn (seismic.py:1332)   1 / 3 quad[c,t] = the scalar-weight / bidiagonal misfit of d - syn in
+//   the orders of misfit.hpp (one thread per 64-sample tile, then one thread joins the tiles)
 template <int MODE>
 __global__ void __launch_bounds__(256) k_split_combine(const double *part, int64_t C, int64_t T, int64_t N, int R,
                                                       const double *data, const double *wscalar, double *out, double *quad,
@@ -468,7 +446,7 @@ __global__ void __launch_bounds__(256) k_split_combine(const double *part, int64
         double syn = pp[0];
         for (int r = 1; r < R; r++) syn += pp[(int64_t)r * N];
         if (MODE == GF_STORE_SYN) out[ct * N + n] = syn;
-        else if (MODE == GF_RESID_SCALAR) v = wscalar[t] * (data[t * N + n] - syn);
+        else if (MODE == GF_RESID_SCALAR) v = scalar_t(wscalar[t], data[t * N + n], syn);
         else if (MODE == GF_RESID_BAND1) v = data[t * N + n] - syn;              // seismic.py:1332
         else out[ct * N + n] = data[t * N + n] - syn;
     }
@@ -476,65 +454,35 @@ __global__ void __launch_bounds__(256) k_split_combine(const double *part, int64
     sq[n] = v;
     __syncthreads();
     const int ntile = (int)((N + 63) / 64);
+    const int n0 = n * 64, nv = (int)min((int64_t)64, N - (int64_t)n0);   // thread n < ntile: tile n
+    // (mode 3: the band rows of the target through LDS: read from memory inside the serial loops they were a round trip per
+    // sample)
+    __shared__ double w[MODE == GF_RESID_BAND1 ? 2 * 256 : 2];
     if (MODE == GF_RESID_BAND1) {
-        // the bidiagonal misfit in the canonical order of quadform.hip (k_quadform_band1): per 64-sample tile the samples
-        // but its last, ascending, + the trace's very last sample; then the tiles ascending with every tile's boundary term
-        // (round 6: no residual store, no second kernel behind the patch ranges either)
-        // (the band rows of the target through LDS: read from memory inside the serial loops they were a round trip per
-        // sample)
-        __shared__ double w[2 * 256];
         if (n < N) {
             w[2 * n] = band_w[(t * N + n) * 2];
             w[2 * n + 1] = band_w[(t * N + n) * 2 + 1];
         }
         __syncthreads();
-        if (n < ntile) {
-            const int n0 = n * 64, nv = (int)min((int64_t)64, N - (int64_t)n0);
-            double q = 0.0, ri = sq[n0];
-            for (int i = 0; i + 1 < nv; i++) {
-                const double rn = sq[n0 + i + 1];
-                double y = fma(w[2 * (n0 + i)], ri, 0.0);
-                y = fma(w[2 * (n0 + i) + 1], rn, y);
-                q = fma(y, y, q);
-                ri = rn;
-            }
-            if (n0 + nv == N) {
-                const double y = fma(w[2 * (N - 1)], ri, 0.0);
-                q = fma(y, y, q);
-            }
-            tsum[n] = q;
-        }
-        __syncthreads();
-        if (n == 0) {
-            double s_ = 0.0;
-            for (int k = 0; k < ntile; k++) {
-                s_ += tsum[k];
-                if (k + 1 < ntile) {
-                    const int last = k * 64 + 63;
-                    double y = fma(w[2 * last], sq[last], 0.0);
-                    y = fma(w[2 * last + 1], sq[last + 1], y);
-                    s_ = fma(y, y, s_);
-                }
-            }
-            quad[ct] = s_;
-        }
-        return;
     }
     if (n < ntile) {
-        double q = 0.0;
-        const int hi = (int)min((int64_t)64, N - (int64_t)n * 64);
-        for (int i = 0; i < hi; i++) q = fma(sq[n * 64 + i], sq[n * 64 + i], q);
-        tsum[n] = q;
+        const auto r = [&](int i) { return sq[n0 + i]; };
+        if (MODE == GF_RESID_BAND1) tsum[n] = band1_tile<false, 64>(r, [&](int i, int b) { return w[2 * (n0 + i) + b]; }, nv, n0 + nv == N).q;
+        else tsum[n] = scalar_tile<false, 64>(r, nv);
     }
     __syncthreads();
     if (n == 0) {
         double s_ = 0.0;
-        for (int k = 0; k < ntile; k++) s_ += tsum[k];
+        for (int k = 0; k < ntile; k++) {
+            const int last = k * 64 + 63;
+            if (MODE == GF_RESID_BAND1 && k + 1 < ntile) s_ = band1_join(s_, tsum[k], true, w[2 * last], w[2 * last + 1], sq[last], sq[last + 1]);
+            else s_ = tile_join(s_, tsum[k]);
+        }
         quad[ct] = s_;
     }
 }
 
-static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R)
+static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R, bool *band1_done)
 {
     const SeisLib &L = *call.libs[0];
     SeisLib views[4];
@@ -552,7 +500,7 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
     BA_TRY(ctx->scratch(SL_SPLIT, (size_t)call.C * L.T * R * L.N, &part));
     v.out = part;
     v.quad = nullptr; v.data = nullptr; v.wscalar = nullptr; v.band_w = nullptr;
-    BA_TRY(launch_gfstack_impl(ctx, v));
+    BA_TRY(launch_gfstack_impl(ctx, v, band1_done));   // (mode 0: nothing to report yet)
     {
         // (kernel name / plan of the stacking launch stay; the plan says that the library was split)
         const size_t n0 = strlen(ctx->gf_plan);
@@ -563,27 +511,13 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
     const dim3 grid((unsigned)(call.C * L.T));
     BA_CHECK(call.C * L.T < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");
     ScopedTimer tm(ctx, "gfcombine");
-    switch (call.mode) {
-    case GF_STORE_SYN:
-        hipLaunchKernelGGL(k_split_combine<GF_STORE_SYN>, grid, dim3(256), 0, ctx->stream, part, call.C, L.T, L.N, R, call.data,
-                           call.wscalar, call.out, call.quad, (const double *)nullptr);
-        break;
-    case GF_RESID_SCALAR:
-        hipLaunchKernelGGL(k_split_combine<GF_RESID_SCALAR>, grid, dim3(256), 0, ctx->stream, part, call.C, L.T, L.N, R, call.data,
-                           call.wscalar, call.out, call.quad, (const double *)nullptr);
-        break;
-    case GF_RESID_BAND1:
-        if (GfKnobs::get(gf_knobs(ctx).qf_fuse, 1) != 0) {
-            hipLaunchKernelGGL(k_split_combine<GF_RESID_BAND1>, grid, dim3(256), 0, ctx->stream, part, call.C, L.T, L.N, R, call.data,
-                               call.wscalar, call.out, call.quad, call.band_w);
-            ctx->gf_band_fused = true;
-            break;
-        }
-        [[fallthrough]];
-    default:
-        hipLaunchKernelGGL(k_split_combine<GF_RESID_STORE>, grid, dim3(256), 0, ctx->stream, part, call.C, L.T, L.N, R, call.data,
-                           call.wscalar, call.out, call.quad, (const double *)nullptr);
-    }
+    // (mode 3 without the epilogue, BEATAMD_QF_FUSE=0: the residuals, launch_gfstack runs k_quadform_band1 behind them)
+    int mode = call.mode;
+    if (mode == GF_RESID_BAND1 && !(*band1_done = gf_carries_band1(gf_knobs(ctx), GF_BY_COMBINE))) mode = GF_RESID_STORE;
+    const auto combine = mode == GF_STORE_SYN ? k_split_combine<GF_STORE_SYN> : mode == GF_RESID_SCALAR ? k_split_combine<GF_RESID_SCALAR>
+                       : mode == GF_RESID_BAND1 ? k_split_combine<GF_RESID_BAND1> : k_split_combine<GF_RESID_STORE>;
+    hipLaunchKernelGGL(combine, grid, dim3(256), 0, ctx->stream, part, call.C, L.T, L.N, R, call.data, call.wscalar, call.out,
+                       call.quad, mode == GF_RESID_BAND1 ? call.band_w : (const double *)nullptr);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }
@@ -591,29 +525,24 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
 int launch_gfstack(beatamd_ctx *ctx, const GfStackCall &call)
 {
     const int R = call.libs[0] ? gf_patch_split(*call.libs[0], gf_knobs(ctx), ctx->num_cu) : 1;
+    // mode 3 (bidiagonal whitening operator): evaluated by the kernel that stacks where it carries the epilogue
+    // (gf_carries_band1), else residual store + k_quadform_band1 -- the caller gets quad [C,T] either way
+    bool band1_done = false;
     if (R > 1) {
-        ctx->gf_band_fused = false;
-        BA_TRY(launch_gfstack_split(ctx, call, R));
-        if (call.mode == GF_RESID_BAND1 && !ctx->gf_band_fused) {
-            const SeisLib &L = *call.libs[0];
-            BA_TRY(launch_quadform_banded(ctx, call.band_w, 1, L.N, L.T, call.C, call.out, L.T * L.N, L.N, call.quad, L.T));
-        }
-        return BEATAMD_OK;
+        BA_TRY(launch_gfstack_split(ctx, call, R, &band1_done));
+    } else {
+        if (call.mode == GF_RESID_BAND1)
+            BA_CHECK(call.band_w && call.quad && call.out && call.data, BEATAMD_EINVAL, "gfstack: mode 3 needs band_w, quad, out, data");
+        BA_TRY(launch_gfstack_impl(ctx, call, &band1_done));
     }
-    if (call.mode != GF_RESID_BAND1) return launch_gfstack_impl(ctx, call);
-    // bidiagonal whitening operator: fused into the stacking kernel where that kernel has the epilogue (k_gfstack_ws),
-    // else residual store + k_quadform_banded -- the caller gets quad [C,T] either way
-    BA_CHECK(call.band_w && call.quad && call.out && call.data, BEATAMD_EINVAL, "gfstack: mode 3 needs band_w, quad, out, data");
-    ctx->gf_band_fused = false;
-    BA_TRY(launch_gfstack_impl(ctx, call));
-    if (!ctx->gf_band_fused) {
+    if (call.mode == GF_RESID_BAND1 && !band1_done) {
         const SeisLib &L = *call.libs[0];
         BA_TRY(launch_quadform_banded(ctx, call.band_w, 1, L.N, L.T, call.C, call.out, L.T * L.N, L.N, call.quad, L.T));
     }
     return BEATAMD_OK;
 }
 
-static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
+static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, bool *band1_done)
 {
     GfStackCall k = call;
     const GfKnobs &kn = gf_knobs(ctx);
@@ -680,15 +609,14 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
     // multilinear from 192 chains on: the runs kernel (gfcell.hip).  When its tables can overflow (more row passes than they
     // are sized for) the streaming kernel below is enqueued behind it as a stand-in that works only if they did.
     const int *standin = nullptr;
-    // (mode 3: launch_gfstack_shared and the runs kernel have the epilogue -- round 6 --, the streaming kernel stores the
+    // (mode 3: launch_gfstack_shared and the runs kernel may carry the epilogue, the streaming kernel stores the
     // residuals; as the runs kernel's stand-in it is followed by a guarded k_quadform_band1)
     const int mode_in = k.mode;
-    // (BEATAMD_QF_FUSE=0: residual store + k_quadform_band1 behind every kernel -- A/B, tests)
-    const bool fuse_runs = mode_in == GF_RESID_BAND1 && GfKnobs::get(kn.qf_fuse, 1) != 0;
+    const bool fuse_runs = mode_in == GF_RESID_BAND1 && gf_carries_band1(kn, GF_BY_RUNS);
     if (mode_in == GF_RESID_BAND1 && !fuse_runs) k.mode = GF_RESID_STORE;
     if (!f32_all && gfstack_ml_applicable(k)) {
         BA_TRY(launch_gfstack_ml(ctx, k, ta.rowoff, ta.fac, Ttab, &standin));
-        if (fuse_runs) ctx->gf_band_fused = true;
+        *band1_done = fuse_runs;
         if (!standin) return BEATAMD_OK;
     }
     if (mode_in == GF_RESID_BAND1) k.mode = GF_RESID_STORE;
@@ -721,7 +649,7 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
                         float ms_min = 0.f;
                         for (int rep = 0; rep < 2; rep++) {   // first launch of a size: warm-up (code, tables' scratch)
                             BA_HIP(hipEventRecord(e0, ctx->stream));
-                            BA_TRY(launch_gfstack_shared(ctx, k, ta.rowoff, ta.fac, cgs[i], ucaps[i], Ttab));
+                            BA_TRY(launch_gfstack_shared(ctx, k, ta.rowoff, ta.fac, cgs[i], ucaps[i], Ttab, band1_done));
                             BA_HIP(hipEventRecord(e1, ctx->stream));
                             BA_HIP(hipEventSynchronize(e1));
                             float ms = 0.f;
@@ -754,7 +682,7 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call)
                 }
                 if (it != ctx->gs_tuned.end()) { cg = it->second.first; ucap = it->second.second; }
             }
-            return launch_gfstack_shared(ctx, k, ta.rowoff, ta.fac, cg, ucap, Ttab);
+            return launch_gfstack_shared(ctx, k, ta.rowoff, ta.fac, cg, ucap, Ttab, band1_done);
         }
     }
 

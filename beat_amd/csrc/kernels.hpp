@@ -63,9 +63,18 @@ enum GfMode : int {
     // bidiagonal W) without storing the residuals.  Kernels WITH this epilogue (k_gfstack_ws): the inner samples of a tile
     // in the kernel, the last sample of every tile -- its neighbour is the next tile's first residual -- by the tile-sum
     // kernel from two edge residuals per (chain, target, tile).  Kernels without it store the residuals (mode 2) and
-    // launch_gfstack runs k_quadform_banded behind them: either way the caller gets `quad`.
+    // launch_gfstack runs k_quadform_band1 behind them: either way the caller gets `quad`.
     GF_RESID_BAND1 = 3
 };
+
+// Which kernel carries the bidiagonal epilogue, stated once: the combine kernel of the patch ranges (k_split_combine), the
+// runs kernel (k_gfstack_runs) and k_gfstack_ws on float64 rows; BEATAMD_QF_FUSE=0: none (residual store +
+// k_quadform_band1 behind every kernel -- A/B, tests).  The launch functions report it to launch_gfstack (*band1_done).
+enum GfStacker : int { GF_BY_COMBINE, GF_BY_RUNS, GF_BY_WS, GF_BY_OTHER };
+inline bool gf_carries_band1(const GfKnobs &kn, GfStacker by)
+{
+    return by != GF_BY_OTHER && !GfKnobs::is(kn.qf_fuse, 0);
+}
 
 struct GfStackCall {
     const SeisLib *libs[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -97,19 +106,17 @@ struct GfStackCall {
     const int32_t *active = nullptr;
 };
 int launch_gfstack(beatamd_ctx *ctx, const GfStackCall &call);
-int launch_sum_tiles(beatamd_ctx *ctx, const double *partial, int64_t n, int ntile, double *quad,
-                     const int *guard = nullptr, int want = 0);
-// mode 3: quad[c,t] = sum over tiles of (partial + the tile's last sample: (w0 r_last + w1 r_first(next tile))^2), fixed order;
-// edges [C*T, ntile, 2] = (first, last residual of the tile), NT samples per tile
-int launch_sum_tiles_band1(beatamd_ctx *ctx, const double *partial, const double *edges, const double *band_w, int64_t C,
-                           int64_t T, int64_t N, int ntile, int NT, double *quad, const int *guard = nullptr, int want = 0);
+// quad[i] = the tiles of partial [n = C*T, ntile] joined in ascending order (k_sum_tiles, the orders of misfit.hpp); mode 3
+// (edges given): with every tile's boundary term from edges [C*T, ntile, 2] = (first, last residual of the 64-sample tile)
+int launch_sum_tiles(beatamd_ctx *ctx, const double *partial, int64_t n, int ntile, double *quad, const int *guard = nullptr,
+                     int want = 0, const double *edges = nullptr, const double *band_w = nullptr, int64_t T = 1, int64_t N = 0);
 // g[i] = (double)(float)g[i]; g32[i] = (float)g[i]  (float-storage copy of a GF library)
 int launch_round_to_f32(beatamd_ctx *ctx, double *g, float *g32, int64_t n);
 // gfshared.hip: chain-shared variant (distinct rows staged once per chain group)
 bool gfstack_shared_applicable(const GfStackCall &call, int *cg, int *ucap);
 int gfstack_shared_candidates(const GfStackCall &call, int *cgs, int *ucaps);
 int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &call, const uint32_t *rowoff,
-                          const double *fac, int CG, int ucap, int64_t Ttab);
+                          const double *fac, int CG, int ucap, int64_t Ttab, bool *band1_done);
 
 // gfcell.hip: multilinear stacking with the rows of a cell in registers (518-chain groups, row passes): k_gfstack_runs.
 // *ovf (device, nullable on return): nonzero after the launch = the tables overflowed and nothing was stacked -- the
@@ -137,7 +144,7 @@ struct QuadformCall {
 };
 int launch_quadform(beatamd_ctx *ctx, const QuadformCall &call);
 // banded upper-triangular operators (quadform.hip): the half bandwidth of a stack of matrices (entries beyond it are at most
-// 2^-40 of their matrix's largest; scratch: nd * 8 + 8 bytes), the compact band [nd, M, band + 1], and the quadratic form on it
+// 2^-40 of their row's largest; scratch: nd * M * 8 + 16 bytes), the compact band [nd, M, band + 1], and the quadratic form on it
 constexpr int QF_BAND_LIMIT = 16;
 int launch_band_detect(beatamd_ctx *ctx, const double *A, int64_t nd, int64_t M, void *scratch, int64_t *band_host,
                        double *dropped_rel_host);

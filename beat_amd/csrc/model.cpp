@@ -176,7 +176,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
                 BA_TRY(launch_gfstack(ctx, k));
             } else if (ws->band == 1 && ws->M == wm.N && ws->nd == wm.T && wset_banded(ctx, *ws)) {
                 // bidiagonal whitening operators (the "exponential" noise structure): the misfit rides in the stacking
-                // kernel where it has the epilogue, else residual store + k_quadform_banded (launch_gfstack decides)
+                // kernel where it has the epilogue, else residual store + k_quadform_band1 (launch_gfstack decides)
                 k.mode = GF_RESID_BAND1;
                 k.band_w = ws->wb.get();
                 k.quad = quad;

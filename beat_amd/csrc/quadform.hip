@@ -19,6 +19,7 @@
 // f64 MFMA layouts (cdna_hip_programming.md section 3): A lane l -> A[i=l&15][k=l>>4],
 // B lane l -> B[k=l>>4][j=l&15], C/D reg r of lane l -> row (l>>4)+4r, col l&15.
 #include "kernels.hpp"
+#include "misfit.hpp"
 
 namespace beatamd {
 
@@ -440,7 +441,7 @@ __global__ void __launch_bounds__(256) k_band_pack(const double *A, int64_t nd, 
 int launch_band_detect(beatamd_ctx *ctx, const double *A, int64_t nd, int64_t M, void *scratch, int64_t *band_host,
                        double *dropped_rel_host)
 {
-    // scratch: [nd*M] uint64 row maxima + one uint64 + one int
+    // scratch: [nd*M] uint64 row maxima + one uint64 + one int (padded: nd*M*8 + 16 bytes)
     unsigned long long *rmax = (unsigned long long *)scratch;
     unsigned long long *dropped = rmax + nd * M;
     int *band = reinterpret_cast<int *>(dropped + 1);
@@ -491,8 +492,6 @@ struct QbArgs {
     int want;
 };
 
-// BAND1: the bidiagonal case with the loop over the band unrolled (the same two fused multiply-adds per sample)
-template <int BAND1>
 __global__ void __launch_bounds__(256) k_quadform_banded(QbArgs a)
 {
     __shared__ double red[QB_NC][4];
@@ -506,23 +505,6 @@ __global__ void __launch_bounds__(256) k_quadform_banded(QbArgs a)
     for (int64_t i = tid; i < a.M; i += 256) {
         const double *wr = wb + i * (a.band + 1);
         const int kmax = (int)min(a.band, a.M - 1 - i);
-        if (BAND1) {
-            const double w0 = wr[0], w1 = wr[1];          // (w1 = 0 in the last row)
-            double x0[QB_NC], x1[QB_NC];
-#pragma unroll
-            for (int j = 0; j < QB_NC; j++) {
-                const double *x = a.X + (c0 + min(j, nc - 1)) * a.xs_c + d * a.xs_d + i;
-                x0[j] = x[0];
-                x1[j] = kmax ? x[1] : 0.0;
-            }
-#pragma unroll
-            for (int j = 0; j < QB_NC; j++) {
-                double y = fma(w0, x0[j], 0.0);
-                if (kmax) y = fma(w1, x1[j], y);
-                if (j < nc) q[j] = fma(y, y, q[j]);
-            }
-            continue;
-        }
 #pragma unroll
         for (int j = 0; j < QB_NC; j++) {
             if (j >= nc) break;
@@ -542,14 +524,9 @@ __global__ void __launch_bounds__(256) k_quadform_banded(QbArgs a)
     if (tid < nc) a.quad[(c0 + tid) * a.q_stride + d] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
 }
 
-// ---- bidiagonal operators in the CANONICAL summation order (round 6) ----------------------------------------------------
-// The stacking kernels evaluate this misfit inside their epilogues (GF_RESID_BAND1, gfshared.hip): a lane there holds the 64
-// samples of one tile of one chain, so the order every path follows is
-//     quad = 0;  for tile k = 0, 1, ...:   quad += q_k;   if (k is not the last tile) quad = fma(yb_k, yb_k, quad)
-//     q_k  = sum over the tile's samples i but its last, ascending (fma(y_i, y_i, q)), + the trace's very last sample
-//     y_i  = fma(W[i,i+1], r_{i+1}, fma(W[i,i], r_i, 0));  yb_k = y of the tile's last sample (its neighbour = next tile)
-// and a chain's misfit has the same bits whichever kernel stacked it (batch size, rank count, fused or not).  This kernel is
-// the path of everything without the epilogue (the runs / small-group / streaming kernels, beatamd_mvn_chol_logp_batch):
+// ---- bidiagonal operators in the canonical summation order of misfit.hpp ------------------------------------------------
+// The stacking kernels evaluate this misfit inside their epilogues (GF_RESID_BAND1, gfshared.hip); this kernel is the path
+// of everything without the epilogue (the small-group / streaming kernels, beatamd_mvn_chol_logp_batch):
 // workgroup = (dataset, 16 chains) of 128 threads; the operator's band rows of a chunk of 8 tiles sit in LDS beside the 16
 // chains' residual rows of the chunk (pitch 65: thread <-> (chain, tile) reads its 64 samples conflict-free; every thread
 // has a tile; 76 KB: two workgroups per CU), one thread per chain adds the tiles up.  The rows come in as one index space
@@ -577,7 +554,7 @@ __global__ void __launch_bounds__(QB1_NT) k_quadform_band1(QbArgs a, int ct, int
     double *sacc = ybv + npc * ct;                      // [QB1_NC]
     int *hasb = reinterpret_cast<int *>(sacc + QB1_NC); // [npc][ct]
     const int tid = threadIdx.x, NT = blockDim.x;
-    if (a.guard && (*a.guard != 0) != (a.want != 0)) return;
+    if (a.guard && (*a.guard != 0) != (a.want != 0)) return;   // guard_skips (misfit.hpp), spelled out: see the tile loops
     const int64_t d = blockIdx.y, c0 = (int64_t)blockIdx.x * QB1_NC;
     const int nc = (int)min((int64_t)QB1_NC, a.C - c0);
     const int64_t M = a.M, CH = (int64_t)ct * 64;
@@ -646,32 +623,31 @@ __global__ void __launch_bounds__(QB1_NT) k_quadform_band1(QbArgs a, int ct, int
                     const double *x = xl + jj * xstride + k * QB1_XP;
                     const double *w = wl + k * QB1_WP;
                     const bool trace_end = n0 + nvalid == M;
+                    // q_k and yb_k of misfit.hpp in loops of the kernel's own (band1_tile with an unrolled whole-tile walk):
+                    // through the header's accessors the compiler orders this kernel's prologue differently
                     double q = 0.0, ri = x[0];
                     if (nvalid == 64) {
 #pragma unroll 9
                         for (int i = 0; i < 63; i++) {     // (a whole tile: the trip count is known, the LDS reads run ahead)
                             const double rn = x[i + 1];
-                            double y = fma(w[2 * i], ri, 0.0);
-                            y = fma(w[2 * i + 1], rn, y);
+                            const double y = band1_y(w[2 * i], w[2 * i + 1], ri, rn);
                             q = fma(y, y, q);
                             ri = rn;
                         }
                     } else {
                         for (int i = 0; i + 1 < nvalid; i++) {
                             const double rn = x[i + 1];
-                            double y = fma(w[2 * i], ri, 0.0);
-                            y = fma(w[2 * i + 1], rn, y);
+                            const double y = band1_y(w[2 * i], w[2 * i + 1], ri, rn);
                             q = fma(y, y, q);
                             ri = rn;
                         }
                     }
                     double yb = 0.0;
                     if (trace_end) {
-                        const double y = fma(w[2 * (nvalid - 1)], ri, 0.0);
+                        const double y = band1_y(w[2 * (nvalid - 1)], ri);
                         q = fma(y, y, q);
                     } else {
-                        yb = fma(w[126], ri, 0.0);
-                        yb = fma(w[127], x[QB1_XP], yb);     // first residual of the next tile (last tile: of the next chunk)
+                        yb = band1_y(w[126], w[127], ri, x[QB1_XP]);   // first residual of the next tile (last tile: of the next chunk)
                     }
                     part[jj * ct + k] = q;
                     ybv[jj * ct + k] = yb;
@@ -683,8 +659,8 @@ __global__ void __launch_bounds__(QB1_NT) k_quadform_band1(QbArgs a, int ct, int
                 const int ntl = (int)((nch + 63) / 64);
                 double sq = sacc[j0 + tid];
                 for (int k = 0; k < ntl; k++) {
-                    sq += part[tid * ct + k];
-                    if (hasb[tid * ct + k]) sq = fma(ybv[tid * ct + k], ybv[tid * ct + k], sq);
+                    sq = tile_join(sq, part[tid * ct + k]);
+                    if (hasb[tid * ct + k]) sq = band1_boundary(sq, ybv[tid * ct + k]);
                 }
                 sacc[j0 + tid] = sq;
             }
@@ -698,11 +674,11 @@ int launch_quadform_banded(beatamd_ctx *ctx, const double *wb, int64_t band, int
                            int64_t xs_c, int64_t xs_d, double *quad, int64_t q_stride, const int *guard, int want)
 {
     if (C == 0 || nd == 0) return BEATAMD_OK;
+    QbArgs a;
+    a.wb = wb; a.M = M; a.nd = nd; a.C = C; a.band = band;
+    a.X = X; a.xs_c = xs_c; a.xs_d = xs_d; a.quad = quad; a.q_stride = q_stride;
+    a.guard = guard; a.want = want;
     if (band == 1) {
-        QbArgs b;
-        b.wb = wb; b.M = M; b.nd = nd; b.C = C; b.band = 1;
-        b.X = X; b.xs_c = xs_c; b.xs_d = xs_d; b.quad = quad; b.q_stride = q_stride;
-        b.guard = guard; b.want = want;
         BA_CHECK(nd <= 65535, BEATAMD_EINVAL, "quadform_banded: too many datasets");
         ScopedTimer tm(ctx, "quadform");
         const int ct = (int)std::min<int64_t>(QB1_CT, (M + 63) / 64);
@@ -710,20 +686,16 @@ int launch_quadform_banded(beatamd_ctx *ctx, const double *wb, int64_t band, int
         const size_t lds = qb1_lds(ct, npc);
         BA_HIP(hipFuncSetAttribute((const void *)k_quadform_band1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)qb1_lds(QB1_CT, QB1_NC)));
         hipLaunchKernelGGL(k_quadform_band1, dim3((unsigned)((C + QB1_NC - 1) / QB1_NC), (unsigned)nd), dim3(QB1_NT), lds,
-                           ctx->stream, b, ct, npc);
+                           ctx->stream, a, ct, npc);
         BA_HIP(hipGetLastError());
         return BEATAMD_OK;
     }
-    QbArgs a;
-    a.wb = wb; a.M = M; a.nd = nd; a.C = C; a.band = band;
-    a.X = X; a.xs_c = xs_c; a.xs_d = xs_d; a.quad = quad; a.q_stride = q_stride;
-    a.guard = nullptr; a.want = 0;
     BA_CHECK(guard == nullptr, BEATAMD_EINVAL, "quadform_banded: a guarded launch exists for the bidiagonal kernel only");
     BA_CHECK(nd <= 65535, BEATAMD_EINVAL, "quadform_banded: too many datasets");
     {
         ScopedTimer tm(ctx, "quadform");
         const dim3 grid((unsigned)((C + QB_NC - 1) / QB_NC), (unsigned)nd);
-        hipLaunchKernelGGL(k_quadform_banded<0>, grid, dim3(256), 0, ctx->stream, a);   // (band 1: k_quadform_band1 above)
+        hipLaunchKernelGGL(k_quadform_banded, grid, dim3(256), 0, ctx->stream, a);   // (band 1: k_quadform_band1 above)
     }
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;

@@ -1166,7 +1166,7 @@ def test_banded_whitening_operators(ctx, orc, monkeypatch, M):
 
 
 @pytest.mark.parametrize("N,C,nvar,shifts", [(64, 300, 1, False), (200, 300, 1, True), (130, 1100, 1, False), (192, 257, 2, True),
-                                             (1030, 64, 1, False)])
+                                             (1030, 64, 1, False), (128, 100, 1, False), (578, 100, 1, True)])
 def test_bidiagonal_misfit_inside_the_stacking_kernel(ctx, monkeypatch, N, C, nvar, shifts):
     """round 6: with the reference's "exponential" noise structure (covariance.py:24-51; bidiagonal
     W = chol(inv(C)).T) the misfit sum_i (W[i,i] r_i + W[i,i+1] r_{i+1})^2 (distributions.py:119-138) rides in the
