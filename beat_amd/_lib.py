@@ -86,6 +86,7 @@ _PROTOS = {
     "beatamd_ffi_model_nllk": [_vp, _i32, _pi64],
     "beatamd_ffi_model_destroy": [_vp, _i32],
     "beatamd_ffi_logp_batch": [_vp, _i32, _i64, _vp, _vp],
+    "beatamd_ffi_start_times_batch": [_vp, _i32, _i64, _vp, _vp, _vp],
     "beatamd_ffi_synthetics_batch": [_vp, _i32, _i32, _i64, _vp, _i32, _vp],
     "beatamd_ffi_astep_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp],
     "beatamd_autocovariance_batch": [_vp, _i64, _i64, _vp, _vp, _vp],
@@ -98,6 +99,7 @@ _PROTOS = {
     "beatamd_ctx_gf_plan": [_vp, C.c_char_p, _i64, C.POINTER(_f64), _pi64],
     "beatamd_ctx_gf_tune_log": [_vp, C.c_char_p, _i64],
     "beatamd_gf_patch_ranges": [_i64, _i64, _i64, C.c_int32],
+    "beatamd_fast_sweep_lds": [_i32, _pi32],
     "beatamd_seis_gflib_set_split_targets": [_vp, _i32, _i64],
     "beatamd_ctx_reload_knobs": [_vp],
     "beatamd_ctx_gf_chain_groups": [_vp, _i64, _vp, _vp, _i64, _vp],

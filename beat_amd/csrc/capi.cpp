@@ -801,6 +801,29 @@ int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wav
     return st.finish();
 }
 
+int beatamd_ffi_start_times_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *times,
+                                  int32_t *chain_bad)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(Q && times && C >= 0, BEATAMD_EINVAL, "ffi_start_times: bad argument");
+    BA_TRY(model_check_layout(*m));
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_q;
+    double *d_t, *st0;
+    int32_t *d_b = nullptr, *bad;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.out(times, (size_t)C * m->P, &d_t));
+    if (chain_bad) BA_TRY(st.out(chain_bad, (size_t)C, &d_b));
+    BA_TRY(model_start_times(ctx, *m, C, d_q, &st0, &bad));
+    BA_HIP(hipMemcpyAsync(d_t, st0, (size_t)C * m->P * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_b) BA_HIP(hipMemcpyAsync(d_b, bad, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    BA_TRY(st.finish());            // (host arrays are filled before a raised status word is returned)
+    return ctx->check_status();     // a hypocentre outside the patch grid: the flags say which chains
+}
+
 int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *LL)
 {
     ENTER(ctx);
@@ -1227,6 +1250,14 @@ int32_t beatamd_gf_patch_ranges(int64_t ntargets, int64_t npatches, int64_t nsam
 {
     if (ntargets <= 0 || npatches <= 0 || nsamples <= 0) return 1;
     return (int32_t)gf_patch_ranges(ntargets, npatches, nsamples, num_cu > 0 ? num_cu : 256);
+}
+
+int32_t beatamd_fast_sweep_lds(int32_t ncells, int32_t *waves)
+{
+    if (ncells <= 0 || ncells > SWEEP_MAX_CELLS) return -1;
+    const SweepLdsPlan pl = sweep_lds_plan(ncells);
+    if (waves) *waves = pl.waves;
+    return (int32_t)pl.bytes;
 }
 
 int beatamd_ctx_gf_chain_groups(beatamd_ctx *ctx, int64_t C, const double *key0, const double *key1,

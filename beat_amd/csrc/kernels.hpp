@@ -7,6 +7,14 @@
 namespace beatamd {
 
 // ---- sweep.hip -------------------------------------------------------------------
+// what a sweep launch asks for, by the largest subfault of the batch (a pure function; beatamd_fast_sweep_lds)
+constexpr int SWEEP_MAX_CELLS = 6400;
+struct SweepLdsPlan {
+    int nmax;       // LDS doubles per array per wavefront
+    int waves;      // grids (wavefronts) per workgroup: 4 or 1
+    size_t bytes;   // dynamic LDS of a workgroup
+};
+SweepLdsPlan sweep_lds_plan(int nmax_cells);
 int launch_sweep_explicit(beatamd_ctx *ctx, const double *slow, double h, const int32_t *hi,
                           const int32_t *hj, int ni, int nj, int64_t C, double *out);
 int launch_sweep_model(beatamd_ctx *ctx, const FfiModel &m, const double *Q, int64_t C,

@@ -394,6 +394,17 @@ class Context(object):
                                                      int(bool(residuals)), ptr(out)))
         return out
 
+    def ffi_start_times_batch(self, model_id, Q, npatches, out=None, chain_bad=None):
+        """rupture onset times [C, npatches] of the model at the points Q [C, nparams]; chain_bad (int32 [C], optional,
+        filled also when the call raises): chains whose hypocentre lies outside the patch grid"""
+        self._adopt_stream(Q)
+        Qc = f64(Q)
+        Cn = int(Qc.shape[0])
+        if out is None:
+            out = _empty_like(Qc, (Cn, int(npatches)))
+        check(self._lib.beatamd_ffi_start_times_batch(self._h, model_id, Cn, ptr(Qc), ptr(out), ptr(chain_bad)))
+        return out
+
     def ffi_astep_batch(self, model_id, Q0, L0, delta, scaling, lower, upper, log_u, beta,
                         accepted=None):
         """In-place update of Q0 / L0 (must be contiguous float64); returns accepted (int32)."""

@@ -428,6 +428,11 @@ class LogpForwFunc(object):
         T, N = wm.data.shape
         return self.ctx.ffi_synthetics_batch(self.model_id, wavemap_index, Q, T, N, residuals=residuals)
 
+    def start_times(self, Q, chain_bad=None):
+        """rupture onset times [C, npatches] at the points Q [C, nparams]: the rupture onset loop of the distributed-slip
+        composite (seismic.py:1253-1272) for a batch; chain_bad: see Context.ffi_start_times_batch"""
+        return self.ctx.ffi_start_times_batch(self.model_id, Q, self.problem.npatches, chain_bad=chain_bad)
+
     def release(self):
         """free what this compiled model holds on the device BESIDES the libraries: the model record and the weight sets
         (a dense set is T x N x N doubles: 8.6 GB at config 3).  The function cannot be called afterwards.  Explicit, not

@@ -112,6 +112,17 @@ int beatamd_ctx_gf_tune_log(beatamd_ctx *ctx, char *buf, int64_t buflen);
  * ceil(walks * R / num_cu) * (P / R + 5); 1 = the library as it is.  What a call did is in beatamd_ctx_gf_plan.  No reference
  * counterpart (beat/ffi/base.py:607-709 stacks one chain on one core). */
 int32_t beatamd_gf_patch_ranges(int64_t ntargets, int64_t npatches, int64_t nsamples, int32_t num_cu);
+/* The rupture onset times the model's forward pass starts from: times[C, npatches] = fast sweep of every subfault from
+ * the hypocentre and the velocities in Q plus the subfault's nucleation time (seismic.py:1253-1272), as
+ * beatamd_ffi_logp_batch computes them.  chain_bad[C] (nullable): 1 for a chain whose hypocentre index lies outside the
+ * patch grid; the call then fills both arrays and returns BEATAMD_EINVAL. */
+int beatamd_ffi_start_times_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *times,
+                                  int32_t *chain_bad);
+/* The LDS bytes a workgroup of the rupture-time sweep asks for when the largest subfault of a batch has ncells patches,
+ * and through waves (nullable) how many grids share that workgroup (4 or 1): a pure function, the rule of the launch
+ * (four grids per workgroup while they fit 64 KiB together, one above; at most 160 KiB).  -1: ncells is not in 1..6400,
+ * the limit of beatamd_fast_sweep_batch.  No reference counterpart (fast_sweep_ext.c solves one grid on the host). */
+int32_t beatamd_fast_sweep_lds(int32_t ncells, int32_t *waves);
 /* The target count the rule above sees for a library (default 0: its own T).  R sets the order in which a target's patches
  * are summed, so a rank's block of a library sharded by target (beat_amd/models/sharded.py) is given the whole wavemap's
  * target count: every rank then picks the R of the replicated library, and the likelihoods stay bitwise those of the
