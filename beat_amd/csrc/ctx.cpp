@@ -200,14 +200,9 @@ namespace beatamd {
 void GfKnobs::read_env()
 {
     auto rd = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : KNOB_UNSET; };
-    gf_kernel = rd("BEATAMD_GF_KERNEL"); gs_cg = rd("BEATAMD_GS_CG"); gs_ws = rd("BEATAMD_GS_WS"); gs_dma = rd("BEATAMD_GS_DMA");
-    gs_nt = rd("BEATAMD_GS_NT"); ws_map = rd("BEATAMD_WS_MAP"); gs_pair = rd("BEATAMD_GS_PAIR"); gs_nthint = rd("BEATAMD_GS_NTHINT");
-    gs_order = rd("BEATAMD_GS_ORDER"); gs_fit = rd("BEATAMD_GS_FIT"); gs_win = rd("BEATAMD_GS_WIN"); gf_tinv = rd("BEATAMD_GF_TINV");
-    gs_tune = rd("BEATAMD_GS_TUNE"); gf_order = rd("BEATAMD_GF_ORDER"); gf_cgroup = rd("BEATAMD_GF_CGROUP"); gs_ml = rd("BEATAMD_GS_ML");
-    gc_global = rd("BEATAMD_GC_GLOBAL"); gc_sort = rd("BEATAMD_GC_SORT"); gc_keys = rd("BEATAMD_GC_KEYS"); gc_bands = rd("BEATAMD_GC_BANDS"); gr_cap = rd("BEATAMD_GR_CAP");
-    gr_pass_alloc = rd("BEATAMD_GR_PASS_ALLOC"); gr_var = rd("BEATAMD_GR_VAR"); sweep_v1 = rd("BEATAMD_SWEEP_V1"); qf_band = rd("BEATAMD_QF_BAND"); qf_fuse = rd("BEATAMD_QF_FUSE"); gf_split = rd("BEATAMD_GF_SPLIT"); gm_wave = rd("BEATAMD_GM_WAVE");
-    skip_parked = rd("BEATAMD_SKIP_PARKED");
-    td_strip = rd("BEATAMD_TD_STRIP");
+#define X(member, env) member = rd(env);
+    BEATAMD_GF_KNOBS(X)
+#undef X
 }
 
 const GfKnobs &gf_knobs(beatamd_ctx *ctx)

@@ -114,7 +114,7 @@ public:
 
 struct SeisLib {
     int64_t T = 0, P = 0, D = 0, S = 0, N = 0;
-    // target count the patch-range rule sees (gf_patch_split): 0 = T; the whole wavemap's T for a rank's block of targets
+    // target count the patch-range rule sees (gf_plan_call): 0 = T; the whole wavemap's T for a rank's block of targets
     int64_t split_T = 0;
     double st_min = 0, st_dt = 1, du_min = 0, du_dt = 1;
     double *g = nullptr;  // HBM, (T,P,D,S,N) C-order, N fastest
@@ -248,13 +248,20 @@ struct HyperModel {
 // BEATAMD_KNOBS_LIVE=1 in the environment -- the test suite, the A/B tools -- re-reads them at every stacking call so
 // that one process can compare kernels.  KNOB_UNSET: the variable is not set, the default applies.
 constexpr int KNOB_UNSET = -2147483647;
+// Stated once: X(member, environment variable) -> the fields of GfKnobs and GfKnobs::read_env
+#define BEATAMD_GF_KNOBS(X) \
+    X(gf_kernel, "BEATAMD_GF_KERNEL") X(gs_cg, "BEATAMD_GS_CG") X(gs_ws, "BEATAMD_GS_WS") X(gs_dma, "BEATAMD_GS_DMA") X(gs_nt, "BEATAMD_GS_NT") \
+    X(ws_map, "BEATAMD_WS_MAP") X(gs_pair, "BEATAMD_GS_PAIR") X(gs_nthint, "BEATAMD_GS_NTHINT") X(gs_order, "BEATAMD_GS_ORDER") \
+    X(gs_fit, "BEATAMD_GS_FIT") X(gs_win, "BEATAMD_GS_WIN") X(gf_tinv, "BEATAMD_GF_TINV") X(gs_tune, "BEATAMD_GS_TUNE") \
+    X(gf_order, "BEATAMD_GF_ORDER") X(gf_cgroup, "BEATAMD_GF_CGROUP") X(gs_ml, "BEATAMD_GS_ML") X(gc_global, "BEATAMD_GC_GLOBAL") \
+    X(gc_sort, "BEATAMD_GC_SORT") X(gc_keys, "BEATAMD_GC_KEYS") X(gc_bands, "BEATAMD_GC_BANDS") X(gr_cap, "BEATAMD_GR_CAP") \
+    X(gr_pass_alloc, "BEATAMD_GR_PASS_ALLOC") X(gr_var, "BEATAMD_GR_VAR") X(sweep_v1, "BEATAMD_SWEEP_V1") X(qf_band, "BEATAMD_QF_BAND") \
+    X(qf_fuse, "BEATAMD_QF_FUSE") X(gf_split, "BEATAMD_GF_SPLIT") X(gm_wave, "BEATAMD_GM_WAVE") X(skip_parked, "BEATAMD_SKIP_PARKED") \
+    X(td_strip, "BEATAMD_TD_STRIP")
 struct GfKnobs {
-    int gf_kernel = KNOB_UNSET, gs_cg = KNOB_UNSET, gs_ws = KNOB_UNSET, gs_dma = KNOB_UNSET, gs_nt = KNOB_UNSET,
-        ws_map = KNOB_UNSET, gs_pair = KNOB_UNSET, gs_nthint = KNOB_UNSET, gs_order = KNOB_UNSET, gs_fit = KNOB_UNSET,
-        gs_win = KNOB_UNSET, gf_tinv = KNOB_UNSET, gs_tune = KNOB_UNSET, gf_order = KNOB_UNSET, gf_cgroup = KNOB_UNSET,
-        gs_ml = KNOB_UNSET, gc_global = KNOB_UNSET, gc_sort = KNOB_UNSET, gc_keys = KNOB_UNSET, gc_bands = KNOB_UNSET, gr_cap = KNOB_UNSET,
-        gr_pass_alloc = KNOB_UNSET, gr_var = KNOB_UNSET, sweep_v1 = KNOB_UNSET, qf_band = KNOB_UNSET, qf_fuse = KNOB_UNSET, gf_split = KNOB_UNSET, gm_wave = KNOB_UNSET,
-        skip_parked = KNOB_UNSET, td_strip = KNOB_UNSET;
+#define X(member, env) int member = KNOB_UNSET;
+    BEATAMD_GF_KNOBS(X)
+#undef X
     void read_env();
     static int get(int v, int dflt) { return v == KNOB_UNSET ? dflt : v; }
     static bool is(int v, int x) { return v != KNOB_UNSET && v == x; }       // set and equal to x

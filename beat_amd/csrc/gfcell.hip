@@ -1165,9 +1165,9 @@ __global__ void __launch_bounds__(1024) k_gfstack_runs(GcArgs a)
 // Multilinear batches from 192 chains on take the runs kernel whatever the library's (duration x start-time) grid
 // (row passes); what rules it out: an odd sample count (16-byte LDS-DMA lanes), more than three slip variables,
 // dense-slot / row ids beyond 16 bits or the table kernel's LDS maps, byte offsets beyond 32 bits.
-bool gfstack_ml_applicable(const GfStackCall &k)
+bool gfstack_ml_applicable(const GfStackCall &k, const GfPlan &p)
 {
-    const GfKnobs &kn = *k.knobs;
+    const GfKnobs &kn = *p.knobs;
     const int knob = GfKnobs::get(kn.gs_ml, -1);   // 0: off, 1: forced also for small batches
     const int gfk = GfKnobs::get(kn.gf_kernel, -1);
     const bool cg_fixed = GfKnobs::set(kn.gs_cg);
@@ -1177,33 +1177,34 @@ bool gfstack_ml_applicable(const GfStackCall &k)
     if (L.N % 2 != 0) return false;
     const int64_t DS = L.D * L.S, dense = L.D * (L.S + 1);
     if (DS < 1 || dense > GR_DENSE_MAX || L.D > 255) return false;
-    if (L.T * L.N * 8 >= (int64_t)1 << 32 || DS * L.N * 8 >= (int64_t)1 << 32) return false;
+    if (p.T * L.N * 8 >= (int64_t)1 << 32 || DS * L.N * 8 >= (int64_t)1 << 32) return false;
     const bool forced = knob == 1;
     if (!forced && k.C < 192) return false;          // small batches: k_gfstack_dma groups of 64..256
     if (!forced && cg_fixed) return false;           // an explicit group size asks for the k_gfstack_dma family
     return true;
 }
 
-int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *rowoff, const double *fac, int64_t Ttab,
-                      const int **ovf_out)
+int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &p, const GfLaunch &ln, const int **ovf_out)
 {
     const SeisLib &L = *k.libs[0];
+    const int64_t Ttab = p.Ttab;
+    const int mode = p.mode;
     const int64_t DS = L.D * L.S, dense = L.D * (L.S + 1);
     const int64_t ngroups = (k.C + GC_CG - 1) / GC_CG;
     const int64_t GT = ngroups * Ttab, GTP = GT * L.P;
     // sized in bytes on purpose: the four table slots below hold packed records of mixed types with byte slack behind them
-    void *p = nullptr;
+    void *raw = nullptr;
     *ovf_out = nullptr;
     // row passes: none when every dense slot of a patch (and the row requests they can take) fits a buffer; else the
     // passes are counted on the device and the tables sized for GR_PASS_ALLOC per patch (BEATAMD_GR_CAP: tests)
-    const GfKnobs &kn = *k.knobs;
+    const GfKnobs &kn = *p.knobs;
     const int cap = std::min(GR_CAP, std::max(8, GfKnobs::get(kn.gr_cap, GR_CAP)));
     const bool passes = dense > cap || (L.S > 255 ? dense : dense / 2 + 2 * L.D + 1) > GC_NLOAD * GC_LREQ;
     const int64_t vmax = L.P * (passes ? std::max(1, GfKnobs::get(kn.gr_pass_alloc, GR_PASS_ALLOC)) : 1);
     const int64_t smax = vmax * k.nvar;
 
     GcOrderArgs oa{};
-    oa.C = k.C; oa.T = Ttab; oa.P = L.P; oa.S = L.S; oa.rowoff = rowoff;
+    oa.C = k.C; oa.T = Ttab; oa.P = L.P; oa.S = L.S; oa.rowoff = ln.rowoff;
     // chains that rupture alike share cells patch after patch -> put them into one wavefront (k_gc_order)
     oa.sort = GfKnobs::get(kn.gc_sort, 1) != 0;
     if (GfKnobs::get(kn.gc_keys, 1)) { oa.key[0] = k.order_key[0]; oa.key[1] = k.order_key[1]; }
@@ -1214,25 +1215,25 @@ int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *ro
     ta.C = k.C; ta.T = Ttab; ta.P = L.P; ta.D = L.D; ta.S = L.S; ta.DS = DS;
     ta.nvar = k.nvar; ta.cap = cap;
     ta.vmax = vmax; ta.smax = smax;
-    ta.rowoff = rowoff; ta.fac = fac;
+    ta.rowoff = ln.rowoff; ta.fac = ln.fac;
     for (int v = 0; v < k.nvar; v++) ta.slips[v] = k.slips[v];
-    ta.R = k.patch_split;
+    ta.R = p.R;
     ta.ngtp = GTP;
     ta.order = oa.order;
-    BA_TRY(ctx->get_scratch(SL_GC_STREAM, (size_t)GT * GC_NCONS * (smax + 1) * GR_WSTRIDE + 8192, &p));
-    ta.wtab = (char *)p;
-    BA_TRY(ctx->get_scratch(SL_GC_HDR, (size_t)GT * (smax + 3) * GC_NLOAD * GC_LTAB + 256, &p));
-    ta.ltab = (uint32_t *)p;
+    BA_TRY(ctx->get_scratch(SL_GC_STREAM, (size_t)GT * GC_NCONS * (smax + 1) * GR_WSTRIDE + 8192, &raw));
+    ta.wtab = (char *)raw;
+    BA_TRY(ctx->get_scratch(SL_GC_HDR, (size_t)GT * (smax + 3) * GC_NLOAD * GC_LTAB + 256, &raw));
+    ta.ltab = (uint32_t *)raw;
     // [ucount GTP][npass GTP][voff GTP][nv GT][ovf 1] + cpass bytes
-    BA_TRY(ctx->get_scratch(SL_GS_UCOUNT, (size_t)(3 * GTP + GT + 1) * sizeof(uint32_t) + (size_t)GTP * GC_CG, &p));
-    ta.ucount = (uint32_t *)p;
+    BA_TRY(ctx->get_scratch(SL_GS_UCOUNT, (size_t)(3 * GTP + GT + 1) * sizeof(uint32_t) + (size_t)GTP * GC_CG, &raw));
+    ta.ucount = (uint32_t *)raw;
     ta.npass = ta.ucount + GTP;
     uint32_t *voff = ta.npass + GTP, *nv = voff + GTP;
     int *ovf = reinterpret_cast<int *>(nv + GT);
     ta.cpass = reinterpret_cast<uint8_t *>(ovf + 1);
     // (the line behind the last step is read ahead, never used)
-    BA_TRY(ctx->get_scratch(SL_GC_META, (size_t)GT * GC_NCONS * (smax + 1) * GR_DLINE * sizeof(uint32_t) + 256, &p));
-    ta.dtab = (uint32_t *)p;
+    BA_TRY(ctx->get_scratch(SL_GC_META, (size_t)GT * GC_NCONS * (smax + 1) * GR_DLINE * sizeof(uint32_t) + 256, &raw));
+    ta.dtab = (uint32_t *)raw;
     {
         ScopedTimer tm(ctx, "grouptables");
         const int W = (int)((L.S + 1 + 31) / 32);
@@ -1270,19 +1271,17 @@ int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *ro
     for (int v = 0; v < k.nvar; v++) a.G[v] = k.libs[v]->g;
     a.nvar = k.nvar; a.ucap = cap;
     a.ntile = (int)((L.N + 63) / 64);
-    a.mode = k.mode;
+    a.mode = mode;
     a.C = k.C; a.T = L.T; a.P = L.P; a.N = L.N; a.DS = DS;
     a.Ttab = Ttab; a.rows_per_target = L.P * DS;
-    a.tslot = k.tslot;
+    a.tslot = ln.tslot;
     a.ngroups = ngroups; a.smax = smax;
     a.nv = passes ? nv : nullptr;
     a.ovf = passes ? ovf : nullptr;
     a.wtab = ta.wtab; a.ltab = ta.ltab; a.order = oa.order; a.dtab = ta.dtab;
     a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
-    if (k.mode == GF_RESID_SCALAR || k.mode == GF_RESID_BAND1) {
-        BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
-    }
-    if (k.mode == GF_RESID_BAND1) {
+    if (mode == GF_RESID_SCALAR || mode == GF_RESID_BAND1) BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
+    if (mode == GF_RESID_BAND1) {
         BA_CHECK(k.band_w && k.quad && k.data, BEATAMD_EINVAL, "gfstack: mode 3 needs band_w, quad, data");
         BA_TRY(ctx->scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2, &a.edges));
         a.band_w = k.band_w;
@@ -1297,18 +1296,13 @@ int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *ro
     const size_t ring = std::max<size_t>((size_t)3 * cap * 512, (size_t)GC_NCONS * 16 * GC_TPITCH + (size_t)GC_NCONS * 1024);
     const size_t lds = GC_PARAM_BYTES + ring;
     BA_CHECK(lds <= 160 * 1024, BEATAMD_EINVAL, "internal: k_gfstack_runs row buffers exceed LDS");
-    snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_runs<%d,%d>", k.mode, nth);
+    snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_runs<%d,%d>", mode, nth);
     snprintf(ctx->gf_plan, sizeof(ctx->gf_plan),
              "runs kernel: 518-chain groups, multilinear; %d row slots per LDS buffer (a patch has D*(S+1) = %lld dense slots), %s",
              cap, (long long)dense,
              passes ? "patches that touch more are staged in passes along the duration axis (tables sized for 6 passes per patch; "
                       "beyond that the streaming kernel takes the batch)" : "one pass per patch");
-    ctx->gs_ngtp = GTP;
-    ctx->gs_trep = (double)L.T / (double)Ttab;
-    ctx->gs_N = L.N;
-    ctx->gs_cg = GC_CG;
-    ctx->gs_nvar = k.nvar;
-    ctx->gs_has_passes = passes;
+    gs_record_stats(ctx, k, GTP, Ttab, GC_CG, passes);
     {
         ScopedTimer tm(ctx, "gfstack");
         void (*kern)(GcArgs) = nth ? k_gfstack_runs<1, 0> : k_gfstack_runs<0, 0>;

@@ -1509,7 +1509,6 @@ constexpr int WS_LW = 4;          // loader wavefronts
 constexpr int WS_USTRIDE = 128;   // list entries per vstep in the row-request table (cap <= 96)
 constexpr int WS_CAP_MAX = 96;    // three buffers of 96 + 1 slots x 520 B = 151 KB of the CU's 160 KB
 constexpr int WS_MAXPASS = (WS_CG + WS_CAP_MAX - 1) / WS_CAP_MAX;
-static bool ws_wanted(const GfStackCall &k, int CG);
 
 struct WsTabArgs {
     int nvar, cap;
@@ -1783,12 +1782,11 @@ static int pick_group(int64_t C)
 
 // the distinct-row bound of chain groups of `cg`, or false when their row buffers or the table
 // kernel's maps do not fit LDS (row_passes: the loader / consumer kernel takes any library)
-static bool shared_fit(const GfStackCall &k, int cg, bool row_passes, int *ucap_out)
+static bool shared_fit(const GfStackCall &k, const GfPlan &p, int cg, bool row_passes, int *ucap_out)
 {
     const SeisLib &L = *k.libs[0];
-    const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
     const int64_t DS = L.D * L.S;
-    const int64_t ucap = std::min<int64_t>((int64_t)cg * nrow, DS);
+    const int64_t ucap = std::min<int64_t>((int64_t)cg * p.nrow, DS);
     if (!row_passes) {
         if (2 * ucap * (GS_NT_MAX + 2) * 8 > 158 * 1024) return false;   // two row buffers of the bound
         if (2 * DS * 4 + cg * 4 + 2048 > 60 * 1024) return false;         // presence map + group masks of k_gf_group_tables
@@ -1797,15 +1795,51 @@ static bool shared_fit(const GfStackCall &k, int cg, bool row_passes, int *ucap_
     return true;
 }
 
-// group sizes worth timing for this call (gfstack.hip tunes the choice once per problem shape)
-int gfstack_shared_candidates(const GfStackCall &k, int *cgs, int *ucaps)
+// the kernel of a group size and what it is asked for.  Mode 3: of the kernels launched here k_gfstack_ws on float64 rows
+// has the bidiagonal epilogue (not its pair-gather twin); every other one stores the residuals and launch_gfstack runs
+// k_quadform_band1 behind it
+GfGroup gfstack_group(const GfPlan &p, int cg, int ucap)
 {
-    int n = 0;
+    GfGroup g;
+    g.cg = cg; g.ucap = ucap;
+    g.ws = p.ws512 && cg == WS_CG;
+    g.mode = p.mode;
+    if (p.mode == GF_RESID_BAND1) g.band1 = gf_band1(g.ws && !p.f32 && !p.pair64 && p.fused, GF_BY_WS, &g.mode);
+    return g;
+}
+
+bool gfstack_shared_plan(const GfStackCall &k, GfPlan &p)
+{
+    const SeisLib &L = *k.libs[0];
+    if (L.N % 2 != 0) return false;
+    const GfKnobs &kn = *p.knobs;
+    if (GfKnobs::is(kn.gf_kernel, 0)) return false;   // 0 = streaming kernel, 1 = shared kernel
+    if (!GfKnobs::is(kn.gf_kernel, 1) && k.C < 48) return false;  // too few chains to share rows
+    // 512-chain groups with one row per chain and patch: the loader / consumer kernel, whatever the library's
+    // (duration x start-time) grid (row passes, k_ws_tables)
+    p.ws512 = GfKnobs::get(kn.gs_ws, GS_WS_DEFAULT) != 0 && k.interp != BEATAMD_MULTILINEAR && L.N % 2 == 0 &&
+              !(GfKnobs::set(kn.gs_dma) && kn.gs_dma != 2) && !(GfKnobs::set(kn.gs_nt) && kn.gs_nt != 64);
+    int cg = pick_group(k.C);
+    const int gq = GfKnobs::get(kn.gs_cg, 0);
+    if (gq == 64 || gq == 128 || gq == 256 || gq == 512 || gq == 1024) cg = gq;
+    if (p.R > 1) {      // the loader / consumer kernel or none (the streaming kernel then)
+        if (!p.ws512) return false;
+        cg = WS_CG;
+    }
+    const bool ws = p.ws512 && cg == WS_CG;   // (of the size asked for: a 1024-chain request halved to 512 stays a small-group launch here)
+    // two row buffers of the group's distinct-row bound must fit LDS (prefer >= 2 workgroups per CU): halve the group
+    // until they do
+    while (!ws && std::min<int64_t>((int64_t)cg * p.nrow, L.D * L.S) * (GS_NT_MAX + 2) * 8 > 72 * 1024 && cg > 64) cg /= 2;
+    int ucap = 0;
+    if (!shared_fit(k, p, cg, ws, &ucap)) return false;
+    p.group = gfstack_group(p, cg, ucap);
+    // group sizes worth timing for this call (tune_group_size, gfstack.hip, measures once per problem shape)
+    p.tune = !GfKnobs::set(kn.gs_cg) && !GfKnobs::is(kn.gs_tune, 0);
     const int cand[4] = {512, 256, 128, 64};
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < 4 && p.tune; i++) {
         // patch split (small-N libraries): the loader / consumer kernel only (the small-group kernels index their
         // weight tables by the real patch)
-        if (k.patch_split > 1 && cand[i] != 512) continue;
+        if (p.R > 1 && cand[i] != 512) continue;
         // a group size that would leave more than half of its lanes without a chain only pads
         if (cand[i] > 64 && (int64_t)cand[i] / 2 >= k.C) continue;
         // large batches: small groups stage every distinct row many times over and have never been the fastest
@@ -1814,64 +1848,26 @@ int gfstack_shared_candidates(const GfStackCall &k, int *cgs, int *ucaps)
         if (k.C >= 1024 && cand[i] < 256) continue;
         if (k.C >= 384 && cand[i] < 128) continue;
         int u = 0;
-        if (shared_fit(k, cand[i], ws_wanted(k, cand[i]), &u)) { cgs[n] = cand[i]; ucaps[n] = u; n++; }
+        if (shared_fit(k, p, cand[i], p.ws512 && cand[i] == WS_CG, &u)) p.cand[p.ncand++] = gfstack_group(p, cand[i], u);
     }
-    return n;
-}
-
-bool gfstack_shared_applicable(const GfStackCall &k, int *cg_out, int *ucap_out)
-{
-    const SeisLib &L = *k.libs[0];
-    const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
-    if (L.N % 2 != 0) return false;
-    const GfKnobs &kn = *k.knobs;
-    if (GfKnobs::is(kn.gf_kernel, 0)) return false;   // 0 = streaming kernel, 1 = shared kernel
-    const bool forced = GfKnobs::is(kn.gf_kernel, 1);
-    if (!forced && k.C < 48) return false;  // too few chains to share rows
-    int cg = pick_group(k.C);
-    const int gq = GfKnobs::get(kn.gs_cg, 0);
-    if (gq == 64 || gq == 128 || gq == 256 || gq == 512 || gq == 1024) cg = gq;
-    if (k.patch_split > 1) {      // the loader / consumer kernel or none (the streaming kernel then)
-        if (!ws_wanted(k, WS_CG)) return false;
-        cg = WS_CG;
-    }
-    const bool ws = ws_wanted(k, cg);   // (of the size asked for: a 1024-chain request halved to 512 stays a small-group launch here)
-    // two row buffers of the group's distinct-row bound must fit LDS (prefer >= 2 workgroups per CU): halve the group
-    // until they do
-    while (!ws && std::min<int64_t>((int64_t)cg * nrow, L.D * L.S) * (GS_NT_MAX + 2) * 8 > 72 * 1024 && cg > 64) cg /= 2;
-    if (!shared_fit(k, cg, ws, ucap_out)) return false;
-    *cg_out = cg;
     return true;
 }
 
-// 512-chain groups with one row per chain and patch: the loader / consumer kernel, whatever the library's
-// (duration x start-time) grid (row passes, k_ws_tables)
-static bool ws_wanted(const GfStackCall &k, int CG)
-{
-    const GfKnobs &kn = *k.knobs;
-    const bool want = GfKnobs::get(kn.gs_ws, GS_WS_DEFAULT) != 0;
-    return want && CG == WS_CG && k.interp != BEATAMD_MULTILINEAR && k.libs[0]->N % 2 == 0 &&
-           !(GfKnobs::set(kn.gs_dma) && kn.gs_dma != 2) && !(GfKnobs::set(kn.gs_nt) && kn.gs_nt != 64);
-}
-
 // ---- what launch_gfstack_ws and launch_gfstack_shared do the same way
-// the kernel arguments that do not depend on the kernel chosen; *f32: the call asks for the float copies and every
-// library has one
-static void gs_common_args(GsArgs &a, const GfStackCall &k, int64_t Ttab, int64_t ngroups, bool *f32)
+// the kernel arguments that do not depend on the kernel chosen
+static void gs_common_args(GsArgs &a, const GfStackCall &k, const GfPlan &p, const GfLaunch &ln, int64_t ngroups)
 {
-    const GfKnobs &kn = *k.knobs;
+    const GfKnobs &kn = *p.knobs;
     const SeisLib &L = *k.libs[0];
     memset(&a, 0, sizeof(a));
-    *f32 = k.f32;
     for (int v = 0; v < k.nvar; v++) {
         a.G[v] = k.libs[v]->g;
         a.G32[v] = k.libs[v]->g32;
-        *f32 = *f32 && a.G32[v] != nullptr;
     }
     a.nvar = k.nvar;
     a.C = k.C; a.T = L.T; a.P = L.P; a.N = L.N;
-    a.Ttab = Ttab; a.rows_per_target = L.P * L.D * L.S;
-    a.tslot = k.tslot;
+    a.Ttab = p.Ttab; a.rows_per_target = L.P * L.D * L.S;
+    a.tslot = ln.tslot;
     a.ngroups = ngroups;
     a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     a.nthint = GfKnobs::set(kn.gs_nthint) ? (kn.gs_nthint != 0) : (GS_NTHINT_DEFAULT && ngroups == 1);
@@ -1886,8 +1882,7 @@ static int64_t gs_grid(GsArgs &a, const GfKnobs &kn)
     return a.xcd_order ? ((a.T * a.ntile + 7) / 8) * 8 * a.ngroups : a.ngroups * a.T * a.ntile;
 }
 
-// what beatamd_ctx_gf_group_stats reports of the launch
-static void gs_record_stats(beatamd_ctx *ctx, const GfStackCall &k, int64_t GTP, int64_t Ttab, int cg, bool has_passes)
+void gs_record_stats(beatamd_ctx *ctx, const GfStackCall &k, int64_t GTP, int64_t Ttab, int cg, bool has_passes)
 {
     ctx->gs_ngtp = GTP;
     ctx->gs_trep = (double)k.libs[0]->T / (double)Ttab;
@@ -1897,10 +1892,12 @@ static void gs_record_stats(beatamd_ctx *ctx, const GfStackCall &k, int64_t GTP,
     ctx->gs_has_passes = has_passes;
 }
 
-static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint32_t *rowoff, int64_t Ttab)
+static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &p, const GfLaunch &ln, const GfGroup &g)
 {
-    const GfKnobs &kn = *k.knobs;
+    const GfKnobs &kn = *p.knobs;
     const SeisLib &L = *k.libs[0];
+    const int64_t Ttab = p.Ttab;
+    const int mode = g.mode;
     const int64_t ngroups = (k.C + WS_CG - 1) / WS_CG;
     const int64_t GT = ngroups * Ttab, GTP = GT * L.P;
     // row slots of an LDS buffer: what a patch can touch at most, in whole bank windows, up to the 96 that three
@@ -1914,9 +1911,9 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     memset(&ta, 0, sizeof(ta));
     ta.nvar = k.nvar; ta.cap = cap;
     ta.C = k.C; ta.T = Ttab; ta.P = L.P; ta.DS = L.D * L.S; ta.vmax = vmax;
-    ta.rowoff = rowoff;
+    ta.rowoff = ln.rowoff;
     for (int v = 0; v < k.nvar; v++) ta.slips[v] = k.slips[v];
-    ta.R = k.patch_split;
+    ta.R = p.R;
     // several groups: cut the batch into its groups by bisection along the order keys (the fused model path hands the
     // hypocentre): a compact piece of the fault per group = fewer distinct rows to stage per group and patch.  Scheduling only.
     if (ngroups > 1 && k.order_key[0].base && k.order_key[1].base && GfKnobs::get(kn.gc_global, 1) != 0)
@@ -1954,9 +1951,8 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     BA_HIP(hipGetLastError());
 
     GsArgs a;
-    bool f32;   // float copies: the pair gather of k_gfstack_wsp<1>
-    gs_common_args(a, k, Ttab, ngroups, &f32);
-    const bool pair64 = GfKnobs::is(kn.gs_pair, 1);   // A/B: ds_read_b128 pairs
+    const bool f32 = p.f32, pair64 = p.pair64;   // float copies: the pair gather of k_gfstack_wsp<1>; A/B: ds_read_b128 pairs
+    gs_common_args(a, k, p, ln, ngroups);
     a.nrow = 1;
     a.CG = WS_CG; a.ucap = cap; a.ustride = WS_USTRIDE;
     a.nt = 64; a.dma = 2; a.ws = 3;
@@ -1966,10 +1962,8 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     a.order = ta.order;
     a.uent = ta.uent; a.ucount = ta.ucount; a.slot = ta.slot; a.w = ta.w;
     a.w_var_stride = ta.w_var_stride;
-    if (k.mode == GF_RESID_SCALAR || k.mode == GF_RESID_BAND1) {
-        BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
-    }
-    if (k.mode == GF_RESID_BAND1) {
+    if (mode == GF_RESID_SCALAR || mode == GF_RESID_BAND1) BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
+    if (mode == GF_RESID_BAND1) {
         BA_TRY(ctx->scratch(SL_EDGES, (size_t)k.C * L.T * a.ntile * 2, &a.edges));
         a.band_w = k.band_w;
     }
@@ -1981,10 +1975,10 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     lds = std::max<size_t>(lds, (64 + 8 * 64 * 17) * sizeof(double));   // the epilogue's data tile + the residual-store tiles of the 8 consumers
     BA_CHECK(lds <= 160 * 1024, BEATAMD_EINVAL, "internal: k_gfstack_ws row buffers exceed LDS");
     if (f32 || pair64)
-        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_ws%s<%d,%d,%d>", f32 ? "32" : "p64", k.mode, a.ws,
+        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_ws%s<%d,%d,%d>", f32 ? "32" : "p64", mode, a.ws,
                  a.nthint);
     else
-        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_ws<%d,%d,%d,%d>", 1, k.mode, a.ws, a.nthint);
+        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_ws<%d,%d,%d,%d>", 1, mode, a.ws, a.nthint);
     snprintf(ctx->gf_plan, sizeof(ctx->gf_plan),
              "loader/consumer kernel: 512-chain groups, nearest neighbour; %d row slots per LDS buffer (a patch can touch min(512, "
              "D*S = %lld) rows), %s", cap, (long long)(L.D * L.S),
@@ -1992,7 +1986,7 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     gs_record_stats(ctx, k, GTP, Ttab, WS_CG, maxpass > 1);
     {
         ScopedTimer tm(ctx, "gfstack");
-        BA_TRY(launch_ws(k.mode, dim3((unsigned)nblocks), lds, ctx->stream, a, f32 ? 1 : (pair64 ? 2 : 0)));
+        BA_TRY(launch_ws(mode, dim3((unsigned)nblocks), lds, ctx->stream, a, f32 ? 1 : (pair64 ? 2 : 0)));
     }
     BA_HIP(hipGetLastError());
     if (a.partial)   // (modes 1 and 3; mode 3 has edges)
@@ -2000,23 +1994,61 @@ static int launch_gfstack_ws(beatamd_ctx *ctx, const GfStackCall &k, const uint3
     return BEATAMD_OK;
 }
 
-int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint32_t *rowoff,
-                          const double *fac, int CG, int ucap, int64_t Ttab, bool *band1_done)
+// one launch of the small-group kernel with row buffers of `ucap` slots: twin 0 alone and unguarded, 1 the fitted twin
+// (guarded by "count <= slots"), 2 the full-size twin behind it (guarded by the opposite).  a: the arguments both twins
+// share; nt / ntile as launched go back into it (the same for both twins)
+static int launch_dma_twin(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &p, const GfGroup &g, GsArgs &shared, int twin,
+                           int ucap, bool windowed, int64_t GTP)
 {
-    GfStackCall k = k_in;
-    if (k.mode == GF_RESID_BAND1) {
-        // of the kernels launched here k_gfstack_ws on float64 rows has the bidiagonal epilogue (not its pair-gather twin);
-        // every other one stores the residuals and launch_gfstack runs k_quadform_band1 behind it
-        bool f32 = k.f32;
-        for (int v = 0; v < k.nvar; v++) f32 = f32 && k.libs[v]->g32 != nullptr;
-        const bool ws64 = ws_wanted(k, CG) && !f32 && !GfKnobs::is(k.knobs->gs_pair, 1);
-        *band1_done = gf_carries_band1(*k.knobs, ws64 ? GF_BY_WS : GF_BY_OTHER);
-        if (!*band1_done) k.mode = GF_RESID_STORE;
-    }
-    if (ws_wanted(k, CG)) return launch_gfstack_ws(ctx, k, rowoff, Ttab);
-    const GfKnobs &kn = *k.knobs;
     const SeisLib &L = *k.libs[0];
-    const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
+    const int nrow = p.nrow, CG = g.cg, mode = g.mode;
+    GsArgs a = shared;
+    a.ucap = ucap;
+    a.guard_mode = twin;
+    size_t lds = (size_t)ucap * (a.nt + 2) * sizeof(double);
+    // two row buffers (the candidates were chosen so that they fit); BEATAMD_GS_DMA=1: the ds_read_b128 layout (A/B)
+    BA_CHECK(2 * lds <= 158 * 1024, BEATAMD_EINVAL, "internal: k_gfstack_dma row buffers exceed LDS");
+    a.dma = GfKnobs::is(p.knobs->gs_dma, 1) ? 1 : 2;   // 2: ds_read_b64 / pitch NT+1 (default); 1: b128 / pitch NT+2
+    if (a.nt == 32 && a.dma != 2) { a.nt = 64; a.ntile = (int)((L.N + 63) / 64); lds = (size_t)ucap * (a.nt + 2) * sizeof(double); }
+    BA_CHECK(CG != 1024 || a.dma == 2, BEATAMD_EINVAL, "gfstack: 1024-chain groups need the LDS-DMA kernel");
+    BA_CHECK(!windowed || a.dma == 2, BEATAMD_EINVAL, "internal: window slots need the ds_read_b64 kernel");
+    a.ws = 0;
+    a.f32pair = 0;
+    if (a.dma == 2 && a.nt == 64 && CG <= 512 && p.f32) {   // float copies: k_gfstack_dmaf (64-sample tiles, groups up to 512 chains)
+        a.f32pair = 1;
+        lds = std::max<size_t>((size_t)ucap * (a.nt + 2) * sizeof(float) * 2, 64 * sizeof(double));
+    } else {
+        lds *= 2;
+    }
+    const dim3 grid((unsigned)gs_grid(a, *p.knobs));
+    if (a.f32pair)
+        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_dmaf<%d,%d,%d>", CG / 64, nrow, mode);
+    else
+        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "%s<%d,%d,%d,%d,%d>",
+                 "k_gfstack_dma", CG / 64, nrow, mode, a.nt, a.dma == 2 ? 1 : 0);
+    gs_record_stats(ctx, k, GTP, p.Ttab, CG, false);
+    snprintf(ctx->gf_plan, sizeof(ctx->gf_plan),
+             "lane <-> chain kernel with %d-chain groups (%s): row buffers of %d slots%s", CG,
+             k.C < 384 ? "small batch" : nrow == 4 ? "multilinear below 192 chains or an odd sample count" : "group size measured fastest",
+             ucap, twin ? " sized by the previous launch's distinct-row count" : "");
+    if (CG == 1024) BA_TRY(launch_shared_nrow<16>(nrow, mode, grid, lds, ctx->stream, a));
+    else if (CG == 512) BA_TRY(launch_shared_nrow<8>(nrow, mode, grid, lds, ctx->stream, a));
+    else if (CG == 256) BA_TRY(launch_shared_nrow<4>(nrow, mode, grid, lds, ctx->stream, a));
+    else if (CG == 128) BA_TRY(launch_shared_nrow<2>(nrow, mode, grid, lds, ctx->stream, a));
+    else BA_TRY(launch_shared_nrow<1>(nrow, mode, grid, lds, ctx->stream, a));
+    BA_HIP(hipGetLastError());
+    shared.nt = a.nt; shared.ntile = a.ntile;
+    return BEATAMD_OK;
+}
+
+int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &p, const GfLaunch &ln, const GfGroup &g)
+{
+    if (g.ws) return launch_gfstack_ws(ctx, k, p, ln, g);
+    const GfKnobs &kn = *p.knobs;
+    const SeisLib &L = *k.libs[0];
+    const int nrow = p.nrow, CG = g.cg, mode = g.mode;
+    int ucap = g.ucap;
+    const int64_t Ttab = p.Ttab;
     const int64_t ngroups = (k.C + CG - 1) / CG;
     const int64_t GTP = ngroups * Ttab * L.P;
 
@@ -2024,7 +2056,7 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     memset(&ga, 0, sizeof(ga));
     ga.nrow = nrow; ga.nvar = k.nvar; ga.CG = CG;
     ga.C = k.C; ga.T = Ttab; ga.P = L.P; ga.DS = L.D * L.S;
-    ga.rowoff = rowoff; ga.fac = fac;
+    ga.rowoff = ln.rowoff; ga.fac = ln.fac;
     for (int v = 0; v < k.nvar; v++) ga.slips[v] = k.slips[v];
     ga.ucap = ucap;
     ga.ustride = (ucap + 63) / 64 * 64;   // covers the unclamped first-pass ids of 8 waves
@@ -2036,7 +2068,6 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     ga.w_var_stride = (nrow == 1) ? ngroups * L.P * CG : GTP * 4 * CG;
     BA_TRY(ctx->scratch(SL_GS_W, (size_t)ga.w_var_stride * k.nvar + (size_t)3 * 4 * CG, &ga.w));
     const bool fit_lds = CG <= 128 && !GfKnobs::is(kn.gs_fit, 0);
-    ga.umax = nullptr;
     if (fit_lds) {
         BA_TRY(ctx->scratch(SL_GS_UMAX, 1, &ga.umax));
         BA_HIP(hipMemsetAsync(ga.umax, 0, sizeof(uint32_t), ctx->stream));
@@ -2065,21 +2096,14 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
     BA_HIP(hipGetLastError());
 
     GsArgs a;
-    bool f32;   // float copies: k_gfstack_dmaf (LDS-DMA kernel, 64-sample tiles, groups up to 512 chains)
-    gs_common_args(a, k, Ttab, ngroups, &f32);
+    gs_common_args(a, k, p, ln, ngroups);
     a.nrow = nrow;
     a.CG = CG; a.ucap = ucap; a.ustride = ga.ustride;
-    a.nt = 64;
-    {
-        if (GfKnobs::is(kn.gs_nt, 32)) a.nt = 32;
-        if (CG == 1024) a.nt = 32;
-    }
+    a.nt = GfKnobs::is(kn.gs_nt, 32) || CG == 1024 ? 32 : 64;
     a.ntile = (int)((L.N + a.nt - 1) / a.nt);
     a.urows = ga.urows; a.uent = ga.uent; a.ucount = ga.ucount; a.slot = ga.slot; a.w = ga.w;
     a.w_var_stride = ga.w_var_stride;
-    if (k.mode == GF_RESID_SCALAR) {
-        BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
-    }
+    if (mode == GF_RESID_SCALAR) BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     BA_CHECK(ngroups * L.T * a.ntile < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");
     // Small chain groups (1-2 wavefronts per workgroup) reach the 2 waves/SIMD the kernels are
     // built for only if several workgroups fit a CU's LDS: their row buffers are sized by the
@@ -2114,56 +2138,12 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k_in, const uint3
         }
     }
     // (fitted twin first, then the full-size twin; a single unguarded launch otherwise)
-    const int full_ucap = ucap;
-    const int nt0 = a.nt, ntile0 = a.ntile;
-    ScopedTimer tm(ctx, "gfstack");   // (both twins: one timing)
-    for (int twin = (ucap_fit ? 1 : 0); twin <= (ucap_fit ? 2 : 0); twin++) {
-    ucap = (twin == 1) ? ucap_fit : full_ucap;
-    a.nt = nt0; a.ntile = ntile0;
-    a.ucap = ucap;
-    a.guard_mode = twin;
     a.guard_fit = ucap_fit;
     a.guard_umax = ga.umax;
-    size_t lds = (size_t)ucap * (a.nt + 2) * sizeof(double);
-    {
-        // two row buffers (the candidates were chosen so that they fit); BEATAMD_GS_DMA=1: the ds_read_b128 layout (A/B)
-        BA_CHECK(2 * lds <= 158 * 1024, BEATAMD_EINVAL, "internal: k_gfstack_dma row buffers exceed LDS");
-        a.dma = GfKnobs::is(kn.gs_dma, 1) ? 1 : 2;   // 2: ds_read_b64 / pitch NT+1 (default); 1: b128 / pitch NT+2
-        if (a.nt == 32 && a.dma != 2) { a.nt = 64; a.ntile = (int)((L.N + 63) / 64); lds = (size_t)ucap * (a.nt + 2) * sizeof(double); }
-        BA_CHECK(CG != 1024 || a.dma == 2, BEATAMD_EINVAL, "gfstack: 1024-chain groups need the LDS-DMA kernel");
-        BA_CHECK(!ga.windowed || a.dma == 2, BEATAMD_EINVAL, "internal: window slots need the ds_read_b64 kernel");
-        a.ws = 0;
-        a.f32pair = 0;
-        if (a.dma == 2 && a.nt == 64 && CG <= 512 && f32) {
-            a.f32pair = 1;
-            lds = std::max<size_t>((size_t)ucap * (a.nt + 2) * sizeof(float) * 2, 64 * sizeof(double));
-        } else {
-            lds *= 2;
-        }
-    }
-    const int64_t nblocks = gs_grid(a, kn);
-    if (a.f32pair)
-        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack_dmaf<%d,%d,%d>", CG / 64, nrow, k.mode);
-    else
-        snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "%s<%d,%d,%d,%d,%d>",
-                 "k_gfstack_dma", CG / 64, nrow, k.mode, a.nt, a.dma == 2 ? 1 : 0);
-    gs_record_stats(ctx, k, GTP, Ttab, CG, false);
-    snprintf(ctx->gf_plan, sizeof(ctx->gf_plan),
-             "lane <-> chain kernel with %d-chain groups (%s): row buffers of %d slots%s", CG,
-             k.C < 384 ? "small batch" : nrow == 4 ? "multilinear below 192 chains or an odd sample count" : "group size measured fastest",
-             ucap, twin ? " sized by the previous launch's distinct-row count" : "");
-    {
-        dim3 grid((unsigned)nblocks);
-        if (CG == 1024) BA_TRY(launch_shared_nrow<16>(nrow, k.mode, grid, lds, ctx->stream, a));
-        else if (CG == 512) BA_TRY(launch_shared_nrow<8>(nrow, k.mode, grid, lds, ctx->stream, a));
-        else if (CG == 256) BA_TRY(launch_shared_nrow<4>(nrow, k.mode, grid, lds, ctx->stream, a));
-        else if (CG == 128) BA_TRY(launch_shared_nrow<2>(nrow, k.mode, grid, lds, ctx->stream, a));
-        else BA_TRY(launch_shared_nrow<1>(nrow, k.mode, grid, lds, ctx->stream, a));
-    }
-    BA_HIP(hipGetLastError());
-    }
-    BA_HIP(hipGetLastError());
-    if (k.mode == GF_RESID_SCALAR) BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad));
+    ScopedTimer tm(ctx, "gfstack");   // (both twins: one timing)
+    if (ucap_fit) BA_TRY(launch_dma_twin(ctx, k, p, g, a, 1, ucap_fit, ga.windowed, GTP));
+    BA_TRY(launch_dma_twin(ctx, k, p, g, a, ucap_fit ? 2 : 0, ucap, ga.windowed, GTP));
+    if (mode == GF_RESID_SCALAR) BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad));
     return BEATAMD_OK;
 }
 

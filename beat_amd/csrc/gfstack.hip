@@ -379,7 +379,7 @@ static void launch_nvar(int nvar, int mode, dim3 grid, hipStream_t s, const GfAr
     else launch_mode<INTERP, 3, VEC, W>(mode, grid, s, a);
 }
 
-static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, bool *band1_done);
+static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, const GfPlan &p, GfLaunch &ln);
 
 // ---- patch split of small-N libraries --------------------------------------------------------------------------------
 // A (target, 64-sample tile) walk over P patches is a SERIAL path of P (x slip variables) steps per workgroup; a library
@@ -412,14 +412,6 @@ int gf_patch_ranges(int64_t T, int64_t P, int64_t N, int num_cu)
         if (cost < best_cost) { best = d; best_cost = cost; }
     }
     return best;
-}
-
-static int gf_patch_split(const SeisLib &L, const GfKnobs &kn, int num_cu)
-{
-    const int knob = GfKnobs::get(kn.gf_split, -1);
-    if (knob == 0 || knob == 1) return 1;
-    if (knob > 1) return (L.P % knob == 0 && L.N <= 256) ? knob : 1;
-    return gf_patch_ranges(L.split_T > 0 ? L.split_T : L.T, L.P, L.N, num_cu);
 }
 
 __global__ void __launch_bounds__(256) k_split_tslot(int64_t Tv, int R, const int32_t *tslot, int32_t *out)
@@ -482,38 +474,133 @@ __global__ void __launch_bounds__(256) k_split_combine(const double *part, int64
     }
 }
 
-static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R, bool *band1_done)
+// ---- the plan of a stacking call (kernels.hpp): the one place where the selection lives ----------------------------------
+GfPlan gf_plan_call(const GfStackCall &k, const GfKnobs &kn, int num_cu)
+{
+    GfPlan p;
+    const SeisLib &L = *k.libs[0];
+    p.knobs = &kn;
+    const int split = GfKnobs::get(kn.gf_split, -1);
+    p.R = split == 0 || split == 1 ? 1 : split > 1 ? ((L.P % split == 0 && L.N <= 256) ? split : 1)
+                                   : gf_patch_ranges(L.split_T > 0 ? L.split_T : L.T, L.P, L.N, num_cu);
+    p.T = L.T * p.R; p.P = L.P / p.R;
+    // Without explicit start times and without station shifts the start-time and duration indices of a chain are the same
+    // for every target (seismic.py:1283-1296 tiles starttimes0 over the targets): the tables are then built once per
+    // (chain, patch) instead of T times.
+    p.tinv = !k.st.explicit_st && !k.st.shift_off && !GfKnobs::is(kn.gf_tinv, 0);
+    // ... and with station corrections only on the station: one table slot per distinct shift variable (the channels of
+    // a station share it)
+    p.slots = !k.st.explicit_st && k.st.shift_off && k.st.nslot > 0 && !GfKnobs::is(kn.gf_tinv, 0);
+    // patch split: every table slot once per patch range -- R slots without station shifts, nslot * R with them; virtual
+    // target t*R + r uses slot (slot of t)*R + r
+    p.Ttab = p.tinv ? p.R : p.slots ? (int64_t)k.st.nslot * p.R : p.T;
+    p.nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
+    // float storage requested and every library has its float copy: the lane <-> chain kernels read it (the
+    // cell kernel works on the float64 rows)
+    p.f32 = k.f32;
+    for (int v = 0; v < k.nvar; v++) p.f32 = p.f32 && k.libs[v]->g32 != nullptr;
+    p.pair64 = GfKnobs::is(kn.gs_pair, 1);
+    p.fused = !GfKnobs::is(kn.qf_fuse, 0);
+    // patch ranges: the stackers store the ranges' partial synthetics, k_split_combine carries the epilogue (mode 3 without
+    // it, BEATAMD_QF_FUSE=0: the residuals, k_quadform_band1 behind them)
+    p.mode = p.R > 1 ? (int)GF_STORE_SYN : k.mode;
+    p.mode_combine = k.mode;
+    if (p.R > 1 && k.mode == GF_RESID_BAND1) p.band1 = gf_band1(p.fused, GF_BY_COMBINE, &p.mode_combine);
+    // multilinear from 192 chains on: the runs kernel (gfcell.hip).  When its tables can overflow (more row passes than they
+    // are sized for) the streaming kernel is enqueued behind it as a stand-in that works only if they did.
+    // (mode 3: the chain-shared stackers and the runs kernel may carry the epilogue, the streaming kernel stores the
+    // residuals; as the runs kernel's stand-in it is followed by a guarded k_quadform_band1)
+    const bool band1 = p.mode == GF_RESID_BAND1;
+    p.mode_standin = band1 ? (int)GF_RESID_STORE : p.mode;
+    if (!p.f32 && gfstack_ml_applicable(k, p)) {
+        p.stacker = GF_RUNS;
+        p.standin_band1 = band1 && p.fused;
+        if (band1) p.band1 = gf_band1(p.fused, GF_BY_RUNS, &p.mode);
+    } else if (gfstack_shared_plan(k, p)) {
+        p.stacker = GF_GROUPS;   // (mode and mode 3 per group size: gfstack_group)
+    } else if (band1) {
+        p.band1 = gf_band1(false, GF_BY_NONE, &p.mode);   // (the streaming kernel has no bidiagonal epilogue)
+    }
+    return p;
+}
+
+// Chains per workgroup: which size is fastest depends on the library (distinct rows a group can share, D*S), the batch
+// and the population, so it is MEASURED once per problem shape -- every candidate is launched on the real inputs (the
+// kernels are bitwise equal for every group size, the outputs are simply rewritten) and the fastest is kept.
+// BEATAMD_GS_CG fixes the size, BEATAMD_GS_TUNE=0 uses the static table of pick_group (measured on config 3).
+static int tune_group_size(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &p, const GfLaunch &ln, GfGroup *out)
+{
+    const SeisLib &L = *k.libs[0];
+    // (key: the batch in whole 512-chain groups, capped -- 4096 and 4100 chains choose alike --; the epilogue
+    // mode costs every group size the same and is not part of it)
+    const int64_t cbucket = k.C < 512 ? k.C : 512 * std::min<int64_t>((k.C + 511) / 512, 16);
+    const std::vector<int64_t> key = {cbucket, p.nrow, k.nvar, L.T, L.P, L.D, L.S, L.N, p.Ttab, p.f32 ? 1 : 0};
+    auto it = ctx->gs_tuned.find(key);
+    if (it == ctx->gs_tuned.end()) {
+        const int nc = p.ncand;
+        int best = -1;
+        float best_ms = 0.f, ms_of[4] = {0.f, 0.f, 0.f, 0.f};
+        hipEvent_t e0, e1;
+        BA_HIP(hipEventCreate(&e0)); BA_HIP(hipEventCreate(&e1));
+        for (int i = 0; i < nc && nc > 1; i++) {
+            float ms_min = 0.f;
+            for (int rep = 0; rep < 2; rep++) {   // first launch of a size: warm-up (code, tables' scratch)
+                BA_HIP(hipEventRecord(e0, ctx->stream));
+                BA_TRY(launch_gfstack_shared(ctx, k, p, ln, p.cand[i]));
+                BA_HIP(hipEventRecord(e1, ctx->stream));
+                BA_HIP(hipEventSynchronize(e1));
+                BA_HIP(hipEventElapsedTime(&ms_min, e0, e1));
+            }
+            ms_of[i] = ms_min;
+            if (best < 0 || ms_min < best_ms) { best = i; best_ms = ms_min; }
+            // a candidate twice as slow as the best so far: the smaller sizes behind it only stage more rows
+            if (ms_min > 2.f * best_ms) break;
+        }
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        if (nc == 1) best = 0;
+        if (best >= 0) it = ctx->gs_tuned.emplace(key, std::make_pair(p.cand[best].cg, p.cand[best].ucap)).first;
+        // what was measured, once per problem shape: beatamd_ctx_gf_tune_log (and stderr under BEATAMD_VERBOSE)
+        char *w = ctx->gf_tune_log; size_t left = sizeof(ctx->gf_tune_log);
+        int n = snprintf(w, left, "group size for %lld chains (T %lld, P %lld, D*S %lld, N %lld, %d row(s) per chain): ",
+                         (long long)k.C, (long long)L.T, (long long)L.P, (long long)(L.D * L.S), (long long)L.N, p.nrow);
+        for (int i = 0; i < nc && n > 0 && (size_t)n < left; i++) {
+            w += n; left -= (size_t)n;
+            n = ms_of[i] > 0.f ? snprintf(w, left, "%d: %.3f ms%s", p.cand[i].cg, ms_of[i], i + 1 < nc ? ", " : "")
+                               : snprintf(w, left, "%d: %s%s", p.cand[i].cg, nc == 1 ? "only candidate" : "not timed", i + 1 < nc ? ", " : "");
+        }
+        if (best >= 0 && n > 0 && (size_t)n < left) { w += n; left -= (size_t)n; snprintf(w, left, " -> %d", p.cand[best].cg); }
+        if (getenv("BEATAMD_VERBOSE")) fprintf(stderr, "beat_amd: %s\n", ctx->gf_tune_log);
+    }
+    *out = it != ctx->gs_tuned.end() ? gfstack_group(p, it->second.first, it->second.second) : p.group;
+    return BEATAMD_OK;
+}
+
+static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, const GfPlan &p, GfLaunch &ln)
 {
     const SeisLib &L = *call.libs[0];
+    const int R = p.R;
     SeisLib views[4];
     GfStackCall v = call;
     v.active = nullptr;   // (k_split_combine reads every chain's partial synthetics)
     for (int i = 0; i < call.nvar; i++) {
         views[i] = *call.libs[i];
-        views[i].T = L.T * R;
-        views[i].P = L.P / R;
+        views[i].T = p.T; views[i].P = p.P;
         v.libs[i] = &views[i];
     }
-    v.patch_split = R;
-    v.mode = GF_STORE_SYN;
     double *part;
     BA_TRY(ctx->scratch(SL_SPLIT, (size_t)call.C * L.T * R * L.N, &part));
     v.out = part;
     v.quad = nullptr; v.data = nullptr; v.wscalar = nullptr; v.band_w = nullptr;
-    BA_TRY(launch_gfstack_impl(ctx, v, band1_done));   // (mode 0: nothing to report yet)
-    {
-        // (kernel name / plan of the stacking launch stay; the plan says that the library was split)
-        const size_t n0 = strlen(ctx->gf_plan);
-        snprintf(ctx->gf_plan + n0, sizeof(ctx->gf_plan) - n0, "; %lld-sample traces: patches stacked in %d ranges of %lld "
-                 "(%lld walks instead of %lld), partial synthetics summed in range order", (long long)L.N, R, (long long)(L.P / R),
-                 (long long)(L.T * R * ((L.N + 63) / 64)), (long long)(L.T * ((L.N + 63) / 64)));
-    }
+    BA_TRY(launch_gfstack_impl(ctx, v, p, ln));
+    // (kernel name / plan of the stacking launch stay; the plan says that the library was split)
+    const size_t n0 = strlen(ctx->gf_plan);
+    snprintf(ctx->gf_plan + n0, sizeof(ctx->gf_plan) - n0, "; %lld-sample traces: patches stacked in %d ranges of %lld "
+             "(%lld walks instead of %lld), partial synthetics summed in range order", (long long)L.N, R, (long long)(L.P / R),
+             (long long)(L.T * R * ((L.N + 63) / 64)), (long long)(L.T * ((L.N + 63) / 64)));
     const dim3 grid((unsigned)(call.C * L.T));
     BA_CHECK(call.C * L.T < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large");
     ScopedTimer tm(ctx, "gfcombine");
-    // (mode 3 without the epilogue, BEATAMD_QF_FUSE=0: the residuals, launch_gfstack runs k_quadform_band1 behind them)
-    int mode = call.mode;
-    if (mode == GF_RESID_BAND1 && !(*band1_done = gf_carries_band1(gf_knobs(ctx), GF_BY_COMBINE))) mode = GF_RESID_STORE;
+    const int mode = p.mode_combine;
     const auto combine = mode == GF_STORE_SYN ? k_split_combine<GF_STORE_SYN> : mode == GF_RESID_SCALAR ? k_split_combine<GF_RESID_SCALAR>
                        : mode == GF_RESID_BAND1 ? k_split_combine<GF_RESID_BAND1> : k_split_combine<GF_RESID_STORE>;
     hipLaunchKernelGGL(combine, grid, dim3(256), 0, ctx->stream, part, call.C, L.T, L.N, R, call.data, call.wscalar, call.out,
@@ -522,169 +609,79 @@ static int launch_gfstack_split(beatamd_ctx *ctx, const GfStackCall &call, int R
     return BEATAMD_OK;
 }
 
+// plan -> (split view) -> tables -> stacker -> (mode-3 fallback)
 int launch_gfstack(beatamd_ctx *ctx, const GfStackCall &call)
 {
-    const int R = call.libs[0] ? gf_patch_split(*call.libs[0], gf_knobs(ctx), ctx->num_cu) : 1;
-    // mode 3 (bidiagonal whitening operator): evaluated by the kernel that stacks where it carries the epilogue
-    // (gf_carries_band1), else residual store + k_quadform_band1 -- the caller gets quad [C,T] either way
-    bool band1_done = false;
-    if (R > 1) {
-        BA_TRY(launch_gfstack_split(ctx, call, R, &band1_done));
+    const SeisLib &L = *call.libs[0];
+    BA_CHECK(call.nvar >= 1 && call.nvar <= 3, BEATAMD_EINVAL, "gfstack: 1..3 slip variables supported");
+    for (int v = 1; v < call.nvar; v++) {
+        const SeisLib &M = *call.libs[v];
+        BA_CHECK(M.T == L.T && M.P == L.P && M.D == L.D && M.S == L.S && M.N == L.N && M.st_min == L.st_min && M.st_dt == L.st_dt &&
+                     M.du_min == L.du_min && M.du_dt == L.du_dt,
+                 BEATAMD_EINVAL, "gfstack: libraries of the slip variables differ in shape/grid");
+    }
+    BA_CHECK(L.T * L.P * L.D * L.S < (int64_t)0xffffffffLL, BEATAMD_EINVAL, "gfstack: library has more than 2^32 rows");
+    const GfPlan p = gf_plan_call(call, gf_knobs(ctx), ctx->num_cu);
+    GfLaunch ln;
+    if (p.R > 1) {
+        BA_TRY(launch_gfstack_split(ctx, call, p, ln));
     } else {
         if (call.mode == GF_RESID_BAND1)
             BA_CHECK(call.band_w && call.quad && call.out && call.data, BEATAMD_EINVAL, "gfstack: mode 3 needs band_w, quad, out, data");
-        BA_TRY(launch_gfstack_impl(ctx, call, &band1_done));
+        BA_TRY(launch_gfstack_impl(ctx, call, p, ln));
     }
-    if (call.mode == GF_RESID_BAND1 && !band1_done) {
-        const SeisLib &L = *call.libs[0];
+    // mode 3 (bidiagonal whitening operator): evaluated by the kernel that stacks where it carries the epilogue, else
+    // residual store + k_quadform_band1 -- the caller gets quad [C,T] either way
+    if ((p.stacker == GF_GROUPS && p.R == 1 ? ln.group.band1 : p.band1) == GF_BY_QUADFORM)
         BA_TRY(launch_quadform_banded(ctx, call.band_w, 1, L.N, L.T, call.C, call.out, L.T * L.N, L.N, call.quad, L.T));
-    }
     return BEATAMD_OK;
 }
 
-static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, bool *band1_done)
+// tables -> stacker, of the library as it is stacked (k: the request, or its view in patch ranges)
+static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &p, GfLaunch &ln)
 {
-    GfStackCall k = call;
-    const GfKnobs &kn = gf_knobs(ctx);
-    k.knobs = &kn;
+    const GfKnobs &kn = *p.knobs;
     const SeisLib &L = *k.libs[0];
-    BA_CHECK(k.nvar >= 1 && k.nvar <= 3, BEATAMD_EINVAL, "gfstack: 1..3 slip variables supported");
-    for (int v = 1; v < k.nvar; v++) {
-        const SeisLib &M = *k.libs[v];
-        BA_CHECK(M.T == L.T && M.P == L.P && M.D == L.D && M.S == L.S && M.N == L.N &&
-                     M.st_min == L.st_min && M.st_dt == L.st_dt && M.du_min == L.du_min &&
-                     M.du_dt == L.du_dt,
-                 BEATAMD_EINVAL, "gfstack: libraries of the slip variables differ in shape/grid");
-    }
-    BA_CHECK(L.T * L.P * L.D * L.S < (int64_t)0xffffffffLL, BEATAMD_EINVAL,
-             "gfstack: library has more than 2^32 rows");
     if (k.C == 0) return BEATAMD_OK;
-    // Without explicit start times and without station shifts the start-time and duration
-    // indices of a chain are the same for every target (seismic.py:1283-1296 tiles starttimes0
-    // over the targets): the tables are then built once per (chain, patch) instead of T times.
-    const bool tinv = !k.st.explicit_st && !k.st.shift_off && !GfKnobs::is(kn.gf_tinv, 0);
-    // ... and with station corrections only on the station: one table slot per distinct shift variable (the channels of
-    // a station share it)
-    const bool slots = !k.st.explicit_st && k.st.shift_off && k.st.nslot > 0 && !GfKnobs::is(kn.gf_tinv, 0);
-    // patch split (L is the VIEW [T*R, P/R, ...]): every table slot once per patch range -- R slots without station
-    // shifts, nslot * R with them; virtual target t*R + r uses slot (slot of t)*R + r
-    const int64_t R = k.patch_split;
-    const int64_t Ttab = tinv ? R : slots ? (int64_t)k.st.nslot * R : L.T;
-    k.tslot = slots ? k.st.tslot : nullptr;
-    if (R > 1 && (tinv || slots)) {
+    const int64_t R = p.R, Ttab = p.Ttab;
+    ln.tslot = p.slots ? k.st.tslot : nullptr;
+    if (R > 1 && (p.tinv || p.slots)) {
         int32_t *vslot;
         BA_TRY(ctx->scratch(SL_TSLOT, (size_t)L.T, &vslot));
         hipLaunchKernelGGL(k_split_tslot, dim3((unsigned)((L.T + 255) / 256)), dim3(256), 0, ctx->stream, L.T, (int)R,
-                           slots ? k.st.tslot : nullptr, vslot);
-        k.tslot = vslot;
+                           p.slots ? k.st.tslot : nullptr, vslot);
+        ln.tslot = vslot;
     }
     const int64_t CTP = k.C * Ttab * L.P;
-    const int nrow = k.interp == BEATAMD_MULTILINEAR ? 4 : 1;
 
     TabArgs ta;
-    ta.interp = k.interp;
-    ta.R = R;
+    ta.interp = k.interp; ta.R = R;
     ta.C = k.C; ta.T = Ttab; ta.P = L.P; ta.D = L.D; ta.S = L.S;
     ta.st_min = L.st_min; ta.st_dt = L.st_dt; ta.du_min = L.du_min; ta.du_dt = L.du_dt;
-    ta.durations = k.durations;
-    ta.st = k.st;
-    if (slots) ta.st.shift_off = k.st.slot_shift_off;
+    ta.durations = k.durations; ta.st = k.st;
+    if (p.slots) ta.st.shift_off = k.st.slot_shift_off;
     ta.status = ctx->d_status;
-    BA_TRY(ctx->scratch(SL_ROWOFF, (size_t)CTP * nrow, &ta.rowoff));
+    BA_TRY(ctx->scratch(SL_ROWOFF, (size_t)CTP * p.nrow, &ta.rowoff));
     ta.fac = nullptr;
-    if (nrow == 4) {
-        BA_TRY(ctx->scratch(SL_WEIGHTS, (size_t)CTP * 4, &ta.fac));
-    }
+    if (p.nrow == 4) BA_TRY(ctx->scratch(SL_WEIGHTS, (size_t)CTP * 4, &ta.fac));
     {
         ScopedTimer tm(ctx, "tables");
         hipLaunchKernelGGL(k_gf_tables, dim3((unsigned)((CTP + 255) / 256)), dim3(256), 0,
                            ctx->stream, ta);
     }
     BA_HIP(hipGetLastError());
+    ln.rowoff = ta.rowoff; ln.fac = ta.fac;
 
-    // float storage requested and every library has its float copy: the lane <-> chain kernels read it (the
-    // cell kernel works on the float64 rows)
-    bool f32_all = k.f32;
-    for (int v = 0; v < k.nvar; v++) f32_all = f32_all && k.libs[v]->g32 != nullptr;
-    // multilinear from 192 chains on: the runs kernel (gfcell.hip).  When its tables can overflow (more row passes than they
-    // are sized for) the streaming kernel below is enqueued behind it as a stand-in that works only if they did.
     const int *standin = nullptr;
-    // (mode 3: launch_gfstack_shared and the runs kernel may carry the epilogue, the streaming kernel stores the
-    // residuals; as the runs kernel's stand-in it is followed by a guarded k_quadform_band1)
-    const int mode_in = k.mode;
-    const bool fuse_runs = mode_in == GF_RESID_BAND1 && gf_carries_band1(kn, GF_BY_RUNS);
-    if (mode_in == GF_RESID_BAND1 && !fuse_runs) k.mode = GF_RESID_STORE;
-    if (!f32_all && gfstack_ml_applicable(k)) {
-        BA_TRY(launch_gfstack_ml(ctx, k, ta.rowoff, ta.fac, Ttab, &standin));
-        *band1_done = fuse_runs;
+    if (p.stacker == GF_RUNS) {
+        BA_TRY(launch_gfstack_ml(ctx, k, p, ln, &standin));
         if (!standin) return BEATAMD_OK;
+    } else if (p.stacker == GF_GROUPS) {
+        ln.group = p.group;
+        if (p.tune) BA_TRY(tune_group_size(ctx, k, p, ln, &ln.group));
+        return launch_gfstack_shared(ctx, k, p, ln, ln.group);
     }
-    if (mode_in == GF_RESID_BAND1) k.mode = GF_RESID_STORE;
-    if (!standin) {
-        int cg = 0, ucap = 0;
-        if (gfstack_shared_applicable(k, &cg, &ucap)) {
-            k.mode = mode_in;
-            // Chains per workgroup: which size is fastest depends on the library (distinct rows a
-            // group can share, D*S), the batch and the population, so it is MEASURED once per
-            // problem shape -- every candidate is launched on the real inputs (the kernels are
-            // bitwise equal for every group size, the outputs are simply rewritten) and the
-            // fastest is kept.  BEATAMD_GS_CG fixes the size, BEATAMD_GS_TUNE=0 uses the static
-            // table of pick_group (measured on config 3).
-            const bool tune = !GfKnobs::set(kn.gs_cg) && !GfKnobs::is(kn.gs_tune, 0);
-            if (tune) {
-                // (key: the batch in whole 512-chain groups, capped -- 4096 and 4100 chains choose alike --; the epilogue
-                // mode costs every group size the same and is not part of it)
-                const int64_t cbucket = k.C < 512 ? k.C : 512 * std::min<int64_t>((k.C + 511) / 512, 16);
-                const std::vector<int64_t> key = {cbucket, nrow, k.nvar, L.T, L.P, L.D, L.S, L.N, Ttab, f32_all ? 1 : 0};
-                auto it = ctx->gs_tuned.find(key);
-                if (it == ctx->gs_tuned.end()) {
-                    int cgs[4], ucaps[4];
-                    const int nc = gfstack_shared_candidates(k, cgs, ucaps);
-                    int best = -1;
-                    float best_ms = 0.f, ms_of[4] = {0.f, 0.f, 0.f, 0.f};
-                    hipEvent_t e0, e1;
-                    BA_HIP(hipEventCreate(&e0));
-                    BA_HIP(hipEventCreate(&e1));
-                    for (int i = 0; i < nc && nc > 1; i++) {
-                        float ms_min = 0.f;
-                        for (int rep = 0; rep < 2; rep++) {   // first launch of a size: warm-up (code, tables' scratch)
-                            BA_HIP(hipEventRecord(e0, ctx->stream));
-                            BA_TRY(launch_gfstack_shared(ctx, k, ta.rowoff, ta.fac, cgs[i], ucaps[i], Ttab, band1_done));
-                            BA_HIP(hipEventRecord(e1, ctx->stream));
-                            BA_HIP(hipEventSynchronize(e1));
-                            float ms = 0.f;
-                            BA_HIP(hipEventElapsedTime(&ms, e0, e1));
-                            if (rep == 1) ms_min = ms;
-                        }
-                        ms_of[i] = ms_min;
-                        if (best < 0 || ms_min < best_ms) { best = i; best_ms = ms_min; }
-                        // a candidate twice as slow as the best so far: the smaller sizes behind it only stage more rows
-                        if (ms_min > 2.f * best_ms) break;
-                    }
-                    (void)hipEventDestroy(e0);
-                    (void)hipEventDestroy(e1);
-                    if (nc == 1) best = 0;
-                    if (best >= 0) it = ctx->gs_tuned.emplace(key, std::make_pair(cgs[best], ucaps[best])).first;
-                    // what was measured, once per problem shape: beatamd_ctx_gf_tune_log (and stderr under BEATAMD_VERBOSE)
-                    {
-                        char *w = ctx->gf_tune_log;
-                        size_t left = sizeof(ctx->gf_tune_log);
-                        int n = snprintf(w, left, "group size for %lld chains (T %lld, P %lld, D*S %lld, N %lld, %d row(s) per chain): ",
-                                         (long long)k.C, (long long)L.T, (long long)L.P, (long long)(L.D * L.S), (long long)L.N, nrow);
-                        for (int i = 0; i < nc && n > 0 && (size_t)n < left; i++) {
-                            w += n; left -= (size_t)n;
-                            n = ms_of[i] > 0.f ? snprintf(w, left, "%d: %.3f ms%s", cgs[i], ms_of[i], i + 1 < nc ? ", " : "")
-                                               : snprintf(w, left, "%d: %s%s", cgs[i], nc == 1 ? "only candidate" : "not timed", i + 1 < nc ? ", " : "");
-                        }
-                        if (best >= 0 && n > 0 && (size_t)n < left) { w += n; left -= (size_t)n; snprintf(w, left, " -> %d", cgs[best]); }
-                        if (getenv("BEATAMD_VERBOSE")) fprintf(stderr, "beat_amd: %s\n", ctx->gf_tune_log);
-                    }
-                }
-                if (it != ctx->gs_tuned.end()) { cg = it->second.first; ucap = it->second.second; }
-            }
-            return launch_gfstack_shared(ctx, k, ta.rowoff, ta.fac, cg, ucap, Ttab, band1_done);
-        }
-    }
+    const int mode = standin ? p.mode_standin : p.mode;
 
     GfArgs a;
     memset(&a, 0, sizeof(a));
@@ -694,28 +691,20 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, bool *
     }
     a.T = L.T; a.P = L.P; a.N = L.N;
     a.Ttab = Ttab; a.rows_per_target = L.P * L.D * L.S;
-    a.tslot = k.tslot;
+    a.tslot = ln.tslot;
     a.C = k.C;
     a.R = R;
-    {
-        a.order = GfKnobs::get(kn.gf_order, 1);
-        a.cgroup = GfKnobs::get(kn.gf_cgroup, 128);
-        if (a.cgroup < 1) a.cgroup = 1;
-    }
-    a.rowoff = ta.rowoff;
-    a.fac = ta.fac;
-    a.data = k.data;
-    a.wscalar = k.wscalar;
-    a.out = k.out;
+    a.order = GfKnobs::get(kn.gf_order, 1);
+    a.cgroup = std::max(1, GfKnobs::get(kn.gf_cgroup, 128));
+    a.rowoff = ta.rowoff; a.fac = ta.fac;
+    a.data = k.data; a.wscalar = k.wscalar; a.out = k.out;
     a.guard = standin;
     const int W = (L.N % 2 == 0) ? 2 : 1;
     const int VEC = 1;
     const int64_t tile_w = (int64_t)256 * W * VEC;
     a.ntile = (int)((L.N + tile_w - 1) / tile_w);
-    if (k.mode == GF_RESID_SCALAR) {
-        // (a stand-in keeps its tile sums apart from those of the kernel it stands in for)
-        BA_TRY(ctx->scratch(standin ? SL_PARTIAL2 : SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
-    }
+    // (a stand-in keeps its tile sums apart from those of the kernel it stands in for)
+    if (mode == GF_RESID_SCALAR) BA_TRY(ctx->scratch(standin ? SL_PARTIAL2 : SL_PARTIAL, (size_t)k.C * L.T * a.ntile, &a.partial));
     const int64_t nblocks = k.C * L.T * a.ntile;
     BA_CHECK(nblocks < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gfstack: batch too large (%lld blocks)",
              (long long)nblocks);
@@ -723,26 +712,22 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &call, bool *
     dim3 grid((unsigned)(standin ? std::min<int64_t>(nblocks, (int64_t)ctx->num_cu * 8) : nblocks));
     if (!standin) {
         snprintf(ctx->last_gf_kernel, sizeof(ctx->last_gf_kernel), "k_gfstack<%d,%d,%d,%d,%d>",
-                 k.interp == BEATAMD_MULTILINEAR ? 1 : 0, k.nvar, VEC, W, k.mode);
+                 k.interp == BEATAMD_MULTILINEAR ? 1 : 0, k.nvar, VEC, W, mode);
         snprintf(ctx->gf_plan, sizeof(ctx->gf_plan), "streaming kernel: %s", k.C < 48 ? "fewer than 48 chains share too few rows" :
                  L.N % 2 ? "odd sample count (the chain-shared kernels move 16-byte lanes)" : "chosen by BEATAMD_GF_KERNEL or no chain-shared kernel fits this library");
         ctx->gs_ngtp = 0;
     }
     {
         ScopedTimer tm(ctx, standin ? "gfstack_standin" : "gfstack");
-        if (k.interp == BEATAMD_NEAREST_NEIGHBOR) {
-            if (W == 2) launch_nvar<0, 1, 2>(k.nvar, k.mode, grid, ctx->stream, a);
-            else launch_nvar<0, 1, 1>(k.nvar, k.mode, grid, ctx->stream, a);
-        } else {
-            if (W == 2) launch_nvar<1, 1, 2>(k.nvar, k.mode, grid, ctx->stream, a);
-            else launch_nvar<1, 1, 1>(k.nvar, k.mode, grid, ctx->stream, a);
-        }
+        const auto launch = k.interp == BEATAMD_NEAREST_NEIGHBOR ? (W == 2 ? launch_nvar<0, 1, 2> : launch_nvar<0, 1, 1>)
+                                                                 : (W == 2 ? launch_nvar<1, 1, 2> : launch_nvar<1, 1, 1>);
+        launch(k.nvar, mode, grid, ctx->stream, a);
     }
     BA_HIP(hipGetLastError());
-    if (k.mode == GF_RESID_SCALAR) BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad, standin, 1));
+    if (mode == GF_RESID_SCALAR) BA_TRY(launch_sum_tiles(ctx, a.partial, k.C * L.T, a.ntile, k.quad, standin, 1));
     // stand-in of the runs kernel in mode 3: the misfit of the residuals just stored, only when the tables overflowed
-    if (standin && fuse_runs)
-        BA_TRY(launch_quadform_banded(ctx, call.band_w, 1, L.N, L.T, k.C, k.out, L.T * L.N, L.N, k.quad, L.T, standin, 1));
+    if (standin && p.standin_band1)
+        BA_TRY(launch_quadform_banded(ctx, k.band_w, 1, L.N, L.T, k.C, k.out, L.T * L.N, L.N, k.quad, L.T, standin, 1));
     return BEATAMD_OK;
 }
 

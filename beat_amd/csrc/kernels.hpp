@@ -75,15 +75,6 @@ enum GfMode : int {
     GF_RESID_BAND1 = 3
 };
 
-// Which kernel carries the bidiagonal epilogue, stated once: the combine kernel of the patch ranges (k_split_combine), the
-// runs kernel (k_gfstack_runs) and k_gfstack_ws on float64 rows; BEATAMD_QF_FUSE=0: none (residual store +
-// k_quadform_band1 behind every kernel -- A/B, tests).  The launch functions report it to launch_gfstack (*band1_done).
-enum GfStacker : int { GF_BY_COMBINE, GF_BY_RUNS, GF_BY_WS, GF_BY_OTHER };
-inline bool gf_carries_band1(const GfKnobs &kn, GfStacker by)
-{
-    return by != GF_BY_OTHER && !GfKnobs::is(kn.qf_fuse, 0);
-}
-
 struct GfStackCall {
     const SeisLib *libs[4] = {nullptr, nullptr, nullptr, nullptr};
     int nvar = 1;
@@ -102,13 +93,6 @@ struct GfStackCall {
     // optional scheduling hint: two per-chain sort keys that put chains which rupture alike next to each other
     // (the fused model path: hypocentre strike / dip of the first subfault).  Never changes a result.
     ChainVec order_key[2];
-    // PATCH SPLIT (round 6, small-N libraries): the libraries are VIEWS [T*R, P/R, D, S, N] of the real ones (virtual
-    // target t*R + r = target t, patches [r*P/R, (r+1)*P/R)), the tables are built per virtual slot and the stacking
-    // kernels run unchanged on R times as many, R times shorter (target, tile) walks; slips / start times / durations
-    // are read at the REAL patch r*P/R + p.  Set by launch_gfstack only.
-    int patch_split = 1;
-    const GfKnobs *knobs = nullptr;   // set by launch_gfstack (gf_knobs(ctx)): the selection functions read them here
-    const int32_t *tslot = nullptr;   // set by launch_gfstack: table slot of a target when targets share tables (device [T])
     // optional [C] mask (the fused Metropolis step: proposals inside the prior box).  A kernel that honours it may leave the
     // outputs of chains with active[c] == 0 unwritten; one that ignores it evaluates them (their points are in the grid).
     const int32_t *active = nullptr;
@@ -120,11 +104,66 @@ int launch_sum_tiles(beatamd_ctx *ctx, const double *partial, int64_t n, int nti
                      int want = 0, const double *edges = nullptr, const double *band_w = nullptr, int64_t T = 1, int64_t N = 0);
 // g[i] = (double)(float)g[i]; g32[i] = (float)g[i]  (float-storage copy of a GF library)
 int launch_round_to_f32(beatamd_ctx *ctx, double *g, float *g32, int64_t n);
-// gfshared.hip: chain-shared variant (distinct rows staged once per chain group)
-bool gfstack_shared_applicable(const GfStackCall &call, int *cg, int *ucap);
-int gfstack_shared_candidates(const GfStackCall &call, int *cgs, int *ucaps);
-int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &call, const uint32_t *rowoff,
-                          const double *fac, int CG, int ucap, int64_t Ttab, bool *band1_done);
+// ---- the plan of one stacking call: every decision taken before anything is launched, taken once (gf_plan_call, gfstack.hip,
+// and its callees next to the kernels whose limits they state).  The launch functions read it and decide nothing.
+// Who evaluates the bidiagonal misfit (mode 3): the combine kernel of the patch ranges (k_split_combine), the runs kernel
+// (k_gfstack_runs) and k_gfstack_ws on float64 rows carry the epilogue; behind every other kernel -- and behind all of them
+// under BEATAMD_QF_FUSE=0 (A/B, tests) -- the residuals are stored and k_quadform_band1 follows.
+enum GfBand1 : int { GF_BY_NONE, GF_BY_COMBINE, GF_BY_RUNS, GF_BY_WS, GF_BY_QUADFORM };
+inline GfBand1 gf_band1(bool carries, GfBand1 by, int *mode)   // mode 3 asked of a kernel -> who evaluates it, the kernel's mode
+{
+    if (!carries) *mode = GF_RESID_STORE;
+    return carries ? by : GF_BY_QUADFORM;
+}
+enum GfStacker : int { GF_STREAMING, GF_RUNS, GF_GROUPS };
+// one group size of the chain-shared (lane <-> chain) stackers: chains per group, distinct-row bound, epilogue mode, the
+// kernel (k_gfstack_ws, loader / consumer, or the small-group k_gfstack_dma family)
+struct GfGroup {
+    int cg = 0, ucap = 0, mode = 0;
+    bool ws = false;
+    GfBand1 band1 = GF_BY_NONE;
+};
+struct GfPlan {
+    const GfKnobs *knobs = nullptr;   // the knobs in force, read once per call
+    // PATCH SPLIT (round 6, small-N libraries): the libraries are VIEWS [T*R, P/R, D, S, N] of the real ones (virtual
+    // target t*R + r = target t, patches [r*P/R, (r+1)*P/R)), the tables are built per virtual slot and the stacking
+    // kernels run unchanged on R times as many, R times shorter (target, tile) walks; slips / start times / durations
+    // are read at the REAL patch r*P/R + p.
+    int R = 1;
+    int64_t T = 0, P = 0;             // the library as it is stacked: T*R targets of P/R patches
+    bool tinv = false, slots = false; // index tables shared by all targets / by the targets of a station slot
+    int64_t Ttab = 0;                 // table slots per chain
+    int nrow = 1;                     // library rows per chain and patch (multilinear: 4)
+    // float storage asked for and every library has its float copy; BEATAMD_GS_PAIR=1: k_gfstack_ws gathers ds_read_b128 pairs
+    // (A/B); the kernels that have the bidiagonal epilogue use it (BEATAMD_QF_FUSE=0: none); 512-chain groups take k_gfstack_ws
+    bool f32 = false, pair64 = false, fused = true, ws512 = false;
+    GfStacker stacker = GF_STREAMING;
+    // epilogue modes: of the runs kernel or the streaming kernel as the stacker, of the streaming kernel standing in for
+    // the runs kernel (mode 3: followed by a guarded k_quadform_band1?), of k_split_combine (R > 1: the stackers get mode 0)
+    int mode = 0, mode_standin = 0, mode_combine = 0;
+    bool standin_band1 = false;
+    GfBand1 band1 = GF_BY_NONE;       // who evaluates mode 3 (GF_GROUPS with R == 1: the GfGroup launched says)
+    // GF_GROUPS: the group size in force, and the sizes to measure where it is measured (ctx->gs_tuned keeps the result)
+    GfGroup group, cand[4];
+    int ncand = 0;
+    bool tune = false;
+};
+GfPlan gf_plan_call(const GfStackCall &call, const GfKnobs &kn, int num_cu);
+// what a launch adds, products of the device and of the context's state: the table slot of a (virtual) target when targets
+// share tables (device [T]), the index tables of k_gf_tables, GF_GROUPS: the group launched (the plan's or the measured one)
+struct GfLaunch {
+    const int32_t *tslot = nullptr;
+    const uint32_t *rowoff = nullptr;
+    const double *fac = nullptr;
+    GfGroup group;
+};
+// what beatamd_ctx_gf_group_stats reports of a chain-shared launch
+void gs_record_stats(beatamd_ctx *ctx, const GfStackCall &k, int64_t GTP, int64_t Ttab, int cg, bool has_passes);
+// gfshared.hip: chain-shared variant (distinct rows staged once per chain group).  gfstack_shared_plan: false = no group
+// size fits this call, else p.ws512, p.group, p.tune, p.cand; gfstack_group: the GfGroup of a size
+bool gfstack_shared_plan(const GfStackCall &call, GfPlan &p);
+GfGroup gfstack_group(const GfPlan &p, int cg, int ucap);
+int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &call, const GfPlan &p, const GfLaunch &ln, const GfGroup &g);
 
 // gfcell.hip: multilinear stacking with the rows of a cell in registers (518-chain groups, row passes): k_gfstack_runs.
 // *ovf (device, nullable on return): nonzero after the launch = the tables overflowed and nothing was stacked -- the
@@ -134,9 +173,8 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &call, const uint3
 // sorting in LDS: C <= 8192, <= 64 groups); members = nullptr when the batch is larger or a key is missing
 int launch_chain_members(beatamd_ctx *ctx, int64_t C, const ChainVec key[2], int64_t cg, int64_t ngroups, const uint32_t **members,
                          int strips = 0);
-bool gfstack_ml_applicable(const GfStackCall &call);
-int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &call, const uint32_t *rowoff,
-                      const double *fac, int64_t Ttab, const int **ovf);
+bool gfstack_ml_applicable(const GfStackCall &call, const GfPlan &p);
+int launch_gfstack_ml(beatamd_ctx *ctx, const GfStackCall &call, const GfPlan &p, const GfLaunch &ln, const int **ovf);
 
 // ---- quadform.hip ----------------------------------------------------------------
 // quad[c,d] = || A_d x_{c,d} ||^2 ; A [nd or 1, M, M] row-major ; x(c,d,k) = X[c*xs_c + d*xs_d + k]
