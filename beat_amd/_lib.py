@@ -67,6 +67,10 @@ _PROTOS = {
     "beatamd_geo_gflib_create": [_vp, _i64, _i64, _vp, _pi32],
     "beatamd_geo_gflib_destroy": [_vp, _i32],
     "beatamd_geo_stack_all_batch": [_vp, _i32, _i64, _vp, _i32, _vp],
+    "beatamd_geo_ensemble_create": [_vp, _vp, _i64, _i64, _pi32],
+    "beatamd_geo_ensemble_destroy": [_vp, _i32],
+    "beatamd_geo_ensemble_stack": [_vp, _i32, _vp, _vp],
+    "beatamd_pred_covariance_batch": [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp],
     "beatamd_weights_create": [_vp, _i32, _i64, _i64, _vp, _vp, _pi32],
     "beatamd_weights_update": [_vp, _i32, _i32, _i64, _vp, _vp],
     "beatamd_weights_destroy": [_vp, _i32],

@@ -12,10 +12,14 @@ What is bitwise the reference and what is not (tests/test_gpu_covariance_edges.p
 - the whitening operator and log-determinant (``chol_inverse_batch[_flags]``): another factorisation
   order than the reference's ``cholesky(inv(C))``; within c n u kappa(C) (u = 2^-53, c = 4) of it.
 """
+import logging
+
 import numpy as np
 
 from .engine import get_context
 from .utility import ensure_cov_psd, running_window_rms  # noqa: F401
+
+logger = logging.getLogger("beat_amd.covariance")
 
 
 def exponential_data_covariance(n, dt, tzero):
@@ -172,4 +176,140 @@ class NoiseCovarianceUpdate(object):
             f.update_weights(i, W, logdet)
         f.ctx.synchronize()
         self.last_ms = (time.perf_counter() - t0) * 1e3
+        self.n_updates += 1
+
+
+class VelocityModelCovarianceUpdate(object):
+    """The geodetic half of the ``update`` argument of ``smc_sample``: the velocity-model prediction covariance ``C_pv``
+    of every geodetic dataset from an ensemble of Green's function libraries, each computed in a perturbed crust model
+    (GeodeticDistributerComposite.update_weights, geodetic.py:1130-1202; heart.py:158-253):
+
+        mu_k = sum_var G_{k,var}.T . slip_var at the MAP point, every variant k (raw: no odw, no corrections) ->
+        cov_pv = numpy.cov(mu[:, dataset], rowvar=0) -> covariance.pred_v ->
+        chol_inverse, log_pdet of data + pred_g + pred_v -> weights
+
+    on the device: ``beatamd_geo_ensemble_stack``, ``beatamd_pred_covariance_batch`` onto the resident ``data + pred_g``,
+    ``beatamd_chol_inverse_batch_flags``, ``LogpForwFunc.update_geodetic_weights``.  No matrix visits the host.
+
+    DEVIATION.  The reference passes ``cov_pv`` alone through ``utility.ensure_cov_psd`` before adding it; with fewer
+    variants than points it is rank deficient, so that always ends in the eigenvalue repair, which lifts the null space
+    to eps.  Here the raw sample covariance is added and the factorisation of the TOTAL decides.  A dataset whose total the
+    device factorisation flags takes the reference's own route on the host: ``ensure_cov_psd(cov_pv)``, then
+    ``beat_amd.heart.Covariance`` for operator and log-determinant (``n_host_route`` counts them); if that fails too,
+    ``numpy.linalg.LinAlgError`` naming the dataset is raised and the model's weights are untouched -- all new operators
+    are computed before any is installed.
+
+    covariances: the datasets' ``beat_amd.heart.Covariance`` objects; their ``pred_v`` is set to the new term as a device
+    tensor that is downloaded only when read, ``slog_pdet`` follows.  ``data + pred_g`` is uploaded once per pair of
+    arrays (assigning a new array to ``.data`` / ``.pred_g`` is seen; after changing one in place call
+    ``refresh_base()``).  With ``thresh`` (5) variants or fewer nothing is computed or installed, as in the reference
+    (geodetic.py:1151-1152, 1191-1195).  ``reference_crust_ind`` names the variant the model was compiled with (its row of
+    the stack is the model's mu bit for bit)."""
+
+    thresh = 5
+
+    def __init__(self, logp_func, ensemble, covariances, reference_crust_ind=0):
+        g = logp_func.problem.geodetic
+        if g is None:
+            raise ValueError("the model has no geodetic composite")
+        self.f, self.ensemble, self.covariances = logp_func, ensemble, list(covariances)
+        if len(self.covariances) != len(g.sizes):
+            raise ValueError("%d covariances for %d geodetic datasets" % (len(self.covariances), len(g.sizes)))
+        if list(ensemble.varnames) != list(logp_func.problem.slip_varnames):
+            raise ValueError("the ensemble's slip variables %s are not the model's %s"
+                             % (list(ensemble.varnames), list(logp_func.problem.slip_varnames)))
+        if ensemble.nsamples != sum(g.sizes):
+            raise ValueError("the ensemble's libraries have %d observations, the datasets %d" % (ensemble.nsamples, sum(g.sizes)))
+        if reference_crust_ind not in ensemble.crust_inds:
+            raise ValueError("crust variant %r is not in the ensemble %s" % (reference_crust_ind, ensemble.crust_inds))
+        self.reference_crust_ind = reference_crust_ind
+        self._base, self._base_key = None, None
+        self.last_ms, self.n_updates, self.n_host_route = 0.0, 0, 0
+
+    def refresh_base(self):
+        """forget the uploaded ``data + pred_g`` (after an in-place change of a covariance's arrays)"""
+        self._base, self._base_key = None, None
+
+    def _bases(self, dev):
+        import torch
+        key = [(id(c._terms["data"]), id(c._terms["pred_g"])) for c in self.covariances]
+        if self._base is None or key != self._base_key:
+            self._base = [torch.from_numpy(np.ascontiguousarray(c._term("data") + c._term("pred_g"), dtype=np.float64)).to(dev)
+                          for c in self.covariances]
+            # (_term may have replaced a missing pred_g by zeros: the key is taken afterwards)
+            self._base_key = [(id(c._terms["data"]), id(c._terms["pred_g"])) for c in self.covariances]
+        return self._base
+
+    def point_slips(self, q_map):
+        """the slip variables of the point, in the model's order -> (nvar * npatches,) numpy"""
+        lay = self.f.problem.layout
+        q = np.ascontiguousarray(q_map, dtype=np.float64).ravel()
+        P = self.ensemble.npatches
+        return np.concatenate([q[lay.offsets[v]:lay.offsets[v] + P] for v in self.f.problem.slip_varnames])
+
+    def crust_synthetics(self, q_map):
+        """(K, Nobs) torch-cuda: the raw synthetics of every crust variant at the point (geodetic.py:1167-1176)"""
+        import torch
+        dev = torch.device("cuda", self.f.ctx.device)
+        self.ensemble.init_optimization(self.f.ctx)
+        return self.ensemble.stack_all(torch.from_numpy(self.point_slips(q_map)).to(dev))
+
+    def update_weights(self, q_map):
+        import time
+        import torch
+        from .heart import Covariance
+        f = self.f
+        self.n_updates += 1
+        K = self.ensemble.n_variations
+        if K <= self.thresh:
+            logger.info("Not updating geodetic velocity model-covariances because number of model variations is too low! "
+                        "< %i" % self.thresh)
+            self.last_ms = 0.0
+            return
+        f.ctx.synchronize()
+        t0 = time.perf_counter()
+        dev = torch.device("cuda", f.ctx.device)
+        sizes = list(f.problem.geodetic.sizes)
+        X = self.crust_synthetics(q_map)
+        cov_pv = f.ctx.pred_covariance_batch(X, sizes)                          # the raw term, for covariance.pred_v
+        total = f.ctx.pred_covariance_batch(X, sizes, base=self._bases(dev))    # data + pred_g + pred_v
+        Ws, lps, pvs = [], [], []
+        for i, cov in enumerate(self.covariances):
+            W, lp, bad = f.ctx.chol_inverse_batch_flags(total[i].unsqueeze(0))
+            pv = cov_pv[i]
+            if int(bad[0]):
+                self.n_host_route += 1
+                pv = ensure_cov_psd(cov_pv[i].cpu().numpy())                    # geodetic.py:1189
+                try:
+                    host = Covariance(data=cov.data, pred_g=cov.pred_g, pred_v=pv)
+                    W, lp = torch.from_numpy(host.chol_inverse).to(dev), float(host.log_pdet)
+                except np.linalg.LinAlgError as e:
+                    raise np.linalg.LinAlgError("geodetic dataset %d: the total covariance (data + pred_g + pred_v) is not "
+                                                "positive definite: %s" % (i, e))
+            else:
+                W, lp = W[0], float(lp[0])
+            Ws.append(W)
+            lps.append(lp)
+            pvs.append(pv)
+        f.update_geodetic_weights(Ws, lps)
+        for cov, pv, lp in zip(self.covariances, pvs, lps):
+            cov.pred_v = pv
+            cov.slog_pdet.set_value(np.float64(lp))
+        f.ctx.synchronize()
+        self.last_ms = (time.perf_counter() - t0) * 1e3
+
+
+class CovarianceUpdates(object):
+    """Several updates as the one ``update=`` of ``smc_sample``: ``update_weights(q)`` calls each in order, as the reference
+    problem loops over its composites (a joint run: the seismic noise update, then the geodetic prediction covariance)."""
+
+    def __init__(self, *updates):
+        self.updates = list(updates)
+        self.last_ms, self.n_updates = 0.0, 0
+
+    def update_weights(self, q_map):
+        self.last_ms = 0.0
+        for u in self.updates:
+            u.update_weights(q_map)
+            self.last_ms += float(getattr(u, "last_ms", 0.0))
         self.n_updates += 1

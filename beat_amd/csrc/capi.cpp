@@ -318,6 +318,128 @@ int beatamd_geo_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C, con
     return st.finish();
 }
 
+// ------------------------------------------------------------------ velocity-model prediction covariance
+int beatamd_geo_ensemble_create(beatamd_ctx *ctx, const int32_t *lib_ids, int64_t K, int64_t nvar, int32_t *ens_id)
+{
+    ENTER(ctx);
+    BA_CHECK(lib_ids && ens_id && K >= 1 && K <= 65535 && nvar >= 1 && nvar <= 4, BEATAMD_EINVAL,
+             "geo_ensemble_create: bad argument (1..65535 variants of 1..4 slip variables)");
+    std::vector<int32_t> ids;
+    BA_TRY(host_copy(ctx, lib_ids, (size_t)(K * nvar), ids));
+    std::unique_ptr<GeoEnsemble> e(new GeoEnsemble());
+    e->K = K;
+    e->nvar = nvar;
+    e->libs = ids;
+    for (size_t i = 0; i < ids.size(); i++) {
+        GeoLib *l;
+        BA_TRY(find_geolib(ctx, ids[i], &l));
+        if (i == 0) {
+            e->P = l->P;
+            e->Nobs = l->Nobs;
+        }
+        BA_CHECK(l->P == e->P && l->Nobs == e->Nobs, BEATAMD_EINVAL,
+                 "geo_ensemble_create: library %d is (%lld, %lld), the first one (%lld, %lld)", ids[i], (long long)l->P,
+                 (long long)l->Nobs, (long long)e->P, (long long)e->Nobs);
+        e->ptrs.push_back(l->g.get());
+    }
+    BA_TRY(e->table.alloc_copy(ctx, e->ptrs.data(), e->ptrs.size()));
+    *ens_id = add_obj(ctx->geoens, std::move(e));
+    return BEATAMD_OK;
+}
+
+int beatamd_geo_ensemble_destroy(beatamd_ctx *ctx, int32_t ens_id)
+{
+    ENTER(ctx);
+    return destroy_obj(ctx, ctx->geoens, ens_id, "geodetic library ensemble");
+}
+
+int beatamd_geo_ensemble_stack(beatamd_ctx *ctx, int32_t ens_id, const double *slips, double *X)
+{
+    ENTER(ctx);
+    GeoEnsemble *e;
+    BA_TRY(find_obj(ctx->geoens, ens_id, "geodetic library ensemble", &e));
+    BA_CHECK(slips && X, BEATAMD_EINVAL, "geo_ensemble_stack: NULL array");
+    for (size_t i = 0; i < e->libs.size(); i++) {
+        const GeoLib *l = get_obj(ctx->geolibs, e->libs[i]);
+        BA_CHECK(l && l->g.get() == e->ptrs[i], BEATAMD_EINVAL,
+                 "geo_ensemble_stack: library %d of the ensemble was destroyed or replaced", e->libs[i]);
+    }
+    Staging st(ctx);
+    const double *d_sl;
+    double *d_x;
+    BA_TRY(st.in(slips, (size_t)(e->nvar * e->P), &d_sl));
+    BA_TRY(st.out(X, (size_t)(e->K * e->Nobs), &d_x));
+    BA_TRY(launch_crust_stack(ctx, e->table.get(), e->K, (int)e->nvar, e->P, e->Nobs, d_sl, d_x));
+    return st.finish();
+}
+
+int beatamd_pred_covariance_batch(beatamd_ctx *ctx, int64_t K, int64_t Nobs, const double *X, int64_t nd, const int64_t *sizes,
+                                  const double *const *base, double *const *out)
+{
+    ENTER(ctx);
+    BA_CHECK(X && sizes && out && Nobs >= 0 && nd >= 0, BEATAMD_EINVAL, "pred_covariance_batch: bad argument");
+    BA_CHECK(K >= 2, BEATAMD_EINVAL, "pred_covariance_batch: a sample covariance needs at least 2 variants, got %lld",
+             (long long)K);
+    BA_CHECK(!is_device_ptr(base) && !is_device_ptr(out), BEATAMD_EINVAL,
+             "pred_covariance_batch: the lists of matrix pointers are host arrays (the matrices may live on either side)");
+    if (nd == 0) return BEATAMD_OK;
+    std::vector<int64_t> n;
+    BA_TRY(host_copy(ctx, sizes, (size_t)nd, n));
+    // a matrix may live on either side: the host ones are mirrored in one array of this call (a composite has any number
+    // of datasets, Staging a fixed number of slots), bases in front of the outputs
+    int64_t total = 0, nmax = 0;
+    size_t host_elems = 0;
+    for (int64_t i = 0; i < nd; i++) {
+        BA_CHECK(n[i] > 0 && out[i], BEATAMD_EINVAL, "pred_covariance_batch: dataset %lld is empty or has no output", (long long)i);
+        total += n[i];
+        nmax = std::max(nmax, n[i]);
+        const size_t nn = (size_t)(n[i] * n[i]);
+        if (base && base[i] && !is_device_ptr(base[i])) host_elems += nn;
+        if (!is_device_ptr(out[i])) host_elems += nn;
+    }
+    BA_CHECK(total == Nobs, BEATAMD_EINVAL, "pred_covariance_batch: the dataset sizes add up to %lld, X has %lld columns",
+             (long long)total, (long long)Nobs);
+    DevMem<double> mirror;
+    if (host_elems) BA_TRY(mirror.alloc(host_elems));
+    std::vector<PredCovSet> sets((size_t)nd);
+    struct Back { double *host; const double *dev; size_t bytes; };
+    std::vector<Back> back;
+    size_t used = 0;
+    int64_t off = 0;
+    for (int64_t i = 0; i < nd; i++) {
+        const size_t nn = (size_t)(n[i] * n[i]);
+        PredCovSet &s = sets[(size_t)i];
+        s.off = off;
+        s.n = n[i];
+        s.base = base ? base[i] : nullptr;
+        if (s.base && !is_device_ptr(s.base)) {
+            BA_HIP(hipMemcpyAsync(mirror.get() + used, s.base, nn * 8, hipMemcpyHostToDevice, ctx->stream));
+            s.base = mirror.get() + used;
+            used += nn;
+        }
+        s.out = out[i];
+        if (!is_device_ptr(s.out)) {
+            s.out = mirror.get() + used;
+            back.push_back(Back{out[i], s.out, nn * 8});
+            used += nn;
+        }
+        off += n[i];
+    }
+    Staging st(ctx);
+    const double *d_x;
+    double *d_D;
+    PredCovSet *d_sets;
+    BA_TRY(st.in(X, (size_t)(K * Nobs), &d_x));
+    BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)(K * Nobs), &d_D));
+    BA_TRY(ctx->scratch(SL_MISC, (size_t)nd, &d_sets));
+    BA_HIP(hipMemcpyAsync(d_sets, sets.data(), sets.size() * sizeof(PredCovSet), hipMemcpyHostToDevice, ctx->stream));
+    BA_TRY(launch_pred_covariance(ctx, K, Nobs, d_x, d_D, nd, nmax, d_sets));
+    for (const Back &b : back) BA_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    // the table and the mirror are this call's: the stream is drained before they go
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    return st.finish();
+}
+
 // ------------------------------------------------------------------ likelihood
 static int wset_fill(beatamd_ctx *ctx, WeightSet *w, const double *weights, const double *slog)
 {

@@ -268,6 +268,7 @@ int beatamd_ctx_destroy(beatamd_ctx *c)
     c->hypers.clear();
     c->wsets.clear();
     c->laps.clear();
+    c->geoens.clear();
     c->geolibs.clear();
     c->seislibs.clear();
     for (auto &s : c->scratch_bufs) s.release();

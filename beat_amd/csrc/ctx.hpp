@@ -134,6 +134,16 @@ struct GeoLib {
     DevMem<double> g;  // (P, Nobs)
 };
 
+// the libraries of the crust-model variants of one geodetic composite (geodetic.py:1161-1176): K variants of nvar slip
+// variables, all of one shape.  The ensemble owns no library: it names them (ids, variant-major) and keeps the table of
+// their device pointers that k_crust_stack reads; a stack on an ensemble whose library went or was replaced is refused
+struct GeoEnsemble {
+    int64_t K = 0, nvar = 0, P = 0, Nobs = 0;
+    std::vector<int32_t> libs;              // [K * nvar]
+    std::vector<const double *> ptrs;       // the libraries' storage when the table was written
+    DevMem<const double *> table;           // device [K * nvar]
+};
+
 struct WeightSet {
     int kind = BEATAMD_W_SCALAR;
     int64_t nd = 0, M = 0;
@@ -286,6 +296,7 @@ struct beatamd_ctx {
     std::vector<beatamd::DevBuf> scratch_bufs;
     std::vector<std::unique_ptr<beatamd::SeisStore>> seislibs;
     std::vector<std::unique_ptr<beatamd::GeoLib>> geolibs;
+    std::vector<std::unique_ptr<beatamd::GeoEnsemble>> geoens;
     std::vector<std::unique_ptr<beatamd::WeightSet>> wsets;
     std::vector<std::unique_ptr<beatamd::Laplacian>> laps;
     std::vector<std::unique_ptr<beatamd::FfiModel>> models;

@@ -440,4 +440,19 @@ int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int6
 int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
                          const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid);
 
+// ---- predcov.hip: velocity-model prediction covariance of the geodetic datasets (geodetic.py:1130-1202)
+// X[k, :] = sum_v G_{k,v}.T . slips_v for the K variants of a library ensemble (k_crust_stack); G: device table [K * nvar],
+// variant-major; slips [nvar * P]
+int launch_crust_stack(beatamd_ctx *ctx, const double *const *G, int64_t K, int nvar, int64_t P, int64_t Nobs,
+                       const double *slips, double *X);
+// out_i = base_i + cov(X[:, o_i : o_i + n_i], rowvar=0) for the datasets of a composite in one launch (k_pred_center,
+// k_pred_cov); D [K, Nobs]: device scratch for the centred columns; sets: device table [nd], nmax = the largest n_i
+struct PredCovSet {
+    int64_t off, n;        // first column of the dataset in X, its size
+    const double *base;    // device [n, n] or nullptr (zeros)
+    double *out;           // device [n, n]
+};
+int launch_pred_covariance(beatamd_ctx *ctx, int64_t K, int64_t Nobs, const double *X, double *D, int64_t nd, int64_t nmax,
+                           const PredCovSet *sets);
+
 }  // namespace beatamd

@@ -203,6 +203,59 @@ class Context(object):
         check(self._lib.beatamd_geo_stack_all_batch(self._h, lib_id, Cn, ptr(sl), int(acc), ptr(out)))
         return out
 
+    # -- velocity-model prediction covariance (csrc/predcov.hip)
+    def geo_ensemble_create(self, lib_ids, K, nvar):
+        """the libraries of K crust-model variants for nvar slip variables (ids of geo_gflib_create, variant-major
+        (K, nvar)); all of one shape"""
+        ids = np.ascontiguousarray(lib_ids, dtype=np.int32).ravel()
+        if ids.size != int(K) * int(nvar):
+            raise ValueError("geo_ensemble_create: %d library ids for %d variants of %d variables" % (ids.size, K, nvar))
+        eid = C.c_int32()
+        check(self._lib.beatamd_geo_ensemble_create(self._h, ptr(ids), int(K), int(nvar), C.byref(eid)))
+        return eid.value
+
+    def geo_ensemble_destroy(self, ens_id):
+        check(self._lib.beatamd_geo_ensemble_destroy(self._h, ens_id))
+
+    def geo_ensemble_stack(self, ens_id, K, nobs, slips):
+        """slips (nvar * P,) at one point -> X (K, nobs): the synthetics of every variant (geodetic.py:1167-1176);
+        numpy or torch-cuda in, same kind out"""
+        self._adopt_stream(slips)
+        sl = f64(slips)
+        X = _empty_like(sl, (int(K), int(nobs)))
+        check(self._lib.beatamd_geo_ensemble_stack(self._h, ens_id, ptr(sl), ptr(X)))
+        return X
+
+    def pred_covariance_batch(self, X, sizes, base=None, out=None):
+        """X (K, Nobs) -> list of (n_i, n_i): base_i + numpy.cov(X[:, o_i:o_i + n_i], rowvar=0) per dataset, in the fixed
+        order of k_pred_center / k_pred_cov (tests/predcov_ref.py restates it bit for bit).  base: None or a list whose
+        entries are None (zeros) or contiguous float64 (n_i, n_i) arrays on either side; out: None (allocated on X's
+        side) or such a list, written in place."""
+        self._adopt_stream(X)
+        x = f64(X)
+        if x.ndim != 2:
+            raise ValueError("pred_covariance_batch: X must be (K, Nobs)")
+        K, nobs = int(x.shape[0]), int(x.shape[1])
+        n = _i64arr(sizes).ravel()
+        nd = int(n.size)
+        base = [None] * nd if base is None else list(base)
+        if out is None:
+            out = [_empty_like(x, (int(k), int(k))) for k in n]
+        out = list(out)
+        if len(base) != nd or len(out) != nd:
+            raise ValueError("pred_covariance_batch: %d sizes, %d base and %d output matrices" % (nd, len(base), len(out)))
+        for i, k in enumerate(n):
+            for a, what in ((base[i], "base"), (out[i], "out")):
+                if a is not None and (tuple(a.shape) != (int(k), int(k)) or f64(a) is not a):
+                    raise ValueError("pred_covariance_batch: %s[%d] must be a contiguous float64 (%d, %d) array"
+                                     % (what, i, k, k))
+        if any(o is None for o in out):
+            raise ValueError("pred_covariance_batch: every dataset needs an output matrix")
+        pb = (C.c_void_p * max(nd, 1))(*[ptr(b) for b in base])
+        po = (C.c_void_p * max(nd, 1))(*[ptr(o) for o in out])
+        check(self._lib.beatamd_pred_covariance_batch(self._h, K, nobs, ptr(x), nd, ptr(n), C.addressof(pb), C.addressof(po)))
+        return out
+
     # -- weights / likelihood
     def weights_create_scalar(self, w, slog_pdet, M):
         w, sl = f64(w).ravel(), f64(slog_pdet).ravel()

@@ -490,3 +490,70 @@ class GeodeticGFLibrary(GFLibrary):
     def stack_all_batch(self, slips, out=None):
         self.init_optimization(self._ctx)
         return self._ctx.geo_stack_all_batch(self.lib_id, self.nsamples, slips, out)
+
+
+class GeodeticGFEnsemble(object):
+    """The static libraries of several crust-model variants: ``libraries`` {crust_ind: {varname: GeodeticGFLibrary}}, what
+    the reference's geodetic composite holds after ``load_gfs(crust_inds=...)`` (geodetic.py:951-991) and stacks variant by
+    variant in ``update_weights`` (geodetic.py:1161-1176).  All libraries share one shape.  Variants are ordered by
+    ``crust_ind``; ``varnames`` (default: the first variant's order) fixes the order of the slip variables -- a model's
+    ``slip_varnames`` where the ensemble serves ``beat_amd.covariance.VelocityModelCovarianceUpdate``."""
+
+    def __init__(self, libraries, varnames=None):
+        if not libraries:
+            raise GFLibraryError("an ensemble needs at least one crust variant")
+        self.crust_inds = sorted(libraries)
+        self.varnames = list(varnames) if varnames is not None else list(libraries[self.crust_inds[0]])
+        self.libraries = {ci: {v: libraries[ci][v] for v in self.varnames} for ci in self.crust_inds}
+        shapes = {(gf.npatches, gf.nsamples) for libs in self.libraries.values() for gf in libs.values()}
+        if len(shapes) != 1:
+            raise GFLibraryError("the libraries of an ensemble differ in shape: %s" % sorted(shapes))
+        self.npatches, self.nsamples = shapes.pop()
+        self.ens_id, self._ctx, self._lib_ids = None, None, None
+
+    n_variations = property(lambda self: len(self.crust_inds))
+
+    @classmethod
+    def load(cls, directory, crust_inds, varnames):
+        """the files ``load_gfs(crust_inds=...)`` reads: <directory>/geodetic_<var>_static_<crust_ind>.{traces.npy,yaml}"""
+        return cls({int(ci): {v: load_gf_library(directory, get_gf_prefix("geodetic", v, "static", int(ci))) for v in varnames}
+                    for ci in crust_inds}, varnames)
+
+    def index(self, crust_ind):
+        """row of ``stack_all`` that holds the variant ``crust_ind``"""
+        return self.crust_inds.index(crust_ind)
+
+    def init_optimization(self, ctx=None):
+        ctx = ctx or self._ctx or get_context()
+        ids = []
+        for ci in self.crust_inds:
+            for v in self.varnames:
+                gf = self.libraries[ci][v]
+                gf.init_optimization(ctx)
+                ids.append(gf.lib_id)
+        if self.ens_id is not None and self._ctx is ctx and ids == self._lib_ids:
+            return
+        self.release()
+        self._ctx, self._lib_ids = ctx, ids
+        self.ens_id = ctx.geo_ensemble_create(ids, len(self.crust_inds), len(self.varnames))
+
+    def release(self):
+        """drop the device table (the libraries stay with their owners)"""
+        if self.ens_id is not None:
+            self._ctx.geo_ensemble_destroy(self.ens_id)
+            self.ens_id = None
+
+    def stack_all(self, point_slips):
+        """-> (K, nsamples): mu of every variant at one point, variant k = sum over the variables of G_{k,var}.T . slips_var
+        (raw: no odw, no corrections).  point_slips: {varname: (npatches,)} or an array (nvar, npatches) in ``varnames``
+        order; numpy -> numpy, torch-cuda -> tensor on the same device"""
+        if isinstance(point_slips, dict):
+            point_slips = np.stack([np.asarray(point_slips[v], dtype=np.float64) for v in self.varnames])
+        if not (hasattr(point_slips, "data_ptr") and not isinstance(point_slips, np.ndarray)):
+            point_slips = np.ascontiguousarray(point_slips, dtype=np.float64)
+        sl = point_slips.reshape(-1)
+        if sl.shape[0] != len(self.varnames) * self.npatches:
+            raise ValueError("expected %d slips (%d variables of %d patches), got %d"
+                             % (len(self.varnames) * self.npatches, len(self.varnames), self.npatches, sl.shape[0]))
+        self.init_optimization()
+        return self._ctx.geo_ensemble_stack(self.ens_id, len(self.crust_inds), self.nsamples, sl)

@@ -77,8 +77,16 @@ class Covariance(object):
             self.update_slog_pdet()
 
     # -- the three terms as attributes
+    def _resolve(self, name):
+        """the stored term; one that a covariance update left on the device (a torch-cuda tensor) is downloaded when it is
+        first read and kept as a numpy array from then on"""
+        m = self._terms[name]
+        if hasattr(m, "is_cuda"):
+            m = self._terms[name] = m.detach().cpu().numpy()
+        return m
+
     def _get(name):
-        return property(lambda self: self._terms[name],
+        return property(lambda self: self._resolve(name),
                         lambda self, value: self._terms.__setitem__(name, value))
 
     data, pred_g, pred_v = _get("data"), _get("pred_g"), _get("pred_v")
@@ -91,8 +99,8 @@ class Covariance(object):
         """the term as an array of the data covariance's shape (zeros when absent)"""
         if name not in TERMS:
             raise NotImplementedError("Covariance term %s not supported" % name)
-        ref = self._terms["data"]
-        m = self._terms[name]
+        ref = self._resolve("data")
+        m = self._resolve(name)
         if m is None or (np.size(m) != np.size(ref) and not np.any(m)):
             m = np.zeros_like(ref, dtype="float64")
             self._terms[name] = m

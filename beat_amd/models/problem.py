@@ -636,6 +636,41 @@ class LogpForwFunc(object):
             _log_band(self.ctx, self._wsets[wavemap_index], "wavemap %d (update)" % wavemap_index)
         wm.weights, wm.slog_pdet = w, _host(sl)
 
+    def update_geodetic_weights(self, weights, slog_pdets):
+        """geodetic.py:1197-1202: new ``chol_inverse`` (an (n_i, n_i) operator, or a scalar where the dataset was compiled
+        with one) and log-determinant per geodetic dataset, numpy or torch-cuda.  Kind and size must match the dataset's
+        weight set (checked here and by the library); every operator is checked before the first is installed.  The
+        cached |W d|^2 of the diagnostics go with the weights (``beatamd_weights_update``)."""
+        import torch
+        self._ready()
+        g = self.problem.geodetic
+        if g is None:
+            raise ValueError("the model has no geodetic composite")
+        nd = len(g.sizes)
+        weights = list(weights)
+        slog = [float(s) for s in np.ravel(_host(slog_pdets) if torch.is_tensor(slog_pdets) else
+                                           [_host(s) for s in slog_pdets])]
+        if len(weights) != nd or len(slog) != nd:
+            raise ValueError("%d weights and %d log-determinants for %d geodetic datasets" % (len(weights), len(slog), nd))
+        new = []
+        for k, (n, W, old) in enumerate(zip(g.sizes, weights, g.weights)):
+            if torch.is_tensor(W) and W.is_cuda:
+                w = W.detach().double().contiguous()
+            else:
+                w = np.ascontiguousarray(_host(W), dtype=np.float64)
+            dense = np.ndim(old) != 0
+            want = (n, n) if dense else ()
+            if tuple(w.shape) == (1,) + want:
+                w = w.reshape(want)
+            if tuple(w.shape) != want:
+                raise ValueError("geodetic dataset %d holds %s weights: expected shape %s, got %s"
+                                 % (k, "dense" if dense else "scalar", want, tuple(w.shape)))
+            new.append(w.reshape((1, n, n) if dense else (1,)))
+        for ws, w, sl in zip(self._geo_wsets, new, slog):
+            self.ctx.weights_update(ws, w, np.array([sl]))
+        g.weights = [w[0] if w.ndim == 3 else float(w[0]) for w in new]
+        g.slog_pdets = slog
+
 
 def _log_band(ctx, wset, what):
     """once per weights_create / weights_update of a dense set: how the library evaluates it (the

@@ -194,6 +194,10 @@ class TargetShardedLogp(object):
         w = weights[a:b] if hasattr(weights, "__getitem__") else weights
         self.local.update_weights(wavemap_index, w, slog_pdet[a:b])
 
+    def update_geodetic_weights(self, weights, slog_pdets):
+        """the geodetic composite is replicated: every rank installs the same operators in its local model"""
+        self.local.update_geodetic_weights(weights, slog_pdets)
+
     def update_llks(self, Q, out=None):
         raise NotImplementedError("update_llks of a target-sharded model is not offered yet (the seismic columns would be "
                                   "all-gathered like the likelihood vector): estimate the hyper-parameters on the "

@@ -199,6 +199,36 @@ int beatamd_geo_gflib_destroy(beatamd_ctx *ctx, int32_t lib_id);
 int beatamd_geo_stack_all_batch(beatamd_ctx *ctx, int32_t lib_id, int64_t C,
                                 const double *slips, int32_t accumulate, double *out);
 
+/* ---------------------------------------------------------------- velocity-model prediction covariance -------
+ * replaces: the crust-variant loop of GeodeticDistributerComposite.update_weights
+ *                                                        beat/models/geodetic.py:1161-1176
+ *           (mu_k = sum over slip variables of gfs[key(crust_ind, var)].stack_all(point[var]), ffi/base.py:292-305)
+ * An ensemble names K * nvar existing beatamd_geo_gflib libraries, variant-major (lib_ids[k * nvar + v]; host or
+ * device array): the libraries of K crust-model variants for nvar slip variables.  All must share (P, Nobs), else
+ * BEATAMD_EINVAL.  The ensemble owns none of them; stacking an ensemble one of whose libraries was destroyed or
+ * re-created is BEATAMD_EINVAL.
+ *   stack: slips [nvar*P] (one point) -> X [K, Nobs].  Per (variant, observation) the operation sequence of
+ *   beatamd_geo_stack_all_batch / the model's geodetic composite (variables ascending, patches ascending, one fma per
+ *   term from 0): the row of the variant that is a model's own library is that model's mu bit for bit. */
+int beatamd_geo_ensemble_create(beatamd_ctx *ctx, const int32_t *lib_ids, int64_t K, int64_t nvar, int32_t *ens_id);
+int beatamd_geo_ensemble_destroy(beatamd_ctx *ctx, int32_t ens_id);
+int beatamd_geo_ensemble_stack(beatamd_ctx *ctx, int32_t ens_id, const double *slips, double *X);
+/* replaces: cov_pv = num.cov(crust_synths[i], rowvar=0) per dataset and its addition to the other covariance terms
+ *                                                        beat/models/geodetic.py:1185-1190, beat/heart.py:158-164
+ *   X [K, Nobs] (the ensemble's synthetics), nd datasets of sizes[i] columns each (their sum is Nobs), dataset i at
+ *   column offset o_i = sizes[0] + ... + sizes[i-1]:
+ *       mean_j = (sum_k X[k,j]) / K;   D[k,j] = X[k,j] - mean_j;
+ *       out[i][a,b] = base[i][a,b] + (sum_k D[k,o_i+a] * D[k,o_i+b]) / (K - 1)
+ *   every sum over k ascending from 0, plain products and sums, true divisions: a numpy restatement gives the same
+ *   bits, and out[i] is exactly symmetric where base[i] is.  base (or an entry of it) NULL: zeros.  base / out are
+ *   host arrays of nd pointers; the matrices [sizes[i], sizes[i]] they point to, X and sizes may live on either side.
+ *   K < 2 is BEATAMD_EINVAL (numpy divides by zero).  DEVIATION: the reference passes cov_pv through
+ *   utility.ensure_cov_psd (utility.py:1034-1056) before adding it; here the raw sample covariance is added and the
+ *   factorisation of the total (beatamd_chol_inverse_batch_flags) decides -- beat_amd.covariance repairs on the host
+ *   what that flags. */
+int beatamd_pred_covariance_batch(beatamd_ctx *ctx, int64_t K, int64_t Nobs, const double *X, int64_t nd,
+                                  const int64_t *sizes, const double *const *base, double *const *out);
+
 /* ---------------------------------------------------------------- likelihood -------
  * replaces: multivariate_normal_chol(datasets, weights, hyperparams, residuals)
  *                                              beat/models/distributions.py:72-140
