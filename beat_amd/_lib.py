@@ -95,6 +95,7 @@ _PROTOS = {
     "beatamd_ffi_astep_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp],
     "beatamd_autocovariance_batch": [_vp, _i64, _i64, _vp, _vp, _vp],
     "beatamd_scaled_toeplitz_batch": [_vp, _i64, _i64, _vp, _vp, _vp],
+    "beatamd_ball_rms_batch": [_vp, _i64, _vp, _vp, _vp, _f64, _vp, _vp, _vp],
     "beatamd_ffi_astep_batch_betas": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "beatamd_ffi_mstep_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _i64, _i32, _i32, C.c_uint64, C.c_uint32, _i64,
                                 _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp],

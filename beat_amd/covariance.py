@@ -9,6 +9,10 @@ What is bitwise the reference and what is not (tests/test_gpu_covariance_edges.p
   ``torch.mean`` sums in another order and changed about a third of the values in the last bit.
 - ``scaled_toeplitz_batch``: bitwise ``toeplitz(coeffs) * stds[:, None] * stds[None, :]``.
 - ``running_window_rms_batch`` (device): running sums instead of ``numpy.convolve``; equal to rounding.
+- ``k_nearest_neighbor_rms`` / ``non_toeplitz_covariance_2d[_batch]`` (csrc/noise2d.hip): the radius and the neighbour sets
+  are the reference's bit for bit (exact ties included); the KD-tree returns a point's neighbours in no defined order, so
+  the reference's last bits of ``stds`` are not defined either -- the kernel sums in ONE stated order that depends on the
+  point and the scene size alone (tests/noise2d_ref.py restates it bit for bit), within (count + 3) 2^-53 of the reference.
 - the whitening operator and log-determinant (``chol_inverse_batch[_flags]``): another factorisation
   order than the reference's ``cholesky(inv(C))``; within c n u kappa(C) (u = 2^-53, c = 4) of it.
 """
@@ -84,6 +88,114 @@ def non_toeplitz_covariance_batch(data, window_size):
     ctx = get_context()
     coeffs = ctx.autocovariance_batch(np.ascontiguousarray(data / stds))
     return ctx.scaled_toeplitz_batch(coeffs, stds)
+
+
+def k_nearest_neighbor_rms(coords, data, k=None, max_dist_perc=0.2):
+    """covariance.py:774-811: running rms on irregularly sampled 2-d data -- per point the sample standard deviation
+    (ddof = 1) of the data over all points within ``max_dist_perc`` of the largest point distance.  coords (n, 2), data (n,);
+    numpy or torch-cuda, same kind out.  Only the ``max_dist_perc`` branch runs here (``beatamd_ball_rms_batch``); the
+    ``k`` nearest neighbours branch is not offered."""
+    if k and max_dist_perc:
+        raise ValueError("Either k or max_dist_perc should be defined!")
+    if k is not None:
+        raise NotImplementedError("k_nearest_neighbor_rms: the k nearest neighbours branch is not implemented, "
+                                  "use max_dist_perc")
+    if max_dist_perc is None:
+        raise ValueError("Either k or max_dist_perc should be defined!")
+    n = int(data.shape[0])
+    return get_context().ball_rms_batch(coords, data, [n], max_dist_perc)[2]
+
+
+def toeplitz_covariance_2d(coords, data, max_dist_perc=0.2):
+    """covariance.py:814-828 -> (toeplitz matrix, stds); host arrays"""
+    from scipy.linalg import toeplitz
+    coords, data = np.ascontiguousarray(coords, dtype=np.float64), np.ascontiguousarray(data, dtype=np.float64)
+    stds = k_nearest_neighbor_rms(coords=coords, data=data, max_dist_perc=max_dist_perc)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        coeffs = autocovariance(data / stds)
+    return toeplitz(coeffs), stds
+
+
+def non_toeplitz_covariance_2d(coords, data, max_dist_perc):
+    """covariance.py:831-848: scaled non-Toeplitz covariance for non-stationary errors of 2-d geospatial data"""
+    coords, data = np.ascontiguousarray(coords, dtype=np.float64), np.ascontiguousarray(data, dtype=np.float64)
+    return non_toeplitz_covariance_2d_batch(coords, data, [data.size], max_dist_perc)[0]
+
+
+def non_toeplitz_covariance_2d_batch(coords, data, sizes, max_dist_perc, stds=None):
+    """All scenes of a geodetic composite: coords (Ntot, 2) and data (Ntot,) concatenated over datasets of ``sizes``
+    points -> list of (n_i, n_i) matrices ``toeplitz(autocovariance(data_i / stds_i)) * stds_i stds_i^T``; numpy or
+    torch-cuda in, same kind out.  One launch group for the neighbourhood statistic of all scenes, then the existing
+    autocovariance and scaled-Toeplitz kernels per scene (their batches share one length).  A scene with a point that has
+    no neighbour comes back with NaN, as in the reference.  stds: the statistic where the caller has it already."""
+    ctx = get_context()
+    if stds is None:
+        stds = ctx.ball_rms_batch(coords, data, sizes, max_dist_perc)[2]
+    out, o = [], 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for n in (int(n) for n in sizes):
+            s = stds[o:o + n].reshape(1, n)
+            coeffs = ctx.autocovariance_batch((data[o:o + n].reshape(1, n) / s))
+            out.append(ctx.scaled_toeplitz_batch(coeffs, s)[0])
+            o += n
+    return out
+
+
+NoiseStructureCatalog2d = {
+    "import": ones_data_covariance,
+    "non-toeplitz": ones_data_covariance,
+}
+
+
+def available_noise_structures_2d():
+    return list(NoiseStructureCatalog2d.keys())
+
+
+class GeodeticNoiseAnalyser(object):
+    """covariance.py:154-233: the data covariance of a geodetic dataset by ``config.structure`` ("import": the dataset's
+    own, "non-toeplitz": estimated from the residual of ``result`` for SAR scenes; any other dataset type keeps its
+    ``covariance.data``).
+
+    config: anything with ``structure`` and ``max_dist_perc``.  dataset: ``typ``, ``id``, ``ncoords``, ``covariance``,
+    ``east_shifts`` / ``north_shifts`` [m]; where it has ``update_local_coords`` (pyrocko's projection about the event) it
+    is called with ``events[0]`` as in the reference, otherwise the shifts are taken as they are."""
+
+    def __init__(self, config, events=None):
+        avail = available_noise_structures_2d()
+        if config.structure not in avail:
+            raise AttributeError('Selected noise structure "%s" not supported! Implemented'
+                                 " noise structures: %s" % (config.structure, ", ".join(avail)))
+        self.events = events
+        self.config = config
+
+    def get_structure(self, dataset):
+        return NoiseStructureCatalog2d[self.config.structure](dataset.ncoords)
+
+    def do_import(self, dataset):
+        if dataset.covariance.data is not None:
+            return dataset.covariance.data
+        raise ValueError("Data covariance for dataset %s needs to be defined!" % dataset.id)
+
+    def do_non_toeplitz(self, dataset, result):
+        if dataset.typ == "SAR":
+            if hasattr(dataset, "update_local_coords"):
+                dataset.update_local_coords(self.events[0])
+            coords = np.vstack([dataset.east_shifts, dataset.north_shifts]).T
+            scaling = non_toeplitz_covariance_2d(coords, result.processed_res, max_dist_perc=self.config.max_dist_perc)
+        else:
+            scaling = dataset.covariance.data
+        if np.isnan(scaling).any():
+            raise ValueError("Estimated Non-Toeplitz covariance matrix for dataset %s contains Nan! "
+                             "Please increase 'max_dist_perc'!" % dataset.id)
+        return scaling
+
+    def get_data_covariance(self, dataset, result=None):
+        covariance_structure = self.get_structure(dataset)
+        if self.config.structure == "import":
+            scaling = self.do_import(dataset)
+        elif self.config.structure == "non-toeplitz":
+            scaling = self.do_non_toeplitz(dataset, result)
+        return ensure_cov_psd(scaling * covariance_structure)
 
 
 def get_data_covariances(structure, scalings):
@@ -230,12 +342,29 @@ class VelocityModelCovarianceUpdate(object):
         """forget the uploaded ``data + pred_g`` (after an in-place change of a covariance's arrays)"""
         self._base, self._base_key = None, None
 
-    def _bases(self, dev):
+    @staticmethod
+    def _base_of(c, t, dev):
+        """``data + pred_g`` of one dataset on the device; t: a device-resident data term to take instead of ``c``'s.  A data
+        term that already lives on the device is the base as it is (``pred_g`` missing) or takes the uploaded ``pred_g``
+        there: no host round trip.  Host arrays are summed on the host and uploaded."""
         import torch
+        if t is None and hasattr(c._terms["data"], "is_cuda"):
+            t = c._terms["data"]
+        if t is None:
+            return torch.from_numpy(np.ascontiguousarray(c._term("data") + c._term("pred_g"), dtype=np.float64)).to(dev)
+        g = c._terms["pred_g"]
+        if g is None:
+            return t
+        return t + (g.to(dev) if hasattr(g, "is_cuda") else torch.from_numpy(np.ascontiguousarray(g, dtype=np.float64)).to(dev))
+
+    def _bases(self, dev, data_terms=None):
+        """the datasets' ``data + pred_g`` on the device: kept from call to call per pair of arrays of the Covariance
+        objects; formed anew where the caller hands the data terms over (``data_terms``: one device tensor or None each)"""
+        if data_terms is not None:
+            return [self._base_of(c, t, dev) for c, t in zip(self.covariances, data_terms)]
         key = [(id(c._terms["data"]), id(c._terms["pred_g"])) for c in self.covariances]
         if self._base is None or key != self._base_key:
-            self._base = [torch.from_numpy(np.ascontiguousarray(c._term("data") + c._term("pred_g"), dtype=np.float64)).to(dev)
-                          for c in self.covariances]
+            self._base = [self._base_of(c, None, dev) for c in self.covariances]
             # (_term may have replaced a missing pred_g by zeros: the key is taken afterwards)
             self._base_key = [(id(c._terms["data"]), id(c._terms["pred_g"])) for c in self.covariances]
         return self._base
@@ -254,34 +383,29 @@ class VelocityModelCovarianceUpdate(object):
         self.ensemble.init_optimization(self.f.ctx)
         return self.ensemble.stack_all(torch.from_numpy(self.point_slips(q_map)).to(dev))
 
-    def update_weights(self, q_map):
-        import time
+    def compute(self, q_map, data_terms=None):
+        """everything up to the installation -> (operators, log-determinants, pred_v terms, repaired data terms or None).
+        data_terms: device tensors to take for the datasets' ``data`` instead of the Covariance objects' (the noise update
+        hands its new estimates over before anything is installed)"""
         import torch
         from .heart import Covariance
         f = self.f
-        self.n_updates += 1
-        K = self.ensemble.n_variations
-        if K <= self.thresh:
-            logger.info("Not updating geodetic velocity model-covariances because number of model variations is too low! "
-                        "< %i" % self.thresh)
-            self.last_ms = 0.0
-            return
-        f.ctx.synchronize()
-        t0 = time.perf_counter()
         dev = torch.device("cuda", f.ctx.device)
         sizes = list(f.problem.geodetic.sizes)
         X = self.crust_synthetics(q_map)
         cov_pv = f.ctx.pred_covariance_batch(X, sizes)                          # the raw term, for covariance.pred_v
-        total = f.ctx.pred_covariance_batch(X, sizes, base=self._bases(dev))    # data + pred_g + pred_v
-        Ws, lps, pvs = [], [], []
+        total = f.ctx.pred_covariance_batch(X, sizes, base=self._bases(dev, data_terms))    # data + pred_g + pred_v
+        Ws, lps, pvs, datas = [], [], [], []
         for i, cov in enumerate(self.covariances):
             W, lp, bad = f.ctx.chol_inverse_batch_flags(total[i].unsqueeze(0))
-            pv = cov_pv[i]
+            pv, data = cov_pv[i], None
             if int(bad[0]):
                 self.n_host_route += 1
                 pv = ensure_cov_psd(cov_pv[i].cpu().numpy())                    # geodetic.py:1189
                 try:
-                    host = Covariance(data=cov.data, pred_g=cov.pred_g, pred_v=pv)
+                    if data_terms is not None and data_terms[i] is not None:
+                        data = ensure_cov_psd(data_terms[i].cpu().numpy())      # covariance.py:233
+                    host = Covariance(data=cov.data if data is None else data, pred_g=cov.pred_g, pred_v=pv)
                     W, lp = torch.from_numpy(host.chol_inverse).to(dev), float(host.log_pdet)
                 except np.linalg.LinAlgError as e:
                     raise np.linalg.LinAlgError("geodetic dataset %d: the total covariance (data + pred_g + pred_v) is not "
@@ -291,12 +415,218 @@ class VelocityModelCovarianceUpdate(object):
             Ws.append(W)
             lps.append(lp)
             pvs.append(pv)
+            datas.append(data)
+        return Ws, lps, pvs, datas
+
+    def update_weights(self, q_map):
+        import time
+        f = self.f
+        self.n_updates += 1
+        if self.ensemble.n_variations <= self.thresh:
+            logger.info("Not updating geodetic velocity model-covariances because number of model variations is too low! "
+                        "< %i" % self.thresh)
+            self.last_ms = 0.0
+            return
+        f.ctx.synchronize()
+        t0 = time.perf_counter()
+        Ws, lps, pvs, _ = self.compute(q_map)
         f.update_geodetic_weights(Ws, lps)
         for cov, pv, lp in zip(self.covariances, pvs, lps):
             cov.pred_v = pv
             cov.slog_pdet.set_value(np.float64(lp))
         f.ctx.synchronize()
         self.last_ms = (time.perf_counter() - t0) * 1e3
+
+
+class GeodeticNoiseCovarianceUpdate(object):
+    """The data half of the geodetic ``update`` of ``smc_sample``: with ``noise_estimator.structure == "non-toeplitz"``
+    the reference re-estimates every SAR scene's DATA covariance from the residual at the stage's MAP point before it adds
+    the prediction covariances and factorises (GeodeticDistributerComposite.update_weights, geodetic.py:1130-1202 ->
+    analyse_noise :143-174 -> GeodeticNoiseAnalyser.do_non_toeplitz, covariance.py:193-210 -> non_toeplitz_covariance_2d
+    :831-848 -> toeplitz_covariance_2d :814-828 -> k_nearest_neighbor_rms :774-811):
+
+        res = d - mu - sum of corrections at the point (no odw factor: assemble_results :201-232, get_synthetics :1086-1128)
+        stds = k_nearest_neighbor_rms(coords, res, max_dist_perc) -> coeffs = autocovariance(res / stds) ->
+        C_d = toeplitz(coeffs) * stds stds^T -> covariance.data -> chol_inverse, log_pdet of data + pred_g + pred_v -> weights
+
+    on the device: ``beatamd_ffi_geo_residuals_batch`` (the model's own mu), ``beatamd_ball_rms_batch``,
+    ``beatamd_autocovariance_batch``, ``beatamd_scaled_toeplitz_batch``, the sum of the terms,
+    ``beatamd_chol_inverse_batch_flags``, ``LogpForwFunc.update_geodetic_weights``.  No matrix visits the host.
+
+    THE RESIDUAL.  ``mu`` is ``geodetic_residuals(q, residuals=False)``, the likelihood's own synthetics bit for bit.  The
+    data and every correction's basis columns are uploaded once; per update ``res = d - mu`` and then, term by term in the
+    order the model subtracts them (``corrections.correction_tables``), ``res_i = res_i - corr`` with ``corr = B[:, 0] *
+    c_0`` and ``corr = corr + B[:, k] * c_k`` for the further columns, the coefficients read from the point (or the
+    problem's fixed values): one IEEE operation per element and step, so numpy gives the same bits.
+
+    DEVIATION.  The reference passes the DATA term alone through ``utility.ensure_cov_psd`` (covariance.py:233) before the
+    prediction terms are added.  Here the factorisation of the TOTAL decides: a dataset whose total the device
+    factorisation flags takes the reference's route on the host -- ``ensure_cov_psd(C_d)``, then
+    ``beat_amd.heart.Covariance`` for operator and log-determinant (``n_host_route`` counts them); if that fails too,
+    ``numpy.linalg.LinAlgError`` naming the dataset is raised.  Whatever is raised -- that, or the reference's ValueError
+    for a scene whose estimate contains NaN (a point without a neighbour, or a neighbourhood of equal values) -- the
+    model's weights and the Covariance objects are untouched: everything is computed before anything is installed.
+
+    coords: one (n_i, 2) array of local east / north shifts [m] per dataset (the caller's: the reference derives them with
+    pyrocko's ``update_local_coords``).  covariances: the datasets' ``beat_amd.heart.Covariance`` objects; ``data`` becomes
+    the new term as a device tensor that is downloaded only when read, ``slog_pdet`` follows.  typs: the datasets' types,
+    default all "SAR"; any other type keeps its data term (covariance.py:201-202).  velocity: a
+    ``VelocityModelCovarianceUpdate`` of the same model and Covariance objects -- the update then runs in the reference's
+    order, data term first, ``pred_v`` from the ensemble at the same point next, and ONE factorisation per dataset of the
+    final total; the result is bit for bit that of ``CovarianceUpdates(noise, velocity)``, which factorises twice."""
+
+    def __init__(self, logp_func, coords, covariances, max_dist_perc, typs=None, velocity=None):
+        g = logp_func.problem.geodetic
+        if g is None:
+            raise ValueError("the model has no geodetic composite")
+        if not hasattr(logp_func, "geodetic_residuals"):
+            raise NotImplementedError("the geodetic noise update needs the whole geodetic composite in one compiled model")
+        nd = len(g.sizes)
+        self.f, self.covariances = logp_func, list(covariances)
+        if len(self.covariances) != nd:
+            raise ValueError("%d covariances for %d geodetic datasets" % (len(self.covariances), nd))
+        coords = [np.ascontiguousarray(c, dtype=np.float64) for c in coords]
+        if len(coords) != nd:
+            raise ValueError("%d coordinate arrays for %d geodetic datasets" % (len(coords), nd))
+        for i, (c, n) in enumerate(zip(coords, g.sizes)):
+            if c.shape != (n, 2):
+                raise ValueError("geodetic dataset %d: coordinates of shape %s, expected (%d, 2)" % (i, c.shape, n))
+        self.typs = ["SAR"] * nd if typs is None else list(typs)
+        if len(self.typs) != nd:
+            raise ValueError("%d dataset types for %d geodetic datasets" % (len(self.typs), nd))
+        if not np.isfinite(max_dist_perc):
+            raise ValueError("max_dist_perc must be finite")
+        if velocity is not None and (velocity.f is not logp_func or
+                                     any(a is not b for a, b in zip(velocity.covariances, self.covariances))):
+            raise ValueError("the velocity update must act on the same model and Covariance objects")
+        self.coords, self.max_dist_perc, self.velocity = coords, float(max_dist_perc), velocity
+        self.sar = [i for i, t in enumerate(self.typs) if t == "SAR"]
+        self._dev = None
+        self.last_ms, self.n_updates, self.n_host_route = 0.0, 0, 0
+
+    def _resident(self):
+        """what is uploaded once: the data, the SAR scenes' coordinates, the correction terms' basis columns"""
+        import torch
+        from .models.corrections import correction_tables
+        if self._dev is None:
+            f = self.f
+            g = f.problem.geodetic
+            dev = torch.device("cuda", f.ctx.device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)   # noqa: E731
+            ds, ncol, basis, offs, fixs = correction_tables(g.corrections, g.sizes, f.problem.layout, g.fixed)
+            self._dev = dict(dev=dev, data=up(g.data), terms=list(zip(ds, [up(B.T) for B in basis], offs, fixs)),
+                             coords=up(np.concatenate([self.coords[i] for i in self.sar])) if self.sar else None)
+        return self._dev
+
+    def residuals(self, q_map):
+        """(Nobs,) torch-cuda: ``d - mu - sum of corrections`` at the point, without the odw factor (the class docstring
+        says how)"""
+        import torch
+        r = self._resident()
+        g = self.f.problem.geodetic
+        q = np.ascontiguousarray(q_map, dtype=np.float64).ravel()
+        mu = self.f.geodetic_residuals(torch.from_numpy(q.reshape(1, -1)).to(r["dev"]), residuals=False)[0]
+        res = r["data"] - mu
+        starts = np.concatenate([[0], np.cumsum(g.sizes)])
+        for d, Bt, off, fix in r["terms"]:
+            coef = [float(q[o]) if o >= 0 else float(v) for o, v in zip(off, fix)]
+            corr = Bt[0] * coef[0]
+            for k in range(1, len(coef)):
+                corr = corr + Bt[k] * coef[k]
+            a, b = int(starts[d]), int(starts[d + 1])
+            res[a:b] = res[a:b] - corr
+        return res
+
+    def data_covariances(self, q_map):
+        """-> (one (n_i, n_i) torch-cuda matrix per dataset, None where the dataset is no SAR scene; residuals (Nobs,);
+        stds of the SAR scenes, concatenated).  Raises the reference's ValueError where an estimate contains NaN."""
+        import torch
+        f = self.f
+        g = f.problem.geodetic
+        r = self._resident()
+        res = self.residuals(q_map)
+        out = [None] * len(g.sizes)
+        if not self.sar:
+            return out, res, None
+        starts = np.concatenate([[0], np.cumsum(g.sizes)])
+        sizes = [g.sizes[i] for i in self.sar]
+        if len(self.sar) == len(g.sizes):
+            rs = res
+        else:
+            rs = torch.cat([res[int(starts[i]):int(starts[i + 1])] for i in self.sar])
+        rs = rs.contiguous()
+        _, _, stds = f.ctx.ball_rms_batch(r["coords"], rs, sizes, self.max_dist_perc)
+        # a NaN or a zero among the stds is a NaN in the matrix (0 / 0 on the diagonal at the latest): one read of one flag
+        bad = ~torch.isfinite(stds) | (stds == 0.0)
+        if bool(bad.any()):
+            o = np.concatenate([[0], np.cumsum(sizes)])
+            first = int(torch.nonzero(bad)[0, 0])
+            d = self.sar[int(np.searchsorted(o, first, side="right")) - 1]
+            raise ValueError("Estimated Non-Toeplitz covariance matrix for dataset %s contains Nan! "
+                             "Please increase 'max_dist_perc'!" % d)                  # covariance.py:204-208
+        for i, C in zip(self.sar, non_toeplitz_covariance_2d_batch(None, rs, sizes, None, stds=stds)):
+            out[i] = C
+        return out, res, stds
+
+    def update_weights(self, q_map):
+        import time
+        import torch
+        from .heart import Covariance
+        f = self.f
+        f.ctx.synchronize()
+        t0 = time.perf_counter()
+        dev = torch.device("cuda", f.ctx.device)
+        Cd, _, _ = self.data_covariances(q_map)
+        vel = self.velocity
+        if vel is not None and vel.ensemble.n_variations <= vel.thresh:
+            logger.info("Not updating geodetic velocity model-covariances because number of model variations is too low! "
+                        "< %i" % vel.thresh)
+            vel.n_updates += 1
+            vel.last_ms = 0.0
+            vel = None
+        if vel is not None:
+            # the reference's order: data term, pred_v at the same point, ONE factorisation of the final total
+            routed = vel.n_host_route
+            Ws, lps, pvs, datas = vel.compute(q_map, data_terms=Cd)
+            self.n_host_route += vel.n_host_route - routed
+            vel.n_updates += 1
+        else:
+            Ws, lps, pvs, datas = [], [], None, []
+            for i, cov in enumerate(self.covariances):
+                total, data = VelocityModelCovarianceUpdate._base_of(cov, Cd[i], dev), None
+                pv = cov._terms["pred_v"]
+                if pv is not None:
+                    total = total + (pv.to(dev) if hasattr(pv, "is_cuda") else
+                                     torch.from_numpy(np.ascontiguousarray(pv, dtype=np.float64)).to(dev))
+                W, lp, bad = f.ctx.chol_inverse_batch_flags(total.unsqueeze(0))
+                if int(bad[0]):
+                    self.n_host_route += 1
+                    try:
+                        data = ensure_cov_psd(cov.data if Cd[i] is None else Cd[i].cpu().numpy())    # covariance.py:233
+                        host = Covariance(data=data, pred_g=cov.pred_g, pred_v=cov.pred_v)
+                        W, lp = torch.from_numpy(host.chol_inverse).to(dev), float(host.log_pdet)
+                    except np.linalg.LinAlgError as e:
+                        raise np.linalg.LinAlgError("geodetic dataset %d: the total covariance (data + pred_g + pred_v) is "
+                                                    "not positive definite: %s" % (i, e))
+                else:
+                    W, lp = W[0], float(lp[0])
+                Ws.append(W)
+                lps.append(lp)
+                datas.append(data)
+        f.update_geodetic_weights(Ws, lps)
+        for i, (cov, lp) in enumerate(zip(self.covariances, lps)):
+            if datas[i] is not None:
+                cov.data = datas[i]
+            elif Cd[i] is not None:
+                cov.data = Cd[i]
+            if pvs is not None:
+                cov.pred_v = pvs[i]
+            cov.slog_pdet.set_value(np.float64(lp))
+        f.ctx.synchronize()
+        self.last_ms = (time.perf_counter() - t0) * 1e3
+        if self.velocity is not None and vel is not None:
+            vel.last_ms = self.last_ms
+        self.n_updates += 1
 
 
 class CovarianceUpdates(object):

@@ -1318,6 +1318,42 @@ int beatamd_scaled_toeplitz_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const
     return st.finish();
 }
 
+int beatamd_ball_rms_batch(beatamd_ctx *ctx, int64_t nd, const int64_t *sizes, const double *coords, const double *data,
+                           double max_dist_perc, double *radius, int32_t *counts, double *stds)
+{
+    ENTER(ctx);
+    BA_CHECK(sizes && coords && data && radius && counts && stds, BEATAMD_EINVAL, "ball_rms_batch: NULL array");
+    BA_CHECK(nd > 0 && nd <= 65535, BEATAMD_EINVAL, "ball_rms_batch: 1..65535 datasets, got %lld", (long long)nd);
+    BA_CHECK(std::isfinite(max_dist_perc), BEATAMD_EINVAL, "ball_rms_batch: max_dist_perc is not finite");
+    std::vector<int64_t> n;
+    BA_TRY(host_copy(ctx, sizes, (size_t)nd, n));
+    std::vector<BallSet> sets((size_t)nd);
+    int64_t total = 0, nmax = 0;
+    for (int64_t i = 0; i < nd; i++) {
+        BA_CHECK(n[i] > 0, BEATAMD_EINVAL, "ball_rms_batch: dataset %lld has %lld points", (long long)i, (long long)n[i]);
+        sets[(size_t)i] = BallSet{total, n[i]};
+        total += n[i];
+        nmax = std::max(nmax, n[i]);
+    }
+    Staging st(ctx);
+    const double *d_c, *d_d;
+    double *d_r, *d_s, *d_pmax;
+    int32_t *d_n;
+    BallSet *d_sets;
+    BA_TRY(st.in(coords, (size_t)total * 2, &d_c));
+    BA_TRY(st.in(data, (size_t)total, &d_d));
+    BA_TRY(st.out(radius, (size_t)nd, &d_r));
+    BA_TRY(st.out(counts, (size_t)total, &d_n));
+    BA_TRY(st.out(stds, (size_t)total, &d_s));
+    BA_TRY(ctx->scratch(SL_PARTIAL, (size_t)total, &d_pmax));
+    BA_TRY(ctx->scratch(SL_MISC, (size_t)nd, &d_sets));
+    BA_HIP(hipMemcpyAsync(d_sets, sets.data(), sets.size() * sizeof(BallSet), hipMemcpyHostToDevice, ctx->stream));
+    BA_TRY(launch_ball_rms(ctx, nd, nmax, d_sets, d_c, d_d, max_dist_perc, d_pmax, d_r, d_n, d_s));
+    // the table is this call's: the stream is drained before it goes
+    BA_HIP(hipStreamSynchronize(ctx->stream));
+    return st.finish();
+}
+
 // ------------------------------------------------------------------ introspection
 int beatamd_ctx_last_kernel(beatamd_ctx *ctx, char *buf, int64_t buflen)
 {

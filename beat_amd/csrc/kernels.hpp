@@ -455,4 +455,13 @@ struct PredCovSet {
 int launch_pred_covariance(beatamd_ctx *ctx, int64_t K, int64_t Nobs, const double *X, double *D, int64_t nd, int64_t nmax,
                            const PredCovSet *sets);
 
+// ---- noise2d.hip: the 2-d neighbourhood statistic of the geodetic "non-toeplitz" noise structure (covariance.py:774-811)
+// radius [nd], counts / stds [Ntot] of the datasets of a composite in one call (k_ball_maxd2, k_ball_radius, k_ball_rms);
+// sets: device table [nd], nmax = the largest n; pmax [Ntot]: device scratch for the per-point largest squared distance
+struct BallSet {
+    int64_t off, n;   // first point of the dataset in the concatenated arrays, its size
+};
+int launch_ball_rms(beatamd_ctx *ctx, int64_t nd, int64_t nmax, const BallSet *sets, const double *coords, const double *data,
+                    double max_dist_perc, double *pmax, double *radius, int32_t *counts, double *stds);
+
 }  // namespace beatamd

@@ -347,6 +347,25 @@ class Context(object):
         check(self._lib.beatamd_scaled_toeplitz_batch(self._h, nd, n, ptr(c), ptr(s), ptr(out)))
         return out
 
+    def ball_rms_batch(self, coords, data, sizes, max_dist_perc):
+        """covariance.k_nearest_neighbor_rms (covariance.py:774-811, max_dist_perc branch) for the datasets of a composite
+        in one call: coords (Ntot, 2) east / north, data (Ntot,), both concatenated over datasets of ``sizes`` points ->
+        (radius (nd,), counts (Ntot,) int32, stds (Ntot,)) in the one order include/beat_amd.h states
+        (tests/noise2d_ref.py restates it bit for bit).  numpy in -> numpy out, torch-cuda in -> tensors on the same device."""
+        c, d = f64(coords), f64(data)
+        self._adopt_stream(c, d)
+        n = _i64arr(sizes).ravel()
+        nd, ntot = int(n.size), int(n.sum()) if n.size else 0
+        if tuple(c.shape) != (ntot, 2) or tuple(d.shape) != (ntot,):
+            raise ValueError("ball_rms_batch: coords %s and data %s for %d points in all: expected (%d, 2) and (%d,)"
+                             % (tuple(c.shape), tuple(d.shape), ntot, ntot, ntot))
+        if _is_dev(c) != _is_dev(d):
+            raise ValueError("ball_rms_batch: coords and data must live on the same side")
+        radius, counts, stds = _empty_like(c, (nd,)), _empty_like(c, (ntot,), np.int32), _empty_like(c, (ntot,))
+        check(self._lib.beatamd_ball_rms_batch(self._h, nd, ptr(n), ptr(c), ptr(d), float(max_dist_perc), ptr(radius),
+                                               ptr(counts), ptr(stds)))
+        return radius, counts, stds
+
     # -- fused FFI model
     def ffi_model_create(self, layout, n_patch_dip, n_patch_strike, patch_size):
         nd = np.ascontiguousarray(n_patch_dip, dtype=np.int32)

@@ -132,7 +132,7 @@ class Covariance(object):
     def inverse_d(self):
         if self._terms["data"] is None:
             raise AttributeError("No data covariance matrix defined!")
-        return self._inv(self._terms["data"], "No covariances given!")
+        return self._inv(self._resolve("data"), "No covariances given!")
 
     # -- factors and weights
     def chol(self, factor=1.0):

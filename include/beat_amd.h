@@ -429,6 +429,29 @@ int beatamd_autocovariance_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const 
 int beatamd_scaled_toeplitz_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *coeffs,
                                   const double *stds, double *out);
 
+/* replaces: covariance.k_nearest_neighbor_rms(coords, data, max_dist_perc=...)   beat/covariance.py:774-811
+ *           (the max_dist_perc branch; what GeodeticNoiseAnalyser.do_non_toeplitz :193-210 reaches through
+ *           non_toeplitz_covariance_2d :831-848 and toeplitz_covariance_2d :814-828 for every SAR scene when
+ *           GeodeticDistributerComposite.update_weights, geodetic.py:1145-1148, re-estimates the data covariances)
+ *   nd datasets of sizes[i] points, concatenated: coords [Ntot, 2] (east, north), data [Ntot] -> radius [nd],
+ *   counts [Ntot] (neighbours of each point, itself included), stds [Ntot].  Arrays may live on either side.
+ *   THE ORDER, per dataset of n points, plain products and sums (no contraction):
+ *       d2(i,j) = dx*dx + dy*dy;   radius = sqrt(max_ij d2) * max_dist_perc  (sqrt correctly rounded: bit for bit
+ *       utility.distances(coords, coords).max() * max_dist_perc);   j neighbours i iff d2(i,j) <= radius*radius
+ *       (the same sets as scipy's KDTree.query_ball_point, exact ties included);
+ *       a sum over the neighbours of i: 64 partials, partial l takes the neighbours j == l (mod 64) in ascending j
+ *       from 0, then partial[l] += partial[l + h] for l < h, h = 32, 16, 8, 4, 2, 1;
+ *       mean = sum(x_j) / count;   stds[i] = sqrt(sum((x_j - mean)^2) / (count - 1));   count < 2: NaN (as numpy.std
+ *       with ddof = 1).
+ *   It depends on (i, n) alone -- not on the launch geometry, not on the other datasets of the call.  The KD-tree
+ *   returns neighbours in no defined order, so the reference's last bits are not defined either: stds agree with it
+ *   to (count + 3) 2^-53 relative.  nd <= 0, a dataset of size 0 and a non-finite max_dist_perc: BEATAMD_EINVAL. */
+int beatamd_ball_rms_batch(beatamd_ctx *ctx, int64_t nd, const int64_t *sizes,
+                           const double *coords /* [Ntot, 2] east, north */,
+                           const double *data /* [Ntot] */, double max_dist_perc,
+                           double *radius /* [nd] */, int32_t *counts /* [Ntot] */,
+                           double *stds /* [Ntot] */);
+
 /* ---------------------------------------------------------------- SMC stage transition ----
  * The population (end points Q [C,nparams], likelihood vectors L [C,nllk]) stays in HBM between
  * stages; these entries run on device pointers (host pointers are staged like everywhere else).
