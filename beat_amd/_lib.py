@@ -114,6 +114,12 @@ _PROTOS = {
     "beatamd_smc_population_factor": [_vp, _i64, _i64, _vp, _vp, _vp],
     "beatamd_proposal_draw": [_vp, _i64, _i64, _i64, _vp, C.c_uint64, C.c_uint32, _i64, _i32, _vp, _vp],
     "beatamd_proposal_draw_univariate": [_vp, _i64, _i64, _i32, _vp, C.c_uint64, C.c_uint32, _i64, _vp, _vp],
+    "beatamd_proposal_draw_grouped": [_vp, _i64, _i64, _i64, _i64, _vp, C.c_uint64, C.c_uint32, _i64, _i32, _vp, _vp],
+    "beatamd_ffi_mstep_batch_grouped": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _i32, C.c_uint64, C.c_uint32, _i64,
+                                        _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp],
+    "beatamd_group_moments_reset": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "beatamd_group_moments_update": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp],
+    "beatamd_group_moments_factor": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "beatamd_gather_rows": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
     "beatamd_metropolis_tune": [_vp, _i64, _vp, _vp, _i32],
     "beatamd_ffi_model_nterm": [_vp, _i32, _pi64],

@@ -1285,6 +1285,23 @@ int beatamd_ffi_mstep_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, doubl
                        &d, accepted_sum, n_accepted);
 }
 
+int beatamd_ffi_mstep_batch_grouped(beatamd_ctx *ctx, int32_t model_id, int64_t C, int64_t G, double *Q0, double *L0,
+                                    const double *factor, int64_t K, int32_t df, uint64_t seed, uint32_t step,
+                                    int64_t first_chain, const double *scaling, const double *lower, const double *upper,
+                                    double beta, const double *betas, int32_t *accepted, int32_t *accepted_sum,
+                                    int64_t *n_accepted)
+{
+    BA_CHECK(ctx != nullptr, BEATAMD_EINVAL, "ctx is NULL");
+    BA_CHECK(factor && first_chain >= 0 && df >= 0 && df <= 64 && K > 0, BEATAMD_EINVAL, "ffi_mstep_grouped: bad argument");
+    BA_CHECK(G >= 1 && G <= 65535 && C >= 0 && C % G == 0, BEATAMD_EINVAL,
+             "ffi_mstep_grouped: %lld chains do not fall into %lld equal groups", (long long)C, (long long)G);
+    StepDraw d;
+    d.factor = factor; d.K = K; d.kind = -1; d.df = df; d.groups = G;
+    d.seed = seed; d.step = step; d.first_chain = (uint64_t)first_chain;
+    return astep_entry(ctx, model_id, C, Q0, L0, nullptr, scaling, lower, upper, nullptr, betas ? 1.0 : beta, betas, accepted,
+                       &d, accepted_sum, n_accepted);
+}
+
 // ------------------------------------------------------------------ noise covariance
 int beatamd_autocovariance_batch(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *data,
                                  const double *mean, double *out)
@@ -1522,6 +1539,91 @@ int beatamd_proposal_draw(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t nparam
     }
     BA_TRY(draw_multivariate(ctx, C, K, nparams, d_f, df, seed, step, (uint64_t)first_chain, d_d, d_u));
     BA_TRY(launch_step_advance(ctx));
+    return st.finish();
+}
+
+int beatamd_proposal_draw_grouped(beatamd_ctx *ctx, int64_t C, int64_t G, int64_t K, int64_t nparams, const double *factor,
+                                  uint64_t seed, uint32_t step, int64_t first_chain, int32_t df, double *delta, double *log_u)
+{
+    ENTER(ctx);
+    BA_CHECK(factor && delta && C >= 0 && K > 0 && nparams > 0 && df >= 0 && df <= 64 && first_chain >= 0, BEATAMD_EINVAL,
+             "proposal_draw_grouped: bad argument");
+    BA_CHECK(G >= 1 && G <= 65535 && C % G == 0, BEATAMD_EINVAL,
+             "proposal_draw_grouped: %lld chains do not fall into %lld equal groups", (long long)C, (long long)G);
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_f;
+    double *d_d, *d_u = nullptr;
+    BA_TRY(st.in(factor, (size_t)G * K * nparams, &d_f));
+    BA_TRY(st.out(delta, (size_t)C * nparams, &d_d));
+    if (log_u) {
+        BA_TRY(st.out(log_u, (size_t)C, &d_u));
+    }
+    BA_TRY(draw_multivariate(ctx, C, K, nparams, d_f, df, seed, step, (uint64_t)first_chain, d_d, d_u, G));
+    BA_TRY(launch_step_advance(ctx));
+    return st.finish();
+}
+
+// ------------------------------------------------------------------ PT proposal adaptation (ptadapt.hip)
+static int group_moments_shape(beatamd_ctx *ctx, const char *who, int64_t G, int64_t n)
+{
+    BA_CHECK(G >= 1 && G <= GM_MAX_G && n >= 1 && n <= GM_MAX_N, BEATAMD_EINVAL,
+             "%s: 1..%d groups of 1..%d parameters, got %lld of %lld", who, GM_MAX_G, GM_MAX_N, (long long)G, (long long)n);
+    return BEATAMD_OK;
+}
+
+int beatamd_group_moments_reset(beatamd_ctx *ctx, int64_t G, int64_t nparams, double *state, int64_t R, const double *Q,
+                                double *ref)
+{
+    ENTER(ctx);
+    BA_CHECK(state && (!ref || (Q && R >= 1 && R <= GM_MAX_R)), BEATAMD_EINVAL, "group_moments_reset: bad argument");
+    BA_TRY(group_moments_shape(ctx, "group_moments_reset", G, nparams));
+    Staging st(ctx);
+    const double *d_q = nullptr;
+    double *d_s, *d_r = nullptr;
+    BA_TRY(st.out(state, (size_t)(G * group_moments_stride(nparams)), &d_s));
+    if (ref) {
+        BA_TRY(st.in(Q, (size_t)(G * R * nparams), &d_q));
+        BA_TRY(st.out(ref, (size_t)(G * nparams), &d_r));
+    }
+    BA_TRY(launch_group_moments_reset(ctx, G, nparams, d_s, R, d_q, d_r));
+    return st.finish();
+}
+
+int beatamd_group_moments_update(beatamd_ctx *ctx, int64_t G, int64_t R, int64_t nparams, const double *Q, const double *like,
+                                 int64_t like_stride, const double *ref, double *state)
+{
+    ENTER(ctx);
+    BA_CHECK(Q && like && ref && state && like_stride > 0, BEATAMD_EINVAL, "group_moments_update: bad argument");
+    BA_TRY(group_moments_shape(ctx, "group_moments_update", G, nparams));
+    BA_CHECK(R >= 1 && R <= GM_MAX_R, BEATAMD_EINVAL, "group_moments_update: 1..%d rows per group, got %lld", GM_MAX_R,
+             (long long)R);
+    Staging st(ctx);
+    const double *d_q, *d_l, *d_r;
+    double *d_s;
+    BA_TRY(st.in(Q, (size_t)(G * R * nparams), &d_q));
+    BA_TRY(st.in(like, (size_t)((G * R - 1) * like_stride + 1), &d_l));
+    BA_TRY(st.in(ref, (size_t)(G * nparams), &d_r));
+    BA_TRY(st.out(state, (size_t)(G * group_moments_stride(nparams)), &d_s, true));
+    BA_TRY(launch_group_moments_update(ctx, G, R, nparams, d_q, d_l, like_stride, d_r, d_s));
+    return st.finish();
+}
+
+int beatamd_group_moments_factor(beatamd_ctx *ctx, int64_t G, int64_t nparams, const double *state, double *factor,
+                                 double *cov, int32_t *flags)
+{
+    ENTER(ctx);
+    BA_CHECK(state && factor && flags, BEATAMD_EINVAL, "group_moments_factor: NULL argument");
+    BA_TRY(group_moments_shape(ctx, "group_moments_factor", G, nparams));
+    Staging st(ctx);
+    const double *d_s;
+    double *d_f, *d_c = nullptr;
+    int32_t *d_fl;
+    BA_TRY(st.in(state, (size_t)(G * group_moments_stride(nparams)), &d_s));
+    BA_TRY(st.out(factor, (size_t)(G * nparams * nparams), &d_f, true));   // (a flagged group's factor stays as it is)
+    if (cov) BA_TRY(st.out(cov, (size_t)(G * nparams * nparams), &d_c));
+    BA_TRY(st.out(flags, (size_t)G, &d_fl));
+    BA_TRY(launch_group_moments_factor(ctx, G, nparams, d_s, d_f, d_c, d_fl));
     return st.finish();
 }
 

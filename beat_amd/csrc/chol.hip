@@ -191,6 +191,21 @@ static int potrf_lower(beatamd_ctx *ctx, int64_t nbatch, int64_t np, double *A, 
     return BEATAMD_OK;
 }
 
+int launch_potrf_lower(beatamd_ctx *ctx, int64_t nbatch, int64_t np, double *A, int32_t *notpsd)
+{
+    BA_CHECK(A && notpsd && nbatch > 0 && nbatch <= 65535 && np > 0 && np % CH_NB == 0, BEATAMD_EINVAL,
+             "potrf_lower: bad argument");
+    const int nblk = (int)(np / CH_NB);
+    double *X, *Dinv, *logd;   // (k_chol_diag leaves the inverses of the diagonal blocks in X and Dinv)
+    BA_TRY(ctx->scratch(SL_CHOL_X, (size_t)nbatch * np * np, &X));
+    BA_TRY(ctx->scratch(SL_CHOL_D, (size_t)nbatch * nblk * CH_NB * CH_NB, &Dinv));
+    BA_TRY(ctx->scratch(SL_CHOL_L, (size_t)nbatch * nblk, &logd));
+    BA_HIP(hipMemsetAsync(notpsd, 0, (size_t)nbatch * sizeof(int32_t), ctx->stream));
+    BA_TRY(potrf_lower(ctx, nbatch, np, A, Dinv, X, logd, notpsd));
+    BA_HIP(hipGetLastError());
+    return BEATAMD_OK;
+}
+
 int launch_chol_inverse(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const double *C, double *W, double *log_pdet,
                         int32_t *notpsd)
 {

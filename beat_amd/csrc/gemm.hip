@@ -33,6 +33,7 @@ struct GemmArgs {
     int ncb;
     // batched / accumulating form used by the blocked factorisations (chol.hip)
     int64_t sA, sB, sO;   // element strides between the matrices of a batch (blockIdx.y)
+    int64_t sR;           // the same for row_scale
     double alpha;         // O = alpha * (A . Bop) [+ O when accumulate]
     int accumulate;
     int lower_only;       // M x N output with M == N: tiles strictly above the diagonal are skipped
@@ -69,6 +70,7 @@ __global__ void __launch_bounds__(256) k_gemm_f64(GemmArgs a)
     a.A += (int64_t)blockIdx.y * a.sA;
     a.B += (int64_t)blockIdx.y * a.sB;
     a.O += (int64_t)blockIdx.y * a.sO;
+    if (a.row_scale) a.row_scale += (int64_t)blockIdx.y * a.sR;
 
     // A tile [64 x 16]: thread -> row lr, 4 consecutive k
     const int lr = tid >> 2, lk = (tid & 3) * 4;
@@ -167,7 +169,7 @@ int launch_gemm_f64(beatamd_ctx *ctx, const GemmCall &k)
     a.b_kn = k.b_kn;
     a.b_upper = k.b_kn ? 0 : k.b_upper;
     a.vec_ok = (k.lda % 2 == 0) && (k.ldb % 2 == 0) && (((uintptr_t)k.A | (uintptr_t)k.B) % 16 == 0);
-    a.sA = k.sA; a.sB = k.sB; a.sO = k.sO;
+    a.sA = k.sA; a.sB = k.sB; a.sO = k.sO; a.sR = k.sR;
     a.alpha = k.alpha; a.accumulate = k.accumulate;
     a.lower_only = k.lower_only;
     a.b_lower = k.b_kn ? k.b_lower : 0;

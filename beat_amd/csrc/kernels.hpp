@@ -346,6 +346,7 @@ struct GemmCall {
     // batched / accumulating form (chol.hip): O = alpha * A.Bop (+ O); matrices sA/sB/sO apart
     int nbatch = 1;
     int64_t sA = 0, sB = 0, sO = 0;
+    int64_t sR = 0;   // row_scale entries between the matrices of a batch
     double alpha = 1.0;
     int accumulate = 0;
     int lower_only = 0;   // M == N: tiles strictly above the diagonal are skipped
@@ -362,6 +363,9 @@ int launch_chol_inverse(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const doubl
 int launch_gram_cholesky(beatamd_ctx *ctx, int64_t K, int64_t n, const double *F, double *R);
 // M = Wn . inv(Wo) for stacks of upper-triangular matrices (device pointers)
 int launch_triu_ratio(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const double *Wn, const double *Wo, double *M);
+// lower Cholesky factors of the padded matrices A [nbatch][np][np] in place (np a multiple of 64, identity in the
+// padding; lower triangles read); notpsd [nbatch] (device) = 1 where a pivot was not positive
+int launch_potrf_lower(beatamd_ctx *ctx, int64_t nbatch, int64_t np, double *A, int32_t *notpsd);
 // X[b, :] = inv(W[b]) . X[b, :] for upper-triangular W (one vector per matrix, back substitution)
 int launch_triu_solve_vec(beatamd_ctx *ctx, int64_t nbatch, int64_t n, const double *W, double *X);
 
@@ -383,11 +387,12 @@ int launch_philox_univariate(beatamd_ctx *ctx, double *delta, int64_t C, int64_t
 int launch_step_advance(beatamd_ctx *ctx);
 // small parameter vectors (K, np <= 64): draws + factor product + propose in one launch; kind -1
 // multivariate (factor [K, np]), 0..3 the per-parameter families (factor = scales [np], K == np)
+// groups > 1 (multivariate; C a multiple of it): factor [groups, K, np], chain c draws with factor c / (C / groups)
 bool draw_propose_applicable(int64_t K, int64_t np);
 int launch_draw_propose(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, int kind, const double *factor,
                         int df, uint64_t seed, uint32_t step, uint64_t first_chain, const double *Q0,
                         const double *scaling, const double *lower, const double *upper, double *Qprop,
-                        double *log_u, int32_t *inbounds);
+                        double *log_u, int32_t *inbounds, int64_t groups = 1);
 int launch_philox_chain(beatamd_ctx *ctx, int64_t C, uint64_t seed, uint32_t step, uint64_t first_chain,
                         int df, double *log_u, double *row_scale);
 // the step around the forward model (metropolis.py:276-422 pieces): propose before it, accept behind it
@@ -439,6 +444,20 @@ int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int6
 // an index outside the grid or a non-finite sample raises the status word
 int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
                          const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid);
+
+// ---- ptadapt.hip: streaming likelihood-weighted moments of groups of chains and the proposal factors out of them
+// state of a group: GM_HDR header doubles (m, S0, Sw2, count, nbad, 3 spare), S1 [n], S2 [n, n] (lower triangle)
+constexpr int GM_HDR = 8, GM_MAX_R = 1024, GM_MAX_N = 2048, GM_MAX_G = 64;
+inline int64_t group_moments_stride(int64_t n) { return GM_HDR + n + n * n; }
+// empty state; ref (nullable) [G, n] = mean of the R rows of every group of Q
+int launch_group_moments_reset(beatamd_ctx *ctx, int64_t G, int64_t n, double *state, int64_t R, const double *Q, double *ref);
+// the R rows of every group (rows g R .. g R + R - 1 of Q [G R, n]; like[(g R + r) like_stride]; ref [G, n]) into state
+int launch_group_moments_update(beatamd_ctx *ctx, int64_t G, int64_t R, int64_t n, const double *Q, const double *like,
+                                int64_t like_stride, const double *ref, double *state);
+// factor [G, n, n] upper with F^T F = cov, cov [G, n, n] (nullable), flags [G]: 0 ok, 1 bad moments, 2 not positive definite
+// (the factor of a flagged group is not written)
+int launch_group_moments_factor(beatamd_ctx *ctx, int64_t G, int64_t n, const double *state, double *factor, double *cov,
+                                int32_t *flags);
 
 // ---- predcov.hip: velocity-model prediction covariance of the geodetic datasets (geodetic.py:1130-1202)
 // X[k, :] = sum_v G_{k,v}.T . slips_v for the K variants of a library ensemble (k_crust_stack); G: device table [K * nvar],

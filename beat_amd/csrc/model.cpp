@@ -321,7 +321,7 @@ int model_obs_quads(beatamd_ctx *ctx, FfiModel &m)
 
 // ------------------------------------------------------------------ fused Metropolis step
 int draw_multivariate(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, const double *factor, int df, uint64_t seed,
-                      uint32_t step, uint64_t first_chain, double *delta, double *log_u)
+                      uint32_t step, uint64_t first_chain, double *delta, double *log_u, int64_t groups)
 {
     double *z, *rs = nullptr;
     BA_TRY(ctx->scratch(SL_Z, (size_t)C * K, &z));
@@ -334,6 +334,11 @@ int draw_multivariate(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, const 
     g.O = delta; g.ldo = np;
     g.M = C; g.N = np; g.K = K;
     g.row_scale = rs;
+    if (groups > 1) {   // one product per group: an entry's sum over k is the one of the single product
+        const int64_t R = C / groups;
+        g.M = R; g.nbatch = (int)groups;
+        g.sA = R * K; g.sB = K * np; g.sO = R * np; g.sR = R;
+    }
     g.timer = "proposal";
     return launch_gemm_f64(ctx, g);
 }
@@ -349,10 +354,10 @@ static int draw_proposals(beatamd_ctx *ctx, const StepDraw &draw, int64_t C, int
     *lu_out = lu;
     if (draw_propose_applicable(K, np))
         return launch_draw_propose(ctx, C, K, np, draw.kind, d_f, draw.df, draw.seed, draw.step, draw.first_chain, d_q0, d_sc,
-                                   d_lo, d_up, qprop, lu, inb);
+                                   d_lo, d_up, qprop, lu, inb, draw.groups);
     BA_TRY(ctx->scratch(SL_DELTA, (size_t)C * np, &de));
     if (draw.kind < 0) {
-        BA_TRY(draw_multivariate(ctx, C, K, np, d_f, draw.df, draw.seed, draw.step, draw.first_chain, de, lu));
+        BA_TRY(draw_multivariate(ctx, C, K, np, d_f, draw.df, draw.seed, draw.step, draw.first_chain, de, lu, draw.groups));
     } else {
         BA_TRY(launch_philox_univariate(ctx, de, C, np, draw.kind, d_f, draw.seed, draw.step, draw.first_chain));
         BA_TRY(launch_philox_chain(ctx, C, draw.seed, draw.step, draw.first_chain, 0, lu, nullptr));
@@ -388,7 +393,7 @@ int astep_impl(beatamd_ctx *ctx, FfiModel &m, int64_t C, double *Q0, double *L0,
     if (draw) {
         BA_CHECK(is_device_ptr(Q0) && (!acc_sum || is_device_ptr(acc_sum)) && (!n_acc || is_device_ptr(n_acc)),
                  BEATAMD_EINVAL, "ffi_mstep: chain states and counters live on the device");
-        BA_TRY(st.in(draw->factor, (size_t)(draw->kind < 0 ? draw->K * np : np), &d_f));
+        BA_TRY(st.in(draw->factor, (size_t)(draw->kind < 0 ? draw->groups * draw->K * np : np), &d_f));
         BA_TRY(draw_proposals(ctx, *draw, C, np, d_f, d_q0, d_sc, d_lo, d_up, qprop, inb, &d_lu));
     } else {
         BA_TRY(st.in(delta, (size_t)C * np, &d_de));

@@ -65,10 +65,12 @@ struct StepDraw {
     int32_t kind = -1, df = 0;
     uint64_t seed = 0, first_chain = 0;
     uint32_t step = 0;
+    int64_t groups = 1;               // multivariate: factor [groups, K, np], chain c draws with factor c / (C / groups)
 };
+// (groups > 1: factor [groups, K, np], the chains in `groups` equal runs, one factor each)
 // delta [C, np] = z . factor for z ~ N(0, 1) [C, K] drawn here, the rows scaled to multivariate t for df > 0; log_u [C] nullable
 int draw_multivariate(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, const double *factor, int df, uint64_t seed,
-                      uint32_t step, uint64_t first_chain, double *delta, double *log_u);
+                      uint32_t step, uint64_t first_chain, double *delta, double *log_u, int64_t groups = 1);
 int astep_impl(beatamd_ctx *ctx, FfiModel &m, int64_t C, double *Q0, double *L0, const double *delta, const double *scaling,
                const double *lower, const double *upper, const double *log_u, double beta, const double *betas,
                int32_t *accepted, const StepDraw *draw = nullptr, int32_t *acc_sum = nullptr, int64_t *n_acc = nullptr);

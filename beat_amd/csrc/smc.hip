@@ -370,6 +370,7 @@ struct DrawProposeArgs {
     int64_t C, K, np;
     int kind;                 // -1 multivariate (factor [K, np], df), else the univariate family
     const double *factor;     // [K, np] or the per-parameter scales [np]
+    int64_t cpg, sF;          // chains per proposal group (C: one factor for all) and the factors' stride
     int df;
     uint64_t seed, first_chain;
     uint32_t step;
@@ -388,12 +389,15 @@ __global__ void __launch_bounds__(256) k_draw_propose(DrawProposeArgs a)
     __shared__ int ok[DP_CB];
     const uint32_t step = a.step_dev ? *a.step_dev : a.step;
     const int tid = threadIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.x * DP_CB;
-    const int nc = (int)min((int64_t)DP_CB, a.C - c0);
+    // a workgroup's chains share a factor: the groups are cut into workgroups one by one
+    const int64_t bpg = (a.cpg + DP_CB - 1) / DP_CB, grp = (int64_t)blockIdx.x / bpg;
+    const int64_t c0 = grp * a.cpg + ((int64_t)blockIdx.x - grp * bpg) * DP_CB;
+    const int nc = (int)min((int64_t)DP_CB, (grp + 1) * a.cpg - c0);
+    const double *factor = a.factor + grp * a.sF;
     const int K = (int)a.K, np = (int)a.np;
     const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
     if (a.kind < 0)
-        for (int i = tid; i < K * np; i += 256) Fs[i] = a.factor[i];
+        for (int i = tid; i < K * np; i += 256) Fs[i] = factor[i];
     const int npair = (K + 1) / 2;
     for (int i = tid; i < nc * npair; i += 256) {
         const int c = i / npair, j = i - c * npair;
@@ -404,8 +408,8 @@ __global__ void __launch_bounds__(256) k_draw_propose(DrawProposeArgs a)
             philox4x32_10((uint32_t)j, gc, step, 0u, k0, k1, r);
             box_muller(r, x, y);
         } else {
-            philox_scaled_pair(a.kind, (uint32_t)j, gc, step, k0, k1, a.factor[2 * j],
-                               (2 * j + 1 < K) ? a.factor[2 * j + 1] : 0.0, a.status, x, y);
+            philox_scaled_pair(a.kind, (uint32_t)j, gc, step, k0, k1, factor[2 * j],
+                               (2 * j + 1 < K) ? factor[2 * j + 1] : 0.0, a.status, x, y);
         }
         zs[c][2 * j] = x;
         if (2 * j + 1 < K) zs[c][2 * j + 1] = y;
@@ -449,17 +453,18 @@ bool draw_propose_applicable(int64_t K, int64_t np) { return K >= 1 && K <= DP_M
 int launch_draw_propose(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, int kind, const double *factor,
                         int df, uint64_t seed, uint32_t step, uint64_t first_chain, const double *Q0,
                         const double *scaling, const double *lower, const double *upper, double *Qprop,
-                        double *log_u, int32_t *inbounds)
+                        double *log_u, int32_t *inbounds, int64_t groups)
 {
     if (C == 0) return BEATAMD_OK;
     DrawProposeArgs a;
     a.C = C; a.K = K; a.np = np; a.kind = kind; a.factor = factor; a.df = df;
+    a.cpg = C / groups; a.sF = groups > 1 ? K * np : 0;
     a.seed = seed; a.first_chain = first_chain; a.step = step; a.step_dev = ctx->step_dev;
     a.status = ctx->d_status;
     a.Q0 = Q0; a.scaling = scaling; a.lower = lower; a.upper = upper;
     a.Qprop = Qprop; a.log_u = log_u; a.inbounds = inbounds;
     ScopedTimer tm(ctx, "proposal");
-    hipLaunchKernelGGL(k_draw_propose, dim3((unsigned)((C + DP_CB - 1) / DP_CB)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_draw_propose, dim3((unsigned)(groups * ((a.cpg + DP_CB - 1) / DP_CB))), dim3(256), 0, ctx->stream, a);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

@@ -520,6 +520,25 @@ class Context(object):
             None if n_accepted is None else ptr(n_accepted)))
         return accepted
 
+    def ffi_mstep_batch_grouped(self, model_id, Q0, L0, factors, df, seed, step, first_chain, scaling, lower, upper,
+                                beta, accepted, accepted_sum=None, n_accepted=None):
+        """``ffi_mstep_batch`` with one multivariate factor per group of chains (beatamd_ffi_mstep_batch_grouped):
+        ``factors`` [G, K, nparams], chain c draws with factor c // (C // G)"""
+        self._adopt_stream(Q0, L0)
+        Cn = int(Q0.shape[0])
+        fa, sc, lo, up = f64(factors), f64(scaling), f64(lower), f64(upper)
+        if fa.ndim != 3:
+            raise ValueError("ffi_mstep_batch_grouped: factors must be (groups, K, nparams)")
+        G, K = int(fa.shape[0]), int(fa.shape[1])
+        scalar = np.ndim(beta) == 0 and not hasattr(beta, "data_ptr")
+        be = None if scalar else f64(beta)
+        check(self._lib.beatamd_ffi_mstep_batch_grouped(
+            self._h, model_id, Cn, G, ptr(Q0), ptr(L0), ptr(fa), K, int(df), int(seed) & (2 ** 64 - 1),
+            int(step) & 0xffffffff, int(first_chain), ptr(sc), ptr(lo), ptr(up), float(beta) if scalar else 1.0,
+            None if scalar else ptr(be), ptr(accepted), None if accepted_sum is None else ptr(accepted_sum),
+            None if n_accepted is None else ptr(n_accepted)))
+        return accepted
+
     # -- introspection
     def last_kernel(self):
         """name<template arguments> of the stacking kernel the most recent call launched"""
@@ -627,6 +646,86 @@ class Context(object):
                                               int(step) & 0xffffffff, int(first_chain), int(df), ptr(delta),
                                               ptr(log_u)))
         return delta, log_u
+
+    def proposal_draw_grouped(self, factors, n_chains, seed, step, first_chain=0, df=0, delta=None, log_u=None,
+                              want_log_u=True):
+        """``proposal_draw`` with one factor per group of chains: factors (G, K, nparams), chain c of the call draws with
+        factor c // (n_chains // G) (beatamd_proposal_draw_grouped); -> (delta, log_u)"""
+        self._adopt_stream(factors)
+        F = f64(factors)
+        if F.ndim != 3:
+            raise ValueError("proposal_draw_grouped: factors must be (groups, K, nparams)")
+        G, K, npar = int(F.shape[0]), int(F.shape[1]), int(F.shape[2])
+        if delta is None:
+            delta = _empty_like(F, (int(n_chains), npar))
+        if log_u is None and want_log_u:
+            log_u = _empty_like(F, (int(n_chains),))
+        check(self._lib.beatamd_proposal_draw_grouped(self._h, int(n_chains), G, K, npar, ptr(F), int(seed) & (2 ** 64 - 1),
+                                                      int(step) & 0xffffffff, int(first_chain), int(df), ptr(delta),
+                                                      ptr(log_u)))
+        return delta, log_u
+
+    # -- PT proposal adaptation: streaming likelihood-weighted moments per group of chains (ptadapt.hip)
+    @staticmethod
+    def group_moments_stride(nparams):
+        """doubles of one group's state: header (m, S0, Sw2, count, nbad, 3 spare), S1 [n], S2 [n, n] (lower triangle)"""
+        return 8 + int(nparams) + int(nparams) ** 2
+
+    def group_moments_reset(self, state, nparams, Q=None, ref=None):
+        """state (G, 8 + n + n*n), numpy or torch-cuda, in place: m = -inf, every sum 0.  With Q (G * R, n) and ref (G, n):
+        ref[g] = mean of the group's rows, written in place (the reference point of the window that opens)"""
+        self._adopt_stream(state)
+        S = self._group_state(state, nparams)
+        G, R, Qc = int(S.shape[0]), 0, None
+        if ref is not None:
+            Qc = f64(Q)
+            if isinstance(ref, np.ndarray) and not (ref.flags.c_contiguous and ref.dtype == np.float64):
+                raise ValueError("group_moments_reset: ref must be C-contiguous float64 (written in place)")
+            if int(Qc.shape[0]) % G or int(Qc.shape[1]) != int(nparams) or tuple(f64(ref).shape) != (G, int(nparams)):
+                raise ValueError("group_moments_reset: Q (G * R, nparams), ref (G, nparams) for the G groups of the state")
+            R = int(Qc.shape[0]) // G
+        check(self._lib.beatamd_group_moments_reset(self._h, G, int(nparams), ptr(S), R, ptr(Qc),
+                                                    None if ref is None else ptr(ref)))
+        return state
+
+    def _group_state(self, state, nparams):
+        ok = state.flags.c_contiguous and state.dtype == np.float64 if isinstance(state, np.ndarray) else True
+        S = f64(state)
+        if not ok or S.ndim != 2 or int(S.shape[1]) != self.group_moments_stride(nparams):
+            raise ValueError("group moments: state must be C-contiguous float64 (groups, 8 + nparams + nparams^2)")
+        return S
+
+    def group_moments_update(self, state, Q, like, ref, like_stride=1):
+        """add the rows of Q (G * R, n) -- R consecutive rows per group -- with weights exp(like - running maximum) to
+        state, in place; like: (G * R,) array, or a strided view (see ``sampler.ops._Base``) with like_stride; ref (G, n)"""
+        self._adopt_stream(state, Q)
+        Qc, rf = f64(Q), f64(ref)
+        lk = f64(like)
+        npar = int(Qc.shape[1])
+        S = self._group_state(state, npar)
+        G = int(S.shape[0])
+        if int(Qc.shape[0]) % G or tuple(rf.shape) != (G, npar):
+            raise ValueError("group_moments_update: Q (G * R, nparams), ref (G, nparams) for the G groups of the state")
+        check(self._lib.beatamd_group_moments_update(self._h, G, int(Qc.shape[0]) // G, npar, ptr(Qc), ptr(lk),
+                                                     int(like_stride), ptr(rf), ptr(S)))
+        return state
+
+    def group_moments_factor(self, state, nparams, factor, want_cov=False):
+        """-> (factor, cov or None, flags int32 (G,)): the upper Cholesky factors (G, n, n) of the groups' weighted sample
+        covariances written into ``factor`` (a flagged group's is left untouched; flags: 1 degenerate or non-finite
+        moments, 2 not positive definite)"""
+        self._adopt_stream(state, factor)
+        S = self._group_state(state, nparams)
+        G, n = int(S.shape[0]), int(nparams)
+        if isinstance(factor, np.ndarray) and not (factor.flags.c_contiguous and factor.dtype == np.float64):
+            raise ValueError("group_moments_factor: factor must be C-contiguous float64 (written in place)")
+        F = f64(factor)
+        if tuple(F.shape) != (G, n, n):
+            raise ValueError("group_moments_factor: factor must be (groups, nparams, nparams)")
+        cov = _empty_like(S, (G, n, n)) if want_cov else None
+        flags = _empty_like(S, (G,), np.int32)
+        check(self._lib.beatamd_group_moments_factor(self._h, G, n, ptr(S), ptr(F), ptr(cov), ptr(flags)))
+        return factor, cov, flags
 
     def proposal_draw_univariate(self, kind, scale, n_chains, seed, step, first_chain=0, delta=None, log_u=None,
                                  want_log_u=True):

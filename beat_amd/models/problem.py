@@ -372,6 +372,12 @@ class LogpForwFunc(object):
         return self.ctx.ffi_mstep_batch(self.model_id, Q0, L0, factor, kind, df, seed, step, first_chain,
                                         scaling, lower, upper, beta, accepted, accepted_sum, n_accepted)
 
+    def mstep_batch_grouped(self, Q0, L0, factors, df, seed, step, first_chain, scaling, lower, upper, beta,
+                            accepted, accepted_sum=None, n_accepted=None):
+        """``mstep_batch`` with one multivariate factor per group of chains (the temperatures of a PT run)"""
+        return self.ctx.ffi_mstep_batch_grouped(self.model_id, Q0, L0, factors, df, seed, step, first_chain,
+                                                scaling, lower, upper, beta, accepted, accepted_sum, n_accepted)
+
     def round_libraries_to_f32(self):
         """Float-storage mode (SURVEY 8(f) row 2 "optional fp32 layout"), an explicit and IRREVERSIBLE choice of
         the caller: every seismic library of the model is rounded in HBM to float-representable values

@@ -39,6 +39,7 @@ class BatchedMetropolis(object):
         self._acc = torch.zeros(self.n_chains, dtype=torch.int32, device=self.device)
         self.seed = int(seed)
         self.factor, self.df = None, 0
+        self.group_factors = None             # (groups, K, nparams): one multivariate factor per run of chains
         self.kind, self.uscale = None, None   # per-parameter proposal family and its scales
         self.use_chain_batch = True   # take target.chain_batch (a whole run in one launch) where it applies
 
@@ -61,7 +62,24 @@ class BatchedMetropolis(object):
             return self._set_univariate(proposal_name, cov)
         self.df = proposal_df(proposal_name)
         self.kind = None
+        self.group_factors = None
         self.factor = self.torch.from_numpy(covariance_factor(cov)).to(self.device)
+
+    def set_group_proposals(self, factors):
+        """one multivariate proposal per group of chains: factors (groups, K, nparams) on self.device, F_g^T F_g the
+        covariance of group g; the chains fall into `groups` equal consecutive runs (the temperatures of a PT rank, whose
+        workers each learn their own proposal: beat/sampler/pt.py:758-761).  The family (normal / t) stays the one of
+        ``set_proposal``; the tensor is used as it is, so updating it in place changes the proposals"""
+        if self.kind is not None or self.factor is None:
+            raise ValueError("group proposals belong to a multivariate family: call set_proposal first")
+        if factors.dim() != 3 or int(factors.shape[2]) != int(self.lower.shape[0]) or self.n_chains % int(factors.shape[0]):
+            raise ValueError("set_group_proposals: factors (groups, K, nparams) with %d chains a multiple of groups, got %s"
+                             % (self.n_chains, tuple(factors.shape)))
+        self.group_factors = factors.contiguous()
+
+    def clear_group_proposals(self):
+        """back to the one proposal of ``set_proposal``"""
+        self.group_factors = None
 
     def set_proposal_from_population(self, population, weights, proposal_name="MultivariateNormal"):
         """proposal with the weighted sample covariance of the population (SMC.calc_covariance,
@@ -185,6 +203,20 @@ class BatchedMetropolis(object):
     def _draw_and_astep(self, Q, L, beta, n_acc=None):
         if self.factor is None and self.kind is None:
             raise RuntimeError("no proposal set: call set_proposal / set_proposal_from_population")
+        if self.group_factors is not None and self.kind is None:
+            G = int(self.group_factors.shape[0])
+            if Q.is_cuda and hasattr(self.target, "mstep_batch_grouped"):
+                self.target.mstep_batch_grouped(Q, L, self.group_factors, self.df, self.seed, self.n_steps_total,
+                                                self.first_chain, self.scaling, self.lower, self.upper, beta, self._acc,
+                                                self.accepted_since_tune, n_acc)
+                return
+            delta, log_u = self.ops.draw(self.group_factors, self.n_chains, self.seed, self.n_steps_total,
+                                         first_chain=self.first_chain, df=self.df, groups=G)
+            self.target.astep_batch(Q, L, delta, self.scaling, self.lower, self.upper, log_u, beta, self._acc)
+            self.accepted_since_tune += self._acc
+            if n_acc is not None:
+                n_acc += self._acc.sum()
+            return
         if Q.is_cuda and hasattr(self.target, "mstep_batch"):
             # draws, proposal, forward model, accept and the acceptance counters: one device call
             self.target.mstep_batch(Q, L, self.factor if self.kind is None else self.uscale, self.kind, self.df,

@@ -19,6 +19,7 @@ import numpy as np
 
 BAD_COVARIANCE = ("Sample covariances contains Inf or NaN! Please try reducing the upper and lower bounds "
                   "of hyper parameters!")
+GROUP_MOMENTS_HDR = 8   # doubles in front of S1 / S2 of a group's moment state: m, S0, Sw2, count, nbad, 3 spare
 TUNE_TABLE = ((0.001, 0.1), (0.05, 0.5), (0.2, 0.9))  # acc <  x -> factor (first match)
 TUNE_TABLE_UP = ((0.95, 10.0), (0.75, 2.0), (0.5, 1.1))  # acc > x -> factor (first match)
 
@@ -81,10 +82,17 @@ class HostOps(object):
             raise ValueError(BAD_COVARIANCE)   # smc.py:181-185
         return self.torch.from_numpy(F)
 
-    def draw(self, factor, n_chains, seed, step, first_chain=0, df=0):
+    def draw(self, factor, n_chains, seed, step, first_chain=0, df=0, groups=None):
+        """groups: factor is (groups, K, nparams) and chain c draws with factor c // (n_chains // groups)"""
         F = self._np(factor)
         rs = np.random.RandomState((int(seed) * 1000003 + int(step) * 7919 + int(first_chain)) % (2 ** 32))
-        rows = rs.standard_normal((n_chains, F.shape[0])) @ F
+        if groups:
+            if F.ndim != 3 or F.shape[0] != groups or n_chains % groups:
+                raise ValueError("draw: %d chains do not fall into the %s groups of the factors" % (n_chains, groups))
+            z = rs.standard_normal((n_chains, F.shape[1])).reshape(groups, n_chains // groups, F.shape[1])
+            rows = np.matmul(z, F).reshape(n_chains, F.shape[2])
+        else:
+            rows = rs.standard_normal((n_chains, F.shape[0])) @ F
         if df:
             g = rs.standard_normal((n_chains, int(df)))
             rows = rows / np.sqrt((g * g).sum(1) / float(df))[:, None]
@@ -111,6 +119,71 @@ class HostOps(object):
 
     def gather(self, src, idx):
         return src[idx.long()].contiguous()
+
+    # -- PT proposal adaptation: numpy twins of beatamd_group_moments_* (csrc/ptadapt.hip; state layout: include/beat_amd.h)
+    def group_moments_alloc(self, n_groups, nparams, like=None):
+        return self.torch.zeros((int(n_groups), GROUP_MOMENTS_HDR + nparams + nparams * nparams), dtype=self.torch.float64)
+
+    def group_moments_reset(self, state, nparams, Q=None, ref=None):
+        st = self._np(state)
+        st[:] = 0.0
+        st[:, 0] = -np.inf
+        if ref is not None:
+            X = self._np(Q).reshape(st.shape[0], -1, nparams)
+            acc = np.zeros((st.shape[0], nparams))
+            for r in range(X.shape[1]):   # replica order
+                acc += X[:, r]
+            self._np(ref)[:] = acc / float(X.shape[1])
+        return state
+
+    def group_moments_update(self, state, Q, like, ref):
+        st, rf = self._np(state), self._np(ref)
+        G, n = rf.shape
+        X = self._np(Q).reshape(G, -1, n)
+        lk = np.asarray(self._np(like), dtype=np.float64).reshape(G, -1)
+        for g in range(G):
+            ok = np.isfinite(lk[g]) & np.isfinite(X[g]).all(1)
+            st[g, 4] += np.count_nonzero(~ok)
+            if not ok.any():
+                continue
+            m_new = max(st[g, 0], lk[g][ok].max())
+            s = np.exp(st[g, 0] - m_new)
+            w = np.exp(lk[g][ok] - m_new)
+            y = X[g][ok] - rf[g]
+            st[g, 0] = m_new
+            st[g, 1] = st[g, 1] * s + w.sum()
+            st[g, 2] = st[g, 2] * (s * s) + (w * w).sum()
+            st[g, 3] += w.size
+            S1 = st[g, GROUP_MOMENTS_HDR:GROUP_MOMENTS_HDR + n]
+            S2 = st[g, GROUP_MOMENTS_HDR + n:].reshape(n, n)
+            S1[:] = S1 * s + w @ y
+            S2[:] = S2 * s + np.tril((y * w[:, None]).T @ y)
+        return state
+
+    def group_moments_factor(self, state, nparams, factor, want_cov=False):
+        """-> (factor, cov or None, flags): flags 1 degenerate / non-finite moments, 2 not positive definite; the factor
+        (upper, F^T F = cov) of a flagged group is left as it is"""
+        st, F = self._np(state), self._np(factor)
+        G, n = st.shape[0], int(nparams)
+        cov = np.zeros((G, n, n))
+        flags = np.zeros(G, dtype=np.int32)
+        for g in range(G):
+            S0, Sw2 = st[g, 1], st[g, 2]
+            S1 = st[g, GROUP_MOMENTS_HDR:GROUP_MOMENTS_HDR + n]
+            S2 = np.tril(st[g, GROUP_MOMENTS_HDR + n:].reshape(n, n))
+            S2 = S2 + np.tril(S2, -1).T   # symmetrised by copy
+            with np.errstate(all="ignore"):
+                fact = 1.0 - Sw2 / (S0 * S0)
+                mu = S1 / S0
+                cov[g] = (S2 / S0 - np.outer(mu, mu)) / fact
+            if not (fact > 0.0) or st[g, 4] > 0 or not np.isfinite(cov[g]).all() or not np.isfinite(st[g, :2]).all():
+                flags[g] = 1
+                continue
+            try:
+                F[g] = np.linalg.cholesky(cov[g]).T
+            except np.linalg.LinAlgError:
+                flags[g] = 2
+        return factor, (self.torch.from_numpy(cov) if want_cov else None), self.torch.from_numpy(flags)
 
     def tune(self, scaling, accepted, interval):
         new = step_tune(scaling.numpy(), accepted.numpy() / float(interval))
@@ -154,8 +227,30 @@ class DeviceOps(object):
                 return R
         return F
 
-    def draw(self, factor, n_chains, seed, step, first_chain=0, df=0):
+    def draw(self, factor, n_chains, seed, step, first_chain=0, df=0, groups=None):
+        """groups: factor is (groups, K, nparams) and chain c draws with factor c // (n_chains // groups)"""
+        if groups:
+            if int(factor.shape[0]) != int(groups):
+                raise ValueError("draw: the factors are not those of %s groups" % groups)
+            return self.ctx.proposal_draw_grouped(factor, n_chains, seed, step, first_chain=first_chain, df=df)
         return self.ctx.proposal_draw(factor, n_chains, seed, step, first_chain=first_chain, df=df)
+
+    # -- PT proposal adaptation (beatamd_group_moments_*, csrc/ptadapt.hip)
+    def group_moments_alloc(self, n_groups, nparams, like=None):
+        import torch
+        return torch.zeros((int(n_groups), self.ctx.group_moments_stride(nparams)), dtype=torch.float64,
+                           device="cuda:%d" % self.ctx.device)
+
+    def group_moments_reset(self, state, nparams, Q=None, ref=None):
+        return self.ctx.group_moments_reset(state, nparams, Q, ref)
+
+    def group_moments_update(self, state, Q, like, ref):
+        """like: 1-D view (may be the strided `like` column of L)"""
+        stride = int(like.stride(0)) if like.dim() == 1 else 1
+        return self.ctx.group_moments_update(state, Q, _Base(like), ref, like_stride=stride)
+
+    def group_moments_factor(self, state, nparams, factor, want_cov=False):
+        return self.ctx.group_moments_factor(state, nparams, factor, want_cov=want_cov)
 
     def draw_univariate(self, kind, scale, n_chains, seed, step, first_chain=0):
         return self.ctx.proposal_draw_univariate(kind, scale, n_chains, seed, step, first_chain=first_chain)

@@ -12,10 +12,18 @@ swap rule, the beta ladder (``update_betas`` :179-221), the beta tuning (``tune_
 :331-354, ``tune`` :37-73) and the swap interval draw are the reference's; the pairing
 order differs (asynchronous first-arrivals are not reproducible) -- statistical, not bit,
 parity.
+
+Proposal adaptation (``update_proposal``): every reference worker re-learns its multivariate proposal from its own trace
+each time its buffer of ``buffer_size`` samples fills (``sample_pt_chain`` :758-761, ``_iter_sample`` base.py:363-393,
+``calc_sample_covariance`` covariance.py:865-909).  Here a temperature is a group of ``n_replicas`` chains; the window's
+likelihood-weighted moments are accumulated on the device after every step (``ProposalWindows``, csrc/ptadapt.hip) and
+each temperature steps with its own factor (``BatchedMetropolis.set_group_proposals``).
 """
 import numpy as np
 
 from .. import parallel
+from ..utility import ensure_cov_psd
+from .base import univariate_proposals
 from .metropolis import BatchedMetropolis
 
 
@@ -119,11 +127,83 @@ class TemperingManager(object):
         return self.update_betas(t_scale)
 
 
+class ProposalWindows(object):
+    """The trace buffers of the temperatures of one rank, as far as the proposal update reads them (backend.py:235-268,
+    base.py:363-393): a window per temperature slot collects the states of its ``n_replicas`` chains after every step as
+    streaming weighted moments; when it holds ``buffer_size`` samples it is closed -- the proposals are re-learned from it
+    iff the round it closes in began after burn-in (``begin_round``) --, emptied, and the last sample put back as the first
+    of the next window (keep_last).  Windows stay with the slot through swaps, as a worker's trace stays with the worker.
+
+    A group whose covariance does not factor (flag 2) is repaired on the host alone: ``utility.ensure_cov_psd`` and a numpy
+    Cholesky; a group with degenerate or non-finite moments (flag 1), or one whose repair fails, keeps its proposal (the
+    reference's cov = None).  Unlike the reference, which passes EVERY matrix through ensure_cov_psd, the factorisation
+    decides which matrices are repaired."""
+
+    def __init__(self, stepper, n_groups, nparams, buffer_size, burnin, updates, closed):
+        if int(buffer_size) < 2:
+            raise ValueError("update_proposal: buffer_size must be at least 2")
+        self.stepper, self.ops, self.torch = stepper, stepper.ops, stepper.torch
+        self.G, self.n = int(n_groups), int(nparams)
+        self.buffer_size, self.burnin = int(buffer_size), int(burnin)
+        self.updates, self.closed = updates, closed
+        self.count, self.update = 0, False
+        self.state = self.ops.group_moments_alloc(self.G, self.n) if self.G else None
+        self.ref = self.torch.zeros((self.G, self.n), dtype=self.torch.float64, device=stepper.device)
+        # every temperature starts from the proposal of set_proposal; the stepper takes the grouped path from the first update
+        self.factors = stepper.factor.unsqueeze(0).repeat(self.G, 1, 1).contiguous()
+
+    def begin_round(self, steps_taken):
+        """sample_pt_chain (pt.py:758-761): decided once per inter-swap run"""
+        self.update = steps_taken > self.burnin
+
+    def _add(self, Q, L):
+        if self.count == 0:
+            self.ops.group_moments_reset(self.state, self.n, Q, self.ref)
+        self.ops.group_moments_update(self.state, Q, L[:, -1], self.ref)
+        self.count += 1
+
+    def after_step(self, Q, L, step):
+        """the states after step number `step` (1-based count of the steps taken) enter the windows"""
+        if self.G == 0:
+            return
+        self._add(Q, L)
+        if self.count < self.buffer_size:
+            return
+        self.closed.append(step)
+        if self.update:
+            self.updates.append((step, self._relearn()))
+        self.count = 0
+        self._add(Q, L)   # keep_last
+
+    def _relearn(self):
+        _, cov, flags = self.ops.group_moments_factor(self.state, self.n, self.factors, want_cov=True)
+        flags = flags.cpu().numpy().copy()
+        for g in np.nonzero(flags == 2)[0]:
+            try:
+                F = np.linalg.cholesky(ensure_cov_psd(cov[g].cpu().numpy())).T
+            except np.linalg.LinAlgError:
+                continue
+            if np.isfinite(F).all():
+                self.factors[g].copy_(self.torch.from_numpy(np.ascontiguousarray(F)))
+        if self.stepper.group_factors is None:
+            self.stepper.set_group_proposals(self.factors)
+            self.factors = self.stepper.group_factors
+        return flags
+
+
 def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n_replicas=1,
               n_samples=1000, swap_interval=(100, 300), beta_tune_interval=10, proposal_cov=None,
-              device=None, random_seed=17, tune_interval=100, record_every=1):
+              device=None, random_seed=17, tune_interval=100, record_every=1, update_proposal=False,
+              buffer_size=5000, burnin=None, proposal_name="MultivariateNormal"):
     """pt.py:793-906 driver.  Returns (posterior samples (n, nparams), their likelihood
     vectors, manager).  Samples of the beta == 1 replicas are recorded after every round.
+
+    update_proposal: every temperature re-learns its multivariate proposal from its own window of ``buffer_size`` samples
+    once ``burnin`` steps (None: int(n_samples * 0.1), pt.py:518) are over (``ProposalWindows``); the per-parameter
+    families never update (base.py:368).  ``man.proposal_updates`` lists (step, flags of this rank's temperatures) per
+    update, ``man.windows_closed`` the steps at which windows closed, ``man.proposal_factors`` the factors in use at the
+    end (None before the first update).  proposal_name: the family of ``BatchedMetropolis.set_proposal`` (for a per-parameter
+    family ``proposal_cov`` is the vector of scales, None: ones).  With several ranks every temperature's replicas must lie on one rank.
 
     Exchange round: all-gather of ONE likelihood per replica, the swap sweep decided
     identically on every rank (shared RandomState), then the permutation is applied where the
@@ -135,14 +215,23 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
                            beta_tune_interval, random_seed)
     n_total = man.n_workers * n_replicas
     start, stop = parallel.chain_block(n_total, rank, world)
+    adapt = bool(update_proposal) and proposal_name not in univariate_proposals
+    if adapt and world > 1:
+        # a temperature's window is accumulated where its replicas live, without a collective: every rank checks every
+        # rank's block, so all of them raise together
+        for r in range(world):
+            if any(b % n_replicas for b in parallel.chain_block(n_total, r, world)):
+                raise ValueError("update_proposal: the chains of rank %d, %s, cut a temperature of %d replicas in two; "
+                                 "choose a rank count whose blocks end at temperature boundaries"
+                                 % (r, parallel.chain_block(n_total, r, world), n_replicas))
     lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
     stepper = BatchedMetropolis(target, lower, upper, stop - start, device=device,
                                 tune_interval=tune_interval, seed=random_seed, first_chain=start)
     dev = stepper.device
     ops = stepper.ops
-    if proposal_cov is None:
+    if proposal_cov is None and proposal_name not in univariate_proposals:
         proposal_cov = np.diag(((upper - lower) * 0.05) ** 2)
-    stepper.set_proposal(proposal_cov)
+    stepper.set_proposal(proposal_cov, proposal_name)
     Qall = lower + (upper - lower) * man.rng.random_sample((n_total, lower.size))
     Q = torch.from_numpy(np.ascontiguousarray(Qall[start:stop])).to(dev)
     L = stepper.evaluate(Q).to(dev)
@@ -152,6 +241,12 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
     p0, p1 = min(start, n_post), min(stop, n_post)
     samples, lsamples = [], []
     rounds = 0
+    man.proposal_updates, man.windows_closed, man.proposal_factors = [], [], None
+    windows = None
+    if adapt:
+        burnin = int(n_samples * 0.1) if burnin is None else int(burnin)
+        windows = ProposalWindows(stepper, (stop - start) // n_replicas, npar, buffer_size, burnin, man.proposal_updates,
+                                  man.windows_closed)
     # wall time and step count of the rounds alone (bench.py's pt_leg): man.loop_seconds / man.loop_steps
     if Q.is_cuda:
         torch.cuda.synchronize(dev)
@@ -159,9 +254,13 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
     t_loop, man.loop_steps = time.perf_counter(), 0
     while sum(len(s) for s in samples) < n_samples:
         betas = torch.from_numpy(man.chain_betas[start:stop].copy()).to(dev)
+        if windows is not None:
+            windows.begin_round(man.loop_steps)
         for _ in range(man.draw_swap_interval()):
             stepper.step(Q, L, betas)
             man.loop_steps += 1
+            if windows is not None:
+                windows.after_step(Q, L, man.loop_steps)
         ops.check()
         QL = torch.cat([Q, L], 1)
         if rounds % record_every == 0:
@@ -178,4 +277,5 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
     if Q.is_cuda:
         torch.cuda.synchronize(dev)
     man.loop_seconds = time.perf_counter() - t_loop
+    man.proposal_factors = stepper.group_factors
     return np.concatenate(samples)[:n_samples], np.concatenate(lsamples)[:n_samples], man

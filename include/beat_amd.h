@@ -739,6 +739,54 @@ int beatamd_halfspace_displacements_batch(beatamd_ctx *ctx, int64_t C, int32_t n
                                           const double *east, const double *north, double nu,
                                           double *out);
 
+/* ---------------------------------------------------------------- PT proposal adaptation ---
+ * replaces: the proposal update of every PT worker (sample_pt_chain, beat/sampler/pt.py:758-761; _iter_sample,
+ *           beat/sampler/base.py:363-393; BaseChain.get_sample_covariance, beat/backend.py:249-268;
+ *           calc_sample_covariance, beat/covariance.py:865-909: likelihood-weighted num.cov(..., aweights=, bias=False),
+ *           then ensure_cov_psd).  The reference holds the window of buffer_size samples; here its weighted moments are
+ *           accumulated on the device after every step, for G groups (temperatures) of R chains (replicas) at once.
+ *
+ *   state [G, 8 + n + n*n] doubles, group by group (a sub-range of groups is a sub-range of the array):
+ *     [0] m       running maximum of `like` (-inf after reset)
+ *     [1] S0      sum of w = exp(like - m)
+ *     [2] Sw2     sum of w^2
+ *     [3] count   rows accumulated
+ *     [4] nbad    rows skipped because their like or state was not finite
+ *     [5..7]      spare (0)
+ *     [8 .. 8+n)  S1 = sum of w y,  y = x - ref
+ *     [8+n ..)    S2 [n, n] = sum of w y y^T, lower triangle (entries above the diagonal stay 0)
+ *
+ *   _reset: the empty state; with ref [G, n] not NULL also ref[g] = mean of rows g*R .. g*R+R-1 of Q, summed in replica
+ *     order (a window opens around the group's present states); Q, R unused otherwise.
+ *   _update: rows g*R .. g*R+R-1 of Q [G*R, n] belong to group g; like[(g*R + r) * like_stride]; ref [G, n] the
+ *     reference point of the group's window (constant while the window is open).  m' = max(m, max like), every
+ *     accumulator is rescaled by exp(m - m') (Sw2 by its square) and the rows are added in replica order.  The sums
+ *     of a group depend on (group, replica, order of the calls) alone -- not on G, on the other groups of the call or
+ *     on where the arrays live.  G <= 64, R <= 1024, n <= 2048.
+ *   _factor: mu = S1/S0, fact = 1 - Sw2/S0^2, cov = (S2/S0 - mu mu^T)/fact (symmetrised by copy) and its upper
+ *     Cholesky factor F [G, n, n], F^T F = cov -- the `factor` of beatamd_proposal_draw.  flags [G]: 0 factored;
+ *     1 fact <= 0, nbad > 0 or a non-finite value (the reference's cov = None: keep the previous proposal);
+ *     2 not positive definite.  The factor of a flagged group is left untouched.  cov [G, n, n] (NULL: not wanted)
+ *     is written for every group (the caller repairs a group flagged 2 with utility.ensure_cov_psd). */
+int beatamd_group_moments_reset(beatamd_ctx *ctx, int64_t G, int64_t nparams, double *state, int64_t R, const double *Q,
+                                double *ref);
+int beatamd_group_moments_update(beatamd_ctx *ctx, int64_t G, int64_t R, int64_t nparams, const double *Q,
+                                 const double *like, int64_t like_stride, const double *ref, double *state);
+int beatamd_group_moments_factor(beatamd_ctx *ctx, int64_t G, int64_t nparams, const double *state, double *factor,
+                                 double *cov, int32_t *flags);
+/* beatamd_proposal_draw / beatamd_ffi_mstep_batch (multivariate) with one factor per group of chains (the proposals a
+ * PT worker learned from its own trace, beat/sampler/pt.py:758-761): factor [G, K, nparams], chain c of the call draws
+ * with factor c / (C / G); C must be a multiple of G.  Philox counters, df, the prior box, parking, the counters and
+ * graph capture are those of the ungrouped entries; with G copies of one factor the results are bit for bit theirs. */
+int beatamd_proposal_draw_grouped(beatamd_ctx *ctx, int64_t C, int64_t G, int64_t K, int64_t nparams,
+                                  const double *factor, uint64_t seed, uint32_t step, int64_t first_chain, int32_t df,
+                                  double *delta, double *log_u);
+int beatamd_ffi_mstep_batch_grouped(beatamd_ctx *ctx, int32_t model_id, int64_t C, int64_t G, double *Q0, double *L0,
+                                    const double *factor, int64_t K, int32_t df, uint64_t seed, uint32_t step,
+                                    int64_t first_chain, const double *scaling, const double *lower,
+                                    const double *upper, double beta, const double *betas, int32_t *accepted,
+                                    int32_t *accepted_sum, int64_t *n_accepted);
+
 #ifdef __cplusplus
 }
 #endif
