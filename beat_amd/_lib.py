@@ -149,6 +149,10 @@ _PROTOS = {
     "beatamd_factor_compact": [_vp, _i64, _i64, _vp, _vp],
     "beatamd_ffi_model_update_data": [_vp, _i32, _i32, _vp],
     "beatamd_halfspace_displacements_batch": [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _f64, _vp],
+    "beatamd_ffi_model_set_lsq_variables": [_vp, _i32, _i32, _i32],
+    "beatamd_ffi_lsq_normal_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "beatamd_nnls_batch": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
+    "beatamd_ffi_lsq_solution_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["beatamd_last_error", "beatamd_version"])

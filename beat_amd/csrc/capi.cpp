@@ -1,4 +1,6 @@
 // capi.cpp -- the extern "C" entry points of include/beat_amd.h (host side of the engine).
+#include <cstdlib>
+
 #include "model.hpp"
 
 using namespace beatamd;
@@ -743,6 +745,7 @@ int beatamd_ffi_model_add_geodetic(beatamd_ctx *ctx, int32_t model_id, const int
     m->P = P;
     m->geo = std::move(g);
     m->has_geo = true;
+    m->lsq_blocks_valid = false;
     return BEATAMD_OK;
 }
 
@@ -807,6 +810,7 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
     BA_CHECK(nterm == 0 || (dataset && ncol && basis && coef_off && coef_fixed), BEATAMD_EINVAL,
              "add_geodetic_corrections: bad argument");
     m->obs_quads_valid = false;
+    m->lsq_blocks_valid = false;
     if (nterm == 0) {
         g.corr_set = true;
         return BEATAMD_OK;
@@ -873,6 +877,7 @@ int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t 
     BA_CHECK(m->P == 0 || l->P == m->P, BEATAMD_EINVAL, "set_laplacian: patch count mismatch");
     if (m->P == 0) m->P = l->P;
     m->lap = lap_id;
+    m->lsq_blocks_valid = false;
     return BEATAMD_OK;
 }
 
@@ -989,6 +994,115 @@ int beatamd_ffi_llks_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const 
     opt.llks = d_l;
     BA_TRY(ffi_logp_device(ctx, *m, C, d_q, nullptr, opt));
     return st.finish();
+}
+
+// ------------------------------------------------------------------ lsq start (lsq.hip)
+int beatamd_ffi_model_set_lsq_variables(beatamd_ctx *ctx, int32_t model_id, int32_t inverted, int32_t zeroed)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(inverted >= 0 && inverted < m->layout.nvar && zeroed >= -1 && zeroed < m->layout.nvar && zeroed != inverted,
+             BEATAMD_EINVAL, "set_lsq_variables: slip variables %d / %d of %d", inverted, zeroed, m->layout.nvar);
+    if (m->lsq_var != inverted) m->lsq_blocks_valid = false;
+    m->lsq_var = inverted;
+    m->lsq_zero_var = zeroed;
+    return BEATAMD_OK;
+}
+
+// BEATAMD_NNLS_MAXITER (tests): the iteration cap instead of 3 n
+static int nnls_maxiter()
+{
+    const char *e = getenv("BEATAMD_NNLS_MAXITER");
+    return e && *e ? atoi(e) : 0;
+}
+
+int beatamd_ffi_lsq_normal_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *N, double *b,
+                                 int32_t *chain_bad)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(Q && N && b && C >= 0, BEATAMD_EINVAL, "ffi_lsq_normal: bad argument");
+    BA_TRY(model_check_layout(*m));
+    if (C == 0) return BEATAMD_OK;
+    const int64_t P = m->P;
+    Staging st(ctx);
+    const double *d_q;
+    double *d_n, *d_b;
+    int32_t *d_bad = nullptr, *bad = nullptr;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.out(N, (size_t)(C * P * P), &d_n));
+    BA_TRY(st.out(b, (size_t)(C * P), &d_b));
+    if (chain_bad) BA_TRY(st.out(chain_bad, (size_t)C, &d_bad));
+    BA_TRY(lsq_normal_device(ctx, *m, C, d_q, d_n, d_b, &bad));
+    if (d_bad) {
+        if (bad) BA_HIP(hipMemcpyAsync(d_bad, bad, (size_t)C * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        else BA_HIP(hipMemsetAsync(d_bad, 0, (size_t)C * sizeof(int32_t), ctx->stream));
+    }
+    BA_TRY(st.finish());            // (host arrays are filled before a raised status word is returned)
+    return ctx->check_status();     // a time outside the library grid: the flags say which chains
+}
+
+int beatamd_nnls_batch(beatamd_ctx *ctx, int64_t C, int64_t n, const double *N, const double *b, double *x, int32_t *iters,
+                       int32_t *status)
+{
+    ENTER(ctx);
+    BA_CHECK(N && b && x && iters && status && C >= 0 && n >= 1, BEATAMD_EINVAL, "nnls: bad argument");
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_n, *d_b;
+    double *d_x;
+    int32_t *d_it, *d_st;
+    BA_TRY(st.in(N, (size_t)(C * n * n), &d_n));
+    BA_TRY(st.in(b, (size_t)(C * n), &d_b));
+    BA_TRY(st.out(x, (size_t)(C * n), &d_x));
+    BA_TRY(st.out(iters, (size_t)C, &d_it));
+    BA_TRY(st.out(status, (size_t)C, &d_st));
+    BA_TRY(launch_nnls(ctx, C, n, d_n, d_b, d_x, d_it, d_st, nnls_maxiter()));
+    return st.finish();
+}
+
+int beatamd_ffi_lsq_solution_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q_in, double *Q_out,
+                                   int32_t *iters, int32_t *status)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(Q_in && Q_out && iters && status && C >= 0, BEATAMD_EINVAL, "ffi_lsq_solution: bad argument");
+    BA_TRY(model_check_layout(*m));
+    if (C == 0) return BEATAMD_OK;
+    const int64_t P = m->P, np = m->layout.nparams;
+    BA_CHECK(m->lsq_var >= 0, BEATAMD_EINVAL,
+             "lsq: the model has no inverted slip variable (beatamd_ffi_model_set_lsq_variables)");
+    Staging st(ctx);
+    const double *d_qi;
+    double *d_qo;
+    int32_t *d_it, *d_st;
+    BA_TRY(st.in(Q_in, (size_t)C * np, &d_qi));
+    BA_TRY(st.out(Q_out, (size_t)C * np, &d_qo));
+    BA_TRY(st.out(iters, (size_t)C, &d_it));
+    BA_TRY(st.out(status, (size_t)C, &d_st));
+    // chains per pass: the normal matrices of a pass stay within 1 GiB of scratch
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(C, ((int64_t)1 << 30) / std::max<int64_t>(1, P * P * 8)));
+    const int maxiter = nnls_maxiter();
+    for (int64_t c0 = 0; c0 < C; c0 += chunk) {
+        const int64_t cc = std::min(chunk, C - c0);
+        double *nm, *bv, *x;
+        int32_t *bad;
+        BA_TRY(ctx->scratch(SL_LSQ_N, (size_t)(cc * P * P), &nm));
+        BA_TRY(ctx->scratch(SL_LSQ_B, (size_t)(cc * P), &bv));
+        BA_TRY(ctx->scratch(SL_LSQ_X, (size_t)(cc * P), &x));
+        BA_TRY(lsq_normal_device(ctx, *m, cc, d_qi + c0 * np, nm, bv, &bad));
+        BA_TRY(launch_nnls(ctx, cc, P, nm, bv, x, d_it + c0, d_st + c0, maxiter));
+        if (d_qo != d_qi)
+            BA_HIP(hipMemcpyAsync(d_qo + c0 * np, d_qi + c0 * np, (size_t)(cc * np) * sizeof(double), hipMemcpyDeviceToDevice,
+                                  ctx->stream));
+        BA_TRY(launch_lsq_scatter(ctx, cc, P, x, d_qo + c0 * np, np, m->layout.slip_off[m->lsq_var],
+                                  m->lsq_zero_var >= 0 ? m->layout.slip_off[m->lsq_zero_var] : -1));
+    }
+    BA_TRY(st.finish());
+    return ctx->check_status();     // a time outside the library grid is the reference's IndexError
 }
 
 // ------------------------------------------------------------------ posterior diagnostics (summary.hip)
@@ -1832,6 +1946,7 @@ int beatamd_ffi_model_update_data(beatamd_ctx *ctx, int32_t model_id, int32_t wa
     BA_CHECK(data && wavemap_index >= 0 && (size_t)wavemap_index < m->wavemaps.size(), BEATAMD_EINVAL,
              "model_update_data: bad argument");
     Wavemap &w = m->wavemaps[wavemap_index];
+    m->lsq_blocks_valid = false;
     m->obs_quads_valid = false;
     BA_HIP(hipMemcpyAsync(w.data.get(), data, (size_t)w.T * w.N * 8, hipMemcpyDefault, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));

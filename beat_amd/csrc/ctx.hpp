@@ -243,6 +243,12 @@ struct FfiModel {
     bool obs_quads_valid = false;
     std::vector<double> obs_quads;
     DevMem<double> d_obs_quads;
+    // lsq start (lsq.hip): which slip variable is inverted and which is set to zero (indices into layout.slip_off, -1:
+    // none), and the chain-independent blocks G_v G_v^T and L^T L [P, P] (lower triangles), formed on first use and kept
+    // until the model's data, corrections or laplacian are replaced
+    int32_t lsq_var = -1, lsq_zero_var = -1;
+    bool lsq_blocks_valid = false;
+    DevMem<double> lsq_GG, lsq_LtL;
 };
 
 // the hyper-parameter model (hyper.hip): term k = kind[k] formula on hyper-parameter hp_index[k] of the nh-vector
@@ -359,7 +365,7 @@ enum Slot : int {
     SL_CHAINBAD, SL_Z, SL_ROWSCALE, SL_CUM, SL_STAGE2, SL_WHITEN,
     SL_CHOL_A, SL_CHOL_X, SL_CHOL_D, SL_CHOL_T, SL_CHOL_L,
     SL_GC_ORDER, SL_GS_ORDER, SL_GC_STREAM, SL_GC_HDR, SL_GC_META, SL_DELTA, SL_LOGU, SL_EDGES, SL_TSLOT, SL_SPLIT, SL_WS_PACK,
-    SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_COUNT
+    SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

@@ -731,4 +731,27 @@ static int launch_gfstack_impl(beatamd_ctx *ctx, const GfStackCall &k, const GfP
     return BEATAMD_OK;
 }
 
+// the index tables alone, one per target and without a patch split, into the caller's buffers (lsq.hip gathers the rows
+// of single patches through them)
+int launch_gf_tables(beatamd_ctx *ctx, const GfStackCall &k, uint32_t *rowoff, double *fac)
+{
+    const SeisLib &L = *k.libs[0];
+    if (k.C == 0) return BEATAMD_OK;
+    BA_CHECK(L.T * L.P * L.D * L.S < (int64_t)0xffffffffLL, BEATAMD_EINVAL, "gfstack: library has more than 2^32 rows");
+    BA_CHECK(rowoff && (k.interp != BEATAMD_MULTILINEAR || fac), BEATAMD_EINVAL, "gf_tables: bad argument");
+    const int64_t CTP = k.C * L.T * L.P;
+    BA_CHECK((CTP + 255) / 256 < (int64_t)0x7fffffff, BEATAMD_EINVAL, "gf_tables: batch too large");
+    TabArgs ta;
+    ta.interp = k.interp; ta.R = 1;
+    ta.C = k.C; ta.T = L.T; ta.P = L.P; ta.D = L.D; ta.S = L.S;
+    ta.st_min = L.st_min; ta.st_dt = L.st_dt; ta.du_min = L.du_min; ta.du_dt = L.du_dt;
+    ta.durations = k.durations; ta.st = k.st;
+    ta.status = ctx->d_status;
+    ta.rowoff = rowoff; ta.fac = fac;
+    ScopedTimer tm(ctx, "tables");
+    hipLaunchKernelGGL(k_gf_tables, dim3((unsigned)((CTP + 255) / 256)), dim3(256), 0, ctx->stream, ta);
+    BA_HIP(hipGetLastError());
+    return BEATAMD_OK;
+}
+
 }  // namespace beatamd

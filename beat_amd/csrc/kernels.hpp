@@ -483,4 +483,25 @@ struct BallSet {
 int launch_ball_rms(beatamd_ctx *ctx, int64_t nd, int64_t nmax, const BallSet *sets, const double *coords, const double *data,
                     double max_dist_perc, double *pmax, double *radius, int32_t *counts, double *stds);
 
+// ---- lsq.hip: non-negative least-squares slip of a batch of chains (problems.py:753-873)
+// the index tables of a stacking call, one per target (k_gf_tables): rowoff [C,T,P,nrow], fac [C,T,P,4] (multilinear)
+int launch_gf_tables(beatamd_ctx *ctx, const GfStackCall &call, uint32_t *rowoff, double *fac);
+// N [C,P,P] (the 64 x 64 tiles of the lower triangle) and b [C,P] (+)= sum_t R_t R_t^T, sum_t R_t d_t of one library
+// (k_lsq_gram, k_lsq_rhs); accumulate: continue the stored sums
+int launch_lsq_seismic(beatamd_ctx *ctx, const SeisLib &lib, int interp, int64_t C, const uint32_t *rowoff, const double *fac,
+                       const double *data, int accumulate, double *Nmat, double *b);
+int launch_lsq_transpose(beatamd_ctx *ctx, const double *A, double *At, int64_t n);
+// N += GG + h^4 LtL on the lower triangle, mirrored; b += Ggeo (dgeo - corr_c) (k_lsq_finish); GG / Ggeo nullable
+int launch_lsq_finish(beatamd_ctx *ctx, int64_t C, int64_t P, double *Nmat, double *b, int has_seis, const double *GG,
+                      const double *LtL, const double *Ggeo, int64_t Nobs, const double *dgeo, GeoCorr corr, const double *Q,
+                      int64_t nparams, int64_t h_off);
+// Lawson-Hanson active set per chain (k_nnls); maxiter <= 0: 3 n.  The factors of one launch stay within
+// NNLS_SCRATCH_BYTES: larger batches run in chunks of chains
+constexpr int NNLS_MAX_N = 1024;
+constexpr int64_t NNLS_SCRATCH_BYTES = (int64_t)256 << 20;
+int launch_nnls(beatamd_ctx *ctx, int64_t C, int64_t n, const double *Nmat, const double *b, double *x, int32_t *iters,
+                int32_t *status, int maxiter);
+int launch_lsq_scatter(beatamd_ctx *ctx, int64_t C, int64_t P, const double *x, double *Qout, int64_t nparams, int64_t v_off,
+                       int64_t zero_off);
+
 }  // namespace beatamd

@@ -319,6 +319,72 @@ int model_obs_quads(beatamd_ctx *ctx, FfiModel &m)
     return BEATAMD_OK;
 }
 
+// ------------------------------------------------------------------ lsq start
+// G_v G_v^T and L^T L, once per model, on the matrix cores (lower tiles; k_lsq_finish reads the lower triangle)
+static int lsq_blocks(beatamd_ctx *ctx, FfiModel &m, const Laplacian &lp, const GeoLib *gl)
+{
+    if (m.lsq_blocks_valid) return BEATAMD_OK;
+    const int64_t P = m.P;
+    BA_TRY(m.lsq_LtL.alloc((size_t)(P * P)));
+    double *Lt;
+    BA_TRY(ctx->scratch(SL_LSQ_U, (size_t)(P * P), &Lt));
+    BA_TRY(launch_lsq_transpose(ctx, lp.L.get(), Lt, P));
+    GemmCall g;
+    g.A = Lt; g.B = Lt; g.lda = P; g.ldb = P; g.O = m.lsq_LtL.get(); g.ldo = P;
+    g.M = P; g.N = P; g.K = P; g.b_kn = 0; g.lower_only = 1; g.timer = "lsq_blocks";
+    BA_TRY(launch_gemm_f64(ctx, g));
+    m.lsq_GG.reset();
+    if (gl) {
+        BA_TRY(m.lsq_GG.alloc((size_t)(P * P)));
+        g.A = gl->g.get(); g.B = gl->g.get(); g.lda = gl->Nobs; g.ldb = gl->Nobs; g.K = gl->Nobs; g.O = m.lsq_GG.get();
+        BA_TRY(launch_gemm_f64(ctx, g));
+    }
+    BA_HIP(hipStreamSynchronize(ctx->stream));   // (the transposed operator lives in a scratch slot)
+    m.lsq_blocks_valid = true;
+    return BEATAMD_OK;
+}
+
+int lsq_normal_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, double *Nmat, double *b, int32_t **chain_bad)
+{
+    const int64_t P = m.P, np = m.layout.nparams;
+    BA_CHECK(m.lap >= 0, BEATAMD_EINVAL,
+             "Least-squares- solution for distributed slip is only available with laplacian regularization!");
+    BA_CHECK(m.lsq_var >= 0 && m.lsq_var < m.layout.nvar, BEATAMD_EINVAL,
+             "lsq: the model has no inverted slip variable (beatamd_ffi_model_set_lsq_variables)");
+    BA_CHECK(!(m.has_geo && m.geo_is_geometry), BEATAMD_EINVAL, "lsq: a geometry-mode geodetic composite is not linear in slip");
+    Laplacian *lp = get_obj(ctx->laps, m.lap);
+    BA_CHECK(lp && lp->P == P, BEATAMD_EINVAL, "model refers to a destroyed laplacian");
+    const GeoLib *gl = nullptr;
+    if (m.has_geo) {
+        gl = get_obj(ctx->geolibs, m.geo.libs[m.lsq_var]);
+        BA_CHECK(gl && gl->P == P, BEATAMD_EINVAL, "geodetic composite refers to a destroyed GF library");
+    }
+    BA_TRY(lsq_blocks(ctx, m, *lp, gl));
+    *chain_bad = nullptr;
+    int has_seis = 0;
+    if (!m.wavemaps.empty()) {
+        double *st0;
+        BA_TRY(model_start_times(ctx, m, C, Q, &st0, chain_bad));
+        for (auto &wm : m.wavemaps) {
+            GfStackCall k;
+            BA_TRY(wavemap_call(ctx, m, wm, C, Q, st0, *chain_bad, &k));
+            const SeisLib *lib = k.libs[m.lsq_var];
+            k.libs[0] = lib;      // (the tables depend on the library's grid alone, the same for every slip variable)
+            uint32_t *rowoff;
+            double *fac = nullptr;
+            const int nrow = wm.interp == BEATAMD_MULTILINEAR ? 4 : 1;
+            BA_TRY(ctx->scratch(SL_ROWOFF, (size_t)(C * lib->T * P * nrow), &rowoff));
+            if (nrow == 4) BA_TRY(ctx->scratch(SL_WEIGHTS, (size_t)(C * lib->T * P * 4), &fac));
+            BA_TRY(launch_gf_tables(ctx, k, rowoff, fac));
+            BA_TRY(launch_lsq_seismic(ctx, *lib, wm.interp, C, rowoff, fac, wm.data.get(), has_seis, Nmat, b));
+            has_seis = 1;
+        }
+    }
+    return launch_lsq_finish(ctx, C, P, Nmat, b, has_seis, m.lsq_GG.get(), m.lsq_LtL.get(), gl ? gl->g.get() : nullptr,
+                             m.has_geo ? m.geo.Nobs : 0, m.has_geo ? m.geo.data.get() : nullptr, m.geo.corr, Q, np,
+                             m.layout.h_laplacian_off);
+}
+
 // ------------------------------------------------------------------ fused Metropolis step
 int draw_multivariate(beatamd_ctx *ctx, int64_t C, int64_t K, int64_t np, const double *factor, int df, uint64_t seed,
                       uint32_t step, uint64_t first_chain, double *delta, double *log_u, int64_t groups)

@@ -58,6 +58,10 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
 int model_obs_quads(beatamd_ctx *ctx, FfiModel &m);
 void drop_obs_quads(beatamd_ctx *ctx);
 
+// lsq start (problems.py:753-873): the normal equations N [C,P,P], b [C,P] of the chains' linear slip problems (device
+// pointers); *chain_bad (a scratch slot): chains whose times leave the library grid
+int lsq_normal_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, double *Nmat, double *b, int32_t **chain_bad);
+
 // proposal source of a step: rows handed in (delta, log_u) or drawn here (factor / scales + Philox key)
 struct StepDraw {
     const double *factor = nullptr;   // [K, np] or the per-parameter scales [np]

@@ -792,6 +792,43 @@ class Context(object):
                                                   ptr(accepted)))
 
     # -- hyper-parameter estimation (csrc/hyper.hip)
+    # -- lsq start (csrc/lsq.hip; reference problems.py:753-873)
+    def ffi_model_set_lsq_variables(self, model_id, inverted, zeroed=-1):
+        check(self._lib.beatamd_ffi_model_set_lsq_variables(self._h, model_id, int(inverted), int(zeroed)))
+
+    def ffi_lsq_normal_batch(self, model_id, Q, npatches, chain_bad=None):
+        """normal equations of the chains' linear slip problems at the points Q [C, nparams] -> N [C, P, P], b [C, P];
+        chain_bad (int32 [C], optional, filled also when the call raises IndexError): chains outside the library grid"""
+        self._adopt_stream(Q)
+        Qc = f64(Q)
+        Cn, P = int(Qc.shape[0]), int(npatches)
+        N, b = _empty_like(Qc, (Cn, P, P)), _empty_like(Qc, (Cn, P))
+        check(self._lib.beatamd_ffi_lsq_normal_batch(self._h, model_id, Cn, ptr(Qc), ptr(N), ptr(b), ptr(chain_bad)))
+        return N, b
+
+    def nnls_batch(self, N, b):
+        """min |A x - d| s.t. x >= 0 from N = A^T A [C, n, n] and b = A^T d [C, n] -> x [C, n], iters [C], status [C]
+        (0 ok, 1 iteration cap, 2 non-finite input / passive block not positive definite)"""
+        self._adopt_stream(N, b)
+        N, b = f64(N), f64(b)
+        Cn, n = int(b.shape[0]), int(b.shape[1])
+        if tuple(N.shape) != (Cn, n, n):
+            raise ValueError("nnls_batch: N %s does not match b %s" % (tuple(N.shape), tuple(b.shape)))
+        x, it, st = _empty_like(b, (Cn, n)), _empty_like(b, (Cn,), np.int32), _empty_like(b, (Cn,), np.int32)
+        check(self._lib.beatamd_nnls_batch(self._h, Cn, n, ptr(N), ptr(b), ptr(x), ptr(it), ptr(st)))
+        return x, it, st
+
+    def ffi_lsq_solution_batch(self, model_id, Q):
+        """Q [C, nparams] -> (Q with the inverted slip variable replaced by its non-negative least-squares solution and
+        the perpendicular one by zeros, iters [C], status [C])"""
+        self._adopt_stream(Q)
+        Qc = f64(Q)
+        Cn = int(Qc.shape[0])
+        out = _empty_like(Qc, tuple(Qc.shape))
+        it, st = _empty_like(Qc, (Cn,), np.int32), _empty_like(Qc, (Cn,), np.int32)
+        check(self._lib.beatamd_ffi_lsq_solution_batch(self._h, model_id, Cn, ptr(Qc), ptr(out), ptr(it), ptr(st)))
+        return out, it, st
+
     def ffi_model_nterm(self, model_id):
         n = C.c_int64()
         check(self._lib.beatamd_ffi_model_nterm(self._h, model_id, C.byref(n)))

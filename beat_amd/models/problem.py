@@ -535,6 +535,56 @@ class LogpForwFunc(object):
             raise ValueError("the model has no geodetic composite")
         return self.ctx.ffi_geo_residuals_batch(self.model_id, Q, int(sum(g.sizes)), residuals=residuals)
 
+    # -- lsq start (csrc/lsq.hip)
+    def _lsq_setup(self, Q=None):
+        """the checks of DistributionOptimizer.lsq_solution (problems.py:768-787) and the model's inverted variable"""
+        self._ready(Q)
+        prob = self.problem
+        if prob.laplacian is None:
+            raise ValueError("Least-squares- solution for distributed slip is only "
+                             "available with laplacian regularization!")
+        inverted = [v for v in ("uparr", "utens") if v in prob.slip_varnames]
+        if len(inverted) != 1:
+            raise ValueError("LSQ distributed slip solution inverts for exactly one of uparr, utens; the sampled slip "
+                             "variables are %s (the reference's stacking of its blocks is shape-consistent for one only)"
+                             % ", ".join(prob.slip_varnames))
+        for wm in prob.wavemaps:
+            if getattr(wm, "is_prewhitened", False):
+                raise ValueError("wavemap %s is pre-whitened: its rows and data hold W.G and W.d, the least-squares "
+                                 "start is defined on the unweighted ones" % wm.name)
+        others = [v for v in prob.slip_varnames if v != inverted[0]]
+        if others not in ([], ["uperp"]):
+            raise ValueError("LSQ distributed slip solution: besides %s only uperp may be sampled, got %s"
+                             % (inverted[0], ", ".join(others)))
+        key = (prob.slip_varnames.index(inverted[0]), prob.slip_varnames.index("uperp") if others else -1)
+        if getattr(self, "_lsq_vars", None) != key:
+            self.ctx.ffi_model_set_lsq_variables(self.model_id, *key)
+            self._lsq_vars = key
+        return inverted[0]
+
+    def lsq_normal_equations(self, Q, chain_bad=None):
+        """Q (C, nparams) -> N (C, P, P), b (C, P): the normal equations A^T A, A^T d of the linear problem that
+        ``lsq_solution`` solves per chain, A and d in the order seismic (wavemap, target, sample), geodetic, laplacian
+        (``include/beat_amd.h``).  numpy in -> numpy out, torch-cuda in -> tensors.  A chain whose times leave the library
+        grid raises IndexError (chain_bad, int32 (C,), is filled first)."""
+        self._lsq_setup(Q)
+        return self.ctx.ffi_lsq_normal_batch(self.model_id, Q, self.problem.npatches, chain_bad=chain_bad)
+
+    def lsq_solution(self, Q, return_info=False):
+        """``DistributionOptimizer.lsq_solution`` (problems.py:753-873) for a batch: Q (C, nparams) -> Q with the inverted
+        slip variable (uparr or utens) replaced by the non-negative least-squares slip at the chain's kinematics and uperp,
+        where sampled, by zeros; every other column bit for bit the input.  The solution is not clipped to the prior box
+        (nor is the reference's).  return_info: also the iteration counts and status words (C,)."""
+        self._lsq_setup(Q)
+        out, it, st = self.ctx.ffi_lsq_solution_batch(self.model_id, Q)
+        stat = _host(st)
+        if np.any(stat == 1):
+            raise RuntimeError("Maximum number of iterations reached.")
+        if np.any(stat == 2):
+            raise ValueError("lsq_solution: the normal equations of chain(s) %s are not finite or not positive definite"
+                             % np.nonzero(stat == 2)[0].tolist())
+        return (out, it, st) if return_info else out
+
     def _hp_columns(self, Q, hypers):
         offs = [self.problem.layout.offset(n, i) for n, i in hypers]
         if hasattr(Q, "data_ptr") and not isinstance(Q, np.ndarray):

@@ -203,6 +203,16 @@ class TargetShardedLogp(object):
                                   "all-gathered like the likelihood vector): estimate the hyper-parameters on the "
                                   "replicated model, or on self.local for this rank's targets")
 
+    def lsq_normal_equations(self, Q, chain_bad=None):
+        raise NotImplementedError("lsq_normal_equations of a target-sharded model is not offered (the Gram matrices of the "
+                                  "ranks' targets would have to be summed in a fixed order): build the start population on "
+                                  "the replicated model")
+
+    def lsq_solution(self, Q, return_info=False):
+        raise NotImplementedError("lsq_solution of a target-sharded model is not offered (the Gram matrices of the ranks' "
+                                  "targets would have to be summed in a fixed order): build the start population on the "
+                                  "replicated model")
+
     def _no_diagnostics(self, what):
         raise NotImplementedError("%s of a target-sharded model is not offered (the seismic columns would be all-gathered "
                                   "like the likelihood vector): take the posterior diagnostics on the replicated model, or "

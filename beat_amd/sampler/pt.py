@@ -194,7 +194,7 @@ class ProposalWindows(object):
 def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n_replicas=1,
               n_samples=1000, swap_interval=(100, 300), beta_tune_interval=10, proposal_cov=None,
               device=None, random_seed=17, tune_interval=100, record_every=1, update_proposal=False,
-              buffer_size=5000, burnin=None, proposal_name="MultivariateNormal"):
+              buffer_size=5000, burnin=None, proposal_name="MultivariateNormal", start=None):
     """pt.py:793-906 driver.  Returns (posterior samples (n, nparams), their likelihood
     vectors, manager).  Samples of the beta == 1 replicas are recorded after every round.
 
@@ -205,11 +205,15 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
     end (None before the first update).  proposal_name: the family of ``BatchedMetropolis.set_proposal`` (for a per-parameter
     family ``proposal_cov`` is the vector of scales, None: ones).  With several ranks every temperature's replicas must lie on one rank.
 
+    start: (n_workers * n_replicas, nparams) start points of the replicas instead of the prior draws (a wrong length is the
+    reference's TypeError, sampler/smc.py:429-436); the draws are still taken from the manager's stream.
+
     Exchange round: all-gather of ONE likelihood per replica, the swap sweep decided
     identically on every rank (shared RandomState), then the permutation is applied where the
     states live: local rows by a device gather, rows that change rank point to point
     (``parallel.exchange_rows``).  The replica states themselves are never gathered."""
     import torch
+    start_points = start      # (`start` names this rank's first chain below)
     rank, world, _ = parallel.ensure_group()
     man = TemperingManager(n_chains_posterior, n_chains_tempered, n_replicas, swap_interval,
                            beta_tune_interval, random_seed)
@@ -233,6 +237,9 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
         proposal_cov = np.diag(((upper - lower) * 0.05) ** 2)
     stepper.set_proposal(proposal_cov, proposal_name)
     Qall = lower + (upper - lower) * man.rng.random_sample((n_total, lower.size))
+    if start_points is not None:
+        from .smc import check_start
+        Qall = check_start(start_points, n_total, lower.size)
     Q = torch.from_numpy(np.ascontiguousarray(Qall[start:stop])).to(dev)
     L = stepper.evaluate(Q).to(dev)
     npar = Q.shape[1]

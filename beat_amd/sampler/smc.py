@@ -90,11 +90,17 @@ class SMC(object):
         return None if self.L_all is None else self._host(self.L_all[:, -1])
 
     # ------------------------------------------------------------------ population
-    def initialize_population(self):
+    def initialize_population(self, start=None):
         """metropolis.py:125-152: prior draws (Uniform boxes) for every chain; identical on
-        every rank because the seeded RandomState is shared.  -> this rank's block on the device"""
+        every rank because the seeded RandomState is shared.  -> this rank's block on the device
+
+        start: (n_chains, nparams) start points instead of the draws (smc.py:429-436, e.g.
+        ``beat_amd.models.lsq.lsq_start_population``), the same array on every rank.  The prior draws are still taken
+        from the shared stream, so everything drawn later (the resampling draws) is what the random start would draw."""
         u = self.rng.random_sample((self.n_chains, self.lower.size))
         pop = self.lower + (self.upper - self.lower) * u
+        if start is not None:
+            pop = check_start(start, self.n_chains, self.lower.size)
         a, b = self.block
         return self.torch.from_numpy(np.ascontiguousarray(pop[a:b])).to(self.device)
 
@@ -192,6 +198,20 @@ class SMC(object):
                 on_step(i, Q, L, acc)
         self.stage_acceptance.append(float(n_acc.item()) / max(1.0, float(n_steps) * Q.shape[0]))
         return Q, L
+
+
+def check_start(start, n_chains, nparams):
+    """the ``start`` argument of the samplers as a host array (n_chains, nparams); a wrong length is the reference's
+    TypeError (sampler/smc.py:429-436)"""
+    if len(start) != n_chains:
+        raise TypeError("Argument `start` should have dicts equal the "
+                        "number of chains (step.N-chains)")
+    if hasattr(start, "detach"):
+        start = start.detach().cpu().numpy()
+    start = np.ascontiguousarray(start, dtype=np.float64)
+    if start.shape != (n_chains, nparams):
+        raise ValueError("start must be (%d, %d), got %s" % (n_chains, nparams, start.shape))
+    return start
 
 
 def _dump_stage(step, homepath, layout, out_names, backend):
@@ -341,7 +361,7 @@ def update_last_samples(step, Q_local):
 
 def smc_sample(n_steps, step, progressbar=False, on_stage=None, max_stages=200, homepath=None,
                layout=None, out_names=None, backend="bin", resume_stage=None, update=None, final_stage=True,
-               async_stage_files=True, buffer_thinning=None):
+               async_stage_files=True, buffer_thinning=None, start=None):
     """smc.py:333-546 stage loop.  Returns the final population (n_chains, nparams), the
     likelihood vectors (host arrays) and the list of betas.  With ``homepath`` every stage leaves
     a ``stage_<k>`` / ``stage_final`` directory of NumpyChain/TextChain traces
@@ -361,6 +381,9 @@ def smc_sample(n_steps, step, progressbar=False, on_stage=None, max_stages=200, 
     of every chain and the last one -- the reference's traces (``buffer_thinning`` of its sampler config,
     beat/backend.py:100-117, 365-404; ``beat summarize`` reads the whole stage) -- instead of the end points only
     (= ``buffer_thinning >= n_steps``).  Each rank writes the files of its own chains.
+
+    ``start``: (n_chains, nparams) start points of stage 0 instead of the prior draws (``SMC.initialize_population``);
+    a wrong length raises the reference's TypeError (smc.py:429-436).  Not used when resuming.
 
     ``final_stage=False`` stops after ``max_stages`` tempering stages WITHOUT the stage at beta = 1 (the state of the
     last stage can be resumed from its directory); by default a run that exhausts ``max_stages`` still ends with the
@@ -385,6 +408,8 @@ def smc_sample(n_steps, step, progressbar=False, on_stage=None, max_stages=200, 
         tm[key] += time.perf_counter() - t0
         return out
 
+    if start is not None:
+        start = check_start(start, step.n_chains, step.lower.size)
     if resume_stage is not None:
         load_stage(step, homepath, resume_stage)
         if update is not None and step.update_map_point is not None:
@@ -393,7 +418,7 @@ def smc_sample(n_steps, step, progressbar=False, on_stage=None, max_stages=200, 
             update.update_weights(step.update_map_point)
     else:
         # stage 0: evaluate the prior population (draws = 1, no move)
-        Q = step.initialize_population()
+        Q = step.initialize_population(start)
         L = timed("sample_s", step.stepper.evaluate, Q)
         timed("gather_s", step.select_end_points, Q, L)
         if update is not None:

@@ -787,6 +787,46 @@ int beatamd_ffi_mstep_batch_grouped(beatamd_ctx *ctx, int32_t model_id, int64_t 
                                     const double *upper, double beta, const double *betas, int32_t *accepted,
                                     int32_t *accepted_sum, int64_t *n_accepted);
 
+/* replaces: DistributionOptimizer.lsq_solution(point)   beat/models/problems.py:753-873
+ *           (the `initialization: lsq` start of an FFI run, beat/config.py:1121-1126, beat/models/base.py:216-231)
+ * With the kinematics of a point fixed, the synthetics are linear in ONE inverted slip variable v (uparr or utens; the
+ * reference's stacking of its blocks is shape-consistent for exactly one); a second sampled slip variable (uperp) is set
+ * to zero.  The rows of the reference's design matrix A and right-hand side d, in this order:
+ *   seismic    per wavemap, target t, sample n: A[(t,n), p] = the synthetic of patch p alone with unit slip
+ *              (seismic.py:1351-1507 with patchidxs=[p]: the library row of v that the point's start time and duration
+ *              select -- itself for nearest neighbour, the four-corner blend of ffi/base.py:663-709 for multilinear);
+ *              d = the wavemap's data.  No weights, no hyper-parameters.
+ *   geodetic   A = G_v^T [Nobs, P]; d = the displacements WITHOUT odw minus the dataset corrections at the point
+ *              (apply_corrections(..., operation="-"), geodetic.py:411-427)
+ *   laplacian  A = L h^2 with h = q[h_laplacian] as sampled (problems.py:845-848); d = 0
+ * A is never formed.  Per chain the entries give the normal equations
+ *     N_c = sum_wm sum_t R_ct R_ct^T + G_v G_v^T + h_c^4 L^T L        b_c = sum_wm sum_t R_ct d_t + G_v (d_geo - corr_c)
+ * (R_ct [P, N]: the chain's rows for target t; G_v G_v^T and L^T L are formed once per model and kept until its data,
+ * corrections or laplacian are replaced) and solve them under x >= 0 by Lawson & Hanson's active set, the algorithm of
+ * scipy.optimize.nnls (problems.py:854).  Every sum has a fixed order that depends on the chain alone: the results of a
+ * chain are bit for bit the same alone, in any batch and in any chunk.
+ * set_lsq_variables: index (into the layout's slip variables) of the inverted variable and of the one set to zero (-1:
+ *   none).  A model without a laplacian is BEATAMD_EINVAL with the reference's text (problems.py:768-772).
+ * lsq_normal_batch: Q [C, nparams] -> N [C, P, P] (exactly symmetric), b [C, P]; chain_bad [C] (nullable): 1 for a chain
+ *   whose times leave the library grid -- the call then fills the arrays and returns BEATAMD_EINDEX, as the likelihood
+ *   flags such chains.
+ * nnls_batch: N [C, n, n] (symmetric; n <= 1024), b [C, n] -> x [C, n], iters [C] (solves of the passive system, at
+ *   least one per variable that enters), status [C]: 0 converged, 1 the cap of 3 n iterations reached (scipy raises
+ *   RuntimeError("Maximum number of iterations reached.")), 2 non-finite N or b or a passive block that is not
+ *   positive definite (x = NaN).  Tolerance on the dual: 10 n 2^-52 max|b|.  One wavefront per chain, the passive
+ *   set's Cholesky factor in n^2 doubles of scratch per chain; batches run in chunks of chains whose scratch stays
+ *   within 256 MiB.
+ * lsq_solution_batch: both of the above, then Q_out = Q_in with v <- x and the zeroed variable <- 0.  The solution is
+ *   NOT clipped to the prior box (the reference does not clip).  Chunks of chains keep the normal matrices within 1 GiB
+ *   of scratch.  Q_in and Q_out may be the same array.  A flagged chain is BEATAMD_EINDEX. */
+int beatamd_ffi_model_set_lsq_variables(beatamd_ctx *ctx, int32_t model_id, int32_t inverted, int32_t zeroed);
+int beatamd_ffi_lsq_normal_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *N, double *b,
+                                 int32_t *chain_bad);
+int beatamd_nnls_batch(beatamd_ctx *ctx, int64_t C, int64_t n, const double *N, const double *b, double *x,
+                       int32_t *iters, int32_t *status);
+int beatamd_ffi_lsq_solution_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q_in, double *Q_out,
+                                   int32_t *iters, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif
