@@ -86,6 +86,9 @@ _PROTOS = {
     "beatamd_ffi_model_add_geodetic_geometry": [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f64,
                                                 _vp, _vp, _i32, _vp, _vp, _vp],
     "beatamd_ffi_model_add_geodetic_corrections": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "beatamd_ffi_model_add_geodetic_corrections_kinds": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "beatamd_pole_coefficients_batch": [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+    "beatamd_pole_coupling_batch": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "beatamd_ffi_model_set_laplacian": [_vp, _i32, _i32],
     "beatamd_ffi_model_nllk": [_vp, _i32, _pi64],
     "beatamd_ffi_model_destroy": [_vp, _i32],

@@ -513,8 +513,10 @@ class GeodeticNoiseCovarianceUpdate(object):
             g = f.problem.geodetic
             dev = torch.device("cuda", f.ctx.device)
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)   # noqa: E731
-            ds, ncol, basis, offs, fixs = correction_tables(g.corrections, g.sizes, f.problem.layout, g.fixed)
-            self._dev = dict(dev=dev, data=up(g.data), terms=list(zip(ds, [up(B.T) for B in basis], offs, fixs)),
+            ds, ncol, basis, offs, fixs, kind, earth = correction_tables(g.corrections, g.sizes, f.problem.layout, g.fixed,
+                                                                         kinds=True)
+            self._dev = dict(dev=dev, data=up(g.data),
+                             terms=list(zip(ds, [up(B.T) for B in basis], offs, fixs, kind, earth)),
                              coords=up(np.concatenate([self.coords[i] for i in self.sar])) if self.sar else None)
         return self._dev
 
@@ -522,14 +524,17 @@ class GeodeticNoiseCovarianceUpdate(object):
         """(Nobs,) torch-cuda: ``d - mu - sum of corrections`` at the point, without the odw factor (the class docstring
         says how)"""
         import torch
+        from .models.corrections import KIND_EULER_POLE, EarthModel, pole_coefficients
         r = self._resident()
         g = self.f.problem.geodetic
         q = np.ascontiguousarray(q_map, dtype=np.float64).ravel()
         mu = self.f.geodetic_residuals(torch.from_numpy(q.reshape(1, -1)).to(r["dev"]), residuals=False)[0]
         res = r["data"] - mu
         starts = np.concatenate([[0], np.cumsum(g.sizes)])
-        for d, Bt, off, fix in r["terms"]:
+        for d, Bt, off, fix, kind, earth in r["terms"]:
             coef = [float(q[o]) if o >= 0 else float(v) for o, v in zip(off, fix)]
+            if kind == KIND_EULER_POLE:     # (pole_lat, pole_lon, omega) -> omega' p, the host statement of k_pole_coef
+                coef = [float(v) for v in pole_coefficients(coef[0], coef[1], coef[2], EarthModel(*earth))]
             corr = Bt[0] * coef[0]
             for k in range(1, len(coef)):
                 corr = corr + Bt[k] * coef[k]

@@ -799,6 +799,17 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
                                                const double *basis, const int64_t *coef_off,
                                                const double *coef_fixed)
 {
+    // every kind 0
+    return beatamd_ffi_model_add_geodetic_corrections_kinds(ctx, model_id, nterm, dataset, ncol, basis, coef_off, coef_fixed,
+                                                            nullptr, nullptr);
+}
+
+int beatamd_ffi_model_add_geodetic_corrections_kinds(beatamd_ctx *ctx, int32_t model_id, int32_t nterm,
+                                                     const int32_t *dataset, const int32_t *ncol,
+                                                     const double *basis, const int64_t *coef_off,
+                                                     const double *coef_fixed, const int32_t *kind,
+                                                     const double *earth)
+{
     ENTER(ctx);
     FfiModel *m;
     BA_TRY(find_model(ctx, model_id, &m));
@@ -822,6 +833,15 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
     BA_TRY(host_copy(ctx, ncol, (size_t)nterm, nc));
     BA_TRY(host_copy(ctx, coef_off, (size_t)nterm * 4, off));
     BA_TRY(host_copy(ctx, coef_fixed, (size_t)nterm * 4, fix));
+    std::vector<int32_t> kd((size_t)nterm, GEO_CORR_LINEAR);
+    std::vector<double> ea((size_t)nterm * 3, 0.0);
+    BA_CHECK((kind == nullptr) == (earth == nullptr), BEATAMD_EINVAL,
+             "add_geodetic_corrections: kind and earth come together");
+    if (kind) {
+        BA_TRY(host_copy(ctx, kind, (size_t)nterm, kd));
+        BA_TRY(host_copy(ctx, earth, (size_t)nterm * 3, ea));
+    }
+    std::vector<PoleTerm> poles;
     const int nd = (int)g.sizes.size();
     std::vector<int64_t> start((size_t)nd, 0);
     for (int d = 1; d < nd; d++) start[d] = start[d - 1] + g.sizes[d - 1];
@@ -846,6 +866,20 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
             t.off[k] = o;
             t.fix[k] = k < nc[j] ? fix[(size_t)j * 4 + k] : 0.0;
         }
+        BA_CHECK(kd[j] == GEO_CORR_LINEAR || kd[j] == GEO_CORR_POLE, BEATAMD_EINVAL,
+                 "add_geodetic_corrections: term %d has the unknown kind %d", j, kd[j]);
+        t.kind = kd[j];
+        if (kd[j] == GEO_CORR_POLE) {
+            BA_CHECK(nc[j] == 3, BEATAMD_EINVAL,
+                     "add_geodetic_corrections: the Euler-pole term %d has %d basis columns, not 3", j, nc[j]);
+            const double *e = &ea[(size_t)j * 3];
+            BA_CHECK(e[0] > 0.0 && e[1] > 0.0 && e[2] >= 0.0 && e[2] < 1.0, BEATAMD_EINVAL,
+                     "add_geodetic_corrections: term %d: earth (radius %g, equator radius %g, oblateness %g)", j, e[0], e[1], e[2]);
+            PoleTerm pt;
+            for (int k = 0; k < 3; k++) { pt.off[k] = t.off[k]; pt.fix[k] = t.fix[k]; pt.earth[k] = e[k]; }
+            t.rec = (int32_t)poles.size();
+            poles.push_back(pt);
+        }
         nbasis += t.n * t.K;
     }
     DevMem<double> d_basis;
@@ -857,10 +891,27 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
     }
     DevMem<GeoCorrTerm> d_terms;
     BA_TRY(d_terms.alloc_copy(ctx, terms.data(), terms.size()));
+    // the pole terms' inputs and one chain's worth of records (the chains' come with the first evaluation,
+    // geo_pole_coefficients): everything that can fail is allocated before anything is installed
+    DevMem<PoleTerm> d_poles;
+    DevMem<double> d_rec;
+    if (!poles.empty()) {
+        BA_TRY(d_poles.alloc_copy(ctx, poles.data(), poles.size()));
+        BA_TRY(d_rec.alloc(poles.size() * 4));
+    }
     g.corr_basis = std::move(d_basis);
     g.corr_terms = std::move(d_terms);
     g.corr.terms = g.corr_terms.get();
     g.corr.nterm = nterm;
+    if (!poles.empty()) {
+        g.pole_terms = std::move(d_poles);
+        g.pole_coef = std::move(d_rec);
+        g.pole_chains = 1;
+        g.corr.npole = (int32_t)poles.size();
+        g.corr.pole_terms = g.pole_terms.get();
+        g.corr.pole_stride = (int64_t)poles.size() * 4;
+        g.corr.pole = g.pole_coef.get();
+    }
     g.corr_set = true;
     return BEATAMD_OK;
 }
@@ -1214,6 +1265,79 @@ int beatamd_standardize_batch(beatamd_ctx *ctx, int32_t kind, const double *S, i
         BA_TRY(launch_gemm_f64(ctx, g));
     }
     if (d_h) BA_TRY(launch_standardize(ctx, C, T, N, nullptr, d_h, d_o, d_o));
+    return st.finish();
+}
+
+static int pole_term_arg(const int64_t *off, const double *fixed, const double *earth, int64_t nparams, PoleTerm *t,
+                         const char *who)
+{
+    for (int k = 0; k < 3; k++) {
+        BA_CHECK(off[k] >= -1 && off[k] < nparams, BEATAMD_EINVAL, "%s: offset %lld of variable %d outside q", who,
+                 (long long)off[k], k);
+        t->off[k] = off[k];
+        t->fix[k] = fixed[k];
+        t->earth[k] = earth[k];
+    }
+    BA_CHECK(earth[0] > 0.0 && earth[1] > 0.0 && earth[2] >= 0.0 && earth[2] < 1.0, BEATAMD_EINVAL,
+             "%s: earth (radius %g, equator radius %g, oblateness %g)", who, earth[0], earth[1], earth[2]);
+    return BEATAMD_OK;
+}
+
+int beatamd_pole_coefficients_batch(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q, int32_t npole,
+                                    const int64_t *var_off, const double *var_fixed, const double *earth, double *out)
+{
+    ENTER(ctx);
+    BA_CHECK(C >= 0 && nparams > 0 && npole >= 1 && npole <= GEO_CORR_MAX && Q && var_off && var_fixed && earth && out,
+             BEATAMD_EINVAL, "pole_coefficients_batch: bad argument");
+    if (C == 0) return BEATAMD_OK;
+    std::vector<int64_t> off;
+    std::vector<double> fix, ea;
+    BA_TRY(host_copy(ctx, var_off, (size_t)npole * 3, off));
+    BA_TRY(host_copy(ctx, var_fixed, (size_t)npole * 3, fix));
+    BA_TRY(host_copy(ctx, earth, (size_t)npole * 3, ea));
+    std::vector<PoleTerm> terms((size_t)npole);
+    for (int j = 0; j < npole; j++)
+        BA_TRY(pole_term_arg(&off[(size_t)j * 3], &fix[(size_t)j * 3], &ea[(size_t)j * 3], nparams, &terms[(size_t)j],
+                             "pole_coefficients_batch"));
+    DevMem<PoleTerm> d_terms;
+    BA_TRY(d_terms.alloc_copy(ctx, terms.data(), terms.size()));
+    Staging st(ctx);
+    const double *d_q;
+    double *d_o;
+    BA_TRY(st.in(Q, (size_t)C * nparams, &d_q));
+    BA_TRY(st.out(out, (size_t)C * npole * 4, &d_o));
+    BA_TRY(launch_pole_coef(ctx, d_terms.get(), npole, d_q, nparams, C, d_o));
+    BA_TRY(st.finish());
+    BA_HIP(hipStreamSynchronize(ctx->stream));   // (the term table goes with this call)
+    return BEATAMD_OK;
+}
+
+int beatamd_pole_coupling_batch(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q, const int64_t *var_off,
+                                const double *var_fixed, const double *earth, int64_t P, const double *Bp, int64_t uparr_off,
+                                double *euler_slips, double *coupling)
+{
+    ENTER(ctx);
+    BA_CHECK(C >= 0 && nparams > 0 && P >= 1 && Q && var_off && var_fixed && earth && Bp && euler_slips && coupling,
+             BEATAMD_EINVAL, "pole_coupling_batch: bad argument");
+    BA_CHECK(uparr_off >= 0 && uparr_off + P <= nparams, BEATAMD_EINVAL,
+             "pole_coupling_batch: uparr [%lld, %lld) outside q of %lld", (long long)uparr_off, (long long)(uparr_off + P),
+             (long long)nparams);
+    if (C == 0) return BEATAMD_OK;
+    std::vector<int64_t> off;
+    std::vector<double> fix, ea;
+    BA_TRY(host_copy(ctx, var_off, 3, off));
+    BA_TRY(host_copy(ctx, var_fixed, 3, fix));
+    BA_TRY(host_copy(ctx, earth, 3, ea));
+    PoleTerm term;
+    BA_TRY(pole_term_arg(off.data(), fix.data(), ea.data(), nparams, &term, "pole_coupling_batch"));
+    Staging st(ctx);
+    const double *d_q, *d_b;
+    double *d_e, *d_c;
+    BA_TRY(st.in(Q, (size_t)C * nparams, &d_q));
+    BA_TRY(st.in(Bp, (size_t)P * 3, &d_b));
+    BA_TRY(st.out(euler_slips, (size_t)C * P, &d_e));
+    BA_TRY(st.out(coupling, (size_t)C * P, &d_c));
+    BA_TRY(launch_pole_coupling(ctx, term, d_q, nparams, C, P, d_b, uparr_off, d_e, d_c));
     return st.finish();
 }
 

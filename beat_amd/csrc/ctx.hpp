@@ -186,16 +186,33 @@ struct Wavemap {
 // coef_k = q[c, off[k]] or, with off[k] < 0, fix[k].  The table lives in device memory; the residual kernels read it
 // through wave-uniform (scalar) loads
 constexpr int GEO_CORR_MAX = 32;   // terms per composite (beatamd_ffi_model_add_geodetic_corrections)
+//
+// kind 1, the Euler pole (corrections.py:90-140, heart.py:4326-4392): K = 3 and the coefficients are not entries of q
+// but omega' p, derived per chain from q[off[0..2]] = (pole_lat, pole_lon, omega) by k_pole_coef (corrections.hip) into
+// the composite's record buffer pole [C, npole, 4] (32-byte records; slot 3 is zero).  `rec` is the term's record
 struct GeoCorrTerm {
     int64_t start, n;
     const double *B;      // device [K, n]: column k at B + k*n
     int64_t off[4];
     double fix[4];
-    int32_t K, pad_;
+    int32_t K, kind;      // kind: GEO_CORR_LINEAR / GEO_CORR_POLE
+    int32_t rec, pad_;    // kind 1: index of the term's record within a chain's records
+};
+constexpr int GEO_CORR_LINEAR = 0, GEO_CORR_POLE = 1;
+// what k_pole_coef reads per pole term: the slots of (pole_lat, pole_lon, omega) [deg, deg, deg/Myr] in q (-1: fix)
+// and the earth's (radius, equatorial radius, oblateness)
+struct PoleTerm {
+    int64_t off[3];
+    double fix[3];
+    double earth[3];
 };
 struct GeoCorr {
     const GeoCorrTerm *terms = nullptr;   // device [nterm]
     int32_t nterm = 0;
+    int32_t npole = 0;                    // pole terms among them
+    const double *pole = nullptr;         // device [C, npole, 4]: the derived coefficients, written by k_pole_coef
+    int64_t pole_stride = 0;              // doubles per chain: npole * 4
+    const PoleTerm *pole_terms = nullptr; // device [npole]
 };
 
 struct Geodetic {
@@ -210,6 +227,11 @@ struct Geodetic {
     GeoCorr corr;                        // what the kernels get: a view of corr_terms
     DevMem<GeoCorrTerm> corr_terms;      // device [corr.nterm]
     DevMem<double> corr_basis;           // device, the terms' basis columns concatenated
+    // pole terms: their inputs, and the derived-coefficient records of pole_chains chains.  Allocated with the table and
+    // grown with the chain count by geo_pole_coefficients (model.cpp), never inside a graph capture
+    DevMem<PoleTerm> pole_terms;         // device [corr.npole]
+    mutable DevMem<double> pole_coef;    // device [pole_chains, corr.npole, 4] (a cache of the evaluator, hence mutable)
+    mutable int64_t pole_chains = 0;
 };
 
 // geometry-mode sources of the geodetic composite (analytic half space)

@@ -239,6 +239,12 @@ int launch_geo_residual(beatamd_ctx *ctx, int64_t C, int64_t Nobs, const double 
                         const double *odw, const double *mu, double *res, const double *Q = nullptr,
                         int64_t nparams = 0, GeoCorr gc = GeoCorr());
 
+// corrections.hip: out [C, npole, 4] = the derived coefficients omega' p of every (chain, pole term) (k_pole_coef);
+// euler_slips, coupling [C, P] of one pole against a patch basis Bp [P, 3] and the back-slip q[c, uparr_off + p]
+int launch_pole_coef(beatamd_ctx *ctx, const PoleTerm *terms, int npole, const double *Q, int64_t nparams, int64_t C, double *out);
+int launch_pole_coupling(beatamd_ctx *ctx, const PoleTerm &term, const double *Q, int64_t nparams, int64_t C, int64_t P,
+                         const double *Bp, int64_t uparr_off, double *euler_slips, double *coupling);
+
 #ifdef __HIPCC__
 // The weighted residual of observation k of chain c with the correction terms of k's dataset subtracted one after the
 // other in table order (geodetic.py:1072-1077, 411-427):
@@ -249,8 +255,11 @@ int launch_geo_residual(beatamd_ctx *ctx, int64_t C, int64_t Nobs, const double 
 // coefficients q[c, off] are wave-uniform wherever the wavefront lies inside one chain (the flat (chain, observation)
 // index lets a wavefront straddle two): that wavefront reads them through scalar loads from the first lane's chain,
 // a straddling one per lane.  The basis columns are the only per-lane loads either way.
+// A pole term (kind 1) takes its three coefficients from the chain's derived records Pc = gc.pole + c * gc.pole_stride
+// (k_pole_coef wrote them ahead of this kernel) instead of q, through the same kind of load; the products, the sum
+// order and the subtraction are the same lines.
 template <bool UNIFORM>
-__device__ __forceinline__ double geo_corr_subtract(const GeoCorr &gc, const double *Qc, int64_t k, double r)
+__device__ __forceinline__ double geo_corr_subtract(const GeoCorr &gc, const double *Qc, const double *Pc, int64_t k, double r)
 {
 #pragma clang fp contract(off)
     typedef const __attribute__((address_space(4))) GeoCorrTerm *TermPtr;
@@ -260,8 +269,9 @@ __device__ __forceinline__ double geo_corr_subtract(const GeoCorr &gc, const dou
         // the whole row and all four coefficient slots at once, ahead of any branch: the compiler batches them into
         // three rounds of scalar loads per term instead of one per field (an unused slot has offset -1 and the fixed
         // value 0; q[0] stands in for its load)
-        struct { int64_t start, n; const double *B; int64_t off[4]; double fix[4]; int K; } t;
+        struct { int64_t start, n; const double *B; int64_t off[4]; double fix[4]; int K, kind, rec; } t;
         t.start = terms[j].start; t.n = terms[j].n; t.B = terms[j].B; t.K = terms[j].K;
+        t.kind = terms[j].kind; t.rec = terms[j].rec;
 #pragma unroll
         for (int kk = 0; kk < 4; kk++) { t.off[kk] = terms[j].off[kk]; t.fix[kk] = terms[j].fix[kk]; }
         double coef[4];
@@ -270,6 +280,11 @@ __device__ __forceinline__ double geo_corr_subtract(const GeoCorr &gc, const dou
             const int64_t o = t.off[kk] < 0 ? 0 : t.off[kk];
             const double q = UNIFORM ? ((ConstPtr)Qc)[o] : Qc[o];
             coef[kk] = t.off[kk] < 0 ? t.fix[kk] : q;
+        }
+        if (t.kind == GEO_CORR_POLE) {   // (the same for every lane)
+            const double *P = Pc + (int64_t)t.rec * 4;
+#pragma unroll
+            for (int kk = 0; kk < 4; kk++) coef[kk] = UNIFORM ? ((ConstPtr)P)[kk] : P[kk];
         }
         const int64_t row = k - t.start;
         if (row < 0 || row >= t.n) continue;
@@ -294,8 +309,9 @@ __device__ __forceinline__ double geo_corrected_residual(const GeoCorr &gc, cons
 #pragma clang fp contract(off)
     const double r = (d - mu) * odw;
     const int c0 = __builtin_amdgcn_readfirstlane((int)c);
-    if (__all(c == (int64_t)c0)) return geo_corr_subtract<true>(gc, Q + (int64_t)c0 * nparams, k, r);
-    return geo_corr_subtract<false>(gc, Q + c * nparams, k, r);
+    if (__all(c == (int64_t)c0))
+        return geo_corr_subtract<true>(gc, Q + (int64_t)c0 * nparams, gc.pole + (int64_t)c0 * gc.pole_stride, k, r);
+    return geo_corr_subtract<false>(gc, Q + c * nparams, gc.pole + c * gc.pole_stride, k, r);
 }
 #endif
 // the hyper model's cached misfits: dst[c*ld + k] = src[c*n + k], k < n; then NaN into the rows of flagged chains

@@ -245,7 +245,7 @@ __global__ void __launch_bounds__(256) k_lsq_finish(LsqFinishArgs a)
         const double *g = a.Ggeo + i * a.Nobs;
         for (int64_t k = lane; k < a.Nobs; k += 64) {
             // apply_corrections(displacements, point, operation="-") (geodetic.py:411-427): no odw factor
-            const double r = geo_corr_subtract<false>(a.corr, Qc, k, a.dgeo[k]);
+            const double r = geo_corr_subtract<false>(a.corr, Qc, a.corr.pole + c * a.corr.pole_stride, k, a.dgeo[k]);
             s = fma(g[k], r, s);
         }
         s = lsq_wave_sum(s);

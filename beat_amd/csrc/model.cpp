@@ -102,6 +102,28 @@ int wavemap_call(beatamd_ctx *ctx, const FfiModel &m, const Wavemap &wm, int64_t
     return BEATAMD_OK;
 }
 
+// The composite's correction table as the kernels of this call get it.  With pole terms: the derived coefficients of
+// the C chains are written first (k_pole_coef, on the stream ahead of the consumer) into the composite's record buffer,
+// which grows with the chain count -- never inside a graph capture (the eager step in front of a capture sizes it)
+int geo_pole_coefficients(beatamd_ctx *ctx, const Geodetic &g, int64_t C, const double *Q, int64_t np, GeoCorr *gc)
+{
+    *gc = g.corr;
+    if (g.corr.npole == 0 || C == 0) return BEATAMD_OK;
+    if (C > g.pole_chains) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        BA_HIP(hipStreamIsCapturing(ctx->stream, &cap));
+        BA_CHECK(cap == hipStreamCaptureStatusNone, BEATAMD_EINVAL,
+                 "pole coefficients: %lld chains inside a graph capture, the buffer holds %lld (run one step before the capture)",
+                 (long long)C, (long long)g.pole_chains);
+        BA_HIP(hipStreamSynchronize(ctx->stream));   // (kernels in flight may read the records that go)
+        g.pole_chains = 0;                           // (alloc frees what was held first: nothing is held if it fails)
+        BA_TRY(g.pole_coef.alloc((size_t)C * g.corr.npole * 4));
+        g.pole_chains = C;
+    }
+    gc->pole = g.pole_coef.get();
+    return launch_pole_coef(ctx, g.corr.pole_terms, g.corr.npole, Q, np, C, g.pole_coef.get());
+}
+
 int geodetic_residual(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const double *Q, double *mu_out, double *res_out)
 {
     const Geodetic &g = m.geo;
@@ -113,7 +135,9 @@ int geodetic_residual(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const doub
     if (m.geo_is_geometry) {
         if (!res_out) return launch_geom_los(ctx, m.geom, Q, np, C, mu_out);
         // synthetics, line of sight and weighted residual in one kernel
-        return launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data.get(), g.odws.get(), res_out, g.corr);
+        GeoCorr gc;
+        BA_TRY(geo_pole_coefficients(ctx, g, C, Q, np, &gc));
+        return launch_geom_los(ctx, m.geom, Q, np, C, nullptr, g.data.get(), g.odws.get(), res_out, gc);
     }
     // every slip variable's G.T . slips in one launch (geodetic.py:1065-1070 sums them)
     const GeoLib *gls[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -126,7 +150,9 @@ int geodetic_residual(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const doub
     }
     BA_TRY(launch_geo_stack(ctx, gls, m.layout.nvar, C, slips, 0, mu_out));
     if (!res_out) return BEATAMD_OK;
-    return launch_geo_residual(ctx, C, g.Nobs, g.data.get(), g.odws.get(), mu_out, res_out, Q, np, g.corr);
+    GeoCorr gc;
+    BA_TRY(geo_pole_coefficients(ctx, g, C, Q, np, &gc));
+    return launch_geo_residual(ctx, C, g.Nobs, g.data.get(), g.odws.get(), mu_out, res_out, Q, np, gc);
 }
 
 int laplacian_quad(beatamd_ctx *ctx, const Laplacian &lap, int64_t C, int64_t nvar, const double *slips, double *quad)
@@ -380,8 +406,10 @@ int lsq_normal_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q,
             has_seis = 1;
         }
     }
+    GeoCorr gc;
+    if (m.has_geo) BA_TRY(geo_pole_coefficients(ctx, m.geo, C, Q, np, &gc));
     return launch_lsq_finish(ctx, C, P, Nmat, b, has_seis, m.lsq_GG.get(), m.lsq_LtL.get(), gl ? gl->g.get() : nullptr,
-                             m.has_geo ? m.geo.Nobs : 0, m.has_geo ? m.geo.data.get() : nullptr, m.geo.corr, Q, np,
+                             m.has_geo ? m.geo.Nobs : 0, m.has_geo ? m.geo.data.get() : nullptr, gc, Q, np,
                              m.layout.h_laplacian_off);
 }
 

@@ -37,6 +37,9 @@ int wavemap_call(beatamd_ctx *ctx, const FfiModel &m, const Wavemap &wm, int64_t
 // geodetic synthetics mu_out [C, Nobs] and weighted, corrected residuals res_out [C, Nobs] (geometry mode writes only the
 // residuals).  res_out == nullptr: the synthetics alone.  Q == nullptr: one chain of (d - 0) * odw, without corrections
 int geodetic_residual(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const double *Q, double *mu_out, double *res_out);
+// *gc = the composite's correction table for a kernel launched next on C chains: with pole terms their derived
+// coefficients are computed first (k_pole_coef) into the composite's own buffer, grown here outside any capture
+int geo_pole_coefficients(beatamd_ctx *ctx, const Geodetic &g, int64_t C, const double *Q, int64_t np, GeoCorr *gc);
 // quad[c, v] = |L s_{c,v}|^2 of the slips [C, nvar, P]
 int laplacian_quad(beatamd_ctx *ctx, const Laplacian &lap, int64_t C, int64_t nvar, const double *slips, double *quad);
 

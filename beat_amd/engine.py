@@ -414,12 +414,42 @@ class Context(object):
             ptr(north), ptr(los), float(nu), ptr(data), ptr(odws), int(sizes.size), ptr(sizes), ptr(ws),
             ptr(hp)))
 
-    def ffi_model_add_geodetic_corrections(self, model_id, dataset, ncol, basis, coef_off, coef_fixed):
+    @staticmethod
+    def check_correction_kinds(ncol, kind, earth):
+        """the argument rules of the ..._kinds entry that need no model, checked ahead of the call (the library checks
+        them again, and the offsets against the model's q): kind 0 or 1; a pole term has three columns and an earth of
+        positive radii and an oblateness in [0, 1).  -> (kind int32 (nterm,), earth float64 (nterm, 3))"""
+        nc = np.ascontiguousarray(ncol, dtype=np.int32)
+        kd = np.ascontiguousarray(kind, dtype=np.int32)
+        if kd.shape != nc.shape:
+            raise ValueError("correction kinds: %d for %d terms" % (kd.size, nc.size))
+        ea = np.ascontiguousarray(earth, dtype=np.float64)
+        if ea.size != 3 * nc.size:
+            raise ValueError("correction earth constants: %d values for %d terms (3 each)" % (ea.size, nc.size))
+        ea = ea.reshape(nc.size, 3)
+        for j in range(nc.size):
+            if kd[j] not in (0, 1):
+                raise ValueError("correction term %d has the unknown kind %d" % (j, kd[j]))
+            if kd[j] == 1:
+                if nc[j] != 3:
+                    raise ValueError("the Euler-pole term %d has %d basis columns, not 3" % (j, nc[j]))
+                r, a, f = ea[j]
+                if not (r > 0.0 and a > 0.0 and 0.0 <= f < 1.0):
+                    raise ValueError("correction term %d: earth (radius %g, equator radius %g, oblateness %g)"
+                                     % (j, r, a, f))
+        return kd, ea
+
+    def ffi_model_add_geodetic_corrections(self, model_id, dataset, ncol, basis, coef_off, coef_fixed, kind=None,
+                                           earth=None):
         """dataset corrections of the model's geodetic composite: per term its dataset index, column count, basis
-        (n x K, one array per term), coefficient offsets in q (-1: fixed) and fixed values (K each)"""
+        (n x K, one array per term), coefficient offsets in q (-1: fixed) and fixed values (K each).  kind / earth
+        (``correction_tables(kinds=True)``): per term 0 (linear) or 1 (Euler pole: the offsets name pole_lat, pole_lon,
+        omega) and its earth constants (radius, equator radius, oblateness) -- the ..._kinds entry"""
         nterm = len(dataset)
         ds = np.ascontiguousarray(dataset, dtype=np.int32)
         nc = np.ascontiguousarray(ncol, dtype=np.int32)
+        if kind is not None:
+            kd, ea = self.check_correction_kinds(nc, kind, earth)
         off = -np.ones((nterm, 4), dtype=np.int64)
         fix = np.zeros((nterm, 4))
         cols = []
@@ -432,6 +462,10 @@ class Context(object):
                 raise ValueError("correction term %d: basis of shape %s, expected (n, %d)" % (j, B.shape, k))
             cols.append(np.ravel(B, order="F"))
         flat = np.ascontiguousarray(np.concatenate(cols)) if cols else np.zeros(0)
+        if kind is not None:
+            check(self._lib.beatamd_ffi_model_add_geodetic_corrections_kinds(
+                self._h, model_id, nterm, ptr(ds), ptr(nc), ptr(flat), ptr(off), ptr(fix), ptr(kd), ptr(ea)))
+            return
         check(self._lib.beatamd_ffi_model_add_geodetic_corrections(
             self._h, model_id, nterm, ptr(ds), ptr(nc), ptr(flat), ptr(off), ptr(fix)))
 
@@ -956,6 +990,43 @@ class Context(object):
             out = _empty_like(r, (Cn, T, N))
         check(self._lib.beatamd_standardize_batch(self._h, kind, ptr(Sc), T, N, Cn, ptr(r), ptr(h), ptr(out)))
         return out
+
+    def pole_coefficients_batch(self, Q, var_off, var_fixed, earth, out=None):
+        """Q (C, nparams) -> (C, npole, 4): the derived Euler-pole coefficients ``omega' p`` (slot 3 zero) of every row
+        and pole, by the kernel the model launches.  var_off / var_fixed / earth: (npole, 3) offsets of (pole_lat,
+        pole_lon, omega) in q (-1: the fixed value) and (radius, equator radius, oblateness)"""
+        self._adopt_stream(Q)
+        Q = f64(Q)
+        Cn, npar = int(Q.shape[0]), int(Q.shape[1])
+        off = np.ascontiguousarray(var_off, dtype=np.int64).reshape(-1, 3)
+        fix = np.ascontiguousarray(var_fixed, dtype=np.float64).reshape(-1, 3)
+        ea = np.ascontiguousarray(earth, dtype=np.float64).reshape(-1, 3)
+        if not (off.shape == fix.shape == ea.shape):
+            raise ValueError("pole_coefficients_batch: offsets, fixed values and earth constants differ in shape")
+        if out is None:
+            out = _empty_like(Q, (Cn, off.shape[0], 4))
+        check(self._lib.beatamd_pole_coefficients_batch(self._h, Cn, npar, ptr(Q), int(off.shape[0]), ptr(off), ptr(fix),
+                                                        ptr(ea), ptr(out)))
+        return out
+
+    def pole_coupling_batch(self, Q, var_off, var_fixed, earth, basis, uparr_off):
+        """Q (C, nparams) -> (euler_slips, coupling), each (C, P): ``euler_pole2slips`` and ``backslip2coupling``
+        (ffi/fault.py:1436-1517) of every row for one pole against the patch basis (P, 3) of
+        ``summary.pole_patch_basis``; uparr_off: offset of the P back-slips in q"""
+        self._adopt_stream(Q)
+        Q = f64(Q)
+        Cn, npar = int(Q.shape[0]), int(Q.shape[1])
+        off = np.ascontiguousarray(var_off, dtype=np.int64).reshape(3)
+        fix = np.ascontiguousarray(var_fixed, dtype=np.float64).reshape(3)
+        ea = np.ascontiguousarray(earth, dtype=np.float64).reshape(3)
+        Bp = f64(basis)
+        if Bp.ndim != 2 or Bp.shape[1] != 3 or _is_dev(Bp) != _is_dev(Q):
+            raise ValueError("pole_coupling_batch: basis must be (P, 3) on Q's side")
+        P = int(Bp.shape[0])
+        es, cp = _empty_like(Q, (Cn, P)), _empty_like(Q, (Cn, P))
+        check(self._lib.beatamd_pole_coupling_batch(self._h, Cn, npar, ptr(Q), ptr(off), ptr(fix), ptr(ea), P, ptr(Bp),
+                                                    int(uparr_off), ptr(es), ptr(cp)))
+        return es, cp
 
     def ensemble_moments_update(self, X, state=None, n_seen=0):
         """fold the rows of X (C, M) into the running column moments ``state`` (5, M) = (mean, M2, min, max, rows

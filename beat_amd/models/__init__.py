@@ -2,6 +2,6 @@ from .problem import (FFIProblem, GeodeticData, LogpForwFunc, ParameterLayout,  
                       SeismicWavemap, prior_logp_func)
 from .distributions import get_hyper_name, multivariate_normal_chol  # noqa: F401,E402
 from .geometry import GeodeticGeometryProblem, los_vectors  # noqa: F401,E402
-from .corrections import (RampConfig, RampCorrection, StrainRateConfig,  # noqa: F401,E402
-                          StrainRateCorrection)
+from .corrections import (EarthModel, EulerPoleConfig, EulerPoleCorrection, RampConfig,  # noqa: F401,E402
+                          RampCorrection, StrainRateConfig, StrainRateCorrection)
 from .hypers import HyperModel, dataset_hypers, estimate_hypers  # noqa: F401,E402

@@ -111,5 +111,5 @@ class GeodeticGeometryProblem(object):
                                             self.sizes, self._wsets, hp_off)
         if self.corrections is not None:
             ctx.ffi_model_add_geodetic_corrections(
-                mid, *correction_tables(self.corrections, self.sizes, self.layout, self.fixed))
+                mid, *correction_tables(self.corrections, self.sizes, self.layout, self.fixed, kinds=True))
         return LogpForwFunc(ctx, mid, self)

@@ -278,7 +278,7 @@ class FFIProblem(object):
             hp_off = [lay.offset(n, i) for n, i in g.hypers]
             ctx.ffi_model_add_geodetic(mid, libs, g.data, g.odws, g.sizes, g._wsets, hp_off)
             if g.corrections is not None:
-                ctx.ffi_model_add_geodetic_corrections(mid, *correction_tables(g.corrections, g.sizes, lay, g.fixed))
+                ctx.ffi_model_add_geodetic_corrections(mid, *correction_tables(g.corrections, g.sizes, lay, g.fixed, kinds=True))
         if self.laplacian is not None:
             L, logdet = self.laplacian
             self._lap = ctx.laplacian_create(L, logdet)

@@ -153,3 +153,66 @@ def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, 
             entry["synthetics"] = np.concatenate(kept) if kept else np.zeros((0, T, N))
         moments[wi] = entry
     return idx, var_reductions, moments
+
+
+def pole_patch_basis(patch_lats, patch_lons, strikevectors_enu, earth=None):
+    """(P, 3) basis of the Euler-pole slip along strike of fault patches (``euler_pole2slips``, ffi/fault.py:1436-1497):
+    the strike vectors go ENU -> NEU as fault.py:1478-1480 swaps them (the third component is left at zero there), and
+    then stand where a dataset's line of sight stands in ``EulerPoleCorrection.basis()``:
+    ``euler_slips = |basis @ coefficients|``.  The patch centres' lats / lons [deg] are the caller's (the reference
+    derives them with pyrocko's ``ne_to_latlon``); earth: ``EarthModel`` (None: the defaults)."""
+    from .models.corrections import EulerPoleConfig
+    sv = np.asarray(strikevectors_enu, dtype=np.float64)
+    neu = np.zeros_like(sv)
+    neu[:, 0] = sv[:, 1]
+    neu[:, 1] = sv[:, 0]
+    corr = EulerPoleConfig(dataset_names=["patches"], enabled=True).init_correction()
+    corr.setup_correction(patch_lats, patch_lons, neu, np.zeros(neu.shape[0], dtype=bool), "patches", earth=earth)
+    return corr.basis()
+
+
+def coupling_ensemble(f, Q, basis, pole_names, earth=None, batch=512):
+    """coupling maps of a batch of draws: ``backslip2coupling(point, euler_pole2slips(point, ...))``
+    (ffi/fault.py:1436-1517) for every row of Q (n, nparams) against the patch basis (P, 3) of ``pole_patch_basis``.
+    pole_names: the (pole_lat, pole_lon, omega) variables of ONE pole -- the reference takes the first of several too;
+    each is looked up in the model's layout, else in the geodetic composite's fixed values.  earth: the EarthModel
+    the basis was built with (None: the defaults).  The back-slip is the layout's ``uparr``.
+    -> dict(coupling (n, P) [percent], euler_slips (n, P), mean, std (P,) of the coupling over the draws, NaN where a
+    draw's ratio is 0 / 0), through ``ensemble_moments``; numpy in -> numpy out, torch-cuda in -> tensors."""
+    from .models.corrections import EarthModel
+    ctx = _ctx_of(f)
+    lay = f.problem.layout
+    fixed = getattr(getattr(f.problem, "geodetic", None), "fixed", None) or {}
+    off, fix = [], []
+    for name in pole_names:
+        if name in lay.offsets:
+            off.append(lay.offset(name, 0))
+            fix.append(0.0)
+        elif name in fixed:
+            off.append(-1)
+            fix.append(float(np.ravel(fixed[name])[0]))
+        else:
+            raise KeyError("pole variable %s is neither sampled nor fixed" % name)
+    if len(off) != 3:
+        raise ValueError("coupling_ensemble: pole_names = (pole_lat, pole_lon, omega) of one pole")
+    earth = (earth if earth is not None else EarthModel()).as_tuple()
+    tensor_in = _is_tensor(Q)
+    Bp = _to_device(ctx, basis)
+    P = int(Bp.shape[0])
+    if lay.varsizes["uparr"] != P:
+        raise ValueError("coupling_ensemble: %d patches in the basis, %d back-slips in the layout" % (P, lay.varsizes["uparr"]))
+    n, batch = int(Q.shape[0]), max(int(batch), 1)
+    es_all, cp_all, state, seen = [], [], None, 0
+    for a in range(0, max(n, 1), batch):          # (an empty population still gives its (0, P) arrays)
+        q = _to_device(ctx, Q[a:a + batch]).contiguous()
+        es, cp = ctx.pole_coupling_batch(q, off, fix, earth, Bp, lay.offset("uparr", 0))
+        state, seen = ctx.ensemble_moments_update(cp, state, seen)
+        es_all.append(es)
+        cp_all.append(cp)
+    import torch
+    out = dict(euler_slips=torch.cat(es_all), coupling=torch.cat(cp_all))
+    if seen:
+        out["mean"], out["std"] = ctx.ensemble_moments_finish(state, seen)[:2]
+    if not tensor_in:
+        out = dict((k, v.cpu().numpy()) for k, v in out.items())
+    return out

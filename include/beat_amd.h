@@ -346,8 +346,8 @@ int beatamd_ffi_model_add_geodetic_geometry(beatamd_ctx *ctx, int32_t model_id, 
  * and the terms of a dataset are subtracted one after the other in list order (the reference's iter_corrections:
  * ramp, then strain rate).  Ramp: K = 3, B = [locy, locx, 1], coefficients (azimuth_ramp, range_ramp, offset) --
  * bit for bit numpy's expression.  Strain rate: K = 4, the velocity-gradient tensor folded into four columns on
- * the host, coefficients (exx, eyy, exy, rotation) -- equal to the reference to rounding.  The Euler-pole term is
- * not offered: its coefficients are not linear in the sampled pole position.
+ * the host, coefficients (exx, eyy, exy, rotation) -- equal to the reference to rounding.  The Euler-pole term
+ * needs the entry below (this one declares every term linear in entries of q).
  * The subtraction happens in the kernel that forms the residual; the stand-alone synthetics are unchanged.
  *   dataset [nterm] non-decreasing   ncol [nterm] 1..4   coef_off, coef_fixed [nterm*4]
  *   basis: the terms concatenated, term j is dataset_sizes[dataset[j]] x ncol[j], column-major
@@ -356,6 +356,45 @@ int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_i
                                                const int32_t *dataset, const int32_t *ncol,
                                                const double *basis, const int64_t *coef_off,
                                                const double *coef_fixed);
+/* The same with a kind per term: kind[j] = 0 is the linear term above (the entry above is this one with every kind 0,
+ * kind == earth == NULL), kind[j] = 1 the Euler-pole correction (beat/models/corrections.py:90-140,
+ * heart.velocities_from_pole beat/heart.py:4326-4392 with earth_shape="ellipsoid", EulerPoleConfig
+ * beat/config.py:840-853; in iter_corrections' order, config.py:904-909, between ramp and strain rate).
+ * A pole term has K = 3 and its coef_off / coef_fixed slots name (pole_lat, pole_lon, omega) [deg, deg, deg / Myr],
+ * each sampled or fixed.  With x_i = ecef(lat_i, lon_i, 0) / r, T_i the ECEF -> NEU rotation (heart.py:4352-4369)
+ * and l_i the line of sight (NEU)
+ *     corr[c,i] = l_i . T_i (w' p x x_i) = (B[i,0]*coef0 + B[i,1]*coef1) + B[i,2]*coef2
+ *     B[i,:] = x_i x (T_i^T l_i)  (host: EulerPoleCorrection.basis(), masked rows zero)      coef = w' p
+ *     p = ecef(pole_lat, pole_lon, 0) / r         w' = omega * 1e-6 * (pi / 180) * r
+ * so the basis is the caller's as for every term; the three coefficients are derived per chain on the device
+ * (k_pole_coef, corrections.hip, which states the order of operations) in front of every kernel that subtracts the
+ * table, into a buffer the model owns ([C, npole, 4] doubles, grown with the chain count outside graph captures).
+ * earth [nterm*3] = (r, equatorial radius a, oblateness f) of the term's ellipsoid [m, m, 1] (ignored for kind 0):
+ * ecef is the closed form N = a / sqrt(1 - e2 sin^2 lat), e2 = 2f - f^2, (N cos lat cos lon, N cos lat sin lon,
+ * N (1 - e2) sin lat); a = r, f = 0 is the reference's earth_shape="sphere".  Equal to the reference's evaluation
+ * within 16 * 2^-53 * |w'| * |l_i|_1. */
+int beatamd_ffi_model_add_geodetic_corrections_kinds(beatamd_ctx *ctx, int32_t model_id, int32_t nterm,
+                                                     const int32_t *dataset, const int32_t *ncol,
+                                                     const double *basis, const int64_t *coef_off,
+                                                     const double *coef_fixed, const int32_t *kind,
+                                                     const double *earth);
+/* the derived coefficients alone: out [C, npole, 4] = (w' p, 0) of every (row of Q, pole), the kernel the model
+ * launches (k_pole_coef).  var_off / var_fixed / earth [npole*3] as above (offset -1: the fixed value) */
+int beatamd_pole_coefficients_batch(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q, int32_t npole,
+                                    const int64_t *var_off, const double *var_fixed, const double *earth,
+                                    double *out);
+/* replaces: euler_pole2slips and backslip2coupling, beat/ffi/fault.py:1436-1517, for a batch of draws Q [C, nparams]
+ *   of ONE pole (the reference takes the first of several too): var_off / var_fixed / earth [3] as above;
+ *   Bp [P, 3] = x_p x (T_p^T s_p) of the patch centres with the strike vectors (NEU) in place of the line of sight
+ *   (host: summary.pole_patch_basis; the patch coordinates are the caller's, ne_to_latlon is pyrocko's);
+ *   uparr_off: the offset of the P back-slips in q.
+ *     euler_slips [C, P] = |(Bp[p,0]*coef0 + Bp[p,1]*coef1) + Bp[p,2]*coef2|            fault.py:1497
+ *     coupling    [C, P] = 100 * clip(uparr / euler_slips, 0, 1)                         fault.py:1514-1517
+ *   with numpy's IEEE semantics: a NaN ratio stays NaN, x / 0 -> +-inf -> 100 / 0.  Rows are independent: a batch
+ *   cut into calls gives the same bits. */
+int beatamd_pole_coupling_batch(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q, const int64_t *var_off,
+                                const double *var_fixed, const double *earth, int64_t P, const double *Bp,
+                                int64_t uparr_off, double *euler_slips, double *coupling);
 int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t lap_id);
 int beatamd_ffi_model_nllk(beatamd_ctx *ctx, int32_t model_id, int64_t *nllk);
 int beatamd_ffi_model_destroy(beatamd_ctx *ctx, int32_t model_id);
