@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("BEATAMD_LIB") or os.path.join(_HERE, "libbeat_amd.so"
 
 NEAREST_NEIGHBOR, MULTILINEAR = 0, 1
 W_SCALAR, W_DENSE = 0, 1
+STF_HALF_SINUSOID = 0
 INTERPOLATIONS = {"nearest_neighbor": NEAREST_NEIGHBOR, "multilinear": MULTILINEAR}
 
 OK, EINVAL, EHIP, EINDEX, ENOMEM, ENAN, ENOTPSD, EBADCOV, EOUTSIDE = 0, -1, -2, -3, -4, -5, -6, -7, -8
@@ -94,6 +95,9 @@ _PROTOS = {
     "beatamd_ffi_model_destroy": [_vp, _i32],
     "beatamd_ffi_logp_batch": [_vp, _i32, _i64, _vp, _vp],
     "beatamd_ffi_start_times_batch": [_vp, _i32, _i64, _vp, _vp, _vp],
+    "beatamd_ffi_magnitudes_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp],
+    "beatamd_ffi_moment_rate_spans_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _f64, _vp],
+    "beatamd_ffi_moment_rates_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _f64, _i32, _i64, _i64, _vp, _vp],
     "beatamd_ffi_synthetics_batch": [_vp, _i32, _i32, _i64, _vp, _i32, _vp],
     "beatamd_ffi_astep_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp],
     "beatamd_autocovariance_batch": [_vp, _i64, _i64, _vp, _vp, _vp],
@@ -140,6 +144,7 @@ _PROTOS = {
     "beatamd_ensemble_moments_update": [_vp, _i64, _i64, _vp, _vp, _i64],
     "beatamd_ensemble_moments_finish": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
     "beatamd_trace_density_update": [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _i64, _i64, _f64, _vp],
+    "beatamd_trace_density_update_ranges": [_vp, _i64, _i64, _i64, _vp, _vp, _f64, _vp, _vp, _i64, _i64, _f64, _vp],
     "beatamd_like_assemble": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp],
     "beatamd_metropolis_propose": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "beatamd_metropolis_accept": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _vp],

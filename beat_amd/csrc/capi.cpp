@@ -1002,6 +1002,137 @@ int beatamd_ffi_start_times_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C,
     return ctx->check_status();     // a hypocentre outside the patch grid: the flags say which chains
 }
 
+// ---- moment, magnitude and moment-rate functions of a batch of draws (momentrate.hip)
+namespace {
+
+// the slip components of a moment: comp_off [ncomp] offsets in q (host or device array), or NULL: the layout's own
+int mr_components(beatamd_ctx *ctx, const FfiModel &m, const int64_t *comp_off, int32_t ncomp, const char *what, MrComps *out)
+{
+    const beatamd_ffi_layout &L = m.layout;
+    if (!comp_off) {
+        out->n = L.nvar;
+        for (int v = 0; v < L.nvar; v++) out->off[v] = L.slip_off[v];
+    } else {
+        BA_CHECK(ncomp >= 1 && ncomp <= 4, BEATAMD_EINVAL, "%s: %d slip components (1 ... 4)", what, ncomp);
+        std::vector<int64_t> off;
+        BA_TRY(host_copy(ctx, comp_off, (size_t)ncomp, off));
+        out->n = ncomp;
+        for (int v = 0; v < ncomp; v++) out->off[v] = off[(size_t)v];
+    }
+    BA_CHECK(out->n >= 1 && out->n <= 4, BEATAMD_EINVAL, "%s: the model has no slip variable", what);
+    for (int v = 0; v < out->n; v++)
+        BA_CHECK(out->off[v] >= 0 && out->off[v] + m.P <= L.nparams, BEATAMD_EINVAL, "%s: slip component %d outside q", what, v);
+    return BEATAMD_OK;
+}
+
+// the onsets of the batch: the caller's (start_times [C,P], chain_bad [C] nullable) or the model's sweep
+int mr_start_times(beatamd_ctx *ctx, const FfiModel &m, Staging &st, int64_t C, const double *d_q, const double *start_times,
+                   const int32_t *chain_bad, const char *what, const double **st0, const int32_t **bad)
+{
+    const beatamd_ffi_layout &L = m.layout;
+    BA_CHECK(m.nsub >= 1 && m.P >= 1, BEATAMD_EINVAL, "%s: the model has no subfault", what);
+    BA_CHECK(L.durations_off >= 0 && L.durations_off + m.P <= L.nparams, BEATAMD_EINVAL, "%s: layout: durations outside q", what);
+    if (start_times) {
+        BA_TRY(st.in(start_times, (size_t)C * m.P, st0));
+        *bad = nullptr;
+        if (chain_bad) BA_TRY(st.in(chain_bad, (size_t)C, bad));
+        return BEATAMD_OK;
+    }
+    BA_CHECK(!chain_bad, BEATAMD_EINVAL, "%s: chain_bad without start_times", what);
+    BA_CHECK(L.velocities_off >= 0 && L.velocities_off + m.P <= L.nparams && L.nuc_strike_off >= 0 &&
+                 L.nuc_strike_off + m.nsub <= L.nparams && L.nuc_dip_off >= 0 && L.nuc_dip_off + m.nsub <= L.nparams &&
+                 L.time_off >= 0 && L.time_off + m.nsub <= L.nparams,
+             BEATAMD_EINVAL, "%s: layout: rupture variables outside q", what);
+    double *t;
+    int32_t *b;
+    BA_TRY(model_start_times(ctx, m, C, d_q, &t, &b));
+    *st0 = t;
+    *bad = b;
+    return BEATAMD_OK;
+}
+
+}  // namespace
+
+int beatamd_ffi_magnitudes_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, const double *moment_per_slip,
+                                 const int64_t *comp_off, int32_t ncomp, double *M0, double *Mw)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(Q && moment_per_slip && M0 && Mw && C >= 0, BEATAMD_EINVAL, "ffi_magnitudes: bad argument");
+    BA_CHECK(m->P >= 1 && m->layout.nparams > 0, BEATAMD_EINVAL, "ffi_magnitudes: the model has no patches");
+    MrComps comps;
+    BA_TRY(mr_components(ctx, *m, comp_off, ncomp, "ffi_magnitudes", &comps));
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_q, *d_k;
+    double *d_m0, *d_mw;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.in(moment_per_slip, (size_t)m->P, &d_k));
+    BA_TRY(st.out(M0, (size_t)C, &d_m0));
+    BA_TRY(st.out(Mw, (size_t)C, &d_mw));
+    BA_TRY(launch_moment_magnitude(ctx, C, m->P, d_q, m->layout.nparams, comps, d_k, d_m0, d_mw));
+    return st.finish();
+}
+
+int beatamd_ffi_moment_rate_spans_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q,
+                                        const double *start_times, const int32_t *chain_bad, double deltat, int64_t *spans)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(Q && spans && C >= 0, BEATAMD_EINVAL, "ffi_moment_rate_spans: bad argument");
+    BA_CHECK(deltat > 0.0 && deltat <= 1.79769313486231570815e+308, BEATAMD_EINVAL, "ffi_moment_rate_spans: deltat %g", deltat);
+    BA_CHECK(m->layout.nparams > 0, BEATAMD_EINVAL, "ffi_moment_rate_spans: layout: nparams must be positive");
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_q, *st0;
+    const int32_t *bad;
+    int64_t *d_s;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(mr_start_times(ctx, *m, st, C, d_q, start_times, chain_bad, "ffi_moment_rate_spans", &st0, &bad));
+    BA_TRY(st.out(spans, (size_t)C * (m->nsub + 1) * 2, &d_s));
+    BA_TRY(launch_moment_rate_span(ctx, *m, C, d_q, st0, bad, deltat, d_s));
+    BA_TRY(st.finish());            // (host arrays are filled before a raised status word is returned)
+    return ctx->check_status();     // a hypocentre outside the patch grid, an onset that is not finite
+}
+
+int beatamd_ffi_moment_rates_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, const double *moment_per_slip,
+                                   const int64_t *comp_off, int32_t ncomp, const double *start_times, const int32_t *chain_bad,
+                                   double deltat, int32_t stf, int64_t kbase, int64_t NT, double *rates, int64_t *spans)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(Q && moment_per_slip && rates && C >= 0, BEATAMD_EINVAL, "ffi_moment_rates: bad argument");
+    BA_CHECK(stf == BEATAMD_STF_HALF_SINUSOID, BEATAMD_EINVAL,
+             "ffi_moment_rates: source-time function %d (only BEATAMD_STF_HALF_SINUSOID = 0 is built)", stf);
+    BA_CHECK(deltat > 0.0 && deltat <= 1.79769313486231570815e+308, BEATAMD_EINVAL, "ffi_moment_rates: deltat %g", deltat);
+    BA_CHECK(NT >= 1 && NT <= MR_NT_MAX, BEATAMD_EINVAL, "ffi_moment_rates: %lld samples per row (1 ... %d: the row lives in LDS)",
+             (long long)NT, MR_NT_MAX);
+    BA_CHECK(kbase >= -((int64_t)1 << 41) && kbase <= ((int64_t)1 << 41), BEATAMD_EINVAL, "ffi_moment_rates: kbase %lld",
+             (long long)kbase);
+    BA_CHECK(m->layout.nparams > 0, BEATAMD_EINVAL, "ffi_moment_rates: layout: nparams must be positive");
+    MrComps comps;
+    BA_TRY(mr_components(ctx, *m, comp_off, ncomp, "ffi_moment_rates", &comps));
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_q, *d_k, *st0;
+    const int32_t *bad;
+    double *d_r;
+    int64_t *d_s;
+    BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
+    BA_TRY(st.in(moment_per_slip, (size_t)m->P, &d_k));
+    BA_TRY(mr_start_times(ctx, *m, st, C, d_q, start_times, chain_bad, "ffi_moment_rates", &st0, &bad));
+    BA_TRY(st.out(rates, (size_t)C * (m->nsub + 1) * NT, &d_r));
+    if (spans) BA_TRY(st.out(spans, (size_t)C * (m->nsub + 1) * 2, &d_s));
+    else BA_TRY(ctx->scratch(SL_MR_SPANS, (size_t)C * (m->nsub + 1) * 2, &d_s));
+    BA_TRY(launch_moment_rate_span(ctx, *m, C, d_q, st0, bad, deltat, d_s));
+    BA_TRY(launch_moment_rate(ctx, *m, C, d_q, st0, comps, d_k, deltat, d_s, kbase, NT, d_r));
+    BA_TRY(st.finish());
+    return ctx->check_status();     // flagged draws and draws outside the grid have NaN rows
+}
+
 int beatamd_ffi_logp_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *LL)
 {
     ENTER(ctx);
@@ -1388,6 +1519,27 @@ int beatamd_trace_density_update(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t
     BA_TRY(launch_trace_density(ctx, E, T, N, d_y, d_t, deltat, d_e, ny, nx, linewidth, d_g));
     BA_TRY(st.finish());
     return ctx->check_status();   // (device arrays too: a line outside the grid is the caller's TypeError now, not later)
+}
+
+int beatamd_trace_density_update_ranges(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin,
+                                        double deltat, const double *extent, const int64_t *ranges, int64_t ny, int64_t nx,
+                                        double linewidth, double *grid)
+{
+    ENTER(ctx);
+    BA_CHECK(Y && tmin && extent && grid && E >= 0 && T >= 0 && N > 0 && ny > 0 && nx > 0, BEATAMD_EINVAL,
+             "trace_density_update_ranges: bad argument");
+    Staging st(ctx);
+    const double *d_y, *d_t, *d_e;
+    const int64_t *d_r = nullptr;
+    double *d_g;
+    BA_TRY(st.in(Y, (size_t)E * T * N, &d_y));
+    BA_TRY(st.in(tmin, (size_t)T, &d_t));
+    BA_TRY(st.in(extent, (size_t)4 * T, &d_e));
+    if (ranges) BA_TRY(st.in(ranges, (size_t)E * T * 2, &d_r));
+    BA_TRY(st.out(grid, (size_t)T * ny * nx, &d_g, true));
+    BA_TRY(launch_trace_density(ctx, E, T, N, d_y, d_t, deltat, d_e, ny, nx, linewidth, d_g, d_r));
+    BA_TRY(st.finish());
+    return ctx->check_status();
 }
 
 // ------------------------------------------------------------------ the hyper-parameter model (hyper.hip)

@@ -187,6 +187,14 @@ int beatamd_ctx::check_status()
             set_error("Line endpoint outside of given grid (an index above the last cell, or below -32768)");
             return BEATAMD_EOUTSIDE;
         }
+        if (st & ST_SPAN_BAD) {
+            set_error("moment rate: an onset or duration that is not finite, a negative duration, or a time index beyond 2^40");
+            return BEATAMD_EINVAL;
+        }
+        if (st & ST_SPAN_OOB) {
+            set_error("moment rate: a draw's time span does not lie within the index grid [kbase, kbase + NT): its rows are NaN");
+            return BEATAMD_EINVAL;
+        }
         if (st & ST_BAD_SCALE) {
             set_error("PoissonProposal: a step width outside (0, 500] (or NaN): the draws of that parameter are NaN");
             return BEATAMD_EINVAL;

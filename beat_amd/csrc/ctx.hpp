@@ -46,7 +46,7 @@ void set_error(const char *fmt, ...);
 
 // device status bits set by kernels (checked at synchronisation points)
 enum : int { ST_INDEX_OOB = 1, ST_BAD_HYPO = 2, ST_NOT_PSD = 4, ST_BAD_COV = 8, ST_BAD_SCALE = 16, ST_LINE_OOB = 32,
-              ST_LINE_NONFINITE = 64 };
+              ST_LINE_NONFINITE = 64, ST_SPAN_BAD = 128, ST_SPAN_OOB = 256 };
 
 struct DevBuf {
     void *p = nullptr;
@@ -387,7 +387,7 @@ enum Slot : int {
     SL_CHAINBAD, SL_Z, SL_ROWSCALE, SL_CUM, SL_STAGE2, SL_WHITEN,
     SL_CHOL_A, SL_CHOL_X, SL_CHOL_D, SL_CHOL_T, SL_CHOL_L,
     SL_GC_ORDER, SL_GS_ORDER, SL_GC_STREAM, SL_GC_HDR, SL_GC_META, SL_DELTA, SL_LOGU, SL_EDGES, SL_TSLOT, SL_SPLIT, SL_WS_PACK,
-    SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_COUNT
+    SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_MR_SPANS, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

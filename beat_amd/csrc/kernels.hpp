@@ -461,6 +461,29 @@ int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int6
 int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
                          const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid);
 
+// the same with per-trace sample ranges [E,T,2] = (first sample, count) (nullptr: every sample): only the segments inside
+// a trace's own range are drawn, a trace with count < 2 draws nothing
+int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
+                         const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid, const int64_t *ranges);
+
+// ---- momentrate.hip: moment, magnitude and moment-rate function of every draw (ffi/fault.py:284-474)
+// the slip components a moment is formed from: offsets in q of n variables of P entries each
+struct MrComps {
+    int64_t off[4];
+    int32_t n;
+};
+constexpr int MR_NT_MAX = 20224;   // samples of a moment-rate row: 158 KiB of the 160 KiB of LDS
+// M0 [C] = sum_p k_p sqrt(sum_comp s^2) in patch order, Mw [C] (k_moment_magnitude)
+int launch_moment_magnitude(beatamd_ctx *ctx, int64_t C, int64_t P, const double *Q, int64_t np, const MrComps &comps,
+                            const double *k, double *M0, double *Mw);
+// spans [C, nsub + 1, 2] = (first index, count) of every subfault's and the total's time axis (k_moment_rate_span)
+int launch_moment_rate_span(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const double *Q, const double *st0,
+                            const int32_t *chain_bad, double deltat, int64_t *spans);
+// out [C, nsub + 1, NT] on the index grid [kbase, kbase + NT): the subfaults' rows (k_moment_rate) and their in-order sum
+// (k_moment_rate_total)
+int launch_moment_rate(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const double *Q, const double *st0, const MrComps &comps,
+                       const double *k, double deltat, const int64_t *spans, int64_t kbase, int64_t NT, double *out);
+
 // ---- ptadapt.hip: streaming likelihood-weighted moments of groups of chains and the proposal factors out of them
 // state of a group: GM_HDR header doubles (m, S0, Sw2, count, nbad, 3 spare), S1 [n], S2 [n, n] (lower triangle)
 constexpr int GM_HDR = 8, GM_MAX_R = 1024, GM_MAX_N = 2048, GM_MAX_G = 64;

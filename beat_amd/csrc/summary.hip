@@ -158,6 +158,7 @@ int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int6
 struct TdArgs {
     int64_t E, T, N;
     const double *Y, *tmin, *extent;   // [E,T,N], [T], [T,4] = (xmin, xmax, ymin, ymax)
+    const int64_t *ranges;             // [E,T,2] = (first sample, count) of every trace, or nullptr: all N samples
     double deltat, linewidth;
     int ny, nx, strip, pad;
     double *grid;                      // [T,ny,nx]
@@ -173,9 +174,23 @@ __device__ __forceinline__ double td_cell(double pos, double lo, double step)
     return rint((pos - lo - step / 2.0) / step);
 }
 
+// the samples [*lo, *hi) of trace `tr` = e * T + t that its range (first, count) leaves inside [0, N); false: fewer than
+// two, the trace draws nothing
+__device__ __forceinline__ bool td_range(const TdArgs &a, int64_t tr, int64_t *lo, int64_t *hi)
+{
+    const int64_t f = a.ranges[2 * tr], n = a.ranges[2 * tr + 1];
+    if (n < 2 || f >= a.N || f < -((int64_t)1 << 62) || (f < 0 && n <= -f)) return false;   // (no sum that can overflow)
+    *lo = f > 0 ? f : 0;
+    *hi = n >= a.N - f ? a.N : f + n;
+    return true;
+}
+
 // every sample's row index and every time's column index: above the grid or below TD_INDEX_MIN -> ST_LINE_OOB
-// (check_line_in_grid's TypeError), not finite -> ST_LINE_NONFINITE.  k_trace_density does not start on a raised word
-__global__ void __launch_bounds__(256) k_trace_density_check(TdArgs a)
+// (check_line_in_grid's TypeError), not finite -> ST_LINE_NONFINITE.  k_trace_density does not start on a raised word.
+// With ranges only the samples inside their trace's range are looked at, each with its time (a time outside every range
+// is never drawn)
+template <bool RANGED>
+__device__ __forceinline__ void td_check(const TdArgs &a)
 {
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -183,11 +198,15 @@ __global__ void __launch_bounds__(256) k_trace_density_check(TdArgs a)
     const int64_t j = i % a.N, t = (i / a.N) % a.T;
     const double *ext = a.extent + 4 * t;
     int bad = 0;
+    if (RANGED) {
+        int64_t lo, hi;
+        if (!td_range(a, i / a.N, &lo, &hi) || j < lo || j >= hi) return;
+    }
     const double ystep = (ext[3] - ext[2]) / (double)(a.ny - 1);
     const double q = td_cell(a.Y[i], ext[2], ystep);
     if (!(fabs(q) <= 1.79769313486231570815e+308)) bad |= ST_LINE_NONFINITE;
     else if (q > (double)(a.ny - 1) || q < TD_INDEX_MIN) bad |= ST_LINE_OOB;
-    if (i < a.T * a.N) {                       // the time axis is the same for every trace of a target
+    if (RANGED || i < a.T * a.N) {           // the time axis is the same for every trace of a target
         const double xstep = (ext[1] - ext[0]) / (double)(a.nx - 1);
         const double c = td_cell(a.tmin[t] + (double)j * a.deltat, ext[0], xstep);
         if (!(fabs(c) <= 1.79769313486231570815e+308) || !(xstep > 0.0)) bad |= ST_LINE_NONFINITE;
@@ -195,6 +214,9 @@ __global__ void __launch_bounds__(256) k_trace_density_check(TdArgs a)
     }
     if (bad) atomicOr(a.status, bad);
 }
+
+__global__ void __launch_bounds__(256) k_trace_density_check(TdArgs a) { td_check<false>(a); }
+__global__ void __launch_bounds__(256) k_trace_density_check_ranged(TdArgs a) { td_check<true>(a); }
 
 // The segments of one trace for the workgroup's columns [s0, s1), TD_THREADS at a time:
 //   set-up  lane <-> segment: cell indices of its two samples, the roles of rows and columns, slope, width, intercept, and
@@ -300,11 +322,11 @@ __device__ __forceinline__ void td_pass(const TdArgs &a, const TdSetup &S, uint3
 // uniform: the segments that can touch the strip (widened by `pad` columns, the reach of the widest line) are one index
 // range, found by bisection once.  Per trace: pass 0 over the range in chunks of TD_THREADS segments, then pass 1 (with
 // one chunk, on the set-up that pass 0 left).  The result does not depend on the strip width or on the chunking.
-__global__ void __launch_bounds__(TD_THREADS) k_trace_density(TdArgs a)
+// RANGED: the kernel with per-trace ranges (k_trace_density_ranged); without them the code is the plain kernel's
+template <bool RANGED>
+__device__ __forceinline__ void td_draw(const TdArgs &a, uint32_t *td_owner, TdSetup &S)
 {
 #pragma clang fp contract(off)
-    extern __shared__ uint32_t td_owner[];
-    __shared__ TdSetup S;
     if (*(volatile int *)a.status & (ST_LINE_OOB | ST_LINE_NONFINITE)) return;   // (k_trace_density_check, uniform)
     const int t = blockIdx.y, tid = threadIdx.x;
     const int s0 = blockIdx.x * a.strip, s1 = min(s0 + a.strip, a.nx - 1);
@@ -334,17 +356,43 @@ __global__ void __launch_bounds__(TD_THREADS) k_trace_density(TdArgs a)
     for (int64_t e = 0; e < a.E; e++) {
         const double *y = a.Y + (e * a.T + t) * a.N;
         int total = 0;
-        for (int64_t seg0 = ilo; seg0 <= ihi; seg0 += TD_THREADS) {
-            total = td_setup(a, S, y, seg0, ihi, tmin, xmin, xstep, ymin, ystep, s0, s1);
+        // RANGED: the trace's own range (first sample, count) cut to [0, N) -- its segments are first + 1 ... first + count - 1,
+        // those of them that can touch the strip lo ... hi (uniform over the workgroup: the barriers stay matched)
+        int64_t lo = ilo, hi = ihi;
+        bool single = one;
+        if (RANGED) {
+            int64_t rf, rend;
+            if (!td_range(a, e * a.T + t, &rf, &rend)) continue;
+            lo = ilo > rf + 1 ? ilo : rf + 1;
+            hi = ihi < rend - 1 ? ihi : rend - 1;
+            if (lo > hi) continue;
+            single = hi - lo < TD_THREADS;
+        }
+        for (int64_t seg0 = lo; seg0 <= hi; seg0 += TD_THREADS) {
+            total = td_setup(a, S, y, seg0, hi, tmin, xmin, xstep, ymin, ystep, s0, s1);
             td_pass<0>(a, S, td_owner, g, seg0, total, s0, s1);
             __syncthreads();
         }
-        for (int64_t seg0 = ilo; seg0 <= ihi; seg0 += TD_THREADS) {
-            if (!one) total = td_setup(a, S, y, seg0, ihi, tmin, xmin, xstep, ymin, ystep, s0, s1);
+        for (int64_t seg0 = lo; seg0 <= hi; seg0 += TD_THREADS) {
+            if (!single) total = td_setup(a, S, y, seg0, hi, tmin, xmin, xstep, ymin, ystep, s0, s1);
             td_pass<1>(a, S, td_owner, g, seg0, total, s0, s1);
             __syncthreads();
         }
     }
+}
+
+__global__ void __launch_bounds__(TD_THREADS) k_trace_density(TdArgs a)
+{
+    extern __shared__ uint32_t td_owner[];
+    __shared__ TdSetup S;
+    td_draw<false>(a, td_owner, S);
+}
+
+__global__ void __launch_bounds__(TD_THREADS) k_trace_density_ranged(TdArgs a)
+{
+    extern __shared__ uint32_t td_owner[];
+    __shared__ TdSetup S;
+    td_draw<true>(a, td_owner, S);
 }
 
 // the owner map's share of the 160 KiB of LDS (TdSetup takes 10 KiB)
@@ -352,6 +400,12 @@ constexpr int TD_LDS_BYTES = 150 * 1024, TD_STRIP = 32, TD_STRIP_MIN = 8;
 
 int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
                          const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid)
+{
+    return launch_trace_density(ctx, E, T, N, Y, tmin, deltat, extent, ny, nx, linewidth, grid, nullptr);
+}
+
+int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
+                         const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid, const int64_t *ranges)
 {
     BA_CHECK(ny >= 2 && ny <= 4096 && nx >= 2 && nx <= 4096, BEATAMD_EINVAL, "trace_density: grid %lld x %lld (2 ... 4096 each)",
              (long long)ny, (long long)nx);
@@ -363,7 +417,7 @@ int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, cons
     const int64_t nchk = (E * T * N + 255) / 256;
     BA_CHECK(nchk < (int64_t)0x7fffffff, BEATAMD_EINVAL, "trace_density: too many samples in one call");
     TdArgs a;
-    a.E = E; a.T = T; a.N = N; a.Y = Y; a.tmin = tmin; a.extent = extent; a.deltat = deltat; a.linewidth = linewidth;
+    a.E = E; a.T = T; a.N = N; a.Y = Y; a.ranges = ranges; a.tmin = tmin; a.extent = extent; a.deltat = deltat; a.linewidth = linewidth;
     a.ny = (int)ny; a.nx = (int)nx; a.grid = grid; a.status = ctx->d_status;
     // a line's half width is at most linewidth * sqrt(2) / 4, its pixels reach ceil(that) + 1 cells from the centre line;
     // one more for the centre line's rounding
@@ -378,13 +432,14 @@ int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, cons
     const int want = GfKnobs::get(gf_knobs(ctx).td_strip, (int)std::max<int64_t>(TD_STRIP_MIN, std::min<int64_t>(TD_STRIP, dense)));
     a.strip = std::max(1, std::min(std::min(want, fit), (int)nx));
     const size_t lds = (size_t)ny * a.strip * sizeof(uint32_t);
+    const auto check = ranges ? k_trace_density_check_ranged : k_trace_density_check;
+    const auto draw = ranges ? k_trace_density_ranged : k_trace_density;
     if (lds + sizeof(TdSetup) > 64 * 1024)
-        BA_HIP(hipFuncSetAttribute((const void *)k_trace_density, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        BA_HIP(hipFuncSetAttribute((const void *)draw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ScopedTimer tm(ctx, "density");
-    hipLaunchKernelGGL(k_trace_density_check, dim3((unsigned)nchk), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(check, dim3((unsigned)nchk), dim3(256), 0, ctx->stream, a);
     BA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_trace_density, dim3((unsigned)((nx - 1 + a.strip - 1) / a.strip), (unsigned)T), dim3(TD_THREADS), lds,
-                       ctx->stream, a);
+    hipLaunchKernelGGL(draw, dim3((unsigned)((nx - 1 + a.strip - 1) / a.strip), (unsigned)T), dim3(TD_THREADS), lds, ctx->stream, a);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

@@ -511,6 +511,92 @@ class Context(object):
         check(self._lib.beatamd_ffi_start_times_batch(self._h, model_id, Cn, ptr(Qc), ptr(out), ptr(chain_bad)))
         return out
 
+    # -- moment, magnitude and moment-rate functions of a batch of draws (csrc/momentrate.hip)
+    def _arg_on_side(self, a, ref, dtype, shape, what):
+        """the optional array argument ``a`` as a contiguous array of ``dtype`` and ``shape`` on ref's side"""
+        if a is None:
+            return None
+        if _is_dev(ref):
+            import torch
+            tdt = {np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64}[dtype]
+            if not _is_dev(a):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ref.device)
+            if a.dtype != tdt or not a.is_contiguous():
+                raise ValueError("%s: device tensors must be contiguous %s" % (what, np.dtype(dtype).name))
+        else:
+            if _is_dev(a):
+                a = a.cpu().numpy()
+            a = np.ascontiguousarray(a, dtype=dtype)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s must be %s, got %s" % (what, tuple(shape), tuple(a.shape)))
+        return a
+
+    @staticmethod
+    def _out_on_side(ref, shape, dtype, out, what):
+        if out is None:
+            if _is_dev(ref):
+                import torch
+                return torch.empty(shape, dtype={np.float64: torch.float64, np.int64: torch.int64}[dtype], device=ref.device)
+            return np.empty(shape, dtype=dtype)
+        ok = tuple(out.shape) == tuple(shape) and _is_dev(out) == _is_dev(ref)
+        if ok and _is_dev(out):
+            ok = out.is_contiguous() and str(out.dtype).endswith(np.dtype(dtype).name)
+        elif ok:
+            ok = out.flags.c_contiguous and out.dtype == dtype
+        if not ok:
+            raise ValueError("%s must be a contiguous %s %s array on Q's side" % (what, np.dtype(dtype).name, tuple(shape)))
+        return out
+
+    def ffi_magnitudes_batch(self, model_id, Q, moment_per_slip, npatches, comp_off=None):
+        """(M0, Mw), each (C,): total moment ``sum_p k_p sqrt(sum_comp s^2)`` in patch order and its moment magnitude
+        (ffi/fault.py:284-359) at the points Q (C, nparams); moment_per_slip (npatches,): the moment of a patch at unit
+        slip; comp_off: offsets in q of the slip variables (None: the layout's own)"""
+        self._adopt_stream(Q)
+        Qc = f64(Q)
+        Cn = int(Qc.shape[0])
+        k = self._arg_on_side(moment_per_slip, Qc, np.float64, (int(npatches),), "moment_per_slip")
+        off = _i64arr(comp_off)
+        M0, Mw = _empty_like(Qc, (Cn,)), _empty_like(Qc, (Cn,))
+        check(self._lib.beatamd_ffi_magnitudes_batch(self._h, model_id, Cn, ptr(Qc), ptr(k), ptr(off),
+                                                     0 if off is None else int(off.size), ptr(M0), ptr(Mw)))
+        return M0, Mw
+
+    def ffi_moment_rate_spans_batch(self, model_id, Q, nsubfaults, npatches, deltat, start_times=None, chain_bad=None,
+                                    out=None):
+        """spans (C, nsubfaults + 1, 2) int64 = (first index, count) of every subfault's moment-rate time axis and, in the
+        last row, the total's (ffi/fault.py:413-420, 461-465); a time is index * deltat.  start_times (C, npatches) /
+        chain_bad (C,) int32: onsets the caller holds (None: the model's sweep).  A flagged draw gets count 0 and the call
+        raises ValueError after filling ``out``"""
+        self._adopt_stream(Q)
+        Qc = f64(Q)
+        Cn = int(Qc.shape[0])
+        st = self._arg_on_side(start_times, Qc, np.float64, (Cn, int(npatches)), "start_times")
+        bad = self._arg_on_side(chain_bad, Qc, np.int32, (Cn,), "chain_bad")
+        out = self._out_on_side(Qc, (Cn, int(nsubfaults) + 1, 2), np.int64, out, "spans")
+        check(self._lib.beatamd_ffi_moment_rate_spans_batch(self._h, model_id, Cn, ptr(Qc), ptr(st), ptr(bad), float(deltat),
+                                                            ptr(out)))
+        return out
+
+    def ffi_moment_rates_batch(self, model_id, Q, moment_per_slip, nsubfaults, npatches, deltat, kbase, NT, comp_off=None,
+                               start_times=None, chain_bad=None, stf=0, out=None, spans=None):
+        """rates (C, nsubfaults + 1, NT) on the index grid [kbase, kbase + NT): the subfaults' moment-rate functions and,
+        in the last row, their sum (ffi/fault.py:361-474).  A draw that does not fit the grid, or is flagged, gets NaN
+        rows and the call raises ValueError after filling ``out`` (and ``spans``, when given)"""
+        self._adopt_stream(Q)
+        Qc = f64(Q)
+        Cn = int(Qc.shape[0])
+        k = self._arg_on_side(moment_per_slip, Qc, np.float64, (int(npatches),), "moment_per_slip")
+        off = _i64arr(comp_off)
+        st = self._arg_on_side(start_times, Qc, np.float64, (Cn, int(npatches)), "start_times")
+        bad = self._arg_on_side(chain_bad, Qc, np.int32, (Cn,), "chain_bad")
+        out = self._out_on_side(Qc, (Cn, int(nsubfaults) + 1, int(NT)), np.float64, out, "rates")
+        if spans is not None:
+            spans = self._out_on_side(Qc, (Cn, int(nsubfaults) + 1, 2), np.int64, spans, "spans")
+        check(self._lib.beatamd_ffi_moment_rates_batch(self._h, model_id, Cn, ptr(Qc), ptr(k), ptr(off),
+                                                       0 if off is None else int(off.size), ptr(st), ptr(bad), float(deltat),
+                                                       int(stf), int(kbase), int(NT), ptr(out), ptr(spans)))
+        return out
+
     def ffi_astep_batch(self, model_id, Q0, L0, delta, scaling, lower, upper, log_u, beta,
                         accepted=None):
         """In-place update of Q0 / L0 (must be contiguous float64); returns accepted (int32)."""
@@ -1063,6 +1149,16 @@ class Context(object):
         a given one is added to and returned.  Traces are taken in ensemble order: cutting an ensemble into calls does
         not change the result.  TypeError: a sample or time beyond the extent's upper side (below the lower side it is
         clipped); ValueError: a non-finite sample, a bad shape."""
+        return self._trace_density(Y, tmin, deltat, extent, None, grid_size, linewidth, grid)
+
+    def trace_density_update_ranges(self, Y, tmin, deltat, extent, ranges, grid_size=(500, 500), linewidth=7, grid=None):
+        """``trace_density_update`` with ranges (E, T, 2) int64 = (first sample, count) of every trace: only the stretch
+        of a trace inside its own range is drawn and checked against the extent, a trace with count < 2 draws nothing --
+        the grid of ``fuzzy_moment_rate`` (plotting/ffi.py:41-79), whose curves each cover their own stretch of the time
+        axis (zero padding would draw segments along rate 0).  ranges None: ``trace_density_update``."""
+        return self._trace_density(Y, tmin, deltat, extent, ranges, grid_size, linewidth, grid)
+
+    def _trace_density(self, Y, tmin, deltat, extent, ranges, grid_size, linewidth, grid):
         self._adopt_stream(Y)
         y = f64(Y)
         if y.ndim != 3:
@@ -1094,8 +1190,13 @@ class Context(object):
         if tuple(grid.shape) != (T, ny, nx) or f64(grid) is not grid or _is_dev(grid) != dev:
             raise ValueError("trace_density_update: grid must be a contiguous float64 (%d, %d, %d) array on Y's side"
                              % (T, ny, nx))
-        check(self._lib.beatamd_trace_density_update(self._h, E, T, N, ptr(y), ptr(tm), float(deltat), ptr(ext), ny, nx,
-                                                     float(linewidth), ptr(grid)))
+        if ranges is None:
+            check(self._lib.beatamd_trace_density_update(self._h, E, T, N, ptr(y), ptr(tm), float(deltat), ptr(ext), ny, nx,
+                                                         float(linewidth), ptr(grid)))
+            return grid
+        rg = self._arg_on_side(ranges, y, np.int64, (E, T, 2), "trace_density_update: ranges")
+        check(self._lib.beatamd_trace_density_update_ranges(self._h, E, T, N, ptr(y), ptr(tm), float(deltat), ptr(ext), ptr(rg),
+                                                            ny, nx, float(linewidth), ptr(grid)))
         return grid
 
     def halfspace_displacements_batch(self, kinds, params, east, north, nu=0.25):

@@ -439,6 +439,64 @@ class LogpForwFunc(object):
         composite (seismic.py:1253-1272) for a batch; chain_bad: see Context.ffi_start_times_batch"""
         return self.ctx.ffi_start_times_batch(self.model_id, Q, self.problem.npatches, chain_bad=chain_bad)
 
+    # -- moment, magnitude and moment-rate functions (csrc/momentrate.hip)
+    def _slip_offsets(self, components, what):
+        """offsets in q of the named slip variables (None: all of the model's, in its order)"""
+        lay = self.problem.layout
+        if components is None:
+            components = self.problem.slip_varnames
+        components = list(components)
+        missing = [v for v in components if v not in self.problem.slip_varnames]
+        if missing or not components:
+            raise ValueError("%s: %s not among the model's slip variables %s"
+                             % (what, ", ".join(missing) or "no component", ", ".join(self.problem.slip_varnames)))
+        return [lay.offset(v, 0) for v in components]
+
+    def magnitudes(self, Q, moment_per_slip, components=None):
+        """(M0, Mw), each (C,), at the points Q (C, nparams): ``FaultGeometry.get_moment`` / ``get_magnitude``
+        (ffi/fault.py:284-359) for a batch.  moment_per_slip (npatches,): the moment of every patch at unit slip
+        (INTEGRATION.md); components: names of the slip variables the total slip is formed from (None: all of them, as
+        ``get_total_slip(components=None)``).  numpy in -> numpy out, torch-cuda in -> tensors."""
+        self._ready(Q)
+        return self.ctx.ffi_magnitudes_batch(self.model_id, Q, moment_per_slip, self.problem.npatches,
+                                             self._slip_offsets(components, "magnitudes"))
+
+    def moment_rates(self, Q, moment_per_slip, deltat, individual=False):
+        """moment-rate functions at the points Q (C, nparams): ``FaultGeometry.get_moment_rate_function``
+        (ffi/fault.py:361-474) for a batch, on ONE index grid for all draws.  Returns a dict:
+
+          rates   (C, NT) the total, or with ``individual`` (C, nsubfaults + 1, NT): the subfaults, then the total; zero
+                  outside a draw's own span; a moment per sample as in the reference
+          kbase   index of sample 0;  times (NT,) = (kbase + arange(NT)) * deltat
+          spans   (C, nsubfaults + 1, 2) int64: (first index, count) of every subfault's own time axis, the total's last
+
+        The span kernel runs first, one device min / max sizes the grid, then the rate kernel.  The slip is
+        sqrt(uparr^2 + uperp^2) as fault.py:412 (the ones the model samples).  numpy in -> numpy out, torch-cuda in ->
+        tensors (kbase stays an int).  ValueError: a hypocentre outside the patch grid."""
+        self._ready(Q)
+        prob = self.problem
+        comps = [v for v in ("uparr", "uperp") if v in prob.slip_varnames]
+        off = self._slip_offsets(comps, "moment_rates")
+        nsub, P = len(prob.n_patch_dip), prob.npatches
+        C = int(Q.shape[0])
+        tensor_in = hasattr(Q, "data_ptr") and not isinstance(Q, np.ndarray)
+        st = self.start_times(Q)                                   # (raises for a flagged draw, as the likelihood's sweep)
+        spans = self.ctx.ffi_moment_rate_spans_batch(self.model_id, Q, nsub, P, deltat, start_times=st)
+        if C:
+            tot = spans[:, nsub]
+            kbase, kend = int(tot[:, 0].min()), int((tot[:, 0] + tot[:, 1]).max())
+        else:
+            kbase, kend = 0, 1
+        NT = kend - kbase
+        rates = self.ctx.ffi_moment_rates_batch(self.model_id, Q, moment_per_slip, nsub, P, deltat, kbase, NT, comp_off=off,
+                                                start_times=st)
+        idx = np.arange(NT, dtype=np.float64)
+        times = (float(kbase) + idx) * float(deltat)
+        if tensor_in:
+            import torch
+            times = torch.from_numpy(times).to(Q.device)
+        return dict(rates=rates if individual else rates[:, nsub], kbase=kbase, times=times, spans=spans)
+
     def release(self):
         """free what this compiled model holds on the device BESIDES the libraries: the model record and the weight sets
         (a dense set is T x N x N doubles: 8.6 GB at config 3).  The function cannot be called afterwards.  Explicit, not

@@ -234,6 +234,14 @@ class TargetShardedLogp(object):
         raise NotImplementedError("synthetics of a target-sharded model: evaluate the local model (self.local.synthetics) for "
                                   "this rank's targets %s" % (self.blocks[wavemap_index][self.rank],))
 
+    def magnitudes(self, Q, moment_per_slip, components=None):
+        """the fault and the parameters are whole on every rank and no library is read: the local model's answer"""
+        return self.local.magnitudes(Q, moment_per_slip, components)
+
+    def moment_rates(self, Q, moment_per_slip, deltat, individual=False):
+        """as ``magnitudes``: the local model's answer, the same on every rank"""
+        return self.local.moment_rates(Q, moment_per_slip, deltat, individual)
+
     def release(self):
         self.local.release()
 

@@ -216,3 +216,118 @@ def coupling_ensemble(f, Q, basis, pole_names, earth=None, batch=512):
     if not tensor_in:
         out = dict((k, v.cpu().numpy()) for k, v in out.items())
     return out
+
+
+def derived_parameters(f, population, moment_per_slip, batch=512, coupling=None):
+    """``FaultGeometry.get_derived_parameters`` (ffi/fault.py:945-954) for every row of ``population`` (n, nparams):
+    (n, 1 + P_coupling) = hstack([moment magnitude, coupling]).  The magnitude is ``f.magnitudes`` over all slip
+    variables of the model (get_magnitude -> get_total_slip(components=None)); moment_per_slip (npatches,): the moment of
+    every patch at unit slip.  coupling: None (no pole: the magnitude alone, (n, 1)) or a dict of the arguments of
+    ``coupling_ensemble`` after (f, Q): basis, pole_names and optionally earth.  numpy in -> numpy out, torch-cuda in ->
+    tensor."""
+    ctx = _ctx_of(f)
+    tensor_in = _is_tensor(population)
+    n, batch = int(population.shape[0]), max(int(batch), 1)
+    import torch
+    mags = []
+    for a in range(0, n, batch):
+        q = _to_device(ctx, population[a:a + batch]).contiguous()
+        mags.append(f.magnitudes(q, moment_per_slip)[1])
+    mw = torch.cat(mags) if mags else torch.zeros(0, dtype=torch.float64, device="cuda:%d" % ctx.device)
+    cols = [mw.reshape(n, 1)]
+    if coupling is not None:
+        cp = coupling_ensemble(f, _to_device(ctx, population), batch=batch, **coupling)["coupling"]
+        cols.append(cp.reshape(n, -1))
+    out = torch.cat(cols, dim=1)
+    return out if tensor_in else out.cpu().numpy()
+
+
+def moment_rate_extent(rates, spans, kbase, deltat):
+    """the extent of ``fuzzy_moment_rate`` (plotting/ffi.py:62-67) on arrays: rates (E, NT) on the index grid from
+    ``kbase``, spans (E, 2) = (first index, count) of every curve's own stretch -> (min_times, max_times, min_rates,
+    max_rates) over those stretches only (a curve's zeros outside its span do not count); curves with count < 1 are left
+    out.  numpy arrays."""
+    rates, spans = np.asarray(rates, dtype=np.float64), np.asarray(spans, dtype=np.int64)
+    first, count = spans[:, 0], spans[:, 1]
+    keep = count > 0
+    if not keep.any():
+        raise ValueError("moment_rate_extent: no curve with a sample")
+    j = np.arange(rates.shape[1], dtype=np.int64)[None, :] + int(kbase)
+    own = (j >= first[:, None]) & (j < (first + count)[:, None]) & keep[:, None]
+    lo = np.where(own, rates, np.inf).min()
+    hi = np.where(own, rates, -np.inf).max()
+    return (float(first[keep].min()) * float(deltat), float((first + count - 1)[keep].max()) * float(deltat), float(lo),
+            float(hi))
+
+
+def truncate_density(grid, nrates):
+    """``grid[grid > nrates / 2] = nrates / 2`` (plotting/ffi.py:75-77), in place; returns grid"""
+    truncate = nrates / 2
+    grid[grid > truncate] = truncate
+    return grid
+
+
+def moment_rate_ensemble(f, population, best, nensemble, moment_per_slip, deltat, individual=False, density=(500, 500),
+                         linewidth=7, batch=512):
+    """``draw_moment_rate`` (plotting/ffi.py:84-181) on arrays: the moment-rate functions of ``nensemble`` draws of
+    ``population`` (n, nparams) picked by ``ensemble_indices``, and of the point ``best`` (nparams,).  R = 1 curve per
+    draw, the total -- or with ``individual`` R = nsubfaults + 1: every subfault, then the total (the reference's
+    "individual" projection draws one figure per subfault).  Returns a dict of numpy arrays:
+
+      indices        (E,) int32
+      best           dict(rates (R, NTb), times (NTb,), kbase): the best point's curves on their own grid
+      times, kbase   (NT,), int: the ensemble's common grid, times = (kbase + arange(NT)) * deltat
+      spans          (E, R, 2) int64: every curve's own stretch (first index, count)
+      mean, std, min, max   (R, NT) over the ensemble through ``ensemble_moments`` (outside a draw's span its rate is 0)
+      density        (R, ny, nx): the ``fuzzy_moment_rate`` grid -- every curve drawn over its own stretch only
+                     (``trace_density_update_ranges``), then truncated at E / 2 (plotting/ffi.py:75-77); None for
+                     ``density=None``
+      extent         (R, 4) = (min_times, max_times, min_rates, max_rates) over the draws' own stretches (:62-67)"""
+    import torch
+    ctx = _ctx_of(f)
+    idx = ensemble_indices(int(population.shape[0]), nensemble)
+    batch = max(int(batch), 1)
+    if _is_tensor(population):
+        ens = population[torch.as_tensor(idx.astype(np.int64), device=population.device)].contiguous()
+    else:
+        ens = _to_device(ctx, np.asarray(population, dtype=np.float64)[idx])
+    best_d = _to_device(ctx, best).reshape(1, -1).to(ens.device).contiguous()
+    prob = f.problem
+    nsub, P, E = len(prob.n_patch_dip), prob.npatches, int(ens.shape[0])
+    rows = slice(0, nsub + 1) if individual else slice(nsub, nsub + 1)
+    b = f.moment_rates(best_d, moment_per_slip, deltat, individual=True)
+    out = dict(indices=idx, best=dict(rates=b["rates"][0, rows].cpu().numpy(), times=b["times"].cpu().numpy(),
+                                      kbase=b["kbase"]))
+    if E == 0:
+        return out
+    off = f._slip_offsets([v for v in ("uparr", "uperp") if v in prob.slip_varnames], "moment_rate_ensemble")
+    k_d = _to_device(ctx, moment_per_slip)
+    starts, spans = [], []
+    for a in range(0, E, batch):                       # the onsets and spans of every batch: the common grid needs all
+        st = f.start_times(ens[a:a + batch])
+        starts.append(st)
+        spans.append(ctx.ffi_moment_rate_spans_batch(f.model_id, ens[a:a + batch], nsub, P, deltat, start_times=st))
+    spans = torch.cat(spans)
+    kbase = int(spans[:, nsub, 0].min())
+    NT = int((spans[:, nsub, 0] + spans[:, nsub, 1]).max()) - kbase
+    rates = torch.empty((E, nsub + 1, NT), dtype=torch.float64, device=ens.device)
+    for i, a in enumerate(range(0, E, batch)):
+        ctx.ffi_moment_rates_batch(f.model_id, ens[a:a + batch], k_d, nsub, P, deltat, kbase, NT, comp_off=off,
+                                   start_times=starts[i], out=rates[a:a + batch])
+    Y = rates[:, rows].contiguous()
+    R = int(Y.shape[1])
+    state, seen = ctx.ensemble_moments_update(Y.view(E, R * NT))
+    mean, std, mn, mx = (v.cpu().numpy().reshape(R, NT) for v in ctx.ensemble_moments_finish(state, seen))
+    sp = spans[:, rows].contiguous()
+    sp_h, Y_h = sp.cpu().numpy(), Y.cpu().numpy()
+    extent = np.array([moment_rate_extent(Y_h[:, r], sp_h[:, r], kbase, deltat) for r in range(R)])
+    out.update(times=(float(kbase) + np.arange(NT, dtype=np.float64)) * float(deltat), kbase=kbase, spans=sp_h, mean=mean,
+               std=std, min=mn, max=mx, extent=extent, density=None)
+    if density is not None:
+        ranges = sp.clone()
+        ranges[:, :, 0] -= kbase
+        tmin = _to_device(ctx, np.full(R, float(kbase) * float(deltat)))
+        grid = ctx.trace_density_update_ranges(Y, tmin, deltat, _to_device(ctx, extent), ranges.contiguous(), density,
+                                               linewidth)
+        out["density"] = truncate_density(grid.cpu().numpy(), E)
+    return out

@@ -118,6 +118,56 @@ int32_t beatamd_gf_patch_ranges(int64_t ntargets, int64_t npatches, int64_t nsam
  * patch grid; the call then fills both arrays and returns BEATAMD_EINVAL. */
 int beatamd_ffi_start_times_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, double *times,
                                   int32_t *chain_bad);
+/* ---- moment, moment magnitude and moment-rate functions of a batch of draws (momentrate.hip) ----
+ * Common arguments: Q [C, nparams]; moment_per_slip [npatches] = the moment of every patch at unit slip (mu * area from
+ * the store: pyrocko's RectangularSource.get_moment is linear in the slip); comp_off [ncomp] (host or device, <= 4) =
+ * offsets in q of the slip variables the total slip is formed from, NULL: the layout's own (get_total_slip with
+ * components=None); start_times [C, npatches] with chain_bad [C] (nullable) = onsets the caller already holds, as
+ * beatamd_ffi_start_times_batch returns them, NULL: the model's own sweep is run.  All arithmetic is FP64, contraction off.
+ *
+ * replaces: FaultGeometry.get_moment / get_magnitude / get_total_slip / get_subfault_patch_moments
+ *           beat/ffi/fault.py:284-359 (per draw, a Python loop over the patches; `beat summarize --calc_derived`
+ *           through get_derived_parameters, fault.py:945-954)
+ *   M0[c] = sum_p k_p * sqrt(sum_comp s_{c,p,comp}^2), the patches added in patch order from 0.0; a patch of zero slip
+ *   contributes exactly 0 (fault.py:309-312).  Mw[c] = log10(M0 * 1e7) / 1.5 - 10.7, 0 where M0 == 0 (fault.py:338-341).
+ *   DEVIATIONS: the reference's num.array(moments).sum() is numpy's pairwise sum (differs within npatches * 2^-53
+ *   relative); the magnitude formula is pyrocko's moment_to_magnitude AS RECALLED -- pyrocko was not available to check
+ *   it against: UNVERIFIED. */
+int beatamd_ffi_magnitudes_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, const double *moment_per_slip,
+                                 const int64_t *comp_off, int32_t ncomp, double *M0, double *Mw);
+/* replaces: the time axes of get_subfault_moment_rate_function / get_moment_rate_function   beat/ffi/fault.py:413-420, 461-465
+ *   spans [C, nsubfaults + 1, 2] (int64) = (first, count) per subfault, the total in row nsubfaults:
+ *       first = floor(min_p start / deltat),  count = ceil((max_p start + max_allP duration) / deltat) + 1 - first
+ *   (the largest duration is the whole fault's, as point["durations"].max()); the total spans all subfaults.
+ *   DEVIATION: integer index grids instead of num.arange on floats -- a time is index * deltat; the lengths agree wherever
+ *   the reference's float steps are exact (deltat a power of two).  A draw flagged in chain_bad (hypocentre outside the
+ *   patch grid) gets count = 0 in every row and the call returns BEATAMD_EINVAL after filling the array; so does a draw
+ *   with an onset or duration that is not finite, a negative duration or an index beyond 2^40 (the reference fails in
+ *   arange there). */
+int beatamd_ffi_moment_rate_spans_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q,
+                                        const double *start_times, const int32_t *chain_bad, double deltat, int64_t *spans);
+/* replaces: get_subfault_patch_stfs / get_subfault_moment_rate_function / get_moment_rate_function
+ *           beat/ffi/fault.py:361-474 (per draw: a Python loop over the patches around pyrocko's stf.discretize_t)
+ *   rates [C, nsubfaults + 1, NT] on the index grid [kbase, kbase + NT) (sample j at (kbase + j) * deltat): rows
+ *   0 .. nsubfaults - 1 the subfaults, row nsubfaults their sum in subfault order (fault.py:466-472); zero outside a
+ *   draw's span; a moment per sample, not divided by deltat, as in the reference.  Per patch, in patch order, with
+ *   t0 = start, t1 = start + duration (anchor -1, beat/ffi/base.py:1013) and m = k_p * sqrt(sum_comp s^2) (fault.py:412
+ *   passes uparr and uperp):
+ *       k0 = round(t0 / deltat), k1 = round(t1 / deltat) (half to even), nt = k1 - k0 + 1
+ *       nt == 1: a = [1];  else  e_i = max(t0, min(t1, k0 deltat + (i - 0.5) deltat)), i = 0 .. nt,
+ *       F_i = -cos((e_i - t0) (pi / duration)), a_i = F_{i+1} - F_i, a_i /= S;   rate[k0 - kbase + i] += a_i * m
+ *   S adds the a_i in one fixed order: 64 strided partial sums (i = l, l + 64, ...), folded 32/16/8/4/2/1.  Rows are
+ *   independent: a batch cut into calls or permuted gives the same bits.  stf: BEATAMD_STF_HALF_SINUSOID; any other value
+ *   is BEATAMD_EINVAL (Boxcar and Triangular are not built).  spans (nullable): as beatamd_ffi_moment_rate_spans_batch.
+ *   NT is limited to 20224 (the row lives in LDS): BEATAMD_EINVAL above.  A draw whose total span does not lie within the
+ *   grid gets NaN rows and the call returns BEATAMD_EINVAL after filling the arrays; so does a draw with count = 0.
+ *   DEVIATIONS: integer index grids (above); the reference's num.sum(amplitudes) is numpy's pairwise sum; the
+ *   discretisation is pyrocko's HalfSinusoidSTF.discretize_t with exponent = 1 (BEAT's default stf_type) AS RECALLED --
+ *   pyrocko was not available to check it against: UNVERIFIED. */
+#define BEATAMD_STF_HALF_SINUSOID 0
+int beatamd_ffi_moment_rates_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q, const double *moment_per_slip,
+                                   const int64_t *comp_off, int32_t ncomp, const double *start_times, const int32_t *chain_bad,
+                                   double deltat, int32_t stf, int64_t kbase, int64_t NT, double *rates, int64_t *spans);
 /* The LDS bytes a workgroup of the rupture-time sweep asks for when the largest subfault of a batch has ncells patches,
  * and through waves (nullable) how many grids share that workgroup (4 or 1): a pure function, the rule of the launch
  * (four grids per workgroup while they fit 64 KiB together, one above; at most 160 KiB).  -1: ncells is not in 1..6400,
@@ -704,6 +754,15 @@ int beatamd_ensemble_moments_finish(beatamd_ctx *ctx, int64_t M, const double *s
 int beatamd_trace_density_update(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin,
                                  double deltat, const double *extent, int64_t ny, int64_t nx, double linewidth,
                                  double *grid);
+/* replaces: fuzzy_moment_rate's loop of draw_line_on_array over moment-rate functions that each cover their own stretch
+ *           of the time axis                      beat/plotting/ffi.py:41-79
+ *   beatamd_trace_density_update with ranges [E,T,2] (int64) = (first sample, count) of every trace: only the segments
+ *   between samples inside a trace's own range are drawn (zero padding would add segments along rate 0), only those
+ *   samples are checked against the extent, and a trace with count < 2 draws nothing.  A range is cut to [0, N).
+ *   ranges == NULL: beatamd_trace_density_update itself, bit for bit. */
+int beatamd_trace_density_update_ranges(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin,
+                                        double deltat, const double *extent, const int64_t *ranges, int64_t ny, int64_t nx,
+                                        double linewidth, double *grid);
 
 /* ---------------------------------------------------------------- library whitening ------
  * rows [nrows, N] (device, in place) <- rows . W^T, W [N,N] = chol_inverse of one dataset: the
