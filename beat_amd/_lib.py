@@ -161,6 +161,10 @@ _PROTOS = {
     "beatamd_ffi_lsq_normal_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp],
     "beatamd_nnls_batch": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     "beatamd_ffi_lsq_solution_batch": [_vp, _i32, _i64, _vp, _vp, _vp, _vp],
+    "beatamd_geo_gf_library": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _vp],
+    "beatamd_smoothing_correlated": [_vp, _i64, _vp, _i32, _vp],
+    "beatamd_model_resolution": [_vp, _i64, _i64, _vp, _vp, _f64, _vp, _vp],
+    "beatamd_division_rating": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["beatamd_last_error", "beatamd_version"])

@@ -2337,4 +2337,93 @@ int beatamd_halfspace_displacements_batch(beatamd_ctx *ctx, int64_t C, int32_t n
     return BEATAMD_OK;
 }
 
+// ------------------------------------------------------------------ geodetic FFI library, fault discretization
+int beatamd_geo_gf_library(beatamd_ctx *ctx, int64_t nrows, const double *params, int64_t nobs, const double *east,
+                           const double *north, const double *los, const double *odw, double nu, double *G)
+{
+    ENTER(ctx);
+    BA_CHECK(params && east && north && los && odw && G && nrows >= 0 && nobs > 0, BEATAMD_EINVAL,
+             "geo_gf_library: bad argument");
+    BA_CHECK(nu > -1.0 && nu < 0.5, BEATAMD_EINVAL, "Poisson ratio outside (-1, 0.5)");
+    if (nrows == 0) return BEATAMD_OK;
+    const int32_t kind = 0;
+    int64_t poff[10];
+    for (int i = 0; i < 10; i++) poff[i] = i;
+    Staging st(ctx);
+    const double *d_p, *d_e, *d_n, *d_l, *d_w;
+    const int32_t *d_k;
+    const int64_t *d_o;
+    double *d_g;
+    BA_TRY(st.in(&kind, (size_t)1, &d_k));
+    BA_TRY(st.in(poff, (size_t)10, &d_o));
+    BA_TRY(st.in(params, (size_t)nrows * 10, &d_p));
+    BA_TRY(st.in(east, (size_t)nobs, &d_e));
+    BA_TRY(st.in(north, (size_t)nobs, &d_n));
+    BA_TRY(st.in(los, (size_t)nobs * 3, &d_l));
+    BA_TRY(st.in(odw, (size_t)nobs, &d_w));
+    BA_TRY(st.out(G, (size_t)nrows * nobs, &d_g));
+    BA_TRY(launch_geo_gf_library(ctx, nrows, d_p, d_k, d_o, nobs, d_e, d_n, d_l, d_w, nu, d_g));
+    BA_TRY(st.finish());
+    BA_HIP(hipStreamSynchronize(ctx->stream));   // `kind`, `poff` are stack temporaries
+    return BEATAMD_OK;
+}
+
+int beatamd_smoothing_correlated(beatamd_ctx *ctx, int64_t P, const double *coords, int32_t kind, double *L)
+{
+    ENTER(ctx);
+    BA_CHECK(coords && L && P >= 0 && P <= 32768, BEATAMD_EINVAL, "smoothing_correlated: bad argument");
+    BA_CHECK(kind == 0 || kind == 1, BEATAMD_EINVAL,
+             "Resolution based discretization does not support \"nearest_neighbor\" correlation function!");
+    if (P == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_c;
+    double *d_l;
+    BA_TRY(st.in(coords, (size_t)P * 3, &d_c));
+    BA_TRY(st.out(L, (size_t)P * P, &d_l));
+    BA_TRY(launch_smoothing_correlated(ctx, P, d_c, kind, d_l));
+    return st.finish();
+}
+
+int beatamd_model_resolution(beatamd_ctx *ctx, int64_t P, int64_t nobs, const double *gfs, const double *L,
+                             double epsilon, double *R, double *diag)
+{
+    ENTER(ctx);
+    BA_CHECK(gfs && L && R && diag && P >= 0 && nobs > 0, BEATAMD_EINVAL, "model_resolution: bad argument");
+    if (P == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_g, *d_l;
+    double *d_r, *d_d;
+    BA_TRY(st.in(gfs, (size_t)P * nobs, &d_g));
+    BA_TRY(st.in(L, (size_t)P * P, &d_l));
+    BA_TRY(st.out(R, (size_t)P * P, &d_r));
+    BA_TRY(st.out(diag, (size_t)P, &d_d));
+    BA_TRY(launch_model_resolution(ctx, P, nobs, d_g, d_l, epsilon, d_r, d_d));
+    BA_TRY(st.finish());
+    return ctx->check_status();   // a factorisation that failed raises, whichever side the outputs live on
+}
+
+int beatamd_division_rating(beatamd_ctx *ctx, int64_t P, int64_t nobs, const double *widths, const double *lengths,
+                            const double *centers, const double *bottom_depth, double depth_penalty,
+                            const double *data_en, const double *mean_R, double *rating, double *dmin)
+{
+    ENTER(ctx);
+    BA_CHECK(widths && lengths && centers && bottom_depth && data_en && mean_R && rating && P >= 0 && nobs > 0,
+             BEATAMD_EINVAL, "division_rating: bad argument");
+    if (P == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_w, *d_l, *d_c, *d_b, *d_e, *d_m;
+    double *d_r, *d_min;
+    BA_TRY(st.in(widths, (size_t)P, &d_w));
+    BA_TRY(st.in(lengths, (size_t)P, &d_l));
+    BA_TRY(st.in(centers, (size_t)P * 3, &d_c));
+    BA_TRY(st.in(bottom_depth, (size_t)P, &d_b));
+    BA_TRY(st.in(data_en, (size_t)nobs * 2, &d_e));
+    BA_TRY(st.in(mean_R, (size_t)P, &d_m));
+    BA_TRY(st.out(rating, (size_t)P, &d_r));
+    if (dmin) BA_TRY(st.out(dmin, (size_t)P, &d_min));
+    else BA_TRY(ctx->scratch(SL_RATE_DMIN, (size_t)P, &d_min));
+    BA_TRY(launch_division_rating(ctx, P, nobs, d_w, d_l, d_c, d_b, depth_penalty, d_e, d_m, d_min, d_r));
+    return st.finish();
+}
+
 }  // extern "C"

@@ -344,6 +344,19 @@ int launch_geom_los(beatamd_ctx *ctx, const GeomSources &g, const double *Q, int
 int launch_geom_disp(beatamd_ctx *ctx, int nsrc, const int32_t *kind, const int64_t *poff,
                      const double *params, int64_t C, int64_t nobs, const double *east,
                      const double *north, double nu, double *out);
+// geolib.hip: G [nrows, nobs] = line-of-sight displacement * odw of nrows unit sources (params [nrows, 10]; kind / poff
+// describe one rectangular source with identity offsets); everything on the device
+int launch_geo_gf_library(beatamd_ctx *ctx, int64_t nrows, const double *params, const int32_t *kind,
+                          const int64_t *poff, int64_t nobs, const double *east, const double *north,
+                          const double *los, const double *odw, double nu, double *G);
+// resolution.hip (device pointers): the correlated smoothing operator (kind 0 gaussian, 1 exponential), the model
+// resolution matrix R [P, P] with its diagonal, and the division rating (dmin [P]: scratch and by-product)
+int launch_smoothing_correlated(beatamd_ctx *ctx, int64_t P, const double *coords, int kind, double *L);
+int launch_model_resolution(beatamd_ctx *ctx, int64_t P, int64_t nobs, const double *gfs, const double *L,
+                            double epsilon, double *R, double *diag);
+int launch_division_rating(beatamd_ctx *ctx, int64_t P, int64_t nobs, const double *widths, const double *lengths,
+                           const double *centers, const double *bottom_depth, double depth_penalty,
+                           const double *data_en, const double *mean_R, double *dmin, double *rating);
 // covariance.py:716-771 on device
 int launch_autocovariance(beatamd_ctx *ctx, int64_t nd, int64_t n, const double *data,
                           const double *mean, double *out);

@@ -1214,6 +1214,89 @@ class Context(object):
                                                               ptr(e), ptr(n), float(nu), ptr(out)))
         return out
 
+    # -- geodetic FFI library and resolution-based discretization (csrc/geolib.hip, csrc/resolution.hip)
+    def _f64_on_side(self, a, device, shape, what):
+        """contiguous float64 ``a`` of ``shape``: a device tensor if ``device`` (host arrays go up), else numpy"""
+        if device:
+            import torch
+            if not _is_dev(a):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:%d" % self.device)
+            a = f64(a)
+        else:
+            a = np.ascontiguousarray(a.cpu().numpy() if _is_dev(a) else a, dtype=np.float64)
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("%s must be %s, got %s" % (what, tuple(shape), tuple(a.shape)))
+        return a
+
+    def _new_f64(self, device, shape):
+        if device:
+            import torch
+            return torch.empty(shape, dtype=torch.float64, device="cuda:%d" % self.device)
+        return np.empty(shape, dtype=np.float64)
+
+    def geo_gf_library(self, params, east, north, los, odw, nu=0.25, device=False):
+        """params (nrows, 10) unit sources in the slots of halfspace_displacements_batch -> G (nrows, nobs) =
+        (disp * los).sum(1) * odw of every row (ffi/base.py:804-821), all rows in one launch.  device: return a
+        torch tensor on this context's GPU (inputs may be on either side)"""
+        dev = bool(device) or _is_dev(params)
+        nrows = int(params.shape[0])
+        nobs = int(odw.shape[0])
+        prm = self._f64_on_side(params, dev, (nrows, 10), "params")
+        e = self._f64_on_side(east, dev, (nobs,), "east")
+        n = self._f64_on_side(north, dev, (nobs,), "north")
+        lo = self._f64_on_side(los, dev, (nobs, 3), "los")
+        w = self._f64_on_side(odw, dev, (nobs,), "odw")
+        self._adopt_stream(prm)
+        G = self._new_f64(dev, (nrows, nobs))
+        check(self._lib.beatamd_geo_gf_library(self._h, nrows, ptr(prm), nobs, ptr(e), ptr(n), ptr(lo), ptr(w),
+                                               float(nu), ptr(G)))
+        return G
+
+    def smoothing_correlated(self, patches_coords, correlation_function="gaussian", device=False):
+        """get_smoothing_operator_correlated (models/laplacian.py:261-298) on the device: coords (P, 3) [km] -> L (P, P);
+        the column sums add the rows in ascending order (beat_amd.models.laplacian states the same order on the host)"""
+        kinds = {"gaussian": 0, "exponential": 1}
+        if correlation_function not in kinds:
+            raise ValueError('Resolution based discretization does not support "nearest_neighbor" correlation function!')
+        dev = bool(device) or _is_dev(patches_coords)
+        P = int(patches_coords.shape[0])
+        c = self._f64_on_side(patches_coords, dev, (P, 3), "patches_coords")
+        self._adopt_stream(c)
+        L = self._new_f64(dev, (P, P))
+        check(self._lib.beatamd_smoothing_correlated(self._h, P, ptr(c), kinds[correlation_function], ptr(L)))
+        return L
+
+    def model_resolution(self, gfs, L, epsilon):
+        """gfs (P, nobs) library rows, L (P, P) -> (R (P, P), diag (P,)) with R = inv(G^T G + eps^4 L^T L) . G^T G for
+        G = gfs.T (ffi/fault.py:1805-1815); same side as ``gfs``; numpy.linalg.LinAlgError if the normal matrix is not
+        positive definite"""
+        dev = _is_dev(gfs)
+        P, nobs = int(gfs.shape[0]), int(gfs.shape[1])
+        g = self._f64_on_side(gfs, dev, (P, nobs), "gfs")
+        Lm = self._f64_on_side(L, dev, (P, P), "L")
+        self._adopt_stream(g)
+        R, d = self._new_f64(dev, (P, P)), self._new_f64(dev, (P,))
+        check(self._lib.beatamd_model_resolution(self._h, P, nobs, ptr(g), ptr(Lm), float(epsilon), ptr(R), ptr(d)))
+        return R, d
+
+    def division_rating(self, widths, lengths, centers, bottom_depths, depth_penalty, data_coords, mean_R):
+        """the division penalties of ffi/fault.py:1884-1929: widths, lengths (P,) [km], centers (P, 3) [km],
+        bottom_depths (P,) [m] of each patch's subfault, data_coords (nobs, 2) [km] east / north, mean_R (P,) ->
+        (rating (P,), patch_data_distance_mins (P,)); same side as ``mean_R``"""
+        dev = _is_dev(mean_R)
+        P, nobs = int(mean_R.shape[0]), int(data_coords.shape[0])
+        w = self._f64_on_side(widths, dev, (P,), "widths")
+        ln = self._f64_on_side(lengths, dev, (P,), "lengths")
+        c = self._f64_on_side(centers, dev, (P, 3), "centers")
+        b = self._f64_on_side(bottom_depths, dev, (P,), "bottom_depths")
+        e = self._f64_on_side(data_coords, dev, (nobs, 2), "data_coords")
+        m = self._f64_on_side(mean_R, dev, (P,), "mean_R")
+        self._adopt_stream(m)
+        rating, dmin = self._new_f64(dev, (P,)), self._new_f64(dev, (P,))
+        check(self._lib.beatamd_division_rating(self._h, P, nobs, ptr(w), ptr(ln), ptr(c), ptr(b), float(depth_penalty),
+                                                ptr(e), ptr(m), ptr(rating), ptr(dmin)))
+        return rating, dmin
+
     def chol_inverse_batch(self, covs):
         """covs (nd, n, n) -> (W (nd, n, n) upper triangular = cholesky(inv(C)).T, log_pdet (nd,));
         numpy or torch-cuda in, same kind out; numpy.linalg.LinAlgError if not positive definite"""

@@ -557,3 +557,88 @@ class GeodeticGFEnsemble(object):
                              % (len(self.varnames) * self.npatches, len(self.varnames), self.npatches, sl.shape[0]))
         self.init_optimization()
         return self._ctx.geo_ensemble_stack(self.ens_id, len(self.crust_inds), self.nsamples, sl)
+
+
+# ---------------------------------------------------------------- geodetic library builder (base.py:804-1002)
+def _halfspace_ctx(engine):
+    from .heart import HalfspaceEngine
+    if not isinstance(engine, HalfspaceEngine):
+        raise TypeError("engine %r provides no static displacements (HalfspaceEngine does; the "
+                        "reference's layered GF-store engine is pyrocko's and out of scope)" % (engine,))
+    return engine.ctx
+
+
+def _patch_rows(patches):
+    """(P, 10) kernel parameters of a PatchSet, an array of rows or a list of sources with ``kernel_parameters``"""
+    if hasattr(patches, "params"):
+        return patches.params
+    if isinstance(patches, np.ndarray):
+        return np.ascontiguousarray(patches, dtype=np.float64).reshape(-1, 10)
+    return np.array([p.kernel_parameters() for p in patches], dtype=np.float64).reshape(-1, 10)
+
+
+def _library_rows(engine, datasets, rows, device):
+    from .heart import concatenate_datasets, km
+    ctx = _halfspace_ctx(engine)
+    _, los_vectors, odws, sizes = concatenate_datasets(datasets)
+    east = np.hstack([d.update_local_coords(None)[1] for d in datasets]) / km
+    north = np.hstack([d.update_local_coords(None)[0] for d in datasets]) / km
+    return ctx.geo_gf_library(rows, east, north, los_vectors, odws, nu=engine.nu, device=device), sizes
+
+
+def geo_construct_gf_linear_patches(engine, datasets=None, targets=None, patches=None, nworkers=1, apply_weight=False,
+                                    return_mapping=False, device=False):
+    """base.py:934-1002: the (npatches, nsamples) Green's-function matrix of ``patches`` (a PatchSet, (P, 10) rows of
+    kernel parameters or sources with ``kernel_parameters``; each carries its slip direction), every patch in ONE kernel
+    launch (csrc/geolib.hip).  ``device``: a torch tensor that never visits the host.  ``apply_weight`` multiplies each
+    dataset's columns with its ``covariance.chol_inverse`` (base.py:991-997).  ``return_mapping`` also returns the
+    samples per dataset, which stand where the reference returns its bijection.  ``targets`` / ``nworkers`` are the
+    reference's arguments and unused: the datasets carry the coordinates, the device the parallelism."""
+    rows = _patch_rows(patches)
+    gfmatrix, sizes = _library_rows(engine, datasets, rows, device)
+    if apply_weight:
+        bounds = np.cumsum([0] + sizes)
+        w_gfs = []
+        for dataset, lo, hi in zip(datasets, bounds[:-1], bounds[1:]):
+            W = dataset.covariance.chol_inverse
+            if device:
+                import torch
+                W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(gfmatrix.device)
+                w_gfs.append(gfmatrix[:, lo:hi] @ W)
+            else:
+                w_gfs.append(gfmatrix[:, lo:hi].dot(W))
+        if device:
+            import torch
+            gfmatrix = torch.cat(w_gfs, dim=1).contiguous()
+        else:
+            gfmatrix = np.hstack(w_gfs)
+    return (gfmatrix, sizes) if return_mapping else gfmatrix
+
+
+def geo_construct_gf_linear(engine, outdirectory="", crust_ind=0, datasets=None, targets=None, fault=None,
+                            varnames=("uparr",), force=False, event=None, nworkers=1):
+    """base.py:824-931: one GeodeticGFLibrary per slip component of ``fault`` (``get_all_patches("geodetic",
+    component=var)`` -> (P, 10) rows), the rows of ALL components filled by one kernel launch.  With ``outdirectory``
+    the libraries are saved in the reference's layout (<outdirectory>/geodetic_<var>_static_<crust_ind>.traces.npy +
+    .yaml); an existing file is kept and loaded unless ``force``.  -> {varname: GeodeticGFLibrary}"""
+    varnames = list(varnames)
+    libs, todo = {}, []
+    for var in varnames:
+        name = get_gf_prefix("geodetic", var, "static", crust_ind)
+        if outdirectory and os.path.exists(os.path.join(outdirectory, name + ".traces.npy")) and not force:
+            libs[var] = load_gf_library(outdirectory, name)
+        else:
+            todo.append(var)
+    if todo:
+        rows = np.vstack([_patch_rows(fault.get_all_patches("geodetic", component=var)) for var in todo])
+        G, _ = _library_rows(engine, datasets, rows, False)
+        npatches = rows.shape[0] // len(todo)
+        for k, var in enumerate(todo):
+            gfs = GeodeticGFLibrary(GeodeticGFLibraryConfig(component=var, crust_ind=crust_ind, datatype="geodetic"))
+            gfs.setup(npatches, G.shape[1], allocate=False)
+            gfs._gfmatrix = np.ascontiguousarray(G[k * npatches:(k + 1) * npatches])
+            gfs.lib_id_dirty = True
+            if outdirectory:
+                gfs.save(outdir=outdirectory)
+            libs[var] = gfs
+    return {var: libs[var] for var in varnames}

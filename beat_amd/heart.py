@@ -184,6 +184,36 @@ class StaticTarget(object):
         self.lons = np.zeros_like(self.east_shifts) if lons is None else np.asarray(lons)
 
 
+class GeodeticDataset(StaticTarget):
+    """the fields of heart.GeodeticDataset / DiffIFG (heart.py:1040-1520) the library builder and the discretizer read:
+    local coordinates [m] relative to the event (all datasets and subfaults share its reference location),
+    the line-of-sight vectors (n, 3) = [Sn, Se, Su], the weights ``odw`` (default ones) and the displacements"""
+
+    def __init__(self, east_shifts, north_shifts, los_vector, odw=None, displacement=None, name=""):
+        super(GeodeticDataset, self).__init__(east_shifts, north_shifts)
+        n = self.east_shifts.size
+        self.los_vector = np.ascontiguousarray(los_vector, dtype=np.float64).reshape(n, 3)
+        self.odw = np.ones(n) if odw is None else np.ascontiguousarray(odw, dtype=np.float64).reshape(n)
+        self.displacement = (np.zeros(n) if displacement is None
+                             else np.ascontiguousarray(displacement, dtype=np.float64).reshape(n))
+        self.name = name
+
+    samples = property(lambda self: self.east_shifts.size)
+
+    def update_local_coords(self, loc=None):
+        """heart.py:1117-1140 -> (north_shifts, east_shifts) [m]; no reprojection"""
+        return self.north_shifts, self.east_shifts
+
+
+def concatenate_datasets(datasets):
+    """heart.py:3495-3530 -> (displacements, los_vectors, odws, sizes); ``sizes`` (samples per dataset, in order)
+    stands where the reference returns its ListToArrayBijection"""
+    disp = np.hstack([d.displacement for d in datasets])
+    los = np.vstack([d.los_vector for d in datasets])
+    odws = np.hstack([d.odw for d in datasets])
+    return disp, los, odws, [int(d.samples) for d in datasets]
+
+
 class HalfspaceSource(object):
     """attribute bag with pyrocko's RectangularSource field names (SI units: m, deg);
     kind "rectangular" | "mogi" (for Mogi: ``volume_change`` [m^3])"""

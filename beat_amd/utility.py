@@ -23,6 +23,42 @@ def repair_covariance(x, epsilon=np.finfo(np.float64).eps):
     return eigvec.dot(np.diag(val)).dot(eigvec.T)
 
 
+def get_data_radiant(data):
+    """utility.py:1611-1619: angle of the data extent, data (n, 2)"""
+    return np.arctan2(data[:, 1].max() - data[:, 1].min(), data[:, 0].max() - data[:, 0].min())
+
+
+def find_elbow(data, theta=None, rotate_left=False):
+    """utility.py:1622-1655: index of the point closest to the turning point of data (n, 2) after rotating it by
+    theta (default: get_data_radiant); -> (index, rotated_data)"""
+    if theta is None:
+        theta = get_data_radiant(data)
+    if rotate_left:
+        theta = 2 * np.pi - theta
+    co, si = np.cos(theta), np.sin(theta)
+    rotation_matrix = np.array(((co, -si), (si, co)))
+    rotated_data = data.dot(rotation_matrix)
+    return rotated_data[:, 1].argmin(), rotated_data
+
+
+def distances(points, ref_points):
+    """utility.py:1695-1723: Cartesian distances (n_points, n_ref_points) of points (n, d) to ref_points (m, d); the d
+    squares are summed in axis order"""
+    nref_points = ref_points.shape[0]
+    ndim = points.shape[1]
+    ndim_ref = ref_points.shape[1]
+    if ndim != ndim_ref:
+        raise TypeError("Coordinates to calculate differences must have the same number "
+                        "of dimensions! Given dimensions are {} and {}".format(ndim, ndim_ref))
+    points_rep = np.tile(points, nref_points).reshape(points.shape[0], nref_points, ndim)
+    return np.sqrt(np.power(points_rep - ref_points, 2).sum(axis=2))
+
+
+def normalized_resolution_spread(resolution, nparams):
+    """ffi/fault.py:2047-2054 (Atzori et al. 2019): between 0 and 1, the closer to zero the better resolved"""
+    return np.linalg.norm(resolution - np.eye(nparams)) / nparams
+
+
 def running_window_rms(data, window_size, mode="valid"):
     """utility.py:1141-1161"""
     data2 = np.power(data, 2)

@@ -925,6 +925,31 @@ int beatamd_nnls_batch(beatamd_ctx *ctx, int64_t C, int64_t n, const double *N, 
 int beatamd_ffi_lsq_solution_batch(beatamd_ctx *ctx, int32_t model_id, int64_t C, const double *Q_in, double *Q_out,
                                    int32_t *iters, int32_t *status);
 
+/* ---- geodetic FFI library and resolution-based fault discretization (csrc/geolib.hip, csrc/resolution.hip)
+ * Reference: geo_construct_gf_linear / geo_construct_gf_linear_patches (beat/ffi/base.py:804-1002),
+ * get_smoothing_operator_correlated (beat/models/laplacian.py:261-298), optimize_discretization
+ * (beat/ffi/fault.py:1520-1987; Atzori & Antonioli 2011, Atzori et al. 2019).  Array arguments may live on either side.
+ * geo_gf_library: params [nrows, 10] (the slots of halfspace_displacements_batch: km, deg, m; rectangular sources, depth
+ *   = top centre; the caller states rake / slip / opening of the slip component in each row, rows ordered
+ *   (component, patch)); east, north [nobs] km; los [nobs, 3] = (Sn, Se, Su); odw [nobs] ->
+ *   G [nrows, nobs] = (u_n S_n + u_e S_e + u_u S_u) * odw (base.py:813), every row in ONE launch.
+ * smoothing_correlated: coords [P, 3] km, kind 0 "gaussian" 1/d^2 | 1 "exponential" 1/exp(d) -> L [P, P], the column
+ *   sums taken over the rows in ascending order, the diagonal their negative.
+ * model_resolution: gfs [P, nobs] (library rows = G^T), L [P, P] -> R [P, P] = inv(G^T G + eps^4 L^T L) . G^T G and
+ *   diag [P] (fault.py:1805-1815).  A normal matrix that is not positive definite is BEATAMD_ENOTPSD.
+ * division_rating: widths, lengths [P] km; centers [P, 3] km (event-relative east, north, depth); bottom_depth [P] m (of
+ *   the patch's subfault); data_en [nobs, 2] km (east, north); mean_R [P] -> rating [P] = area * c1 * c2 * c3 and
+ *   dmin [P] (nullable), the smallest horizontal distance of a patch centre to a data point (fault.py:1884-1929).  The
+ *   argsort and the alpha cut stay with the caller. */
+int beatamd_geo_gf_library(beatamd_ctx *ctx, int64_t nrows, const double *params, int64_t nobs, const double *east,
+                           const double *north, const double *los, const double *odw, double nu, double *G);
+int beatamd_smoothing_correlated(beatamd_ctx *ctx, int64_t P, const double *coords, int32_t kind, double *L);
+int beatamd_model_resolution(beatamd_ctx *ctx, int64_t P, int64_t nobs, const double *gfs, const double *L,
+                             double epsilon, double *R, double *diag);
+int beatamd_division_rating(beatamd_ctx *ctx, int64_t P, int64_t nobs, const double *widths, const double *lengths,
+                            const double *centers, const double *bottom_depth, double depth_penalty,
+                            const double *data_en, const double *mean_R, double *rating, double *dmin);
+
 #ifdef __cplusplus
 }
 #endif
