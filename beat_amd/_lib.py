@@ -83,6 +83,8 @@ _PROTOS = {
     "beatamd_laplacian_logp_batch": [_vp, _i32, _i64, _i64, _vp, _vp, _vp],
     "beatamd_ffi_model_create": [_vp, C.POINTER(FfiLayout), _i32, _vp, _vp, _vp, _pi32],
     "beatamd_ffi_model_add_wavemap": [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32],
+    "beatamd_ffi_model_add_wavemap_spectrum": [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _i64],
+    "beatamd_amp_spectrum_batch": [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp],
     "beatamd_ffi_model_add_geodetic": [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "beatamd_ffi_model_add_geodetic_geometry": [_vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f64,
                                                 _vp, _vp, _i32, _vp, _vp, _vp],

@@ -234,6 +234,8 @@ class NoiseCovarianceUpdate(object):
     factored again.  ``last_ms`` / ``n_repaired`` report the last update."""
 
     def __init__(self, logp_func):
+        from .models.problem import refuse_spectrum_wavemaps
+        refuse_spectrum_wavemaps(getattr(logp_func, "problem", None), "NoiseCovarianceUpdate")
         self.f = logp_func
         self.last_ms, self.n_repaired, self.n_updates = 0.0, 0, 0
 

@@ -637,11 +637,12 @@ int beatamd_ffi_model_create(beatamd_ctx *ctx, const beatamd_ffi_layout *layout,
     return BEATAMD_OK;
 }
 
-int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int32_t *lib_ids,
-                                  const double *data, int32_t wset_id, const int64_t *hp_off,
-                                  const int64_t *shift_off, int32_t interpolation)
+// one wavemap of either domain: `data` is the observed side as the likelihood reads it, [T,N] traces or, with ntrans > 0,
+// [T, hi - lo] amplitude spectra
+static int add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int32_t *lib_ids, const double *data, int32_t wset_id,
+                       const int64_t *hp_off, const int64_t *shift_off, int32_t interpolation, int64_t ntrans, int64_t lo,
+                       int64_t hi)
 {
-    ENTER(ctx);
     FfiModel *m;
     BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(lib_ids && data && hp_off, BEATAMD_EINVAL, "add_wavemap: NULL argument");
@@ -659,12 +660,19 @@ int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int3
     BA_CHECK(l0->P == m->P, BEATAMD_EINVAL,
              "add_wavemap: library has %lld patches, fault has %lld", (long long)l0->P,
              (long long)m->P);
-    WeightSet *ws = get_obj(ctx->wsets, wset_id);
-    BA_CHECK(ws && ws->nd == l0->T && ws->M == l0->N, BEATAMD_EINVAL,
-             "add_wavemap: weight set must hold %lld datasets of %lld samples", (long long)l0->T,
-             (long long)l0->N);
     w.T = l0->T;
     w.N = l0->N;
+    if (ntrans > 0) {
+        BA_TRY(spectrum_check_band(w.N, ntrans, lo, hi));
+        const double *tw;
+        BA_TRY(spectrum_twiddles(ctx, ntrans, &tw));   // (the table exists before any step can be captured)
+        w.domain = BEATAMD_DOMAIN_SPECTRUM;
+        w.ntrans = ntrans; w.lo = lo; w.hi = hi; w.M = hi - lo;
+    }
+    WeightSet *ws = get_obj(ctx->wsets, wset_id);
+    BA_CHECK(ws && ws->nd == l0->T && ws->M == w.nsamples(), BEATAMD_EINVAL,
+             "add_wavemap: weight set must hold %lld datasets of %lld samples%s", (long long)l0->T,
+             (long long)w.nsamples(), ntrans > 0 ? " (spectrum domain: hi - lo bins)" : "");
     w.wset = wset_id;
     w.interp = interpolation;
     const int64_t np = m->layout.nparams;
@@ -675,7 +683,10 @@ int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int3
             BA_CHECK(shift_off[t] >= 0 && shift_off[t] < np, BEATAMD_EINVAL,
                      "add_wavemap: shift_off[%lld] outside q", (long long)t);
     }
-    BA_TRY(w.data.alloc_copy(ctx, data, (size_t)w.T * w.N));
+    if (ntrans > 0)
+        BA_TRY(w.data_spec.alloc_copy(ctx, data, (size_t)w.T * w.M));
+    else
+        BA_TRY(w.data.alloc_copy(ctx, data, (size_t)w.T * w.N));
     BA_TRY(w.hp_off.alloc_copy(ctx, hp_off, (size_t)w.T));
     if (shift_off) {
         BA_TRY(w.shift_off.alloc_copy(ctx, shift_off, (size_t)w.T));
@@ -696,6 +707,43 @@ int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int3
     }
     m->wavemaps.push_back(std::move(w));
     return BEATAMD_OK;
+}
+
+int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int32_t *lib_ids,
+                                  const double *data, int32_t wset_id, const int64_t *hp_off,
+                                  const int64_t *shift_off, int32_t interpolation)
+{
+    ENTER(ctx);
+    return add_wavemap(ctx, model_id, lib_ids, data, wset_id, hp_off, shift_off, interpolation, 0, 0, 0);
+}
+
+int beatamd_ffi_model_add_wavemap_spectrum(beatamd_ctx *ctx, int32_t model_id, const int32_t *lib_ids,
+                                           const double *data_spec, int32_t wset_id, const int64_t *hp_off,
+                                           const int64_t *shift_off, int32_t interpolation, int64_t ntrans, int64_t lo,
+                                           int64_t hi)
+{
+    ENTER(ctx);
+    BA_CHECK(ntrans > 0, BEATAMD_EINVAL, "add_wavemap_spectrum: transform length %lld", (long long)ntrans);
+    return add_wavemap(ctx, model_id, lib_ids, data_spec, wset_id, hp_off, shift_off, interpolation, ntrans, lo, hi);
+}
+
+int beatamd_amp_spectrum_batch(beatamd_ctx *ctx, int64_t R, int64_t N, int64_t ntrans, int64_t lo, int64_t hi,
+                               const double *X, const double *data_spec, int64_t T, double *out)
+{
+    ENTER(ctx);
+    BA_CHECK(X && out && R >= 0, BEATAMD_EINVAL, "amp_spectrum: bad argument");
+    BA_TRY(spectrum_check_band(N, ntrans, lo, hi));
+    BA_CHECK(!data_spec || T > 0, BEATAMD_EINVAL, "amp_spectrum: data_spec given with %lld datasets", (long long)T);
+    if (R == 0) return BEATAMD_OK;
+    const int64_t M = hi - lo;
+    Staging st(ctx);
+    const double *d_x, *d_d = nullptr;
+    double *d_o;
+    BA_TRY(st.in(X, (size_t)R * N, &d_x));
+    if (data_spec) BA_TRY(st.in(data_spec, (size_t)T * M, &d_d));
+    BA_TRY(st.out(out, (size_t)R * M, &d_o));
+    BA_TRY(launch_amp_spectrum(ctx, R, N, N, ntrans, lo, hi, d_x, d_d, T, d_o));
+    return st.finish();
 }
 
 // the datasets of a geodetic composite, checked (`fn`: the entry point, for the messages): g gets sizes, weight sets, Nobs
@@ -964,7 +1012,7 @@ int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wav
     double *d_o, *st0;
     int32_t *chain_bad;
     BA_TRY(st.in(Q, (size_t)C * m->layout.nparams, &d_q));
-    BA_TRY(st.out(out, (size_t)C * wm.T * wm.N, &d_o));
+    BA_TRY(st.out(out, (size_t)C * wm.T * wm.nsamples(), &d_o));
     BA_TRY(model_start_times(ctx, *m, C, d_q, &st0, &chain_bad));
     GfStackCall k;
     BA_TRY(wavemap_call(ctx, *m, wm, C, d_q, st0, chain_bad, &k));
@@ -972,6 +1020,16 @@ int beatamd_ffi_synthetics_batch(beatamd_ctx *ctx, int32_t model_id, int32_t wav
     // although targets share shift variables, the float64 rows although the wavemap is set to float copies, every chain
     k.st.nslot = 0; k.st.tslot = nullptr; k.st.slot_shift_off = nullptr;
     k.f32 = false; k.active = nullptr;
+    if (wm.domain == BEATAMD_DOMAIN_SPECTRUM) {
+        // the time-domain stack into scratch, its amplitude spectra (or data_spec - them, seismic.py:932-941) out
+        k.mode = GF_STORE_SYN;
+        BA_TRY(ctx->scratch(SL_RESID, (size_t)C * wm.T * wm.N, &k.out));
+        BA_TRY(launch_gfstack(ctx, k));
+        BA_TRY(launch_amp_spectrum(ctx, C * wm.T, wm.N, wm.N, wm.ntrans, wm.lo, wm.hi, k.out,
+                                   residuals ? wm.data_spec.get() : nullptr, wm.T, d_o));
+        BA_TRY(ctx->check_status());
+        return st.finish();
+    }
     k.mode = residuals ? GF_RESID_STORE : GF_STORE_SYN;
     k.out = d_o;
     BA_TRY(launch_gfstack(ctx, k));
@@ -2224,7 +2282,9 @@ int beatamd_ffi_model_update_data(beatamd_ctx *ctx, int32_t model_id, int32_t wa
     Wavemap &w = m->wavemaps[wavemap_index];
     m->lsq_blocks_valid = false;
     m->obs_quads_valid = false;
-    BA_HIP(hipMemcpyAsync(w.data.get(), data, (size_t)w.T * w.N * 8, hipMemcpyDefault, ctx->stream));
+    // (a spectrum wavemap's observed side is its [T,M] amplitude spectra)
+    double *dst = w.domain == BEATAMD_DOMAIN_SPECTRUM ? w.data_spec.get() : w.data.get();
+    BA_HIP(hipMemcpyAsync(dst, data, (size_t)w.T * w.nsamples() * 8, hipMemcpyDefault, ctx->stream));
     BA_HIP(hipStreamSynchronize(ctx->stream));
     return BEATAMD_OK;
 }

@@ -279,6 +279,7 @@ int beatamd_ctx_destroy(beatamd_ctx *c)
     c->geoens.clear();
     c->geolibs.clear();
     c->seislibs.clear();
+    c->twiddles.clear();
     for (auto &s : c->scratch_bufs) s.release();
     for (auto &kv : c->timers)
         for (auto &pr : kv.second.pending) {

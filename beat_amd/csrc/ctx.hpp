@@ -179,6 +179,13 @@ struct Wavemap {
     int interp = 0;
     int64_t T = 0, N = 0;
     bool f32 = false;   // read the libraries' float copies where a kernel supports it
+    // spectrum domain (beatamd_ffi_model_add_wavemap_spectrum; spectrum.hip): the likelihood is formed on the amplitude
+    // spectra abs(rfft(., ntrans))[lo:hi] of the stacked traces, M = hi - lo samples per dataset; data_spec [T,M] is the
+    // observed side and `data` stays empty (the entry point takes the observed spectra alone)
+    int domain = BEATAMD_DOMAIN_TIME;
+    int64_t ntrans = 0, lo = 0, hi = 0, M = 0;
+    DevMem<double> data_spec;
+    int64_t nsamples() const { return domain == BEATAMD_DOMAIN_SPECTRUM ? M : N; }   // samples per dataset in the likelihood
 };
 
 // one correction term of a geodetic dataset (geodetic.py:411-427 apply_corrections; corrections.py:46-87 ramp,
@@ -354,6 +361,8 @@ struct beatamd_ctx {
     // device-resident Philox step counter (beatamd_ctx_set_step_counter): the proposal draws read it
     // instead of their `step` argument and advance it, so that a captured step replays correctly
     uint32_t *step_dev = nullptr;
+    // twiddle tables of the amplitude-spectrum kernel, one per transform length (spectrum.hip: spectrum_twiddles)
+    std::map<int64_t, beatamd::DevMem<double>> twiddles;
 
     // grow-only scratch slot
     int get_scratch(int slot, size_t bytes, void **out);
@@ -388,7 +397,7 @@ enum Slot : int {
     SL_CHOL_A, SL_CHOL_X, SL_CHOL_D, SL_CHOL_T, SL_CHOL_L,
     SL_GC_ORDER, SL_GS_ORDER, SL_GC_STREAM, SL_GC_HDR, SL_GC_META, SL_DELTA, SL_LOGU, SL_EDGES, SL_TSLOT, SL_SPLIT, SL_WS_PACK,
     SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_MR_SPANS,
-    SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_COUNT
+    SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_SPEC, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

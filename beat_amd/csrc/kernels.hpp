@@ -535,6 +535,17 @@ struct BallSet {
 int launch_ball_rms(beatamd_ctx *ctx, int64_t nd, int64_t nmax, const BallSet *sets, const double *coords, const double *data,
                     double max_dist_perc, double *pmax, double *radius, int32_t *counts, double *stds);
 
+// ---- spectrum.hip: amplitude spectra abs(rfft(x, ntrans))[lo:hi] of rows of real samples (heart.py:4091-4155)
+constexpr int SPEC_NTRANS_MIN = 2, SPEC_NTRANS_MAX = 8192;
+constexpr int SPEC_WAVE_NTRANS = 512;   // up to here one wavefront per trace, four traces per workgroup; above one workgroup
+// 0 <= lo < hi <= ntrans/2 + 1, 1 <= N <= ntrans, ntrans a power of two in [SPEC_NTRANS_MIN, SPEC_NTRANS_MAX]
+int spectrum_check_band(int64_t N, int64_t ntrans, int64_t lo, int64_t hi);
+// *W = the context's table exp(-2 pi i k / ntrans), k < ntrans/2, made on first use (never inside a graph capture)
+int spectrum_twiddles(beatamd_ctx *ctx, int64_t ntrans, const double **W);
+// out [R, hi - lo] = spec(x_r) of the rows X[r*xs .. r*xs + N), or data_spec[r mod T] - spec(x_r) (data_spec [T, hi - lo])
+int launch_amp_spectrum(beatamd_ctx *ctx, int64_t R, int64_t N, int64_t xs, int64_t ntrans, int64_t lo, int64_t hi,
+                        const double *X, const double *data_spec, int64_t T, double *out);
+
 // ---- lsq.hip: non-negative least-squares slip of a batch of chains (problems.py:753-873)
 // the index tables of a stacking call, one per target (k_gf_tables): rowoff [C,T,P,nrow], fac [C,T,P,4] (multilinear)
 int launch_gf_tables(beatamd_ctx *ctx, const GfStackCall &call, uint32_t *rowoff, double *fac);

@@ -195,7 +195,20 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             BA_TRY(wavemap_call(ctx, m, wm, C, Q, st0, chain_bad, &k));
             k.active = opt.active;
             BA_TRY(ctx->scratch(SL_QUAD, (size_t)C * wm.T, &quad));
-            if (ws->kind == BEATAMD_W_SCALAR) {
+            if (wm.domain == BEATAMD_DOMAIN_SPECTRUM) {
+                // the amplitude is taken after the stack, so nothing of the misfit can ride in the stacking kernel: the
+                // time-domain traces go to scratch, k_amp_spectrum writes data_spec - spec(syn) once, and every weight
+                // kind takes its quadratic form of that (M samples per dataset in place of N from here on)
+                double *spec;
+                BA_CHECK(ws->nd == wm.T && ws->M == wm.M, BEATAMD_EINVAL, "spectrum wavemap: weight set of the wrong size");
+                k.mode = GF_STORE_SYN;
+                BA_TRY(ctx->scratch(SL_RESID, (size_t)C * wm.T * wm.N, &k.out));
+                BA_TRY(ctx->scratch(SL_SPEC, (size_t)C * wm.T * wm.M, &spec));
+                BA_TRY(launch_gfstack(ctx, k));
+                BA_TRY(launch_amp_spectrum(ctx, C * wm.T, wm.N, wm.N, wm.ntrans, wm.lo, wm.hi, k.out, wm.data_spec.get(), wm.T,
+                                           spec));
+                BA_TRY(wset_quad(ctx, *ws, C, spec, wm.T * wm.M, wm.M, quad));
+            } else if (ws->kind == BEATAMD_W_SCALAR) {
                 k.mode = GF_RESID_SCALAR;
                 k.wscalar = ws->w.get();
                 k.quad = quad;
@@ -217,7 +230,7 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
             if (llks)
                 BA_TRY(launch_store_misfits(ctx, C, wm.T, quad, llks + tcol, nterm));
             else
-                BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.N, quad, ws->slog.get(), HpSrc{Q, np, wm.hp_off.get()}, LL + col,
+                BA_TRY(launch_mvn_finish(ctx, C, wm.T, wm.nsamples(), quad, ws->slog.get(), HpSrc{Q, np, wm.hp_off.get()}, LL + col,
                                          nllk));
             col += wm.T;
             tcol += wm.T;
@@ -316,8 +329,10 @@ int model_obs_quads(beatamd_ctx *ctx, FfiModel &m)
     WeightSet *ws;
     for (auto &wm : m.wavemaps) {
         ws = get_obj(ctx->wsets, wm.wset);
-        BA_CHECK(ws && ws->nd == wm.T && ws->M == wm.N, BEATAMD_EINVAL, "wavemap refers to a destroyed weight set");
-        BA_TRY(wset_quad(ctx, *ws, 1, wm.data.get(), wm.T * wm.N, wm.N, dq.get() + col));
+        const int64_t ns = wm.nsamples();   // (a spectrum wavemap's observed side is data_spec [T,M])
+        BA_CHECK(ws && ws->nd == wm.T && ws->M == ns, BEATAMD_EINVAL, "wavemap refers to a destroyed weight set");
+        BA_TRY(wset_quad(ctx, *ws, 1, wm.domain == BEATAMD_DOMAIN_SPECTRUM ? wm.data_spec.get() : wm.data.get(), wm.T * ns, ns,
+                         dq.get() + col));
         col += wm.T;
     }
     if (m.has_geo) {
@@ -378,6 +393,9 @@ int lsq_normal_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q,
     BA_CHECK(m.lsq_var >= 0 && m.lsq_var < m.layout.nvar, BEATAMD_EINVAL,
              "lsq: the model has no inverted slip variable (beatamd_ffi_model_set_lsq_variables)");
     BA_CHECK(!(m.has_geo && m.geo_is_geometry), BEATAMD_EINVAL, "lsq: a geometry-mode geodetic composite is not linear in slip");
+    for (auto &wm : m.wavemaps)
+        BA_CHECK(wm.domain != BEATAMD_DOMAIN_SPECTRUM, BEATAMD_EINVAL,
+                 "lsq: a spectrum-domain wavemap is not linear in slip (the amplitude is taken after the stack)");
     Laplacian *lp = get_obj(ctx->laps, m.lap);
     BA_CHECK(lp && lp->P == P, BEATAMD_EINVAL, "model refers to a destroyed laplacian");
     const GeoLib *gl = nullptr;

@@ -386,6 +386,38 @@ class Context(object):
         check(self._lib.beatamd_ffi_model_add_wavemap(self._h, model_id, ptr(libs), ptr(data), wset_id,
                                                       ptr(hp), ptr(sh), _interp(interpolation)))
 
+    def ffi_model_add_wavemap_spectrum(self, model_id, lib_ids, data_spec, wset_id, hp_off, ntrans, valid_spectrum_indices,
+                                       shift_off=None, interpolation="nearest_neighbor"):
+        """a wavemap in the spectrum domain: data_spec (T, hi - lo) observed amplitude spectra, the weight set of that size"""
+        libs = np.ascontiguousarray(lib_ids, dtype=np.int32)
+        data_spec = np.ascontiguousarray(data_spec, dtype=np.float64)
+        hp = _i64arr(hp_off)
+        sh = _i64arr(shift_off)
+        lo, hi = valid_spectrum_indices
+        if data_spec.ndim != 2 or data_spec.shape[1] != int(hi) - int(lo):
+            raise ValueError("spectrum domain: data_spec must be (T, %d), got %s" % (int(hi) - int(lo), data_spec.shape))
+        check(self._lib.beatamd_ffi_model_add_wavemap_spectrum(self._h, model_id, ptr(libs), ptr(data_spec), wset_id, ptr(hp),
+                                                               ptr(sh), _interp(interpolation), int(ntrans), int(lo), int(hi)))
+
+    def amp_spectrum_batch(self, X, ntrans, valid_spectrum_indices, data_spec=None, out=None):
+        """X (R, N) -> (R, hi - lo) = abs(rfft(X[r], ntrans))[lo:hi] on the device (csrc/spectrum.hip), or with data_spec
+        (T, hi - lo) the residual data_spec[r mod T] - that.  numpy in -> numpy out, torch-cuda in -> tensor."""
+        self._adopt_stream(X)
+        X = f64(X)
+        if X.ndim != 2:
+            raise ValueError("amp_spectrum: X must be (R, N), got %s" % (tuple(X.shape),))
+        R, N = int(X.shape[0]), int(X.shape[1])
+        lo, hi = int(valid_spectrum_indices[0]), int(valid_spectrum_indices[1])
+        T = 0
+        if data_spec is not None:
+            if not hasattr(data_spec, "shape"):
+                data_spec = np.asarray(data_spec, dtype=np.float64)
+            data_spec = self._arg_on_side(data_spec, X, np.float64, (int(data_spec.shape[0]), hi - lo), "data_spec")
+            T = int(data_spec.shape[0])
+        out = self._out_on_side(X, (R, max(hi - lo, 0)), np.float64, out, "out")
+        check(self._lib.beatamd_amp_spectrum_batch(self._h, R, N, int(ntrans), lo, hi, ptr(X), ptr(data_spec), T, ptr(out)))
+        return out
+
     def ffi_model_add_geodetic(self, model_id, geo_lib_ids, data, odws, sizes, wset_ids, hp_off):
         libs = np.ascontiguousarray(geo_lib_ids, dtype=np.int32)
         data = np.ascontiguousarray(data, dtype=np.float64)

@@ -302,6 +302,32 @@ def geo_synthetics(engine, targets, sources, outmode="stacked_array", plot=False
     raise ValueError("Outmode %s not available" % outmode)
 
 
+def fft_transforms(time_domain_signals, valid_spectrum_indices, outmode="array", pad_to_pow2=True, ctx=None):
+    """heart.py:4091-4155 with outmode "array": the amplitude spectra ``abs(rfft(tr, ntrans))[lower_idx:upper_idx]`` of
+    the rows of an (n, N) array, ntrans = nextpow2(N) -- on the device (``beatamd_amp_spectrum_batch``), all rows in one
+    launch instead of one numpy transform per trace.  A numpy array gives a numpy array, a torch-cuda tensor (e.g. the
+    synthetics of an ensemble as ``LogpForwFunc.synthetics`` returns them, reshaped to rows) a tensor on its device: what
+    ``fuzzy_spectrum`` plots.  The other outmodes return pyrocko traces and are not offered; ``pad_to_pow2=False`` (a
+    transform of length N) is offered where N is a power of two, the only lengths the device transform has."""
+    from .engine import get_context
+    from .utility import nextpow2
+    if outmode != "array":
+        raise TypeError("Outmode %s not supported!" % outmode)
+    lower_idx, upper_idx = valid_spectrum_indices
+    x = time_domain_signals
+    if not hasattr(x, "data_ptr") or isinstance(x, np.ndarray):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("fft_transforms: outmode \"array\" takes an (n_data, n_samples) array, got %s" % (tuple(x.shape),))
+    n_samples = int(x.shape[1])
+    ntrans = nextpow2(n_samples)
+    if not pad_to_pow2 and ntrans != n_samples:
+        raise NotImplementedError("fft_transforms: pad_to_pow2=False needs a power-of-two trace length on the device, "
+                                  "got %d samples" % n_samples)
+    ctx = ctx or get_context()
+    return ctx.amp_spectrum_batch(x, ntrans, (int(lower_idx), int(upper_idx)))
+
+
 def seis_synthetics(engine, sources, targets, arrival_taper=None, wavename="any_P", filterer=None,
                     reference_taperer=None, plot=False, nthreads=1, outmode="array",
                     pre_stack_cut=False, taper_tolerance_factor=0.0, arrival_times=None,

@@ -98,7 +98,7 @@ class HyperModel(object):
         M, slog, kind, hp, names, ends = [], [], [], [], [], []
         for wm in prob.wavemaps:
             for t, (name, i) in enumerate(wm.hypers):
-                M.append(wm.data.shape[1]); slog.append(float(wm.slog_pdet[t])); kind.append(KIND_DATASET)
+                M.append(getattr(wm, "nsamples", wm.data.shape[1])); slog.append(float(wm.slog_pdet[t])); kind.append(KIND_DATASET)
                 hp.append(self.layout.offset(name, i))
                 names.append("seis_like_%s_%d" % (wm.name, t))
         if prob.wavemaps:

@@ -79,10 +79,19 @@ class SeismicWavemap(object):
     hypers         list of (hyper-parameter name, index) per dataset
                    (distributions.py:117-126: index 0 unless hp_specific)
     time_shifts    None or (name of the hierarchical variable, station_correction_idxs (T,))
+    domain         "time" | "spectrum" (WaveformFitConfig.domain, heart.py:526).  In the spectrum domain the likelihood
+                   is formed on amplitude spectra, as the reference's geometry mode does it (pytensorf.py:294-311,
+                   heart.py:3086-3095, 4091-4155) -- its own FFI composite refuses the domain (seismic.py:1277-1278), so
+                   this goes beyond it.  ``data`` stays the (T, N) time-domain traces; ``deltat`` (s) and
+                   ``taper_frequencies`` (f_lo, f_hi) [Hz] (``filterer_minmax(filterer)`` in the reference) give
+                       ntrans = nextpow2(N); deltaf = 1 / (ntrans * deltat)                          heart.py:3122-3124
+                       valid_spectrum_indices = (lo, hi) = get_valid_spectrum_data(deltaf, taper_frequencies)
+                   and M = ``nsamples_spectrum`` = hi - lo samples per dataset: weights are (T,) or (T, M, M).
+                   0 <= lo < hi <= ntrans/2 + 1 is required (numpy's slice would silently shorten a longer band).
     """
 
     def __init__(self, gfs, data, weights, slog_pdet, hypers, time_shifts=None,
-                 interpolation="nearest_neighbor", name="any_P_0"):
+                 interpolation="nearest_neighbor", name="any_P_0", domain="time", deltat=None, taper_frequencies=None):
         self.gfs = gfs
         self.data = np.ascontiguousarray(data, dtype=np.float64)
         self.weights = weights
@@ -93,10 +102,66 @@ class SeismicWavemap(object):
         self.name = name
         self._wset = None
         self.is_prewhitened = False
+        if domain not in ("time", "spectrum"):
+            raise ValueError("wavemap %s: domain must be \"time\" or \"spectrum\", got %r" % (name, domain))
+        self.domain = domain
+        self.deltat, self.taper_frequencies = deltat, taper_frequencies
+        self.ntrans, self.valid_spectrum_indices, self._data_spec = None, None, None
+        if domain == "spectrum":
+            self._setup_spectrum()
+
+    def _setup_spectrum(self):
+        from ..utility import get_valid_spectrum_data, nextpow2
+        what = "wavemap %s in the spectrum domain" % self.name
+        if self.deltat is None or not float(self.deltat) > 0.0:
+            raise ValueError("%s needs the sampling interval deltat > 0 of its traces" % what)
+        if self.taper_frequencies is None or len(self.taper_frequencies) != 2:
+            raise ValueError("%s needs taper_frequencies = (f_lo, f_hi)" % what)
+        if self.data.ndim != 2 or self.data.shape[1] < 2:
+            raise ValueError("%s needs (T, N) time-domain data with N >= 2" % what)
+        T, N = self.data.shape
+        ntrans = nextpow2(N)
+        if not 2 <= ntrans <= 8192:
+            raise ValueError("%s: transform length %d outside [2, 8192]" % (what, ntrans))
+        deltaf = 1.0 / (ntrans * float(self.deltat))
+        lo, hi = get_valid_spectrum_data(deltaf, [float(f) for f in self.taper_frequencies])
+        if not 0 <= lo < hi <= ntrans // 2 + 1:
+            raise ValueError("%s: the band %s Hz gives the spectrum indices [%d, %d), outside the %d bins of a transform of "
+                             "%d samples at deltaf = %g Hz (numpy's slice would shorten it silently)"
+                             % (what, tuple(self.taper_frequencies), lo, hi, ntrans // 2 + 1, ntrans, deltaf))
+        self.ntrans, self.valid_spectrum_indices = ntrans, (lo, hi)
+        M = hi - lo
+        w = np.shape(self.weights)
+        if w not in ((T,), (T, M, M)):
+            raise ValueError("%s: weights must be (%d,) or (%d, %d, %d) -- M = hi - lo spectrum samples, not the %d time "
+                             "samples -- got %s" % (what, T, T, M, M, N, w))
 
     @property
     def n_t(self):
         return self.data.shape[0]
+
+    @property
+    def nsamples_spectrum(self):
+        """M = hi - lo, samples per dataset of a spectrum wavemap (None in the time domain)"""
+        if self.domain != "spectrum":
+            return None
+        return self.valid_spectrum_indices[1] - self.valid_spectrum_indices[0]
+
+    @property
+    def nsamples(self):
+        """samples per dataset as the likelihood counts them: N, or M in the spectrum domain"""
+        return self.nsamples_spectrum if self.domain == "spectrum" else self.data.shape[1]
+
+    @property
+    def data_spec(self):
+        """(T, M) observed amplitude spectra, the reference's own host arithmetic for the observed side (prepare_data,
+        heart.py:3086-3095 -> fft_transforms): ``abs(rfft(data, ntrans, axis=1))[:, lo:hi]``"""
+        if self.domain != "spectrum":
+            return None
+        if self._data_spec is None:
+            lo, hi = self.valid_spectrum_indices
+            self._data_spec = np.ascontiguousarray(np.abs(np.fft.rfft(self.data, self.ntrans, axis=1))[:, lo:hi])
+        return self._data_spec
 
     def prewhitened(self, ctx=None, inplace=False):
         """Pre-whitened twin of this wavemap: every library row
@@ -109,6 +174,9 @@ class SeismicWavemap(object):
         skipped), in place on the HBM-resident library, chunked so that no second library copy is
         needed when ``inplace``.  A weight update (seismic.py:1509-1534) re-whitens rows and data in
         place with ``M_t = W_new,t . inv(W_old,t)`` (``LogpForwFunc.update_weights``)."""
+        if self.domain == "spectrum":
+            raise ValueError("wavemap %s is in the spectrum domain: it cannot be pre-whitened, |rfft(W s)| is not "
+                             "W |rfft(s)| (the amplitude does not commute with the whitening operator)" % self.name)
         import torch
 
         from ..engine import get_context
@@ -249,7 +317,7 @@ class FFIProblem(object):
             T, N = wm.data.shape
             w = np.asarray(wm.weights, dtype=np.float64)
             if w.ndim == 1:
-                wm._wset = ctx.weights_create_scalar(w, wm.slog_pdet, N)
+                wm._wset = ctx.weights_create_scalar(w, wm.slog_pdet, wm.nsamples)
             else:
                 wm._wset = ctx.weights_create_dense(w, wm.slog_pdet)
                 _log_band(ctx, wm._wset, "wavemap %s" % getattr(wm, "name", len(owned_wm)))
@@ -259,8 +327,12 @@ class FFIProblem(object):
             if wm.time_shifts is not None:
                 name, sidx = wm.time_shifts
                 shift_off = [lay.offset(name, int(i)) for i in sidx]
-            ctx.ffi_model_add_wavemap(mid, libs, wm.data, wm._wset, hp_off, shift_off,
-                                      wm.interpolation)
+            if wm.domain == "spectrum":
+                ctx.ffi_model_add_wavemap_spectrum(mid, libs, wm.data_spec, wm._wset, hp_off, wm.ntrans,
+                                                   wm.valid_spectrum_indices, shift_off, wm.interpolation)
+            else:
+                ctx.ffi_model_add_wavemap(mid, libs, wm.data, wm._wset, hp_off, shift_off,
+                                          wm.interpolation)
         if self.geodetic is not None:
             g = self.geodetic
             libs = []
@@ -432,6 +504,10 @@ class LogpForwFunc(object):
         numpy or torch-cuda in, same kind out"""
         wm = self.problem.wavemaps[wavemap_index]
         T, N = wm.data.shape
+        if _is_spectrum(wm):
+            # [C, T, M] amplitude spectra of the stacked traces, or data_spec - spectra: the reference's geometry-mode
+            # get_synthetics of a spectrum wavemap (seismic.py:932-941)
+            N = wm.nsamples_spectrum
         return self.ctx.ffi_synthetics_batch(self.model_id, wavemap_index, Q, T, N, residuals=residuals)
 
     def start_times(self, Q, chain_bad=None):
@@ -569,6 +645,14 @@ class LogpForwFunc(object):
         """column labels of ``variance_reductions`` / ``obs_quads``"""
         return list(self.problem.out_names[:self.ndata])
 
+    @property
+    def dataset_nsamples(self):
+        """samples per dataset, in the order of ``dataset_names``: N of a time-domain wavemap, M = hi - lo of a spectrum
+        wavemap, the size of a geodetic dataset"""
+        g = self.problem.geodetic
+        n = [int(getattr(wm, "nsamples", wm.data.shape[1])) for wm in self.problem.wavemaps for _ in range(wm.n_t)]
+        return n + ([int(s) for s in g.sizes] if g is not None else [])
+
     def obs_quads(self):
         """|W_k d_k|^2 per dataset -> (ndata,) numpy: the denominators ``data.T.dot(icov).dot(data)`` of the variance
         reduction (seismic.py:612-616, geodetic.py:497-501; geodetic data with its odw factor: DESIGN.md 3.9).  Cached
@@ -596,6 +680,7 @@ class LogpForwFunc(object):
     # -- lsq start (csrc/lsq.hip)
     def _lsq_setup(self, Q=None):
         """the checks of DistributionOptimizer.lsq_solution (problems.py:768-787) and the model's inverted variable"""
+        refuse_spectrum_wavemaps(self.problem, "the least-squares start")
         self._ready(Q)
         prob = self.problem
         if prob.laplacian is None:
@@ -660,6 +745,8 @@ class LogpForwFunc(object):
         h is read from Q as the model reads it (per dataset or shared).
         wavemap_index: a wavemap -> (C, T, N); "geodetic" -> list of (C, n_k) per dataset (the sizes differ).
         A pre-whitened wavemap is refused: its residuals are whitened by another operator already."""
+        if wavemap_index != "geodetic":
+            refuse_spectrum_wavemaps(self.problem, "standardized_residuals", wavemap_index)
         self._ready(Q)
         if wavemap_index == "geodetic":
             g = self.problem.geodetic
@@ -702,6 +789,8 @@ class LogpForwFunc(object):
         import torch
         wm = self.problem.wavemaps[wavemap_index]
         T, N = wm.data.shape
+        if _is_spectrum(wm):
+            N = wm.nsamples_spectrum     # the operators of a spectrum wavemap act on its M = hi - lo spectrum samples
         on_dev = torch.is_tensor(weights) and weights.is_cuda
         if on_dev:
             w = weights.contiguous()
@@ -799,6 +888,29 @@ def _log_band(ctx, wset, what):
 
 def _host(a):
     return a.detach().cpu().numpy() if hasattr(a, "detach") else a
+
+
+def _is_spectrum(wm):
+    return getattr(wm, "domain", "time") == "spectrum"
+
+
+# why each of these stops at a spectrum-domain wavemap (refuse_spectrum_wavemaps)
+_SPECTRUM_REASONS = {
+    "the least-squares start": "the amplitude is taken after the stack, the problem is not linear in the slips",
+    "standardized_residuals": "the standardizing operators of amplitude-spectrum residuals are a follow-up",
+    "NoiseCovarianceUpdate": "the spectral noise-covariance estimate (covariance.py:366-373) is a follow-up",
+    "TargetShardedLogp": "sharding the targets of a spectrum wavemap over ranks is a follow-up",
+}
+
+
+def refuse_spectrum_wavemaps(problem, what, wavemap_index=None):
+    """NotImplementedError naming the spectrum domain if ``problem`` has a spectrum wavemap (wavemap_index: that one alone);
+    a host check in front of any device call"""
+    wms = list(getattr(problem, "wavemaps", []))
+    for wm in wms if wavemap_index is None else [wms[wavemap_index]]:
+        if _is_spectrum(wm):
+            raise NotImplementedError("%s is not available for wavemap %s in the spectrum domain: %s"
+                                      % (what, wm.name, _SPECTRUM_REASONS[what]))
 
 
 def _standardizing_operators(covariances, n):

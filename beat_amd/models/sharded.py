@@ -81,6 +81,8 @@ class TargetShardedLogp(object):
     is uploaded).  Every rank constructs it with the same arguments."""
 
     def __init__(self, prob, ctx=None, rank=None, world=None):
+        from .problem import refuse_spectrum_wavemaps
+        refuse_spectrum_wavemaps(prob, "TargetShardedLogp")
         import torch
         self.torch = torch
         r, w, _ = parallel.dist_info()

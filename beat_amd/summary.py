@@ -130,6 +130,7 @@ def result_ensemble(f, population, best, nensemble, wavemap_index=0, batch=512, 
     E = int(ens.shape[0])
     for wi in which:
         T, N = f.problem.wavemaps[wi].data.shape
+        N = getattr(f.problem.wavemaps[wi], "nsamples", N)      # (a spectrum wavemap's synthetics are (e, T, M) spectra)
         state, seen, kept = None, 0, []
         for a in range(0, E, batch):
             syn = f.synthetics(ens[a:a + batch], wi)                      # (e, T, N) on the device

@@ -23,6 +23,20 @@ def repair_covariance(x, epsilon=np.finfo(np.float64).eps):
     return eigvec.dot(np.diag(val)).dot(eigvec.T)
 
 
+def nextpow2(n):
+    """pyrocko.trace.nextpow2: the transform length heart.fft_transforms pads a trace of n samples to.  RESTATED FROM
+    MEMORY (pyrocko is not in the tree): ``2 ** ceil(log2(n))``"""
+    return int(2 ** int(np.ceil(np.log2(n))))
+
+
+def get_valid_spectrum_data(deltaf, taper_frequencies=[0, 1.0]):
+    """utility.py:1604-1610: (lower_idx, upper_idx) of the valid frequency range of a spectrum sampled at deltaf"""
+    lower_f, upper_f = taper_frequencies
+    lower_idx = int(np.floor(lower_f / deltaf))
+    upper_idx = int(np.ceil(upper_f / deltaf))
+    return lower_idx, upper_idx
+
+
 def get_data_radiant(data):
     """utility.py:1611-1619: angle of the data extent, data (n, 2)"""
     return np.arctan2(data[:, 1].max() - data[:, 1].min(), data[:, 0].max() - data[:, 0].min())

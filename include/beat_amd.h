@@ -52,6 +52,9 @@ extern "C" {
 #define BEATAMD_W_SCALAR 0 /* W_i = w_i * I   (chol_inverse of sigma^2 I)            */
 #define BEATAMD_W_DENSE 1  /* W_i dense (M,M) row-major, upper-triangular content    */
 
+#define BEATAMD_DOMAIN_TIME 0     /* WaveformFitConfig.domain = "time" (heart.py:526)                  */
+#define BEATAMD_DOMAIN_SPECTRUM 1 /* "spectrum": amplitude spectra, beatamd_ffi_model_add_wavemap_spectrum */
+
 typedef struct beatamd_ctx beatamd_ctx;
 
 const char *beatamd_last_error(void);
@@ -359,6 +362,40 @@ int beatamd_ffi_model_create(beatamd_ctx *ctx, const beatamd_ffi_layout *layout,
 int beatamd_ffi_model_add_wavemap(beatamd_ctx *ctx, int32_t model_id, const int32_t *lib_ids,
                                   const double *data, int32_t wset_id, const int64_t *hp_off,
                                   const int64_t *shift_off, int32_t interpolation);
+/* replaces: the spectrum domain of a wavemap (WaveformFitConfig.domain = "spectrum", beat/heart.py:526) as the
+ *           reference's GEOMETRY mode evaluates it: pytensorf.SeisSynthesizer (beat/pytensorf.py:199-206, 294-311),
+ *           heart.fft_transforms (beat/heart.py:4091-4155), WaveformMapping.prepare_data (beat/heart.py:3086-3095),
+ *           get_valid_spectrum_data (beat/utility.py:1604-1610), get_synthetics (beat/models/seismic.py:932-941).
+ *           BEYOND the reference's FFI mode, which stops with TypeError("FFI is currently only supported for
+ *           time-domain!") (beat/models/seismic.py:1277-1278): the functions above are what the numbers are pinned to.
+ *   A wavemap whose likelihood is formed on amplitude spectra.  The time-domain stack is the one of
+ *   beatamd_ffi_model_add_wavemap (seismic.py:1324-1332: sweep, station shifts, interpolation, out-of-grid chains
+ *   flagged); per chain c and target t
+ *       r[c,t,:] = data_spec[t,:] - abs(rfft(syn[c,t,:], ntrans))[lo:hi]           (zero padded to ntrans)
+ *       logpt[c,t] = multivariate_normal_chol with W_t, M = hi - lo samples        beat/models/distributions.py:108-140
+ *   data_spec [T,M] is the observed side, transformed by the caller (prepare_data does it with numpy on the host);
+ *   wset_id holds T datasets of M samples (scalar, or dense M x M; banded operators are found as for any set).
+ *   ntrans = pyrocko.trace.nextpow2(N) = 2^ceil(log2 N) (restated from memory, pyrocko is not in the tree), a power of
+ *   two with N <= ntrans, 2 <= ntrans <= 8192; 0 <= lo < hi <= ntrans/2 + 1 -- a band numpy's slice would silently
+ *   shorten is BEATAMD_EINVAL here.  Sizes are checked when the wavemap is added.  The covariance of such a dataset is
+ *   M x M; the reference's spectral covariances are built at ntrans//2 + 1 bins (beat/covariance.py:133-135) and cut
+ *   to [lo:hi] by the caller.
+ *   beatamd_ffi_synthetics_batch of such a wavemap returns [C,T,M]: the spectra, or data_spec - spectra.
+ *   beatamd_ffi_lsq_* refuse a model with a spectrum wavemap: the problem is not linear in the slips. */
+int beatamd_ffi_model_add_wavemap_spectrum(beatamd_ctx *ctx, int32_t model_id, const int32_t *lib_ids,
+                                           const double *data_spec, int32_t wset_id, const int64_t *hp_off,
+                                           const int64_t *shift_off, int32_t interpolation, int64_t ntrans, int64_t lo,
+                                           int64_t hi);
+/* replaces: heart.fft_transforms(signals, (lo, hi), outmode="array", pad_to_pow2=True)   beat/heart.py:4091-4155
+ *           (one numpy.fft.rfft per trace in a Python loop)
+ *   X [R,N] -> out [R, hi - lo] = abs(rfft(X[r], ntrans))[lo:hi], FP64, one real-input FFT per row in LDS
+ *   (csrc/spectrum.hip states the operation order); with data_spec [T, hi - lo] (else NULL) out[r] =
+ *   data_spec[r mod T] - that.  A row's bits depend on its samples, N, ntrans, lo, hi alone: not on R, the row's
+ *   position or data_spec (beyond the subtraction).  Zeros give exact zeros; the padding is never read.
+ *   ntrans a power of two, 2 <= ntrans <= 8192, 1 <= N <= ntrans, 0 <= lo < hi <= ntrans/2 + 1, else BEATAMD_EINVAL
+ *   and nothing is launched.  Against numpy: |out - numpy| <= 8 max(1, log2 ntrans) 2^-53 |x_r|_2 per bin (tested). */
+int beatamd_amp_spectrum_batch(beatamd_ctx *ctx, int64_t R, int64_t N, int64_t ntrans, int64_t lo, int64_t hi,
+                               const double *X, const double *data_spec, int64_t T, double *out);
 /* geodetic composite (geodetic.py:1065-1081): geo lib per slip var, data [Nobs],
  * odws [Nobs], dataset sizes [nd] (srmap), one wset per dataset (sizes differ) */
 int beatamd_ffi_model_add_geodetic(beatamd_ctx *ctx, int32_t model_id, const int32_t *geo_lib_ids,
