@@ -239,12 +239,3 @@ def ptr(a):
         return a.data_ptr()
     raise TypeError("cannot take a pointer of %r" % type(a))
 
-
-def f64(a):
-    """C-contiguous float64 view/copy of a host array; device tensors pass through."""
-    if hasattr(a, "data_ptr") and not isinstance(a, np.ndarray):
-        import torch
-        if a.dtype != torch.float64 or not a.is_contiguous():
-            raise ValueError("device tensors must be contiguous float64")
-        return a
-    return np.ascontiguousarray(a, dtype=np.float64)

@@ -20,6 +20,7 @@ import logging
 
 import numpy as np
 
+from ._marshal import upload
 from .engine import get_context
 from .utility import ensure_cov_psd, running_window_rms  # noqa: F401
 
@@ -244,7 +245,7 @@ class NoiseCovarianceUpdate(object):
         import torch
         f = self.f
         dev = torch.device("cuda", f.ctx.device)
-        q = torch.as_tensor(np.ascontiguousarray(q_map, dtype=np.float64).reshape(1, -1)).to(dev)
+        q = upload(np.asarray(q_map, dtype=np.float64).reshape(1, -1), dev)
         res = f.synthetics(q, wavemap_index, residuals=True)[0]            # seismic.py:1332
         wm = f.problem.wavemaps[wavemap_index]
         if getattr(wm, "is_prewhitened", False):
@@ -266,7 +267,7 @@ class NoiseCovarianceUpdate(object):
         dataset on the device (``beatamd_unwhiten_traces``; the first version formed the 64 inverses for this)"""
         import torch
         out = res.clone().contiguous()
-        wo = w_old.to(dev) if torch.is_tensor(w_old) else torch.from_numpy(np.ascontiguousarray(w_old)).to(dev)
+        wo = w_old.to(dev) if torch.is_tensor(w_old) else upload(w_old, dev)
         self.f.ctx.unwhiten_traces(wo.contiguous(), out)
         return out
 
@@ -349,15 +350,14 @@ class VelocityModelCovarianceUpdate(object):
         """``data + pred_g`` of one dataset on the device; t: a device-resident data term to take instead of ``c``'s.  A data
         term that already lives on the device is the base as it is (``pred_g`` missing) or takes the uploaded ``pred_g``
         there: no host round trip.  Host arrays are summed on the host and uploaded."""
-        import torch
         if t is None and hasattr(c._terms["data"], "is_cuda"):
             t = c._terms["data"]
         if t is None:
-            return torch.from_numpy(np.ascontiguousarray(c._term("data") + c._term("pred_g"), dtype=np.float64)).to(dev)
+            return upload(c._term("data") + c._term("pred_g"), dev, np.float64)
         g = c._terms["pred_g"]
         if g is None:
             return t
-        return t + (g.to(dev) if hasattr(g, "is_cuda") else torch.from_numpy(np.ascontiguousarray(g, dtype=np.float64)).to(dev))
+        return t + (g.to(dev) if hasattr(g, "is_cuda") else upload(g, dev, np.float64))
 
     def _bases(self, dev, data_terms=None):
         """the datasets' ``data + pred_g`` on the device: kept from call to call per pair of arrays of the Covariance
@@ -514,7 +514,7 @@ class GeodeticNoiseCovarianceUpdate(object):
             f = self.f
             g = f.problem.geodetic
             dev = torch.device("cuda", f.ctx.device)
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)   # noqa: E731
+            up = lambda a: upload(a, dev, np.float64)   # noqa: E731
             ds, ncol, basis, offs, fixs, kind, earth = correction_tables(g.corrections, g.sizes, f.problem.layout, g.fixed,
                                                                          kinds=True)
             self._dev = dict(dev=dev, data=up(g.data),
@@ -603,8 +603,7 @@ class GeodeticNoiseCovarianceUpdate(object):
                 total, data = VelocityModelCovarianceUpdate._base_of(cov, Cd[i], dev), None
                 pv = cov._terms["pred_v"]
                 if pv is not None:
-                    total = total + (pv.to(dev) if hasattr(pv, "is_cuda") else
-                                     torch.from_numpy(np.ascontiguousarray(pv, dtype=np.float64)).to(dev))
+                    total = total + (pv.to(dev) if hasattr(pv, "is_cuda") else upload(pv, dev, np.float64))
                 W, lp, bad = f.ctx.chol_inverse_batch_flags(total.unsqueeze(0))
                 if int(bad[0]):
                     self.n_host_route += 1

@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 from . import utility
+from ._marshal import upload
 from .heart import HalfspaceEngine, concatenate_datasets
 
 km = 1000.0
@@ -292,7 +293,7 @@ def optimize_discretization(config, fault, datasets, varnames, crust_ind=0, engi
     ctx = _engine_ctx(engine)
     data_coords = _data_coords(datasets, event)
     dev = torch.device("cuda:%d" % ctx.device)
-    d_data = torch.from_numpy(np.ascontiguousarray(data_coords)).to(dev)
+    d_data = upload(data_coords, dev)
 
     # :1602-1627 the initial cut at twice the maximum patch size; the components share one geometry
     patch_widths, patch_lengths = config.get_patch_dimensions()
@@ -357,7 +358,7 @@ def optimize_discretization(config, fault, datasets, varnames, crust_ind=0, engi
 
         # :1773-1831 resolution of every component; L and R stay on the device
         centers = fault.get_event_relative_patch_centers(event)
-        d_centers = torch.from_numpy(np.ascontiguousarray(centers)).to(dev)
+        d_centers = upload(centers, dev)
         smoothing_op = ctx.smoothing_correlated(d_centers, "gaussian")
         resolution_matrices, R_diags = [], []
         for gfs_i, component in enumerate(varnames):
@@ -389,9 +390,7 @@ def optimize_discretization(config, fault, datasets, varnames, crust_ind=0, engi
         if ncandidates:
             # :1886-1929 on the device; the argsort and the alpha cut are O(P) and discrete: host
             d_rating, _ = ctx.division_rating(
-                torch.from_numpy(np.ascontiguousarray(widths)).to(dev),
-                torch.from_numpy(np.ascontiguousarray(lengths)).to(dev), d_centers,
-                torch.from_numpy(np.ascontiguousarray(bottom_depths_sf[sf_of])).to(dev), config.depth_penalty,
+                upload(widths, dev), upload(lengths, dev), d_centers, upload(bottom_depths_sf[sf_of], dev), config.depth_penalty,
                 d_data, torch.from_numpy(mean_R).to(dev))
             rating = d_rating.cpu().numpy()
             rating_idxs = np.array(rating.argsort()[::-1])

@@ -11,32 +11,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import INTERPOLATIONS, check, f64, ptr
-
-
-def _is_dev(a):
-    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) and a.is_cuda
-
-
-def _empty_like(ref, shape, dtype=np.float64):
-    if _is_dev(ref):
-        import torch
-        tdt = {np.float64: torch.float64, np.int32: torch.int32}[dtype]
-        return torch.empty(shape, dtype=tdt, device=ref.device)
-    return np.empty(shape, dtype=dtype)
-
-
-def _i32(a, ref=None):
-    if _is_dev(a):
-        import torch
-        if a.dtype != torch.int32 or not a.is_contiguous():
-            raise ValueError("device index tensors must be contiguous int32")
-        return a
-    return np.ascontiguousarray(a, dtype=np.int32)
-
-
-def _i64arr(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int64)
+from ._lib import INTERPOLATIONS, check, ptr
+from ._marshal import as_input, checked, is_canonical, is_dev, new, on_side, upload
 
 
 def _interp(interpolation):
@@ -71,13 +47,24 @@ class Context(object):
         """Device tensors are produced on torch's current stream: launch there too, so the
         kernels are ordered after their producers without an explicit synchronisation."""
         for a in arrays:
-            if _is_dev(a):
+            if is_dev(a):
                 import torch
                 s = torch.cuda.current_stream(self.device).cuda_stream
                 if s != getattr(self, "_stream", None):
                     check(self._lib.beatamd_ctx_set_stream(self._h, C.c_void_p(s)))
                     self._stream = s
                 return
+
+    def _q_out(self, Q, out, tail):
+        """the opening of every Q -> out call: launch on Q's stream; -> (Q as the library reads it, its chains, ``out`` or
+        -- for None -- a new (chains,) + tail array on Q's side).  tail may be a function of the converted Q; a caller's
+        ``out`` is handed on as it is"""
+        self._adopt_stream(Q)
+        Q = as_input(Q)
+        Cn = int(Q.shape[0])
+        if out is None:
+            out = new(Q, (Cn,) + (tail(Q) if callable(tail) else tail))
+        return Q, Cn, out
 
     def use_torch_stream(self):
         """Launch on torch's current stream of this device (so torch ops interleave in order)."""
@@ -117,15 +104,15 @@ class Context(object):
     # -- fast sweep
     def fast_sweep_batch(self, slowness, patch_size, h_strk, h_dip, num_strk, num_dip):
         self._adopt_stream(slowness)
-        slowness = f64(slowness)
+        slowness = as_input(slowness)
         n = int(num_strk) * int(num_dip)
         Cn = int(slowness.shape[0]) if slowness.ndim == 2 else 1
         if slowness.ndim == 1:
             slowness = slowness.reshape(1, -1)
         if slowness.shape[1] != n:
             raise ValueError("slowness has %d entries per chain, grid has %d" % (slowness.shape[1], n))
-        hs, hd = _i32(h_strk), _i32(h_dip)
-        out = _empty_like(slowness, (Cn, n))
+        hs, hd = as_input(h_strk, np.int32), as_input(h_dip, np.int32)
+        out = new(slowness, (Cn, n))
         check(self._lib.beatamd_fast_sweep_batch(self._h, ptr(slowness), float(patch_size), ptr(hs),
                                                  ptr(hd), int(num_strk), int(num_dip), Cn, ptr(out)))
         return out
@@ -144,8 +131,8 @@ class Context(object):
         check(self._lib.beatamd_seis_gflib_set_split_targets(self._h, lib_id, int(ntargets)))
 
     def seis_gflib_upload(self, lib_id, array, offset=0):
-        a = f64(array)
-        count = int(a.numel()) if _is_dev(a) else int(a.size)
+        a = as_input(array)
+        count = int(a.numel()) if is_dev(a) else int(a.size)
         check(self._lib.beatamd_seis_gflib_upload(self._h, lib_id, ptr(a), int(offset), count))
 
     def seis_gflib_adopt(self, lib_id, device_tensor):
@@ -172,19 +159,19 @@ class Context(object):
         self._adopt_stream(durations, starttimes, slips)
         T, P, D, S, N = dims
         it = _interp(interpolation)
-        du, st, sl = f64(durations), f64(starttimes), f64(slips)
+        du, st, sl = as_input(durations), as_input(starttimes), as_input(slips)
         Cn = int(du.shape[0])
         if tuple(du.shape) != (Cn, P) or tuple(sl.shape) != (Cn, P) or tuple(st.shape) != (Cn, T, P):
             raise ValueError("stack_all_batch: expected durations/slips (C,%d) and starttimes (C,%d,%d)"
                              % (P, T, P))
-        out = _empty_like(du, (Cn, T, N))
+        out = new(du, (Cn, T, N))
         check(self._lib.beatamd_seis_stack_all_batch(self._h, lib_id, Cn, ptr(du), ptr(st), ptr(sl), it,
                                                      ptr(out)))
         return out
 
     # -- geodetic GF library
     def geo_gflib_create(self, G):
-        G = f64(G)
+        G = as_input(G)
         lid = C.c_int32()
         check(self._lib.beatamd_geo_gflib_create(self._h, int(G.shape[0]), int(G.shape[1]), ptr(G),
                                                  C.byref(lid)))
@@ -194,12 +181,8 @@ class Context(object):
         check(self._lib.beatamd_geo_gflib_destroy(self._h, lib_id))
 
     def geo_stack_all_batch(self, lib_id, nobs, slips, out=None):
-        self._adopt_stream(slips)
-        sl = f64(slips)
-        Cn = int(sl.shape[0])
         acc = out is not None
-        if out is None:
-            out = _empty_like(sl, (Cn, nobs))
+        sl, Cn, out = self._q_out(slips, out, (nobs,))
         check(self._lib.beatamd_geo_stack_all_batch(self._h, lib_id, Cn, ptr(sl), int(acc), ptr(out)))
         return out
 
@@ -221,8 +204,8 @@ class Context(object):
         """slips (nvar * P,) at one point -> X (K, nobs): the synthetics of every variant (geodetic.py:1167-1176);
         numpy or torch-cuda in, same kind out"""
         self._adopt_stream(slips)
-        sl = f64(slips)
-        X = _empty_like(sl, (int(K), int(nobs)))
+        sl = as_input(slips)
+        X = new(sl, (int(K), int(nobs)))
         check(self._lib.beatamd_geo_ensemble_stack(self._h, ens_id, ptr(sl), ptr(X)))
         return X
 
@@ -232,21 +215,21 @@ class Context(object):
         entries are None (zeros) or contiguous float64 (n_i, n_i) arrays on either side; out: None (allocated on X's
         side) or such a list, written in place."""
         self._adopt_stream(X)
-        x = f64(X)
+        x = as_input(X)
         if x.ndim != 2:
             raise ValueError("pred_covariance_batch: X must be (K, Nobs)")
         K, nobs = int(x.shape[0]), int(x.shape[1])
-        n = _i64arr(sizes).ravel()
+        n = as_input(sizes, np.int64).ravel()
         nd = int(n.size)
         base = [None] * nd if base is None else list(base)
         if out is None:
-            out = [_empty_like(x, (int(k), int(k))) for k in n]
+            out = [new(x, (int(k), int(k))) for k in n]
         out = list(out)
         if len(base) != nd or len(out) != nd:
             raise ValueError("pred_covariance_batch: %d sizes, %d base and %d output matrices" % (nd, len(base), len(out)))
         for i, k in enumerate(n):
             for a, what in ((base[i], "base"), (out[i], "out")):
-                if a is not None and (tuple(a.shape) != (int(k), int(k)) or f64(a) is not a):
+                if a is not None and not is_canonical(a, np.float64, (int(k), int(k))):
                     raise ValueError("pred_covariance_batch: %s[%d] must be a contiguous float64 (%d, %d) array"
                                      % (what, i, k, k))
         if any(o is None for o in out):
@@ -258,14 +241,14 @@ class Context(object):
 
     # -- weights / likelihood
     def weights_create_scalar(self, w, slog_pdet, M):
-        w, sl = f64(w).ravel(), f64(slog_pdet).ravel()
+        w, sl = as_input(w).ravel(), as_input(slog_pdet).ravel()
         wid = C.c_int32()
         check(self._lib.beatamd_weights_create(self._h, _lib.W_SCALAR, int(w.size), int(M), ptr(w),
                                                ptr(sl), C.byref(wid)))
         return wid.value
 
     def weights_create_dense(self, W, slog_pdet):
-        W, sl = f64(W), f64(slog_pdet).ravel()
+        W, sl = as_input(W), as_input(slog_pdet).ravel()
         if W.ndim == 2:
             W = W.reshape((1,) + W.shape)
         nd, M, M2 = W.shape
@@ -279,9 +262,9 @@ class Context(object):
     def weights_update(self, wset_id, weights, slog_pdet):
         """new weights of an existing set; scalar (nd,) or dense (nd, M, M) -- kind and size are
         checked against the set by the library"""
-        W, sl = f64(weights), f64(slog_pdet).ravel()
+        W, sl = as_input(weights), as_input(slog_pdet).ravel()
         kind = _lib.W_DENSE if W.ndim >= 2 else _lib.W_SCALAR
-        count = int(W.numel()) if _is_dev(W) else int(W.size)
+        count = int(W.numel()) if is_dev(W) else int(W.size)
         check(self._lib.beatamd_weights_update(self._h, wset_id, kind, count, ptr(W), ptr(sl)))
 
     def weights_band(self, wset_id):
@@ -303,14 +286,14 @@ class Context(object):
 
     def mvn_chol_logp_batch(self, wset_id, residuals, hp):
         self._adopt_stream(residuals, hp)
-        r, h = f64(residuals), f64(hp)
+        r, h = as_input(residuals), as_input(hp)
         Cn, nd = int(r.shape[0]), int(r.shape[1])
-        out = _empty_like(r, (Cn, nd))
+        out = new(r, (Cn, nd))
         check(self._lib.beatamd_mvn_chol_logp_batch(self._h, wset_id, Cn, ptr(r), ptr(h), ptr(out)))
         return out
 
     def laplacian_create(self, L, logdet):
-        L = f64(L)
+        L = as_input(L)
         lid = C.c_int32()
         check(self._lib.beatamd_laplacian_create(self._h, int(L.shape[0]), ptr(L), float(logdet),
                                                  C.byref(lid)))
@@ -321,29 +304,29 @@ class Context(object):
 
     def laplacian_logp_batch(self, lap_id, slips, hp):
         self._adopt_stream(slips, hp)
-        s, h = f64(slips), f64(hp)
+        s, h = as_input(slips), as_input(hp)
         Cn, nvar = int(s.shape[0]), int(s.shape[1])
-        out = _empty_like(s, (Cn,))
+        out = new(s, (Cn,))
         check(self._lib.beatamd_laplacian_logp_batch(self._h, lap_id, Cn, nvar, ptr(s), ptr(h), ptr(out)))
         return out
 
     # -- noise covariance estimation
     def autocovariance_batch(self, data):
-        d = f64(data)
+        d = as_input(data)
         self._adopt_stream(d)
         # device traces: the kernel takes each row's mean in numpy's summation order (torch.mean sums in another
         # order and moved the result in the last bits); host traces: numpy's own mean
-        mean = None if _is_dev(d) else np.ascontiguousarray(d.mean(axis=1))
-        out = _empty_like(d, tuple(d.shape))
+        mean = None if is_dev(d) else np.ascontiguousarray(d.mean(axis=1))
+        out = new(d, tuple(d.shape))
         check(self._lib.beatamd_autocovariance_batch(self._h, int(d.shape[0]), int(d.shape[1]), ptr(d),
                                                      ptr(mean), ptr(out)))
         return out
 
     def scaled_toeplitz_batch(self, coeffs, stds):
-        c, s = f64(coeffs), f64(stds)
+        c, s = as_input(coeffs), as_input(stds)
         self._adopt_stream(c, s)
         nd, n = int(c.shape[0]), int(c.shape[1])
-        out = _empty_like(c, (nd, n, n))
+        out = new(c, (nd, n, n))
         check(self._lib.beatamd_scaled_toeplitz_batch(self._h, nd, n, ptr(c), ptr(s), ptr(out)))
         return out
 
@@ -352,16 +335,16 @@ class Context(object):
         in one call: coords (Ntot, 2) east / north, data (Ntot,), both concatenated over datasets of ``sizes`` points ->
         (radius (nd,), counts (Ntot,) int32, stds (Ntot,)) in the one order include/beat_amd.h states
         (tests/noise2d_ref.py restates it bit for bit).  numpy in -> numpy out, torch-cuda in -> tensors on the same device."""
-        c, d = f64(coords), f64(data)
+        c, d = as_input(coords), as_input(data)
         self._adopt_stream(c, d)
-        n = _i64arr(sizes).ravel()
+        n = as_input(sizes, np.int64).ravel()
         nd, ntot = int(n.size), int(n.sum()) if n.size else 0
         if tuple(c.shape) != (ntot, 2) or tuple(d.shape) != (ntot,):
             raise ValueError("ball_rms_batch: coords %s and data %s for %d points in all: expected (%d, 2) and (%d,)"
                              % (tuple(c.shape), tuple(d.shape), ntot, ntot, ntot))
-        if _is_dev(c) != _is_dev(d):
+        if is_dev(c) != is_dev(d):
             raise ValueError("ball_rms_batch: coords and data must live on the same side")
-        radius, counts, stds = _empty_like(c, (nd,)), _empty_like(c, (ntot,), np.int32), _empty_like(c, (ntot,))
+        radius, counts, stds = new(c, (nd,)), new(c, (ntot,), np.int32), new(c, (ntot,))
         check(self._lib.beatamd_ball_rms_batch(self._h, nd, ptr(n), ptr(c), ptr(d), float(max_dist_perc), ptr(radius),
                                                ptr(counts), ptr(stds)))
         return radius, counts, stds
@@ -381,8 +364,8 @@ class Context(object):
                               interpolation="nearest_neighbor"):
         libs = np.ascontiguousarray(lib_ids, dtype=np.int32)
         data = np.ascontiguousarray(data, dtype=np.float64)
-        hp = _i64arr(hp_off)
-        sh = _i64arr(shift_off)
+        hp = as_input(hp_off, np.int64)
+        sh = as_input(shift_off, np.int64)
         check(self._lib.beatamd_ffi_model_add_wavemap(self._h, model_id, ptr(libs), ptr(data), wset_id,
                                                       ptr(hp), ptr(sh), _interp(interpolation)))
 
@@ -391,8 +374,8 @@ class Context(object):
         """a wavemap in the spectrum domain: data_spec (T, hi - lo) observed amplitude spectra, the weight set of that size"""
         libs = np.ascontiguousarray(lib_ids, dtype=np.int32)
         data_spec = np.ascontiguousarray(data_spec, dtype=np.float64)
-        hp = _i64arr(hp_off)
-        sh = _i64arr(shift_off)
+        hp = as_input(hp_off, np.int64)
+        sh = as_input(shift_off, np.int64)
         lo, hi = valid_spectrum_indices
         if data_spec.ndim != 2 or data_spec.shape[1] != int(hi) - int(lo):
             raise ValueError("spectrum domain: data_spec must be (T, %d), got %s" % (int(hi) - int(lo), data_spec.shape))
@@ -403,7 +386,7 @@ class Context(object):
         """X (R, N) -> (R, hi - lo) = abs(rfft(X[r], ntrans))[lo:hi] on the device (csrc/spectrum.hip), or with data_spec
         (T, hi - lo) the residual data_spec[r mod T] - that.  numpy in -> numpy out, torch-cuda in -> tensor."""
         self._adopt_stream(X)
-        X = f64(X)
+        X = as_input(X)
         if X.ndim != 2:
             raise ValueError("amp_spectrum: X must be (R, N), got %s" % (tuple(X.shape),))
         R, N = int(X.shape[0]), int(X.shape[1])
@@ -412,9 +395,9 @@ class Context(object):
         if data_spec is not None:
             if not hasattr(data_spec, "shape"):
                 data_spec = np.asarray(data_spec, dtype=np.float64)
-            data_spec = self._arg_on_side(data_spec, X, np.float64, (int(data_spec.shape[0]), hi - lo), "data_spec")
+            data_spec = on_side(data_spec, X, np.float64, (int(data_spec.shape[0]), hi - lo), "data_spec")
             T = int(data_spec.shape[0])
-        out = self._out_on_side(X, (R, max(hi - lo, 0)), np.float64, out, "out")
+        out = checked(out, X, (R, max(hi - lo, 0)), np.float64, "out")
         check(self._lib.beatamd_amp_spectrum_batch(self._h, R, N, int(ntrans), lo, hi, ptr(X), ptr(data_spec), T, ptr(out)))
         return out
 
@@ -422,9 +405,9 @@ class Context(object):
         libs = np.ascontiguousarray(geo_lib_ids, dtype=np.int32)
         data = np.ascontiguousarray(data, dtype=np.float64)
         odws = np.ascontiguousarray(odws, dtype=np.float64)
-        sizes = _i64arr(sizes)
+        sizes = as_input(sizes, np.int64)
         ws = np.ascontiguousarray(wset_ids, dtype=np.int32)
-        hp = _i64arr(hp_off)
+        hp = as_input(hp_off, np.int64)
         check(self._lib.beatamd_ffi_model_add_geodetic(self._h, model_id, ptr(libs), ptr(data), ptr(odws),
                                                        int(sizes.size), ptr(sizes), ptr(ws), ptr(hp)))
 
@@ -438,9 +421,9 @@ class Context(object):
         los = np.ascontiguousarray(los, dtype=np.float64)
         data = np.ascontiguousarray(data, dtype=np.float64)
         odws = np.ascontiguousarray(odws, dtype=np.float64)
-        sizes = _i64arr(sizes)
+        sizes = as_input(sizes, np.int64)
         ws = np.ascontiguousarray(wset_ids, dtype=np.int32)
-        hp = _i64arr(hp_off)
+        hp = as_input(hp_off, np.int64)
         check(self._lib.beatamd_ffi_model_add_geodetic_geometry(
             self._h, model_id, int(kinds.size), ptr(kinds), ptr(po), ptr(pf), int(east.size), ptr(east),
             ptr(north), ptr(los), float(nu), ptr(data), ptr(odws), int(sizes.size), ptr(sizes), ptr(ws),
@@ -513,21 +496,13 @@ class Context(object):
         check(self._lib.beatamd_ffi_model_destroy(self._h, model_id))
 
     def ffi_logp_batch(self, model_id, Q, nllk, out=None):
-        self._adopt_stream(Q)
-        Q = f64(Q)
-        Cn = int(Q.shape[0])
-        if out is None:
-            out = _empty_like(Q, (Cn, nllk))
+        Q, Cn, out = self._q_out(Q, out, (nllk,))
         check(self._lib.beatamd_ffi_logp_batch(self._h, model_id, Cn, ptr(Q), ptr(out)))
         return out
 
     def ffi_synthetics_batch(self, model_id, wavemap_index, Q, T, N, residuals=False, out=None):
         """synthetics (or data - synthetics) [C, T, N] of one wavemap at the points Q [C, nparams]"""
-        self._adopt_stream(Q)
-        Qc = f64(Q)
-        Cn = int(Qc.shape[0])
-        if out is None:
-            out = _empty_like(Qc, (Cn, int(T), int(N)))
+        Qc, Cn, out = self._q_out(Q, out, (int(T), int(N)))
         check(self._lib.beatamd_ffi_synthetics_batch(self._h, model_id, int(wavemap_index), Cn, ptr(Qc),
                                                      int(bool(residuals)), ptr(out)))
         return out
@@ -535,60 +510,21 @@ class Context(object):
     def ffi_start_times_batch(self, model_id, Q, npatches, out=None, chain_bad=None):
         """rupture onset times [C, npatches] of the model at the points Q [C, nparams]; chain_bad (int32 [C], optional,
         filled also when the call raises): chains whose hypocentre lies outside the patch grid"""
-        self._adopt_stream(Q)
-        Qc = f64(Q)
-        Cn = int(Qc.shape[0])
-        if out is None:
-            out = _empty_like(Qc, (Cn, int(npatches)))
+        Qc, Cn, out = self._q_out(Q, out, (int(npatches),))
         check(self._lib.beatamd_ffi_start_times_batch(self._h, model_id, Cn, ptr(Qc), ptr(out), ptr(chain_bad)))
         return out
 
     # -- moment, magnitude and moment-rate functions of a batch of draws (csrc/momentrate.hip)
-    def _arg_on_side(self, a, ref, dtype, shape, what):
-        """the optional array argument ``a`` as a contiguous array of ``dtype`` and ``shape`` on ref's side"""
-        if a is None:
-            return None
-        if _is_dev(ref):
-            import torch
-            tdt = {np.float64: torch.float64, np.int32: torch.int32, np.int64: torch.int64}[dtype]
-            if not _is_dev(a):
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(ref.device)
-            if a.dtype != tdt or not a.is_contiguous():
-                raise ValueError("%s: device tensors must be contiguous %s" % (what, np.dtype(dtype).name))
-        else:
-            if _is_dev(a):
-                a = a.cpu().numpy()
-            a = np.ascontiguousarray(a, dtype=dtype)
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError("%s must be %s, got %s" % (what, tuple(shape), tuple(a.shape)))
-        return a
-
-    @staticmethod
-    def _out_on_side(ref, shape, dtype, out, what):
-        if out is None:
-            if _is_dev(ref):
-                import torch
-                return torch.empty(shape, dtype={np.float64: torch.float64, np.int64: torch.int64}[dtype], device=ref.device)
-            return np.empty(shape, dtype=dtype)
-        ok = tuple(out.shape) == tuple(shape) and _is_dev(out) == _is_dev(ref)
-        if ok and _is_dev(out):
-            ok = out.is_contiguous() and str(out.dtype).endswith(np.dtype(dtype).name)
-        elif ok:
-            ok = out.flags.c_contiguous and out.dtype == dtype
-        if not ok:
-            raise ValueError("%s must be a contiguous %s %s array on Q's side" % (what, np.dtype(dtype).name, tuple(shape)))
-        return out
-
     def ffi_magnitudes_batch(self, model_id, Q, moment_per_slip, npatches, comp_off=None):
         """(M0, Mw), each (C,): total moment ``sum_p k_p sqrt(sum_comp s^2)`` in patch order and its moment magnitude
         (ffi/fault.py:284-359) at the points Q (C, nparams); moment_per_slip (npatches,): the moment of a patch at unit
         slip; comp_off: offsets in q of the slip variables (None: the layout's own)"""
         self._adopt_stream(Q)
-        Qc = f64(Q)
+        Qc = as_input(Q)
         Cn = int(Qc.shape[0])
-        k = self._arg_on_side(moment_per_slip, Qc, np.float64, (int(npatches),), "moment_per_slip")
-        off = _i64arr(comp_off)
-        M0, Mw = _empty_like(Qc, (Cn,)), _empty_like(Qc, (Cn,))
+        k = on_side(moment_per_slip, Qc, np.float64, (int(npatches),), "moment_per_slip")
+        off = as_input(comp_off, np.int64)
+        M0, Mw = new(Qc, (Cn,)), new(Qc, (Cn,))
         check(self._lib.beatamd_ffi_magnitudes_batch(self._h, model_id, Cn, ptr(Qc), ptr(k), ptr(off),
                                                      0 if off is None else int(off.size), ptr(M0), ptr(Mw)))
         return M0, Mw
@@ -600,11 +536,11 @@ class Context(object):
         chain_bad (C,) int32: onsets the caller holds (None: the model's sweep).  A flagged draw gets count 0 and the call
         raises ValueError after filling ``out``"""
         self._adopt_stream(Q)
-        Qc = f64(Q)
+        Qc = as_input(Q)
         Cn = int(Qc.shape[0])
-        st = self._arg_on_side(start_times, Qc, np.float64, (Cn, int(npatches)), "start_times")
-        bad = self._arg_on_side(chain_bad, Qc, np.int32, (Cn,), "chain_bad")
-        out = self._out_on_side(Qc, (Cn, int(nsubfaults) + 1, 2), np.int64, out, "spans")
+        st = on_side(start_times, Qc, np.float64, (Cn, int(npatches)), "start_times")
+        bad = on_side(chain_bad, Qc, np.int32, (Cn,), "chain_bad")
+        out = checked(out, Qc, (Cn, int(nsubfaults) + 1, 2), np.int64, "spans")
         check(self._lib.beatamd_ffi_moment_rate_spans_batch(self._h, model_id, Cn, ptr(Qc), ptr(st), ptr(bad), float(deltat),
                                                             ptr(out)))
         return out
@@ -615,15 +551,15 @@ class Context(object):
         in the last row, their sum (ffi/fault.py:361-474).  A draw that does not fit the grid, or is flagged, gets NaN
         rows and the call raises ValueError after filling ``out`` (and ``spans``, when given)"""
         self._adopt_stream(Q)
-        Qc = f64(Q)
+        Qc = as_input(Q)
         Cn = int(Qc.shape[0])
-        k = self._arg_on_side(moment_per_slip, Qc, np.float64, (int(npatches),), "moment_per_slip")
-        off = _i64arr(comp_off)
-        st = self._arg_on_side(start_times, Qc, np.float64, (Cn, int(npatches)), "start_times")
-        bad = self._arg_on_side(chain_bad, Qc, np.int32, (Cn,), "chain_bad")
-        out = self._out_on_side(Qc, (Cn, int(nsubfaults) + 1, int(NT)), np.float64, out, "rates")
+        k = on_side(moment_per_slip, Qc, np.float64, (int(npatches),), "moment_per_slip")
+        off = as_input(comp_off, np.int64)
+        st = on_side(start_times, Qc, np.float64, (Cn, int(npatches)), "start_times")
+        bad = on_side(chain_bad, Qc, np.int32, (Cn,), "chain_bad")
+        out = checked(out, Qc, (Cn, int(nsubfaults) + 1, int(NT)), np.float64, "rates")
         if spans is not None:
-            spans = self._out_on_side(Qc, (Cn, int(nsubfaults) + 1, 2), np.int64, spans, "spans")
+            spans = checked(spans, Qc, (Cn, int(nsubfaults) + 1, 2), np.int64, "spans")
         check(self._lib.beatamd_ffi_moment_rates_batch(self._h, model_id, Cn, ptr(Qc), ptr(k), ptr(off),
                                                        0 if off is None else int(off.size), ptr(st), ptr(bad), float(deltat),
                                                        int(stf), int(kbase), int(NT), ptr(out), ptr(spans)))
@@ -635,18 +571,18 @@ class Context(object):
         self._adopt_stream(Q0, delta)
         Cn = int(Q0.shape[0])
         if accepted is None:
-            accepted = _empty_like(Q0, (Cn,), np.int32)
+            accepted = new(Q0, (Cn,), np.int32)
         for a in (Q0, L0):
-            if isinstance(a, np.ndarray) and not (a.flags.c_contiguous and a.dtype == np.float64):
+            if isinstance(a, np.ndarray) and not is_canonical(a):
                 raise ValueError("Q0 / L0 must be C-contiguous float64 (updated in place)")
         # converted arrays are bound to locals: a temporary would be freed before the call reads it
-        de, sc, lo, up, lu = f64(delta), f64(scaling), f64(lower), f64(upper), f64(log_u)
+        de, sc, lo, up, lu = as_input(delta), as_input(scaling), as_input(lower), as_input(upper), as_input(log_u)
         if np.ndim(beta) == 0 and not hasattr(beta, "data_ptr"):
             check(self._lib.beatamd_ffi_astep_batch(self._h, model_id, Cn, ptr(Q0), ptr(L0), ptr(de),
                                                     ptr(sc), ptr(lo), ptr(up), ptr(lu), float(beta),
                                                     ptr(accepted)))
         else:  # one beta per chain (parallel tempering replicas)
-            be = f64(beta)
+            be = as_input(beta)
             check(self._lib.beatamd_ffi_astep_batch_betas(self._h, model_id, Cn, ptr(Q0), ptr(L0),
                                                           ptr(de), ptr(sc), ptr(lo), ptr(up), ptr(lu),
                                                           ptr(be), ptr(accepted)))
@@ -661,10 +597,10 @@ class Context(object):
         self._adopt_stream(Q0, L0)
         Cn = int(Q0.shape[0])
         kind = -1 if kind is None else int(kind)
-        fa, sc, lo, up = f64(factor), f64(scaling), f64(lower), f64(upper)
+        fa, sc, lo, up = as_input(factor), as_input(scaling), as_input(lower), as_input(upper)
         K = int(fa.shape[0]) if kind < 0 else 0
         scalar = np.ndim(beta) == 0 and not hasattr(beta, "data_ptr")
-        be = None if scalar else f64(beta)
+        be = None if scalar else as_input(beta)
         check(self._lib.beatamd_ffi_mstep_batch(
             self._h, model_id, Cn, ptr(Q0), ptr(L0), ptr(fa), K, kind, int(df), int(seed) & (2 ** 64 - 1),
             int(step) & 0xffffffff, int(first_chain), ptr(sc), ptr(lo), ptr(up), float(beta) if scalar else 1.0,
@@ -678,12 +614,12 @@ class Context(object):
         ``factors`` [G, K, nparams], chain c draws with factor c // (C // G)"""
         self._adopt_stream(Q0, L0)
         Cn = int(Q0.shape[0])
-        fa, sc, lo, up = f64(factors), f64(scaling), f64(lower), f64(upper)
+        fa, sc, lo, up = as_input(factors), as_input(scaling), as_input(lower), as_input(upper)
         if fa.ndim != 3:
             raise ValueError("ffi_mstep_batch_grouped: factors must be (groups, K, nparams)")
         G, K = int(fa.shape[0]), int(fa.shape[1])
         scalar = np.ndim(beta) == 0 and not hasattr(beta, "data_ptr")
-        be = None if scalar else f64(beta)
+        be = None if scalar else as_input(beta)
         check(self._lib.beatamd_ffi_mstep_batch_grouped(
             self._h, model_id, Cn, G, ptr(Q0), ptr(L0), ptr(fa), K, int(df), int(seed) & (2 ** 64 - 1),
             int(step) & 0xffffffff, int(first_chain), ptr(sc), ptr(lo), ptr(up), float(beta) if scalar else 1.0,
@@ -734,11 +670,9 @@ class Context(object):
         """how a batch is cut into its chain groups (scheduling only): key0 / key1 (C,) per-chain keys -- the hypocentre
         (strike, dip) in the fused model path -> uint32 array [ngroups, chains_per_group] of chain ids, 0xffffffff behind
         the last chain (recursive bisection along the key of the wider extent, k_gc_cut)"""
-        import torch
-        dev = "cuda:%d" % self.device
-        k0, k1 = [k if _is_dev(k) else torch.as_tensor(np.ascontiguousarray(k, dtype=np.float64)).to(dev) for k in (key0, key1)]
+        k0, k1 = [k if is_dev(k) else upload(k, "cuda:%d" % self.device, np.float64) for k in (key0, key1)]
         self._adopt_stream(k0, k1)
-        k0, k1 = f64(k0), f64(k1)
+        k0, k1 = as_input(k0), as_input(k1)
         Cn = int(k0.numel())
         ng = (Cn + chains_per_group - 1) // chains_per_group
         out = np.empty(ng * chains_per_group, dtype=np.uint32)
@@ -751,9 +685,9 @@ class Context(object):
         """smc.py:133-165 -> (beta_new, weights); likelihoods: (C,) array or a strided view
         described by (tensor, stride, n)"""
         self._adopt_stream(likelihoods)
-        lk = f64(likelihoods)
-        Cn = int(n if n is not None else (lk.numel() if _is_dev(lk) else lk.size))
-        w = _empty_like(lk, (Cn,))
+        lk = as_input(likelihoods)
+        Cn = int(n if n is not None else (lk.numel() if is_dev(lk) else lk.size))
+        w = new(lk, (Cn,))
         b = C.c_double()
         check(self._lib.beatamd_smc_calc_beta(self._h, Cn, ptr(lk), int(stride), float(beta),
                                               float(coef_variation), C.byref(b), ptr(w)))
@@ -761,26 +695,26 @@ class Context(object):
 
     def smc_stage_weights(self, likelihoods, dbeta, stride=1, n=None):
         self._adopt_stream(likelihoods)
-        lk = f64(likelihoods)
-        Cn = int(n if n is not None else (lk.numel() if _is_dev(lk) else lk.size))
-        w = _empty_like(lk, (Cn,))
+        lk = as_input(likelihoods)
+        Cn = int(n if n is not None else (lk.numel() if is_dev(lk) else lk.size))
+        w = new(lk, (Cn,))
         check(self._lib.beatamd_smc_stage_weights(self._h, Cn, ptr(lk), int(stride), float(dbeta), ptr(w)))
         return w
 
     def smc_resample(self, weights, aux):
         """smc.py:290-324 -> resampling indexes (int32)"""
         self._adopt_stream(weights)
-        w = f64(weights)
-        Cn = int(w.numel()) if _is_dev(w) else int(w.size)
-        idx = _empty_like(w, (Cn,), np.int32)
+        w = as_input(weights)
+        Cn = int(w.numel()) if is_dev(w) else int(w.size)
+        idx = new(w, (Cn,), np.int32)
         check(self._lib.beatamd_smc_resample(self._h, Cn, ptr(w), float(aux), ptr(idx)))
         return idx
 
     def smc_population_factor(self, population, weights):
         self._adopt_stream(population, weights)
-        X, w = f64(population), f64(weights)
+        X, w = as_input(population), as_input(weights)
         Cn, npar = int(X.shape[0]), int(X.shape[1])
-        F = _empty_like(X, (Cn, npar))
+        F = new(X, (Cn, npar))
         check(self._lib.beatamd_smc_population_factor(self._h, Cn, npar, ptr(X), ptr(w), ptr(F)))
         return F
 
@@ -788,12 +722,12 @@ class Context(object):
                       want_log_u=True):
         """delta (n_chains, nparams) = z . factor with z from Philox4x32-10; -> (delta, log_u)"""
         self._adopt_stream(factor)
-        F = f64(factor)
+        F = as_input(factor)
         K, npar = int(F.shape[0]), int(F.shape[1])
         if delta is None:
-            delta = _empty_like(F, (int(n_chains), npar))
+            delta = new(F, (int(n_chains), npar))
         if log_u is None and want_log_u:
-            log_u = _empty_like(F, (int(n_chains),))
+            log_u = new(F, (int(n_chains),))
         check(self._lib.beatamd_proposal_draw(self._h, int(n_chains), K, npar, ptr(F), int(seed) & (2 ** 64 - 1),
                                               int(step) & 0xffffffff, int(first_chain), int(df), ptr(delta),
                                               ptr(log_u)))
@@ -804,14 +738,14 @@ class Context(object):
         """``proposal_draw`` with one factor per group of chains: factors (G, K, nparams), chain c of the call draws with
         factor c // (n_chains // G) (beatamd_proposal_draw_grouped); -> (delta, log_u)"""
         self._adopt_stream(factors)
-        F = f64(factors)
+        F = as_input(factors)
         if F.ndim != 3:
             raise ValueError("proposal_draw_grouped: factors must be (groups, K, nparams)")
         G, K, npar = int(F.shape[0]), int(F.shape[1]), int(F.shape[2])
         if delta is None:
-            delta = _empty_like(F, (int(n_chains), npar))
+            delta = new(F, (int(n_chains), npar))
         if log_u is None and want_log_u:
-            log_u = _empty_like(F, (int(n_chains),))
+            log_u = new(F, (int(n_chains),))
         check(self._lib.beatamd_proposal_draw_grouped(self._h, int(n_chains), G, K, npar, ptr(F), int(seed) & (2 ** 64 - 1),
                                                       int(step) & 0xffffffff, int(first_chain), int(df), ptr(delta),
                                                       ptr(log_u)))
@@ -830,10 +764,10 @@ class Context(object):
         S = self._group_state(state, nparams)
         G, R, Qc = int(S.shape[0]), 0, None
         if ref is not None:
-            Qc = f64(Q)
-            if isinstance(ref, np.ndarray) and not (ref.flags.c_contiguous and ref.dtype == np.float64):
+            Qc = as_input(Q)
+            if isinstance(ref, np.ndarray) and not is_canonical(ref):
                 raise ValueError("group_moments_reset: ref must be C-contiguous float64 (written in place)")
-            if int(Qc.shape[0]) % G or int(Qc.shape[1]) != int(nparams) or tuple(f64(ref).shape) != (G, int(nparams)):
+            if int(Qc.shape[0]) % G or int(Qc.shape[1]) != int(nparams) or tuple(as_input(ref).shape) != (G, int(nparams)):
                 raise ValueError("group_moments_reset: Q (G * R, nparams), ref (G, nparams) for the G groups of the state")
             R = int(Qc.shape[0]) // G
         check(self._lib.beatamd_group_moments_reset(self._h, G, int(nparams), ptr(S), R, ptr(Qc),
@@ -841,8 +775,8 @@ class Context(object):
         return state
 
     def _group_state(self, state, nparams):
-        ok = state.flags.c_contiguous and state.dtype == np.float64 if isinstance(state, np.ndarray) else True
-        S = f64(state)
+        ok = is_canonical(state) if isinstance(state, np.ndarray) else True
+        S = as_input(state)
         if not ok or S.ndim != 2 or int(S.shape[1]) != self.group_moments_stride(nparams):
             raise ValueError("group moments: state must be C-contiguous float64 (groups, 8 + nparams + nparams^2)")
         return S
@@ -851,8 +785,8 @@ class Context(object):
         """add the rows of Q (G * R, n) -- R consecutive rows per group -- with weights exp(like - running maximum) to
         state, in place; like: (G * R,) array, or a strided view (see ``sampler.ops._Base``) with like_stride; ref (G, n)"""
         self._adopt_stream(state, Q)
-        Qc, rf = f64(Q), f64(ref)
-        lk = f64(like)
+        Qc, rf = as_input(Q), as_input(ref)
+        lk = as_input(like)
         npar = int(Qc.shape[1])
         S = self._group_state(state, npar)
         G = int(S.shape[0])
@@ -869,13 +803,13 @@ class Context(object):
         self._adopt_stream(state, factor)
         S = self._group_state(state, nparams)
         G, n = int(S.shape[0]), int(nparams)
-        if isinstance(factor, np.ndarray) and not (factor.flags.c_contiguous and factor.dtype == np.float64):
+        if isinstance(factor, np.ndarray) and not is_canonical(factor):
             raise ValueError("group_moments_factor: factor must be C-contiguous float64 (written in place)")
-        F = f64(factor)
+        F = as_input(factor)
         if tuple(F.shape) != (G, n, n):
             raise ValueError("group_moments_factor: factor must be (groups, nparams, nparams)")
-        cov = _empty_like(S, (G, n, n)) if want_cov else None
-        flags = _empty_like(S, (G,), np.int32)
+        cov = new(S, (G, n, n)) if want_cov else None
+        flags = new(S, (G,), np.int32)
         check(self._lib.beatamd_group_moments_factor(self._h, G, n, ptr(S), ptr(F), ptr(cov), ptr(flags)))
         return factor, cov, flags
 
@@ -884,12 +818,12 @@ class Context(object):
         """delta (n_chains, nparams): independent Normal (0) / Cauchy (1) / Laplace (2) draws per
         component times scale[j] (beat/sampler/base.py:129-160); -> (delta, log_u)"""
         self._adopt_stream(scale)
-        sc = f64(scale)
+        sc = as_input(scale)
         npar = int(sc.shape[0])
         if delta is None:
-            delta = _empty_like(sc, (int(n_chains), npar))
+            delta = new(sc, (int(n_chains), npar))
         if log_u is None and want_log_u:
-            log_u = _empty_like(sc, (int(n_chains),))
+            log_u = new(sc, (int(n_chains),))
         check(self._lib.beatamd_proposal_draw_univariate(self._h, int(n_chains), npar, int(kind), ptr(sc),
                                                          int(seed) & (2 ** 64 - 1), int(step) & 0xffffffff,
                                                          int(first_chain), ptr(delta), ptr(log_u)))
@@ -897,11 +831,11 @@ class Context(object):
 
     def gather_rows(self, src, indexes, out=None):
         self._adopt_stream(src, indexes)
-        S = f64(src)
-        idx = _i32(indexes)
-        nout = int(idx.numel()) if _is_dev(idx) else int(idx.size)
+        S = as_input(src)
+        idx = as_input(indexes, np.int32)
+        nout = int(idx.numel()) if is_dev(idx) else int(idx.size)
         if out is None:
-            out = _empty_like(S, (nout, int(S.shape[1])))
+            out = new(S, (nout, int(S.shape[1])))
         check(self._lib.beatamd_gather_rows(self._h, nout, int(S.shape[1]), ptr(S), int(S.shape[0]),
                                             ptr(idx), ptr(out)))
         return out
@@ -931,16 +865,17 @@ class Context(object):
     def metropolis_propose(self, Q0, delta, scaling, lower, upper, Qprop, inbounds):
         """metropolis.py:313-343 for all chains: Qprop = Q0 + delta * scaling inside the prior box, else Q0; inbounds int32 [C]"""
         self._adopt_stream(Q0, Qprop)
-        check(self._lib.beatamd_metropolis_propose(self._h, int(Q0.shape[0]), int(Q0.shape[1]), ptr(f64(Q0)), ptr(f64(delta)),
-                                                   ptr(f64(scaling)), ptr(f64(lower)), ptr(f64(upper)), ptr(Qprop), ptr(inbounds)))
+        check(self._lib.beatamd_metropolis_propose(self._h, int(Q0.shape[0]), int(Q0.shape[1]), ptr(as_input(Q0)),
+                                                   ptr(as_input(delta)), ptr(as_input(scaling)), ptr(as_input(lower)),
+                                                   ptr(as_input(upper)), ptr(Qprop), ptr(inbounds)))
 
     def metropolis_accept(self, Q0, L0, Qprop, Lprop, inbounds, log_u, beta, accepted):
         """metropolis.py:344-385 for all chains, in place on Q0 / L0; beta: float or a device tensor [C]"""
         self._adopt_stream(Q0, L0)
         per_chain = hasattr(beta, "data_ptr")
         check(self._lib.beatamd_metropolis_accept(self._h, int(Q0.shape[0]), int(Q0.shape[1]), int(L0.shape[1]), ptr(Q0), ptr(L0),
-                                                  ptr(Qprop), ptr(Lprop), ptr(inbounds), ptr(f64(log_u)),
-                                                  1.0 if per_chain else float(beta), ptr(f64(beta)) if per_chain else None,
+                                                  ptr(Qprop), ptr(Lprop), ptr(inbounds), ptr(as_input(log_u)),
+                                                  1.0 if per_chain else float(beta), ptr(as_input(beta)) if per_chain else None,
                                                   ptr(accepted)))
 
     # -- hyper-parameter estimation (csrc/hyper.hip)
@@ -952,9 +887,9 @@ class Context(object):
         """normal equations of the chains' linear slip problems at the points Q [C, nparams] -> N [C, P, P], b [C, P];
         chain_bad (int32 [C], optional, filled also when the call raises IndexError): chains outside the library grid"""
         self._adopt_stream(Q)
-        Qc = f64(Q)
+        Qc = as_input(Q)
         Cn, P = int(Qc.shape[0]), int(npatches)
-        N, b = _empty_like(Qc, (Cn, P, P)), _empty_like(Qc, (Cn, P))
+        N, b = new(Qc, (Cn, P, P)), new(Qc, (Cn, P))
         check(self._lib.beatamd_ffi_lsq_normal_batch(self._h, model_id, Cn, ptr(Qc), ptr(N), ptr(b), ptr(chain_bad)))
         return N, b
 
@@ -962,22 +897,19 @@ class Context(object):
         """min |A x - d| s.t. x >= 0 from N = A^T A [C, n, n] and b = A^T d [C, n] -> x [C, n], iters [C], status [C]
         (0 ok, 1 iteration cap, 2 non-finite input / passive block not positive definite)"""
         self._adopt_stream(N, b)
-        N, b = f64(N), f64(b)
+        N, b = as_input(N), as_input(b)
         Cn, n = int(b.shape[0]), int(b.shape[1])
         if tuple(N.shape) != (Cn, n, n):
             raise ValueError("nnls_batch: N %s does not match b %s" % (tuple(N.shape), tuple(b.shape)))
-        x, it, st = _empty_like(b, (Cn, n)), _empty_like(b, (Cn,), np.int32), _empty_like(b, (Cn,), np.int32)
+        x, it, st = new(b, (Cn, n)), new(b, (Cn,), np.int32), new(b, (Cn,), np.int32)
         check(self._lib.beatamd_nnls_batch(self._h, Cn, n, ptr(N), ptr(b), ptr(x), ptr(it), ptr(st)))
         return x, it, st
 
     def ffi_lsq_solution_batch(self, model_id, Q):
         """Q [C, nparams] -> (Q with the inverted slip variable replaced by its non-negative least-squares solution and
         the perpendicular one by zeros, iters [C], status [C])"""
-        self._adopt_stream(Q)
-        Qc = f64(Q)
-        Cn = int(Qc.shape[0])
-        out = _empty_like(Qc, tuple(Qc.shape))
-        it, st = _empty_like(Qc, (Cn,), np.int32), _empty_like(Qc, (Cn,), np.int32)
+        Qc, Cn, out = self._q_out(Q, None, lambda q: tuple(q.shape[1:]))
+        it, st = new(Qc, (Cn,), np.int32), new(Qc, (Cn,), np.int32)
         check(self._lib.beatamd_ffi_lsq_solution_batch(self._h, model_id, Cn, ptr(Qc), ptr(out), ptr(it), ptr(st)))
         return out, it, st
 
@@ -989,11 +921,7 @@ class Context(object):
     def ffi_llks_batch(self, model_id, Q, out=None):
         """the cached misfits |W r|^2 of every dataset (and |L s_v|^2 per slip variable) at the points Q [C, nparams]
         -> [C, nterm]: update_llks of every composite (seismic.py:510-525, geodetic.py:429-444, laplacian.py:141-154)"""
-        self._adopt_stream(Q)
-        Q = f64(Q)
-        Cn = int(Q.shape[0])
-        if out is None:
-            out = _empty_like(Q, (Cn, self.ffi_model_nterm(model_id)))
+        Q, Cn, out = self._q_out(Q, out, lambda q: (self.ffi_model_nterm(model_id),))
         check(self._lib.beatamd_ffi_llks_batch(self._h, model_id, Cn, ptr(Q), ptr(out)))
         return out
 
@@ -1016,12 +944,12 @@ class Context(object):
     def hyper_logp_batch(self, hyper_id, H, llks, out=None):
         """H [C, nh], llks [C, nterm] -> LL [C, nterm + 1] (terms, like): hyper_normal / _eval_prior for C chains"""
         self._adopt_stream(H, llks)
-        H, llks = f64(H), f64(llks)
-        if _is_dev(H) != _is_dev(llks):
+        H, llks = as_input(H), as_input(llks)
+        if is_dev(H) != is_dev(llks):
             raise ValueError("hyper_logp: H and llks must live on the same side")
         Cn = int(H.shape[0])
         if out is None:
-            out = _empty_like(H, (Cn, int(llks.shape[1]) + 1))
+            out = new(H, (Cn, int(llks.shape[1]) + 1))
         check(self._lib.beatamd_hyper_logp_batch(self._h, hyper_id, Cn, ptr(H), ptr(llks), ptr(out)))
         return out
 
@@ -1032,7 +960,7 @@ class Context(object):
         H, LL, scaling, accepted_since_tune"""
         self._adopt_stream(H, LL)
         for a in (H, LL, scaling, llks, lower, upper, scales):
-            f64(a)
+            as_input(a)
         check(self._lib.beatamd_hyper_chain_batch(
             self._h, hyper_id, int(H.shape[0]), int(n_steps), ptr(H), ptr(LL), ptr(scaling), ptr(accepted_since_tune),
             ptr(llks), ptr(lower), ptr(upper), int(kind), ptr(scales), int(seed) & (2 ** 64 - 1), int(step0) & 0xffffffff,
@@ -1043,11 +971,7 @@ class Context(object):
     def wset_quad_batch(self, wset_id, residuals, out=None):
         """residuals (C, nd, M) -> (C, nd): |W_d r|^2 per dataset of a weight set, the misfit kernels of
         ``mvn_chol_logp_batch`` (seismic.py:610-616 nom / denom with W^T W = inv(C))"""
-        self._adopt_stream(residuals)
-        r = f64(residuals)
-        Cn, nd = int(r.shape[0]), int(r.shape[1])
-        if out is None:
-            out = _empty_like(r, (Cn, nd))
+        r, Cn, out = self._q_out(residuals, out, lambda r: (int(r.shape[1]),))
         check(self._lib.beatamd_wset_quad_batch(self._h, wset_id, Cn, ptr(r), ptr(out)))
         return out
 
@@ -1064,22 +988,14 @@ class Context(object):
     def ffi_variance_reductions_batch(self, model_id, Q, ndata, out=None):
         """Q (C, nparams) -> VR (C, ndata) = 1 - |W r|^2 / |W d|^2 per dataset and draw (get_variance_reductions,
         seismic.py:564-634, geodetic.py:446-511)"""
-        self._adopt_stream(Q)
-        Q = f64(Q)
-        Cn = int(Q.shape[0])
-        if out is None:
-            out = _empty_like(Q, (Cn, int(ndata)))
+        Q, Cn, out = self._q_out(Q, out, (int(ndata),))
         check(self._lib.beatamd_ffi_variance_reductions_batch(self._h, model_id, Cn, ptr(Q), ptr(out)))
         return out
 
     def ffi_geo_residuals_batch(self, model_id, Q, nobs, residuals=True, out=None):
         """Q (C, nparams) -> (C, nobs): the geodetic composite's residual (d - mu) * odw - corrections
         (geodetic.py:1072-1077) or, residuals=False, its synthetics mu"""
-        self._adopt_stream(Q)
-        Q = f64(Q)
-        Cn = int(Q.shape[0])
-        if out is None:
-            out = _empty_like(Q, (Cn, int(nobs)))
+        Q, Cn, out = self._q_out(Q, out, (int(nobs),))
         check(self._lib.beatamd_ffi_geo_residuals_batch(self._h, model_id, Cn, ptr(Q), int(bool(residuals)), ptr(out)))
         return out
 
@@ -1088,11 +1004,11 @@ class Context(object):
         get_standardized_residuals (seismic.py:527-562) with S_t = inv(chol(C_t)).  S (T,) scalars or (T, N, N);
         residuals (C, T, N); hp (C, T) or None"""
         self._adopt_stream(residuals)
-        r = f64(residuals)
+        r = as_input(residuals)
         if r.ndim != 3:
             raise ValueError("standardize_batch: residuals must be (C, T, N)")
         Cn, T, N = [int(v) for v in r.shape]
-        Sc = f64(S)
+        Sc = as_input(S)
         if tuple(Sc.shape) == (T,):
             kind = _lib.W_SCALAR
         elif tuple(Sc.shape) == (T, N, N):
@@ -1101,11 +1017,11 @@ class Context(object):
             raise ValueError("standardize_batch: S must be (%d,) or (%d, %d, %d)" % (T, T, N, N))
         h = None
         if hp is not None:
-            h = f64(hp)
+            h = as_input(hp)
             if tuple(h.shape) != (Cn, T):
                 raise ValueError("standardize_batch: hp must be (%d, %d)" % (Cn, T))
         if out is None:
-            out = _empty_like(r, (Cn, T, N))
+            out = new(r, (Cn, T, N))
         check(self._lib.beatamd_standardize_batch(self._h, kind, ptr(Sc), T, N, Cn, ptr(r), ptr(h), ptr(out)))
         return out
 
@@ -1113,17 +1029,13 @@ class Context(object):
         """Q (C, nparams) -> (C, npole, 4): the derived Euler-pole coefficients ``omega' p`` (slot 3 zero) of every row
         and pole, by the kernel the model launches.  var_off / var_fixed / earth: (npole, 3) offsets of (pole_lat,
         pole_lon, omega) in q (-1: the fixed value) and (radius, equator radius, oblateness)"""
-        self._adopt_stream(Q)
-        Q = f64(Q)
-        Cn, npar = int(Q.shape[0]), int(Q.shape[1])
         off = np.ascontiguousarray(var_off, dtype=np.int64).reshape(-1, 3)
         fix = np.ascontiguousarray(var_fixed, dtype=np.float64).reshape(-1, 3)
         ea = np.ascontiguousarray(earth, dtype=np.float64).reshape(-1, 3)
         if not (off.shape == fix.shape == ea.shape):
             raise ValueError("pole_coefficients_batch: offsets, fixed values and earth constants differ in shape")
-        if out is None:
-            out = _empty_like(Q, (Cn, off.shape[0], 4))
-        check(self._lib.beatamd_pole_coefficients_batch(self._h, Cn, npar, ptr(Q), int(off.shape[0]), ptr(off), ptr(fix),
+        Q, Cn, out = self._q_out(Q, out, (off.shape[0], 4))
+        check(self._lib.beatamd_pole_coefficients_batch(self._h, Cn, int(Q.shape[1]), ptr(Q), int(off.shape[0]), ptr(off), ptr(fix),
                                                         ptr(ea), ptr(out)))
         return out
 
@@ -1132,16 +1044,16 @@ class Context(object):
         (ffi/fault.py:1436-1517) of every row for one pole against the patch basis (P, 3) of
         ``summary.pole_patch_basis``; uparr_off: offset of the P back-slips in q"""
         self._adopt_stream(Q)
-        Q = f64(Q)
+        Q = as_input(Q)
         Cn, npar = int(Q.shape[0]), int(Q.shape[1])
         off = np.ascontiguousarray(var_off, dtype=np.int64).reshape(3)
         fix = np.ascontiguousarray(var_fixed, dtype=np.float64).reshape(3)
         ea = np.ascontiguousarray(earth, dtype=np.float64).reshape(3)
-        Bp = f64(basis)
-        if Bp.ndim != 2 or Bp.shape[1] != 3 or _is_dev(Bp) != _is_dev(Q):
+        Bp = as_input(basis)
+        if Bp.ndim != 2 or Bp.shape[1] != 3 or is_dev(Bp) != is_dev(Q):
             raise ValueError("pole_coupling_batch: basis must be (P, 3) on Q's side")
         P = int(Bp.shape[0])
-        es, cp = _empty_like(Q, (Cn, P)), _empty_like(Q, (Cn, P))
+        es, cp = new(Q, (Cn, P)), new(Q, (Cn, P))
         check(self._lib.beatamd_pole_coupling_batch(self._h, Cn, npar, ptr(Q), ptr(off), ptr(fix), ptr(ea), P, ptr(Bp),
                                                     int(uparr_off), ptr(es), ptr(cp)))
         return es, cp
@@ -1151,25 +1063,23 @@ class Context(object):
         seen), Welford in row order: the result does not depend on how the rows are cut into calls.  state None
         (with n_seen 0) allocates one on X's side.  -> (state, n_seen + C)"""
         self._adopt_stream(X)
-        x = f64(X)
+        x = as_input(X)
         if x.ndim != 2:
             raise ValueError("ensemble_moments_update: X must be (C, M)")
         Cn, M = int(x.shape[0]), int(x.shape[1])
         if state is None:
             if n_seen:
                 raise ValueError("ensemble_moments_update: %d rows seen but no state given" % n_seen)
-            state = _empty_like(x, (5, M))
-        if tuple(state.shape) != (5, M) or f64(state) is not state or _is_dev(state) != _is_dev(x):
-            raise ValueError("ensemble_moments_update: state must be a contiguous float64 (5, %d) array on X's side" % M)
+        state = checked(state, x, (5, M), np.float64, "ensemble_moments_update: state", of="X")
         check(self._lib.beatamd_ensemble_moments_update(self._h, Cn, M, ptr(x), ptr(state), int(n_seen)))
         return state, int(n_seen) + Cn
 
     def ensemble_moments_finish(self, state, n):
         """-> (mean, std, min, max), each (M,): std = sqrt(M2 / n) as numpy.std (ddof = 0)"""
         self._adopt_stream(state)
-        s = f64(state)
+        s = as_input(state)
         M = int(s.shape[1])
-        outs = [_empty_like(s, (M,)) for _ in range(4)]
+        outs = [new(s, (M,)) for _ in range(4)]
         check(self._lib.beatamd_ensemble_moments_finish(self._h, M, ptr(s), int(n), *[ptr(o) for o in outs]))
         return tuple(outs)
 
@@ -1192,41 +1102,19 @@ class Context(object):
 
     def _trace_density(self, Y, tmin, deltat, extent, ranges, grid_size, linewidth, grid):
         self._adopt_stream(Y)
-        y = f64(Y)
+        y = as_input(Y)
         if y.ndim != 3:
             raise ValueError("trace_density_update: Y must be (E, T, N)")
         E, T, N = (int(v) for v in y.shape)
         ny, nx = (int(v) for v in grid_size)
-        dev = _is_dev(y)
-
-        def side(a, shape, what):
-            if _is_dev(a) != dev and _is_dev(a):
-                a = a.cpu().numpy()
-            if not _is_dev(a):
-                a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), shape))
-                if dev:
-                    import torch
-                    a = torch.from_numpy(a).to(y.device)
-            a = f64(a)
-            if tuple(a.shape) != shape:
-                raise ValueError("trace_density_update: %s must be %s" % (what, shape))
-            return a
-
-        tm, ext = side(tmin, (T,), "tmin"), side(extent, (T, 4), "extent")
-        if grid is None:
-            if dev:
-                import torch
-                grid = torch.zeros((T, ny, nx), dtype=torch.float64, device=y.device)
-            else:
-                grid = np.zeros((T, ny, nx))
-        if tuple(grid.shape) != (T, ny, nx) or f64(grid) is not grid or _is_dev(grid) != dev:
-            raise ValueError("trace_density_update: grid must be a contiguous float64 (%d, %d, %d) array on Y's side"
-                             % (T, ny, nx))
+        tm = on_side(tmin, y, np.float64, (T,), "trace_density_update: tmin", broadcast=True)
+        ext = on_side(extent, y, np.float64, (T, 4), "trace_density_update: extent", broadcast=True)
+        grid = checked(grid, y, (T, ny, nx), np.float64, "trace_density_update: grid", of="Y", zero=True)
         if ranges is None:
             check(self._lib.beatamd_trace_density_update(self._h, E, T, N, ptr(y), ptr(tm), float(deltat), ptr(ext), ny, nx,
                                                          float(linewidth), ptr(grid)))
             return grid
-        rg = self._arg_on_side(ranges, y, np.int64, (E, T, 2), "trace_density_update: ranges")
+        rg = on_side(ranges, y, np.int64, (E, T, 2), "trace_density_update: ranges")
         check(self._lib.beatamd_trace_density_update_ranges(self._h, E, T, N, ptr(y), ptr(tm), float(deltat), ptr(ext), ptr(rg),
                                                             ny, nx, float(linewidth), ptr(grid)))
         return grid
@@ -1234,52 +1122,33 @@ class Context(object):
     def halfspace_displacements_batch(self, kinds, params, east, north, nu=0.25):
         """params (C, nsrc, 10) -> (C, nsrc, nobs, 3) = (north, east, up) [m]"""
         kinds = np.ascontiguousarray(kinds, dtype=np.int32)
-        prm = f64(params)
+        prm = as_input(params)
         self._adopt_stream(prm)
         Cn, nsrc = int(prm.shape[0]), int(prm.shape[1])
         if tuple(prm.shape[1:]) != (kinds.size, 10):
             raise ValueError("params must be (C, %d, 10)" % kinds.size)
-        e, n = f64(east), f64(north)
-        nobs = int(e.numel()) if _is_dev(e) else int(e.size)
-        out = _empty_like(prm, (Cn, nsrc, nobs, 3))
+        e, n = as_input(east), as_input(north)
+        nobs = int(e.numel()) if is_dev(e) else int(e.size)
+        out = new(prm, (Cn, nsrc, nobs, 3))
         check(self._lib.beatamd_halfspace_displacements_batch(self._h, Cn, nsrc, ptr(kinds), ptr(prm), nobs,
                                                               ptr(e), ptr(n), float(nu), ptr(out)))
         return out
 
     # -- geodetic FFI library and resolution-based discretization (csrc/geolib.hip, csrc/resolution.hip)
-    def _f64_on_side(self, a, device, shape, what):
-        """contiguous float64 ``a`` of ``shape``: a device tensor if ``device`` (host arrays go up), else numpy"""
-        if device:
-            import torch
-            if not _is_dev(a):
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:%d" % self.device)
-            a = f64(a)
-        else:
-            a = np.ascontiguousarray(a.cpu().numpy() if _is_dev(a) else a, dtype=np.float64)
-        if tuple(a.shape) != tuple(shape):
-            raise ValueError("%s must be %s, got %s" % (what, tuple(shape), tuple(a.shape)))
-        return a
-
-    def _new_f64(self, device, shape):
-        if device:
-            import torch
-            return torch.empty(shape, dtype=torch.float64, device="cuda:%d" % self.device)
-        return np.empty(shape, dtype=np.float64)
-
     def geo_gf_library(self, params, east, north, los, odw, nu=0.25, device=False):
         """params (nrows, 10) unit sources in the slots of halfspace_displacements_batch -> G (nrows, nobs) =
         (disp * los).sum(1) * odw of every row (ffi/base.py:804-821), all rows in one launch.  device: return a
         torch tensor on this context's GPU (inputs may be on either side)"""
-        dev = bool(device) or _is_dev(params)
+        side = (bool(device) or is_dev(params), self.device)
         nrows = int(params.shape[0])
         nobs = int(odw.shape[0])
-        prm = self._f64_on_side(params, dev, (nrows, 10), "params")
-        e = self._f64_on_side(east, dev, (nobs,), "east")
-        n = self._f64_on_side(north, dev, (nobs,), "north")
-        lo = self._f64_on_side(los, dev, (nobs, 3), "los")
-        w = self._f64_on_side(odw, dev, (nobs,), "odw")
+        prm = on_side(params, side, np.float64, (nrows, 10), "params")
+        e = on_side(east, side, np.float64, (nobs,), "east")
+        n = on_side(north, side, np.float64, (nobs,), "north")
+        lo = on_side(los, side, np.float64, (nobs, 3), "los")
+        w = on_side(odw, side, np.float64, (nobs,), "odw")
         self._adopt_stream(prm)
-        G = self._new_f64(dev, (nrows, nobs))
+        G = new(side, (nrows, nobs))
         check(self._lib.beatamd_geo_gf_library(self._h, nrows, ptr(prm), nobs, ptr(e), ptr(n), ptr(lo), ptr(w),
                                                float(nu), ptr(G)))
         return G
@@ -1290,11 +1159,11 @@ class Context(object):
         kinds = {"gaussian": 0, "exponential": 1}
         if correlation_function not in kinds:
             raise ValueError('Resolution based discretization does not support "nearest_neighbor" correlation function!')
-        dev = bool(device) or _is_dev(patches_coords)
+        side = (bool(device) or is_dev(patches_coords), self.device)
         P = int(patches_coords.shape[0])
-        c = self._f64_on_side(patches_coords, dev, (P, 3), "patches_coords")
+        c = on_side(patches_coords, side, np.float64, (P, 3), "patches_coords")
         self._adopt_stream(c)
-        L = self._new_f64(dev, (P, P))
+        L = new(side, (P, P))
         check(self._lib.beatamd_smoothing_correlated(self._h, P, ptr(c), kinds[correlation_function], ptr(L)))
         return L
 
@@ -1302,12 +1171,12 @@ class Context(object):
         """gfs (P, nobs) library rows, L (P, P) -> (R (P, P), diag (P,)) with R = inv(G^T G + eps^4 L^T L) . G^T G for
         G = gfs.T (ffi/fault.py:1805-1815); same side as ``gfs``; numpy.linalg.LinAlgError if the normal matrix is not
         positive definite"""
-        dev = _is_dev(gfs)
+        side = (is_dev(gfs), self.device)
         P, nobs = int(gfs.shape[0]), int(gfs.shape[1])
-        g = self._f64_on_side(gfs, dev, (P, nobs), "gfs")
-        Lm = self._f64_on_side(L, dev, (P, P), "L")
+        g = on_side(gfs, side, np.float64, (P, nobs), "gfs")
+        Lm = on_side(L, side, np.float64, (P, P), "L")
         self._adopt_stream(g)
-        R, d = self._new_f64(dev, (P, P)), self._new_f64(dev, (P,))
+        R, d = new(side, (P, P)), new(side, (P,))
         check(self._lib.beatamd_model_resolution(self._h, P, nobs, ptr(g), ptr(Lm), float(epsilon), ptr(R), ptr(d)))
         return R, d
 
@@ -1315,16 +1184,16 @@ class Context(object):
         """the division penalties of ffi/fault.py:1884-1929: widths, lengths (P,) [km], centers (P, 3) [km],
         bottom_depths (P,) [m] of each patch's subfault, data_coords (nobs, 2) [km] east / north, mean_R (P,) ->
         (rating (P,), patch_data_distance_mins (P,)); same side as ``mean_R``"""
-        dev = _is_dev(mean_R)
+        side = (is_dev(mean_R), self.device)
         P, nobs = int(mean_R.shape[0]), int(data_coords.shape[0])
-        w = self._f64_on_side(widths, dev, (P,), "widths")
-        ln = self._f64_on_side(lengths, dev, (P,), "lengths")
-        c = self._f64_on_side(centers, dev, (P, 3), "centers")
-        b = self._f64_on_side(bottom_depths, dev, (P,), "bottom_depths")
-        e = self._f64_on_side(data_coords, dev, (nobs, 2), "data_coords")
-        m = self._f64_on_side(mean_R, dev, (P,), "mean_R")
+        w = on_side(widths, side, np.float64, (P,), "widths")
+        ln = on_side(lengths, side, np.float64, (P,), "lengths")
+        c = on_side(centers, side, np.float64, (P, 3), "centers")
+        b = on_side(bottom_depths, side, np.float64, (P,), "bottom_depths")
+        e = on_side(data_coords, side, np.float64, (nobs, 2), "data_coords")
+        m = on_side(mean_R, side, np.float64, (P,), "mean_R")
         self._adopt_stream(m)
-        rating, dmin = self._new_f64(dev, (P,)), self._new_f64(dev, (P,))
+        rating, dmin = new(side, (P,)), new(side, (P,))
         check(self._lib.beatamd_division_rating(self._h, P, nobs, ptr(w), ptr(ln), ptr(c), ptr(b), float(depth_penalty),
                                                 ptr(e), ptr(m), ptr(rating), ptr(dmin)))
         return rating, dmin
@@ -1332,40 +1201,36 @@ class Context(object):
     def chol_inverse_batch(self, covs):
         """covs (nd, n, n) -> (W (nd, n, n) upper triangular = cholesky(inv(C)).T, log_pdet (nd,));
         numpy or torch-cuda in, same kind out; numpy.linalg.LinAlgError if not positive definite"""
-        if _is_dev(covs):
+        if is_dev(covs):
             self._adopt_stream(covs)
-        C = f64(covs)
+        C = as_input(covs)
         nd, n = int(C.shape[0]), int(C.shape[1])
-        W = _empty_like(C, (nd, n, n))
-        lp = _empty_like(C, (nd,))
+        W = new(C, (nd, n, n))
+        lp = new(C, (nd,))
         check(self._lib.beatamd_chol_inverse_batch(self._h, nd, n, ptr(C), ptr(W), ptr(lp)))
         return W, lp
 
     def chol_inverse_batch_flags(self, covs):
         """like chol_inverse_batch, but a matrix that is not positive definite is reported in the
         returned int32 flags (nd,) instead of raising: -> (W, log_pdet, not_psd)"""
-        if _is_dev(covs):
+        if is_dev(covs):
             self._adopt_stream(covs)
-        C = f64(covs)
+        C = as_input(covs)
         nd, n = int(C.shape[0]), int(C.shape[1])
-        W = _empty_like(C, (nd, n, n))
-        lp = _empty_like(C, (nd,))
-        if _is_dev(C):
-            import torch
-            bad = torch.empty((nd,), dtype=torch.int32, device=C.device)
-        else:
-            bad = np.empty((nd,), dtype=np.int32)
+        W = new(C, (nd, n, n))
+        lp = new(C, (nd,))
+        bad = new(C, (nd,), np.int32)
         check(self._lib.beatamd_chol_inverse_batch_flags(self._h, nd, n, ptr(C), ptr(W), ptr(lp), ptr(bad)))
         return W, lp, bad
 
     def factor_compact(self, factor):
         """tall proposal factor (K, n) -> upper-triangular R (n, n) with R^T R = factor^T factor, or
         None when the Gram matrix is not numerically positive definite"""
-        if _is_dev(factor):
+        if is_dev(factor):
             self._adopt_stream(factor)
-        F = f64(factor)
+        F = as_input(factor)
         K, n = int(F.shape[0]), int(F.shape[1])
-        R = _empty_like(F, (n, n))
+        R = new(F, (n, n))
         try:
             check(self._lib.beatamd_factor_compact(self._h, K, n, ptr(F), ptr(R)))
         except np.linalg.LinAlgError:
@@ -1374,26 +1239,26 @@ class Context(object):
 
     def whitening_ratio_batch(self, W_new, W_old):
         """M (nd, n, n) = W_new . inv(W_old) for upper-triangular whitening operators"""
-        Wn, Wo = f64(W_new), f64(W_old)
+        Wn, Wo = as_input(W_new), as_input(W_old)
         if Wn.shape != Wo.shape or Wn.ndim != 3:
             raise ValueError("W_new and W_old must both be (nd, n, n)")
-        M = _empty_like(Wn, tuple(Wn.shape))
+        M = new(Wn, tuple(Wn.shape))
         check(self._lib.beatamd_whitening_ratio_batch(self._h, int(Wn.shape[0]), int(Wn.shape[1]), ptr(Wn),
                                                       ptr(Wo), ptr(M)))
         return M
 
     def unwhiten_traces(self, W, X):
         """X (nd, n) <- inv(W[t]) . X[t] for upper-triangular W (nd, n, n), in place (back substitution)"""
-        Wd = f64(W)
+        Wd = as_input(W)
         if Wd.ndim != 3 or Wd.shape[1] != Wd.shape[2] or tuple(X.shape) != (Wd.shape[0], Wd.shape[1]):
             raise ValueError("W must be (nd, n, n) and X (nd, n)")
-        if f64(X) is not X:
+        if not is_canonical(X):
             raise ValueError("X must be a contiguous float64 array / tensor (updated in place)")
         check(self._lib.beatamd_unwhiten_traces(self._h, int(Wd.shape[0]), int(Wd.shape[1]), ptr(Wd), ptr(X)))
         return X
 
     def ffi_model_update_data(self, model_id, wavemap_index, data):
-        d = f64(data)
+        d = as_input(data)
         check(self._lib.beatamd_ffi_model_update_data(self._h, int(model_id), int(wavemap_index), ptr(d)))
 
     def whiten_rows_batch(self, rows, W):
@@ -1402,7 +1267,7 @@ class Context(object):
         self._adopt_stream(rows)
         if rows.dim() != 3 or not rows.is_contiguous():
             raise ValueError("whiten_rows_batch: rows must be a contiguous (B, R, N) device tensor")
-        Wc = f64(W)
+        Wc = as_input(W)
         if tuple(Wc.shape) != (rows.shape[0], rows.shape[2], rows.shape[2]):
             raise ValueError("whiten_rows_batch: W must be (%d, %d, %d)" % (rows.shape[0], rows.shape[2], rows.shape[2]))
         check(self._lib.beatamd_whiten_rows_batch(self._h, ptr(rows), int(rows.shape[0]), int(rows.shape[1]),
@@ -1412,7 +1277,7 @@ class Context(object):
     def whiten_rows(self, rows, W):
         """rows (R, N) device tensor, in place: rows <- rows . W^T"""
         self._adopt_stream(rows)
-        Wc = f64(W)
+        Wc = as_input(W)
         check(self._lib.beatamd_whiten_rows(self._h, ptr(rows), int(rows.shape[0]), int(rows.shape[1]),
                                             ptr(Wc)))
         return rows

@@ -19,6 +19,7 @@ import os
 
 import numpy as np
 
+from ._marshal import upload
 from .engine import get_context
 
 gf_dtype = "float64"  # base.py:18
@@ -602,8 +603,7 @@ def geo_construct_gf_linear_patches(engine, datasets=None, targets=None, patches
         for dataset, lo, hi in zip(datasets, bounds[:-1], bounds[1:]):
             W = dataset.covariance.chol_inverse
             if device:
-                import torch
-                W = torch.from_numpy(np.ascontiguousarray(W, dtype=np.float64)).to(gfmatrix.device)
+                W = upload(W, gfmatrix.device, np.float64)
                 w_gfs.append(gfmatrix[:, lo:hi] @ W)
             else:
                 w_gfs.append(gfmatrix[:, lo:hi].dot(W))

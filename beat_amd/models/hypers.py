@@ -22,6 +22,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .. import parallel
+from .._marshal import upload
 from .distributions import _Counter, get_hyper_name
 from .problem import ParameterLayout, hyper_name_laplacian
 
@@ -292,8 +293,8 @@ def estimate_hypers(f, hyper_model=None, n_chains=20, n_steps=25000, tune_interv
     H = hm.lower + (hm.upper - hm.lower) * rs.random_sample((int(n_chains), hm.nh))
     H[0] = (hm.upper + hm.lower) / 2.0
     a, b = parallel.chain_block(n_chains, rank, world)
-    Qd = torch.from_numpy(np.ascontiguousarray(Q[a:b])).to(dev)
-    Hd = torch.from_numpy(np.ascontiguousarray(H[a:b])).to(dev)
+    Qd = upload(Q[a:b], dev)
+    Hd = upload(H[a:b], dev)
     llks = f.update_llks(Qd)
     # a source point outside the library grid raises here, like the reference's IndexError -- on EVERY rank, whichever
     # owns the chain (a rank raising alone would leave the others waiting in the next collective)

@@ -19,6 +19,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .. import _lib
+from .._marshal import upload
 from ..engine import get_context
 from .corrections import correction_tables
 
@@ -188,12 +189,12 @@ class SeismicWavemap(object):
         dev = torch.device("cuda", ctx.device)
         T, N = self.data.shape
         gfs = {}
-        w = torch.from_numpy(np.ascontiguousarray(w)).to(dev)    # (one upload; a host array would be staged per call)
+        w = upload(w, dev)    # (one upload; a host array would be staged per call)
         for name, gf in self.gfs.items():
             if gf._device_tensor is not None:
                 G = gf._device_tensor if inplace else gf._device_tensor.clone()
             else:
-                G = torch.from_numpy(np.ascontiguousarray(gf._gfmatrix)).to(dev)
+                G = upload(gf._gfmatrix, dev)
             ctx.whiten_rows_batch(G.view(T, -1, N), w)
             cfg = gf.config
             g2 = SeismicGFLibrary(SeismicGFLibraryConfig(
@@ -809,7 +810,7 @@ class LogpForwFunc(object):
             dev = torch.device("cuda", self.ctx.device)
             wd = w if on_dev else torch.from_numpy(w).to(dev)
             old = wm._whitened_with
-            old = old if torch.is_tensor(old) else torch.from_numpy(np.ascontiguousarray(old)).to(dev)
+            old = old if torch.is_tensor(old) else upload(old, dev)
             # M is computed and checked (a singular old operator raises here) BEFORE any row is touched
             M = self.ctx.whitening_ratio_batch(wd, old)
             self.ctx.synchronize()
@@ -820,7 +821,7 @@ class LogpForwFunc(object):
                     continue
                 seen.add(gf._device_tensor.data_ptr())
                 self.ctx.whiten_rows_batch(gf._device_tensor.view(T, -1, N), M)
-            d = torch.from_numpy(np.ascontiguousarray(wm.data)).to(dev)
+            d = upload(wm.data, dev)
             self.ctx.whiten_rows_batch(d.view(T, 1, N), M)
             self.ctx.ffi_model_update_data(self.model_id, wavemap_index, d)
             self.ctx.weights_update(self._wsets[wavemap_index], np.ones(T), sl)

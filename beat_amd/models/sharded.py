@@ -27,6 +27,7 @@ rank.
 import numpy as np
 
 from .. import parallel
+from .._marshal import upload
 from .problem import FFIProblem, SeismicWavemap
 
 
@@ -144,7 +145,7 @@ class TargetShardedLogp(object):
         scatter + replicated columns + `like` in k_like_sum's order + NaN flags)"""
         t = self.torch
         as_numpy = not t.is_tensor(Q)
-        Qd = t.as_tensor(np.ascontiguousarray(Q)).to("cuda:%d" % self.ctx.device) if as_numpy else Q
+        Qd = upload(Q, "cuda:%d" % self.ctx.device) if as_numpy else Q
         L_loc = self.local.batch(Qd)
         C = L_loc.shape[0]
         ns = sum(self.n_local)

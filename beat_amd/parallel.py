@@ -19,6 +19,8 @@ import os
 
 import numpy as np
 
+from ._marshal import upload
+
 
 def dist_info():
     """-> (rank, world_size, local_rank): from the initialised process group when there is one,
@@ -207,11 +209,10 @@ def assert_same_on_all_ranks(what, *tensors):
 def broadcast_array(a, src=0):
     """Broadcast a small numpy array from ``src`` (stage decisions are computed identically on
     every rank; this is only used for values that come from host RNG state)."""
-    import torch
     import torch.distributed as dist
     if not _active() or dist.get_world_size() == 1:
         return a
     dev = "cuda" if dist.get_backend() == "nccl" else "cpu"   # (a few bytes: always through the transport's memory)
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t = upload(a, dev)
     dist.broadcast(t, src)
     return t.cpu().numpy()

@@ -11,6 +11,7 @@ update (``beatamd_metropolis_tune``).  Nothing returns to the host inside a stag
 """
 import numpy as np
 
+from .._marshal import upload
 from .base import covariance_factor, proposal_df, univariate_proposals
 from .ops import ops_for
 
@@ -52,7 +53,7 @@ class BatchedMetropolis(object):
         if proposal_name == "Poisson" and not (np.all(sc >= 0.0) and np.all(sc <= 500.0)):
             raise ValueError("PoissonProposal: the step widths (lam) must lie in [0, 500]")
         self.kind = univariate_proposals[proposal_name]
-        self.uscale = self.torch.from_numpy(np.ascontiguousarray(sc)).to(self.device)
+        self.uscale = upload(sc, self.device)
         self.factor, self.df = None, 0
 
     def set_proposal(self, cov, proposal_name="MultivariateNormal"):

@@ -302,7 +302,7 @@ def collective_check(ctx, world):
 
 class _Base(object):
     """a strided device view handed to the C ABI as (base pointer, stride): quacks like the
-    contiguous tensors ``engine.f64`` accepts"""
+    contiguous tensors ``_marshal.as_input`` accepts"""
 
     def __init__(self, t):
         import torch

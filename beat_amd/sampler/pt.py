@@ -22,6 +22,7 @@ each temperature steps with its own factor (``BatchedMetropolis.set_group_propos
 import numpy as np
 
 from .. import parallel
+from .._marshal import upload
 from ..utility import ensure_cov_psd
 from .base import univariate_proposals
 from .metropolis import BatchedMetropolis
@@ -240,7 +241,7 @@ def pt_sample(target, lower, upper, n_chains_posterior=1, n_chains_tempered=7, n
     if start_points is not None:
         from .smc import check_start
         Qall = check_start(start_points, n_total, lower.size)
-    Q = torch.from_numpy(np.ascontiguousarray(Qall[start:stop])).to(dev)
+    Q = upload(Qall[start:stop], dev)
     L = stepper.evaluate(Q).to(dev)
     npar = Q.shape[1]
     # posterior replicas (beta == 1) are the first n_posterior * n_replicas global chains

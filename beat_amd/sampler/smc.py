@@ -23,6 +23,7 @@ import os
 import numpy as np
 
 from .. import parallel
+from .._marshal import upload
 from .base import proposal_df
 from .metropolis import BatchedMetropolis
 from .ops import ops_for
@@ -102,7 +103,7 @@ class SMC(object):
         if start is not None:
             pop = check_start(start, self.n_chains, self.lower.size)
         a, b = self.block
-        return self.torch.from_numpy(np.ascontiguousarray(pop[a:b])).to(self.device)
+        return upload(pop[a:b], self.device)
 
     def select_end_points(self, Q_local, L_local):
         """smc.py:188-240 -- instead of reading trace files: all-gather the ranks' blocks; the
@@ -321,12 +322,11 @@ def load_stage(step, homepath, stage):
     from ..backend import stage_path
     z = np.load(os.path.join(stage_path(homepath, stage), "sampler_state.npz"))
     step.beta, step.old_beta, step.stage = float(z["beta"]), float(z["old_beta"]), int(z["stage"])
-    t = step.torch
     if z["population"].shape[0] != step.n_chains:
         raise ValueError("stage %s holds %d chains, the sampler was set up for %d: resume with the same n_chains"
                          % (stage, z["population"].shape[0], step.n_chains))
-    step.Q_all = t.from_numpy(np.ascontiguousarray(z["population"])).to(step.device)
-    step.L_all = t.from_numpy(np.ascontiguousarray(z["lpoints"])).to(step.device)
+    step.Q_all = upload(z["population"], step.device)
+    step.L_all = upload(z["lpoints"], step.device)
     if "scaling" in z.files:
         if z["scaling"].size != step.n_chains:
             raise ValueError("stage %s holds the step sizes of %d chains, expected %d"

@@ -15,6 +15,7 @@ directories.  There is no CPU fallback: without a GPU they raise.
 """
 import numpy as np
 
+from ._marshal import upload
 from .engine import get_context
 
 
@@ -42,10 +43,7 @@ def _is_tensor(a):
 
 
 def _to_device(ctx, a):
-    import torch
-    if _is_tensor(a):
-        return a
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to("cuda:%d" % ctx.device)
+    return a if _is_tensor(a) else upload(a, "cuda:%d" % ctx.device, np.float64)
 
 
 def posterior_variance_reductions(f, population, batch=512):
