@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("BEATAMD_LIB") or os.path.join(_HERE, "libbeat_amd.so"
 NEAREST_NEIGHBOR, MULTILINEAR = 0, 1
 W_SCALAR, W_DENSE = 0, 1
 STF_HALF_SINUSOID = 0
+POL_MTQT, POL_MT, POL_DC = 0, 1, 2
 INTERPOLATIONS = {"nearest_neighbor": NEAREST_NEIGHBOR, "multilinear": MULTILINEAR}
 
 OK, EINVAL, EHIP, EINDEX, ENOMEM, ENAN, ENOTPSD, EBADCOV, EOUTSIDE = 0, -1, -2, -3, -4, -5, -6, -7, -8
@@ -92,6 +93,10 @@ _PROTOS = {
     "beatamd_ffi_model_add_geodetic_corrections_kinds": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "beatamd_pole_coefficients_batch": [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "beatamd_pole_coupling_batch": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "beatamd_ffi_model_add_polarity": [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _vp, _vp],
+    "beatamd_mt6_batch": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "beatamd_polarity_amplitudes_batch": [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "beatamd_w_to_beta_batch": [_vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "beatamd_ffi_model_set_laplacian": [_vp, _i32, _i32],
     "beatamd_ffi_model_nllk": [_vp, _i32, _pi64],
     "beatamd_ffi_model_destroy": [_vp, _i32],

@@ -842,6 +842,151 @@ int beatamd_ffi_model_add_geodetic_geometry(beatamd_ctx *ctx, int32_t model_id, 
     return BEATAMD_OK;
 }
 
+// ------------------------------------------------------------------ polarity composite (polarity.hip)
+// the source of a polarity call from its host tables: kind, offsets in [-1, nparams), the variables of the kind
+static int pol_source_arg(beatamd_ctx *ctx, int32_t kind, const int64_t *param_off, const double *param_fixed, int64_t nparams,
+                          PolSource *s, const char *who)
+{
+    BA_CHECK(kind == POL_MTQT || kind == POL_MT || kind == POL_DC, BEATAMD_EINVAL, "%s: unknown source kind %d", who, kind);
+    BA_CHECK(param_off && param_fixed, BEATAMD_EINVAL, "%s: NULL source table", who);
+    std::vector<int64_t> off;
+    std::vector<double> fix;
+    BA_TRY(host_copy(ctx, param_off, 6, off));
+    BA_TRY(host_copy(ctx, param_fixed, 6, fix));
+    s->kind = kind;
+    const int nv = kind == POL_MTQT ? 5 : (kind == POL_MT ? 6 : 3);
+    for (int k = 0; k < 6; k++) {
+        BA_CHECK(off[k] >= -1 && off[k] < nparams, BEATAMD_EINVAL, "%s: offset %lld of source variable %d outside q", who,
+                 (long long)off[k], k);
+        s->off[k] = k < nv ? off[k] : -1;
+        s->fix[k] = k < nv ? fix[k] : 0.0;
+    }
+    return BEATAMD_OK;
+}
+
+// U_MAPPING must be strictly increasing for numpy.interp's search to be defined
+static int pol_tables_arg(beatamd_ctx *ctx, int32_t kind, int64_t ntab, const double *utab, const double *btab, const char *who)
+{
+    if (kind != POL_MTQT) return BEATAMD_OK;
+    BA_CHECK(ntab >= 2 && ntab <= 1000000 && utab && btab, BEATAMD_EINVAL, "%s: the mtqt source needs the w -> beta tables", who);
+    std::vector<double> u;
+    BA_TRY(host_copy(ctx, utab, (size_t)ntab, u));
+    for (int64_t i = 1; i < ntab; i++)
+        BA_CHECK(u[i] > u[i - 1], BEATAMD_EINVAL, "%s: the u table is not strictly increasing at %lld", who, (long long)i);
+    return BEATAMD_OK;
+}
+
+int beatamd_ffi_model_add_polarity(beatamd_ctx *ctx, int32_t model_id, int32_t kind, const int64_t *param_off,
+                                   const double *param_fixed, int32_t nmap, const int64_t *n_t, const double *rw,
+                                   const double *obs, double gamma, const int64_t *hp_off, const double *hp_fixed, int64_t ntab,
+                                   const double *utab, const double *btab)
+{
+    ENTER(ctx);
+    FfiModel *m;
+    BA_TRY(find_model(ctx, model_id, &m));
+    BA_CHECK(!m->has_pol, BEATAMD_EINVAL, "model already has a polarity composite");
+    BA_CHECK(nmap >= 1 && nmap <= POL_MAX_MAPS && n_t && rw && obs && hp_off && hp_fixed, BEATAMD_EINVAL,
+             "add_polarity: bad argument (1 to %d polarity maps)", POL_MAX_MAPS);
+    BA_CHECK(gamma >= 0.0 && gamma <= 0.5, BEATAMD_EINVAL, "add_polarity: gamma %g outside [0, 0.5]", gamma);
+    const int64_t np = m->layout.nparams;
+    Polarity p;
+    BA_TRY(pol_source_arg(ctx, kind, param_off, param_fixed, np, &p.src, "add_polarity"));
+    BA_TRY(pol_tables_arg(ctx, kind, ntab, utab, btab, "add_polarity"));
+    std::vector<int64_t> nt, ho;
+    std::vector<double> hf;
+    BA_TRY(host_copy(ctx, n_t, (size_t)nmap, nt));
+    BA_TRY(host_copy(ctx, hp_off, (size_t)nmap, ho));
+    BA_TRY(host_copy(ctx, hp_fixed, (size_t)nmap, hf));
+    p.nmap = nmap;
+    p.gamma = gamma;
+    for (int i = 0; i < nmap; i++) {
+        BA_CHECK(nt[i] >= 1, BEATAMD_EINVAL, "add_polarity: map %d has no station", i);
+        BA_CHECK(ho[i] >= -1 && ho[i] < np, BEATAMD_EINVAL, "add_polarity: hyper-parameter offset of map %d outside q", i);
+        p.NT += nt[i];
+        p.map_end[i] = p.NT;
+        p.hp_off[i] = ho[i];
+        p.hp_fix[i] = hf[i];
+    }
+    for (int i = nmap; i < POL_MAX_MAPS; i++) {
+        p.map_end[i] = p.NT;
+        p.hp_off[i] = -1;
+    }
+    BA_CHECK(p.NT < (int64_t)0x7fffffff, BEATAMD_EINVAL, "add_polarity: too many stations");
+    BA_TRY(p.rw.alloc_copy(ctx, rw, (size_t)p.NT * 6));
+    BA_TRY(p.obs.alloc_copy(ctx, obs, (size_t)p.NT));
+    if (kind == POL_MTQT) {
+        p.ntab = (int32_t)ntab;
+        BA_TRY(p.utab.alloc_copy(ctx, utab, (size_t)ntab));
+        BA_TRY(p.btab.alloc_copy(ctx, btab, (size_t)ntab));
+    }
+    m->pol = std::move(p);
+    m->has_pol = true;
+    return BEATAMD_OK;
+}
+
+// m6 (out [C, 6]) or the amplitudes at NT stations (rw given: out [C, NT]) of a population, by k_polarity
+static int pol_population(beatamd_ctx *ctx, const char *who, int32_t kind, int64_t C, int64_t nparams, const double *Q,
+                          const int64_t *param_off, const double *param_fixed, int64_t ntab, const double *utab,
+                          const double *btab, int64_t NT, const double *rw, double *out)
+{
+    BA_CHECK(C >= 0 && nparams > 0 && Q && out && (!rw || NT >= 1), BEATAMD_EINVAL, "%s: bad argument", who);
+    PolArgs a;
+    BA_TRY(pol_source_arg(ctx, kind, param_off, param_fixed, nparams, &a.src, who));
+    BA_TRY(pol_tables_arg(ctx, kind, ntab, utab, btab, who));
+    if (C == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    BA_TRY(st.in(Q, (size_t)C * nparams, &a.Q));
+    if (kind == POL_MTQT) {
+        BA_TRY(st.in(utab, (size_t)ntab, &a.utab));
+        BA_TRY(st.in(btab, (size_t)ntab, &a.btab));
+        a.ntab = (int32_t)ntab;
+    }
+    if (rw) BA_TRY(st.in(rw, (size_t)NT * 6, &a.rw));
+    a.mode = rw ? POL_OUT_AMP : POL_OUT_M6;
+    a.NT = rw ? NT : 0;
+    a.ld = rw ? NT : 6;
+    a.nparams = nparams;
+    a.C = C;
+    BA_TRY(st.out(out, (size_t)C * a.ld, &a.out));
+    BA_TRY(launch_polarity(ctx, a));
+    return st.finish();
+}
+
+int beatamd_mt6_batch(beatamd_ctx *ctx, int32_t kind, int64_t C, int64_t nparams, const double *Q, const int64_t *param_off,
+                      const double *param_fixed, int64_t ntab, const double *utab, const double *btab, double *m6)
+{
+    ENTER(ctx);
+    return pol_population(ctx, "mt6_batch", kind, C, nparams, Q, param_off, param_fixed, ntab, utab, btab, 0, nullptr, m6);
+}
+
+int beatamd_polarity_amplitudes_batch(beatamd_ctx *ctx, int32_t kind, int64_t C, int64_t nparams, const double *Q,
+                                      const int64_t *param_off, const double *param_fixed, int64_t ntab, const double *utab,
+                                      const double *btab, int64_t NT, const double *rw, double *amplitudes)
+{
+    ENTER(ctx);
+    BA_CHECK(rw, BEATAMD_EINVAL, "polarity_amplitudes_batch: no radiation weights");
+    return pol_population(ctx, "polarity_amplitudes_batch", kind, C, nparams, Q, param_off, param_fixed, ntab, utab, btab, NT,
+                          rw, amplitudes);
+}
+
+int beatamd_w_to_beta_batch(beatamd_ctx *ctx, int64_t n, const double *w, int64_t ntab, const double *utab, const double *btab,
+                            double *beta)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 0 && w && beta, BEATAMD_EINVAL, "w_to_beta_batch: bad argument");
+    BA_TRY(pol_tables_arg(ctx, POL_MTQT, ntab, utab, btab, "w_to_beta_batch"));
+    if (n == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_w, *d_u, *d_b;
+    double *d_o;
+    BA_TRY(st.in(w, (size_t)n, &d_w));
+    BA_TRY(st.in(utab, (size_t)ntab, &d_u));
+    BA_TRY(st.in(btab, (size_t)ntab, &d_b));
+    BA_TRY(st.out(beta, (size_t)n, &d_o));
+    BA_TRY(launch_w_to_beta(ctx, n, d_w, d_u, d_b, (int)ntab, d_o));
+    return st.finish();
+}
+
 int beatamd_ffi_model_add_geodetic_corrections(beatamd_ctx *ctx, int32_t model_id, int32_t nterm,
                                                const int32_t *dataset, const int32_t *ncol,
                                                const double *basis, const int64_t *coef_off,
@@ -1385,6 +1530,8 @@ int beatamd_ffi_variance_reductions_batch(beatamd_ctx *ctx, int32_t model_id, in
     FfiModel *m;
     BA_TRY(find_model(ctx, model_id, &m));
     BA_CHECK(Q && VR && C >= 0, BEATAMD_EINVAL, "ffi_variance_reductions: bad argument");
+    BA_CHECK(!m->has_pol, BEATAMD_EINVAL,
+             "the polarity composite has no Gaussian misfit: variance reductions are not defined for it");
     BA_TRY(model_check_layout(*m));
     const int64_t ndata = model_ndata(*m), nterm = model_nterm(*m);
     if (C == 0 || ndata == 0) return BEATAMD_OK;

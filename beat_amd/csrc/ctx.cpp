@@ -108,6 +108,7 @@ int64_t FfiModel::nllk() const
     int64_t n = 1;  // like
     for (auto &w : wavemaps) n += w.T;
     if (has_geo) n += (int64_t)geo.sizes.size();
+    if (has_pol) n += pol.NT;
     if (lap >= 0) n += 1;
     return n;
 }

@@ -252,6 +252,28 @@ struct GeomSources {
     double nu = 0.25;
 };
 
+// the polarity composite (polarity.hip; beat/models/polarity.py): one point source, nmap polarity maps whose stations
+// stand side by side in rw / obs.  Source slot k is q[off[k]] or, with off[k] < 0, fix[k] (the convention of GeomSources)
+constexpr int POL_MTQT = 0, POL_MT = 1, POL_DC = 2;
+constexpr int POL_MAX_MAPS = 8;
+struct PolSource {
+    int32_t kind = POL_MTQT, pad_ = 0;
+    int64_t off[6] = {-1, -1, -1, -1, -1, -1};
+    double fix[6] = {0, 0, 0, 0, 0, 0};
+};
+struct Polarity {
+    PolSource src;
+    int32_t nmap = 0;
+    int64_t NT = 0;                              // stations of all maps
+    int64_t map_end[POL_MAX_MAPS] = {};          // exclusive end of every map's stations
+    int64_t hp_off[POL_MAX_MAPS] = {};           // the map's sigma in q, or -1: hp_fix
+    double hp_fix[POL_MAX_MAPS] = {};
+    double gamma = 0.2;
+    DevMem<double> rw, obs;                      // device [6, NT], [NT]
+    int32_t ntab = 0;
+    DevMem<double> utab, btab;                   // device [ntab]: U_MAPPING, BETA_MAPPING (mtqt only)
+};
+
 struct FfiModel {
     beatamd_ffi_layout layout;
     int32_t nsub = 0;
@@ -265,6 +287,8 @@ struct FfiModel {
     Geodetic geo;
     bool geo_is_geometry = false;  // mu from analytic sources instead of G.T . slips
     GeomSources geom;
+    bool has_pol = false;
+    Polarity pol;
     int32_t lap = -1;
     int64_t nllk() const;
     // |W_k d_k|^2 of every dataset (beatamd_ffi_obs_quads), computed on first use and kept until the weights, the data

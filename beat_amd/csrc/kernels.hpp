@@ -245,6 +245,28 @@ int launch_pole_coef(beatamd_ctx *ctx, const PoleTerm *terms, int npole, const d
 int launch_pole_coupling(beatamd_ctx *ctx, const PoleTerm &term, const double *Q, int64_t nparams, int64_t C, int64_t P,
                          const double *Bp, int64_t uparr_off, double *euler_slips, double *coupling);
 
+// polarity.hip: one launch for all maps of the composite, a wavefront per chain.  out [C, ld]: the llk columns of the
+// stations (POL_OUT_LLK), their amplitudes (POL_OUT_AMP) or the normalised m6 (POL_OUT_M6; rw, obs not read)
+constexpr int POL_OUT_LLK = 0, POL_OUT_AMP = 1, POL_OUT_M6 = 2;
+struct PolArgs {
+    PolSource src;
+    int32_t nmap = 0, mode = POL_OUT_LLK, ntab = 0, pad_ = 0;
+    int64_t NT = 0;
+    int64_t map_end[POL_MAX_MAPS] = {};
+    int64_t hp_off[POL_MAX_MAPS] = {};
+    double hp_fix[POL_MAX_MAPS] = {};
+    double gamma = 0.2;
+    const double *rw = nullptr, *obs = nullptr, *utab = nullptr, *btab = nullptr;
+    const double *Q = nullptr;
+    int64_t nparams = 0, C = 0;
+    const int32_t *active = nullptr;   // device [C] or nullptr: chains with 0 are skipped
+    double *out = nullptr;
+    int64_t ld = 0;
+};
+int launch_polarity(beatamd_ctx *ctx, const PolArgs &a);
+// out[i] = w_to_beta(w[i]) on the tables (sources.py:379-392), the device function of k_polarity
+int launch_w_to_beta(beatamd_ctx *ctx, int64_t n, const double *w, const double *utab, const double *btab, int ntab, double *out);
+
 #ifdef __HIPCC__
 // The weighted residual of observation k of chain c with the correction terms of k's dataset subtracted one after the
 // other in table order (geodetic.py:1072-1077, 411-427):

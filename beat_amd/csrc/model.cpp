@@ -50,7 +50,7 @@ int model_check_layout(const FfiModel &m)
                      L.nuc_dip_off + m.nsub <= np && L.time_off >= 0 && L.time_off + m.nsub <= np,
                  BEATAMD_EINVAL, "layout: hypocentre variables outside q");
     }
-    BA_CHECK(!m.wavemaps.empty() || m.has_geo || m.lap >= 0, BEATAMD_EINVAL, "model has no composite");
+    BA_CHECK(!m.wavemaps.empty() || m.has_geo || m.has_pol || m.lap >= 0, BEATAMD_EINVAL, "model has no composite");
     return BEATAMD_OK;
 }
 
@@ -172,6 +172,18 @@ static int geodetic_wset(beatamd_ctx *ctx, const Geodetic &g, size_t d, WeightSe
     return BEATAMD_OK;
 }
 
+// the polarity composite's launch up to what its caller wants of it (mode, out, ld, active)
+void polarity_call(const Polarity &p, int64_t C, const double *Q, int64_t np, PolArgs *a)
+{
+    a->src = p.src; a->nmap = p.nmap; a->ntab = p.ntab; a->NT = p.NT;
+    for (int i = 0; i < POL_MAX_MAPS; i++) {
+        a->map_end[i] = p.map_end[i]; a->hp_off[i] = p.hp_off[i]; a->hp_fix[i] = p.hp_fix[i];
+    }
+    a->gamma = p.gamma;
+    a->rw = p.rw.get(); a->obs = p.obs.get(); a->utab = p.utab.get(); a->btab = p.btab.get();
+    a->Q = Q; a->nparams = np; a->C = C;
+}
+
 // ------------------------------------------------------------------ likelihood
 // With opt.llks every composite stops in front of its epilogue and stores the quadratic form it would have handed to it
 // (update_llks: seismic.py:510-525, geodetic.py:429-444, laplacian.py:141-154); the hyper-parameters are then not read
@@ -179,6 +191,9 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
 {
     const int64_t nllk = m.nllk(), nterm = model_nterm(m), np = m.layout.nparams;
     double *const llks = opt.llks;
+    BA_CHECK(!(llks && m.has_pol), BEATAMD_EINVAL,
+             "the polarity composite has no Gaussian misfit: update_llks / variance reductions are not defined for it "
+             "(beat/models/polarity.py defines none)");
     int64_t col = 0, tcol = 0;   // next column of LL / of llks
     LikeGroups grp;
     double *quad;
@@ -285,6 +300,15 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
         tcol += (int64_t)nd;
         grp.end[grp.n++] = (int32_t)col;
     }
+    if (m.has_pol) {
+        // polarity_like is a vector, one entry per station of every map (polarity.py:133): all maps in one launch
+        PolArgs a;
+        polarity_call(m.pol, C, Q, np, &a);
+        a.mode = POL_OUT_LLK; a.out = LL + col; a.ld = nllk; a.active = opt.active;
+        BA_TRY(launch_polarity(ctx, a));
+        col += m.pol.NT;
+        grp.end[grp.n++] = (int32_t)col;
+    }
     if (m.lap >= 0) {
         Laplacian *lp = get_obj(ctx->laps, m.lap);
         BA_CHECK(lp, BEATAMD_EINVAL, "model refers to a destroyed laplacian");
@@ -320,6 +344,8 @@ int ffi_logp_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q, d
 
 int model_obs_quads(beatamd_ctx *ctx, FfiModel &m)
 {
+    BA_CHECK(!m.has_pol, BEATAMD_EINVAL,
+             "the polarity composite has no Gaussian misfit: variance reductions are not defined for it");
     const int64_t ndata = model_ndata(m);
     if (m.obs_quads_valid && (int64_t)m.obs_quads.size() == ndata) return BEATAMD_OK;
     BA_HIP(hipStreamSynchronize(ctx->stream));   // (a kernel in flight may still read the old copy)
@@ -393,6 +419,7 @@ int lsq_normal_device(beatamd_ctx *ctx, FfiModel &m, int64_t C, const double *Q,
     BA_CHECK(m.lsq_var >= 0 && m.lsq_var < m.layout.nvar, BEATAMD_EINVAL,
              "lsq: the model has no inverted slip variable (beatamd_ffi_model_set_lsq_variables)");
     BA_CHECK(!(m.has_geo && m.geo_is_geometry), BEATAMD_EINVAL, "lsq: a geometry-mode geodetic composite is not linear in slip");
+    BA_CHECK(!m.has_pol, BEATAMD_EINVAL, "lsq: a model with a polarity composite has no linear slip problem");
     for (auto &wm : m.wavemaps)
         BA_CHECK(wm.domain != BEATAMD_DOMAIN_SPECTRUM, BEATAMD_EINVAL,
                  "lsq: a spectrum-domain wavemap is not linear in slip (the amplitude is taken after the stack)");

@@ -40,6 +40,8 @@ int geodetic_residual(beatamd_ctx *ctx, const FfiModel &m, int64_t C, const doub
 // *gc = the composite's correction table for a kernel launched next on C chains: with pole terms their derived
 // coefficients are computed first (k_pole_coef) into the composite's own buffer, grown here outside any capture
 int geo_pole_coefficients(beatamd_ctx *ctx, const Geodetic &g, int64_t C, const double *Q, int64_t np, GeoCorr *gc);
+// the polarity composite's launch arguments up to mode, out, ld and active
+void polarity_call(const Polarity &p, int64_t C, const double *Q, int64_t np, PolArgs *a);
 // quad[c, v] = |L s_{c,v}|^2 of the slips [C, nvar, P]
 int laplacian_quad(beatamd_ctx *ctx, const Laplacian &lap, int64_t C, int64_t nvar, const double *slips, double *quad);
 

@@ -357,3 +357,90 @@ def seis_synthetics(engine, sources, targets, arrival_taper=None, wavename="any_
     if outmode == "data":
         return list(synths), np.asarray(tmins)
     raise TypeError("Outmode %s not supported!" % outmode)
+
+
+# ------------------------------------------------------------------ first-motion polarities (heart.py:3891-4088)
+# Station propagation coefficients after Pugh et al. (2016, GJI, Appendix A).  Takeoff angles are measured from the
+# downward vertical, azimuths from north, both in radians; the rows multiply (mnn, mee, mdd, mne, mnd, med).
+def _sincos(takeoff_angles, azimuths):
+    t = np.asarray(takeoff_angles, dtype=np.float64)
+    a = np.asarray(azimuths, dtype=np.float64)
+    return np.sin(t), np.cos(t), np.sin(a), np.cos(a)
+
+
+def radiation_weights_p(takeoff_angles, azimuths):
+    """P waves -> (6, n_stations) (heart.py:3891-3912)"""
+    st, ct, sa, ca = _sincos(takeoff_angles, azimuths)
+    stp2, st2, sa2 = st ** 2, 2 * st * ct, 2 * ca * sa
+    return np.array([stp2 * ca ** 2, stp2 * sa ** 2, ct ** 2, stp2 * sa2, st2 * ca, st2 * sa])
+
+
+def radiation_weights_sv(takeoff_angles, azimuths):
+    """SV waves -> (6, n_stations) (heart.py:3915-3935)"""
+    st, ct, sa, ca = _sincos(takeoff_angles, azimuths)
+    sct = st * ct
+    ct2 = np.cos(2 * np.asarray(takeoff_angles, dtype=np.float64))
+    return np.array([sct * ca ** 2, sct * sa ** 2, -sct, 2 * sct * sa * ca, ct2 * ca, ct2 * sa])
+
+
+def radiation_weights_sh(takeoff_angles, azimuths):
+    """SH waves -> (6, n_stations) (heart.py:3938-3958)"""
+    st, ct, sa, ca = _sincos(takeoff_angles, azimuths)
+    ca2 = np.cos(2 * np.asarray(azimuths, dtype=np.float64))
+    a1 = st * (sa * ca)
+    return np.array([-a1, a1, np.zeros_like(st), st * ca2, -ct * sa, ct * ca])
+
+
+def radiation_gamma(takeoff_angles_rad, azimuths_rad):
+    """unit ray direction -> (3, n_stations) (heart.py:3961-3973)"""
+    st, ct, sa, ca = _sincos(takeoff_angles_rad, azimuths_rad)
+    return np.array([st * ca, st * sa, ct])
+
+
+def radiation_theta(takeoff_angles_rad, azimuths_rad):
+    """SV polarisation direction -> (3, n_stations) (heart.py:3976-3988)"""
+    st, ct, sa, ca = _sincos(takeoff_angles_rad, azimuths_rad)
+    return np.array([ct * ca, ct * sa, -st])
+
+
+def radiation_phi(azimuths_rad):
+    """SH polarisation direction -> (3, n_stations) (heart.py:3991-4001)"""
+    a = np.asarray(azimuths_rad, dtype=np.float64)
+    ca, sa = np.cos(a), np.sin(a)
+    return np.array([-sa, ca, np.zeros_like(ca)])
+
+
+def radiation_matmul(m9, takeoff_angles_rad, azimuths_rad, wavename):
+    """the radiation pattern as the bilinear form direction^T . m9 . gamma per station (heart.py:4004-4025)"""
+    gamma = radiation_gamma(takeoff_angles_rad, azimuths_rad)
+    if wavename == "any_P":
+        left = gamma
+    elif wavename == "any_SV":
+        left = radiation_theta(takeoff_angles_rad, azimuths_rad)
+    elif wavename == "any_SH":
+        left = radiation_phi(azimuths_rad)
+    else:
+        return None
+    return np.einsum("is,ij,js->s", left, np.asarray(m9, dtype=np.float64), gamma)
+
+
+radiation_function_mapping = {"any_P": radiation_weights_p, "any_SH": radiation_weights_sh, "any_SV": radiation_weights_sv}
+
+
+def calculate_radiation_weights(takeoff_angles_rad, azimuths_rad, wavename):
+    """(6, n_stations) propagation coefficients of a wave type (heart.py:4035-4050)"""
+    return radiation_function_mapping[wavename](takeoff_angles_rad, azimuths_rad)
+
+
+def pol_synthetics(source, takeoff_angles_rad=None, azimuths_rad=None, wavename="any_P", radiation_weights=None):
+    """first-motion amplitudes of ``source`` at the stations (heart.py:4053-4088): the tensor scaled to
+    ``sqrt(sum m9^2) = sqrt 2`` times the propagation coefficients.  One source on the host; populations go through
+    ``beat_amd.polarity_binding.polarity_amplitudes_batch``."""
+    from .sources import to6
+    if radiation_weights is None:
+        if takeoff_angles_rad is None or azimuths_rad is None:
+            raise ValueError("Need to either provide radiation weights or takeoff-angles and azimuths!")
+        radiation_weights = calculate_radiation_weights(takeoff_angles_rad, azimuths_rad, wavename=wavename)
+    m9 = np.array(source.pyrocko_moment_tensor().m(), dtype=np.float64)
+    m9 /= np.sqrt(np.sum(m9 ** 2)) / np.sqrt(2.0)
+    return np.asarray(radiation_weights).T.dot(to6(m9))

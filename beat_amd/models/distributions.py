@@ -61,3 +61,18 @@ def multivariate_normal_chol(datasets, weights, hyperparams, residuals, hp_speci
     finally:
         ctx.weights_destroy(wid)
     return out if batched else out[0]
+
+
+def cumulative_normal(x, s=np.sqrt(2)):
+    """distributions.py:143-147"""
+    from scipy.special import erf
+    return 0.5 + 0.5 * erf(np.asarray(x, dtype=np.float64) / s)
+
+
+def polarity_llk(obs_polarities, syn_amplitudes, gamma, sigma):
+    """Polarity likelihood on the cumulative normal (distributions.py:150-173; Weber 2018, GJI, eqs 6, 7), in numpy:
+    ``gamma`` the probability of a wrong reading, ``sigma`` the modelling error of the amplitudes, used as it is.
+    The device form for populations of chains is ``csrc/polarity.hip``."""
+    obs = np.asarray(obs_polarities, dtype=np.float64)
+    p_i = gamma + (1 - 2.0 * gamma) * cumulative_normal(np.asarray(syn_amplitudes, dtype=np.float64) / sigma)
+    return ((1.0 + obs) / 2.0) * np.log(p_i) + ((1.0 - obs) / 2.0) * np.log(1.0 - p_i)

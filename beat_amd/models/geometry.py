@@ -98,6 +98,11 @@ class GeodeticGeometryProblem(object):
                   "h_laplacian_off"):
             setattr(L, f, -1)
         mid = ctx.ffi_model_create(L, [], [], [])
+        self.add_to_model(ctx, mid)
+        return LogpForwFunc(ctx, mid, self)
+
+    def add_to_model(self, ctx, mid):
+        """the geodetic geometry composite (weights, sources, data, corrections) of the device model ``mid``"""
         self._wsets = []
         for n, W, sl in zip(self.sizes, self.weights, self.slog_pdets):
             if np.ndim(W) == 0:
@@ -112,4 +117,3 @@ class GeodeticGeometryProblem(object):
         if self.corrections is not None:
             ctx.ffi_model_add_geodetic_corrections(
                 mid, *correction_tables(self.corrections, self.sizes, self.layout, self.fixed, kinds=True))
-        return LogpForwFunc(ctx, mid, self)

@@ -85,6 +85,8 @@ class HyperModel(object):
 
     def __init__(self, f, ctx=None):
         prob = getattr(f, "problem", f)
+        from .problem import refuse_polarity
+        refuse_polarity(prob, "estimate_hypers / HyperModel")
         self.f = f if prob is not f else None
         self.problem = prob
         self.ctx = ctx if ctx is not None else getattr(f, "ctx", None)

@@ -38,8 +38,9 @@ def lsq_start_population(f, n_chains, random_seed, lower=None, upper=None):
     computes, bit for bit.  Errors are those of ``LogpForwFunc.lsq_solution``."""
     if not hasattr(f, "problem") or not hasattr(f, "lsq_solution"):
         raise TypeError("lsq_start_population needs a compiled FFI model")
-    from .problem import refuse_spectrum_wavemaps
+    from .problem import refuse_polarity, refuse_spectrum_wavemaps
     refuse_spectrum_wavemaps(f.problem, "the least-squares start")      # (not linear in the slips; before anything is drawn)
+    refuse_polarity(f.problem, "lsq_start_population")
     if lower is None or upper is None:
         prob = f.problem
         if prob.lower is None or prob.upper is None:

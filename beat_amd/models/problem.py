@@ -398,7 +398,8 @@ class LogpForwFunc(object):
         self.nparams = problem.layout.size
         self.trust_input = True
         self.return_rvs = bool(return_rvs)
-        nblocks = (len(problem.wavemaps) + (problem.geodetic is not None)
+        self._polarity = getattr(problem, "polarity", None)
+        nblocks = (len(problem.wavemaps) + (problem.geodetic is not None) + (self._polarity is not None)
                    + (problem.laplacian is not None) + 1)
         self._llk_index = nblocks - 1 + (len(problem.layout.varsizes) if self.return_rvs else 0)
         self._dirty = None   # set while a weight update rewrites the HBM library in place
@@ -411,6 +412,8 @@ class LogpForwFunc(object):
                   for wm in self.problem.wavemaps]
         if self.problem.geodetic is not None:
             names.append("geo_like")
+        if self._polarity is not None:
+            names.append("polarity_like")
         if self.problem.laplacian is not None:
             names.append("laplacian_like")
         return names + ["like"]
@@ -427,6 +430,10 @@ class LogpForwFunc(object):
             o += wm.n_t
         if self.problem.geodetic is not None:
             n = len(self.problem.geodetic.sizes)
+            out.append(ll[o:o + n].copy())
+            o += n
+        if self._polarity is not None:   # a vector, one entry per station of every map (polarity.py:133)
+            n = self._polarity.n_t
             out.append(ll[o:o + n].copy())
             o += n
         if self.problem.laplacian is not None:
@@ -618,6 +625,7 @@ class LogpForwFunc(object):
         quadratic forms |W r|^2 the likelihood hands to its epilogues, from the same kernels (the geodetic ones with
         the odw factor, unlike the reference's: DESIGN.md).  The hyper-parameter entries of Q are not read.  numpy in
         -> numpy out, torch-cuda in -> tensor on the same device."""
+        refuse_polarity(self.problem, "update_llks")
         if self.model_id is None:
             raise RuntimeError("this compiled model was released")
         if Q.shape[-1] != self.nparams:
@@ -625,6 +633,28 @@ class LogpForwFunc(object):
         if self._dirty:
             raise RuntimeError("a weight update of this model did not complete: %s" % self._dirty)
         return self.ctx.ffi_llks_batch(self.model_id, Q, out)
+
+    # -- polarity composite (csrc/polarity.hip)
+    def _polarity_or_raise(self, Q):
+        self._ready(Q)
+        if self._polarity is None:
+            raise ValueError("the model has no polarity composite")
+        return self._polarity
+
+    def moment_tensors(self, Q):
+        """Q (C, nparams) -> (C, 6): the normalised (mnn, mee, mdd, mne, mnd, med) of every row -- the tensor that
+        ``heart.pol_synthetics`` multiplies with the propagation coefficients (heart.py:4086-4088) -- by the kernel of
+        the likelihood.  numpy in -> numpy out, torch-cuda in -> tensor."""
+        pol = self._polarity_or_raise(Q)
+        from ..polarity_binding import mt6_batch
+        return mt6_batch(self.ctx, Q, pol.source_kind, *pol.source_tables())
+
+    def polarity_synthetics(self, Q):
+        """Q (C, nparams) -> (C, n_t): ``heart.pol_synthetics`` of every row at the stations of all polarity maps,
+        map by map (``PolarityComposite.get_synthetics(order="list")``, polarity.py:261-291)"""
+        pol = self._polarity_or_raise(Q)
+        from ..polarity_binding import polarity_amplitudes_batch
+        return polarity_amplitudes_batch(self.ctx, Q, pol.source_kind, *pol.source_tables(), rw=pol.radiation_weights())
 
     # -- posterior diagnostics of a population (csrc/summary.hip)
     def _ready(self, Q=None):
@@ -658,6 +688,7 @@ class LogpForwFunc(object):
         """|W_k d_k|^2 per dataset -> (ndata,) numpy: the denominators ``data.T.dot(icov).dot(data)`` of the variance
         reduction (seismic.py:612-616, geodetic.py:497-501; geodetic data with its odw factor: DESIGN.md 3.9).  Cached
         on the device model until weights, data or corrections change."""
+        refuse_polarity(self.problem, "obs_quads")
         self._ready()
         return self.ctx.ffi_obs_quads(self.model_id, self.ndata)
 
@@ -666,6 +697,7 @@ class LogpForwFunc(object):
         ``get_variance_reductions`` (seismic.py:564-634, geodetic.py:446-511) for a batch, as a fraction (the
         reference's plots multiply by 100).  The hyper-parameter entries of Q are not read: ``inverse(exp(2h))``
         scales numerator and denominator alike.  numpy in -> numpy out, torch-cuda in -> tensor on the same device."""
+        refuse_polarity(self.problem, "variance_reductions")
         self._ready(Q)
         return self.ctx.ffi_variance_reductions_batch(self.model_id, Q, self.ndata, out)
 
@@ -682,6 +714,7 @@ class LogpForwFunc(object):
     def _lsq_setup(self, Q=None):
         """the checks of DistributionOptimizer.lsq_solution (problems.py:768-787) and the model's inverted variable"""
         refuse_spectrum_wavemaps(self.problem, "the least-squares start")
+        refuse_polarity(self.problem, "the least-squares start")
         self._ready(Q)
         prob = self.problem
         if prob.laplacian is None:
@@ -746,6 +779,7 @@ class LogpForwFunc(object):
         h is read from Q as the model reads it (per dataset or shared).
         wavemap_index: a wavemap -> (C, T, N); "geodetic" -> list of (C, n_k) per dataset (the sizes differ).
         A pre-whitened wavemap is refused: its residuals are whitened by another operator already."""
+        refuse_polarity(self.problem, "standardized_residuals")
         if wavemap_index != "geodetic":
             refuse_spectrum_wavemaps(self.problem, "standardized_residuals", wavemap_index)
         self._ready(Q)
@@ -912,6 +946,14 @@ def refuse_spectrum_wavemaps(problem, what, wavemap_index=None):
         if _is_spectrum(wm):
             raise NotImplementedError("%s is not available for wavemap %s in the spectrum domain: %s"
                                       % (what, wm.name, _SPECTRUM_REASONS[what]))
+
+
+def refuse_polarity(problem, what):
+    """NotImplementedError if ``problem`` has a polarity composite: a host check in front of any device call"""
+    if getattr(problem, "polarity", None) is not None:
+        raise NotImplementedError("%s is not available for a model with a polarity composite: the reference defines no "
+                                  "Gaussian misfit for it (beat/models/polarity.py has no update_llks, variance "
+                                  "reduction or standardized residual)" % what)
 
 
 def _standardizing_operators(covariances, n):

@@ -82,8 +82,9 @@ class TargetShardedLogp(object):
     is uploaded).  Every rank constructs it with the same arguments."""
 
     def __init__(self, prob, ctx=None, rank=None, world=None):
-        from .problem import refuse_spectrum_wavemaps
+        from .problem import refuse_polarity, refuse_spectrum_wavemaps
         refuse_spectrum_wavemaps(prob, "TargetShardedLogp")
+        refuse_polarity(prob, "TargetShardedLogp")
         import torch
         self.torch = torch
         r, w, _ = parallel.dist_info()

@@ -139,3 +139,41 @@ class SeisSynthesizer(object):
             engine=self.engine, sources=self.sources, targets=self.targets,
             arrival_taper=self.arrival_taper, wavename=self.wavename, filterer=self.filterer,
             pre_stack_cut=self.pre_stack_cut, arrival_times=np.array(self.arrival_times), outmode="array")
+
+
+class PolaritySynthesizer(object):
+    """pytensorf.py:314-369: the first-motion amplitudes of one source at the stations of one polarity map, with the
+    reference's constructor arguments, dict inputs, ``perform`` and ``infer_shape``.
+
+    Only ``is_location_fixed=True``: with a free location the reference re-traces the rays for the takeoff angles
+    (``pmap.update_targets``, pyrocko's cake), which is not part of this package.  One source on the host; the sampler's
+    populations go through the polarity composite (csrc/polarity.hip)."""
+    __props__ = ("engine", "source", "pmap", "is_location_fixed", "always_raytrace")
+
+    def __init__(self, engine, source, pmap, is_location_fixed, always_raytrace):
+        if not is_location_fixed:
+            raise NotImplementedError(
+                "PolaritySynthesizer with a free source location is not available: the takeoff angles would have to be "
+                "ray-traced again for every sample (pyrocko); fix north_shift, east_shift and depth")
+        self.engine, self.source, self.pmap = engine, source, pmap
+        self.is_location_fixed, self.always_raytrace = bool(is_location_fixed), always_raytrace
+        self.varnames = []
+
+    def make_node(self, inputs):
+        self.varnames = list(inputs.keys())
+        return self
+
+    def perform(self, node, inputs, output):
+        from . import heart
+        point = {name: float(np.ravel(np.asarray(v, dtype=np.float64))[0]) for name, v in zip(self.varnames, inputs)}
+        self.source.update(**{k: v for k, v in point.items() if hasattr(self.source, k)})
+        output[0][0] = heart.pol_synthetics(self.source, radiation_weights=self.pmap.get_radiation_weights())
+
+    def __call__(self, inputs):
+        self.make_node(inputs)
+        out = [[None]]
+        self.perform(None, list(inputs.values()), out)
+        return out[0][0]
+
+    def infer_shape(self, fgraph=None, node=None, input_shapes=None):
+        return [(self.pmap.n_t,)]

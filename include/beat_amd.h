@@ -482,6 +482,44 @@ int beatamd_pole_coefficients_batch(beatamd_ctx *ctx, int64_t C, int64_t nparams
 int beatamd_pole_coupling_batch(beatamd_ctx *ctx, int64_t C, int64_t nparams, const double *Q, const int64_t *var_off,
                                 const double *var_fixed, const double *earth, int64_t P, const double *Bp,
                                 int64_t uparr_off, double *euler_slips, double *coupling);
+
+/* ---- polarity composite (csrc/polarity.hip, which states the order of operations) ----------------------------------
+ * Source kinds and their variables, in the order of param_off / param_fixed [6] (offset in q, or -1: the fixed value):
+ *   BEATAMD_POL_MTQT  w, v, kappa, sigma, h        MTQTSource at rho = 1, beat/sources.py:19-40, 372-400, 454-536
+ *   BEATAMD_POL_MT    mnn, mee, mdd, mne, mnd, med as they are (pyrocko's six-vector order, pinned in the tree by
+ *                                                  calculate_radiation_weights == radiation_matmul, heart.py:3891-4050)
+ *   BEATAMD_POL_DC    strike, dip, rake [deg]      Aki & Richards; == MTQT(w = v = 0, kappa = strike, sigma = rake,
+ *                                                  h = cos dip) after the normalisation
+ * utab / btab [ntab]: U_MAPPING and BETA_MAPPING of sources.py:30-36, the caller's data (mtqt only; utab strictly
+ * increasing); the device restates numpy.interp on them bit for bit (sources.py:379-392).
+ * Every kind is normalised as pol_synthetics does: m9 /= sqrt(sum m9^2) / sqrt 2 (heart.py:4086-4087). */
+#define BEATAMD_POL_MTQT 0
+#define BEATAMD_POL_MT 1
+#define BEATAMD_POL_DC 2
+/* replaces: PolarityComposite.get_formula, beat/models/polarity.py:104-134 (PolaritySynthesizer, pytensorf.py:314-369,
+ *           with is_location_fixed; pol_synthetics, heart.py:4053-4088; polarity_llk, models/distributions.py:143-173)
+ *   nmap polarity maps (at most 8) of n_t[i] stations; rw [6, NT] their propagation coefficients side by side
+ *   (NT = sum n_t; heart.py:3891-3958), obs [NT] the observed polarities (+1, -1 or 0) as doubles; gamma the
+ *   probability of a wrong reading (polarity.py:45); hp_off / hp_fixed [nmap]: the map's sigma in q, or -1 and its
+ *   fixed value -- used as it is, not through exp.
+ *   The composite adds NT columns to LL (polarity_like is a vector, polarity.py:133), behind the geodetic ones and in
+ *   front of the laplacian's, as one group of the `like` sum.  One launch per evaluation.  It has no Gaussian misfit:
+ *   beatamd_ffi_llks_batch, ..._obs_quads, ..._variance_reductions_batch and the lsq entries refuse such a model. */
+int beatamd_ffi_model_add_polarity(beatamd_ctx *ctx, int32_t model_id, int32_t kind, const int64_t *param_off,
+                                   const double *param_fixed, int32_t nmap, const int64_t *n_t, const double *rw,
+                                   const double *obs, double gamma, const int64_t *hp_off, const double *hp_fixed,
+                                   int64_t ntab, const double *utab, const double *btab);
+/* replaces: MTQTSource.m6 (sources.py:538-540) / a source's pyrocko_moment_tensor().m6() followed by the normalisation
+ *           of heart.py:4086-4087, for a population: Q [C, nparams] -> m6 [C, 6] */
+int beatamd_mt6_batch(beatamd_ctx *ctx, int32_t kind, int64_t C, int64_t nparams, const double *Q, const int64_t *param_off,
+                      const double *param_fixed, int64_t ntab, const double *utab, const double *btab, double *m6);
+/* replaces: heart.pol_synthetics, heart.py:4053-4088, for a population: amplitudes [C, NT] = rw.T . m6 */
+int beatamd_polarity_amplitudes_batch(beatamd_ctx *ctx, int32_t kind, int64_t C, int64_t nparams, const double *Q,
+                                      const int64_t *param_off, const double *param_fixed, int64_t ntab, const double *utab,
+                                      const double *btab, int64_t NT, const double *rw, double *amplitudes);
+/* replaces: sources.w_to_beta, sources.py:379-392: beta [n] = numpy.interp(3 pi / 8 - w, utab, btab), bit for bit */
+int beatamd_w_to_beta_batch(beatamd_ctx *ctx, int64_t n, const double *w, int64_t ntab, const double *utab, const double *btab,
+                            double *beta);
 int beatamd_ffi_model_set_laplacian(beatamd_ctx *ctx, int32_t model_id, int32_t lap_id);
 int beatamd_ffi_model_nllk(beatamd_ctx *ctx, int32_t model_id, int64_t *nllk);
 int beatamd_ffi_model_destroy(beatamd_ctx *ctx, int32_t model_id);
