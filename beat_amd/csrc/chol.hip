@@ -21,6 +21,7 @@
 //   k_chol_unflip     W[i,j] = X[n-1-i, n-1-j]
 // All GEMMs run batched over the matrices of the stack (grid.y), on the FP64 matrix cores.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -430,7 +431,7 @@ __global__ void __launch_bounds__(1024) k_triu_solve_vec(const double *W, int64_
             double acc = 0.0;
             for (int64_t j = j0 + lane; j < n; j += 64) acc = fma(row[j], ts_x[j], acc);
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);   // wave_butterfly<OpAdd> (wave.hpp); the call changes the code
             if (lane == 0) part[r] = acc;
         }
         // the diagonal block into LDS
@@ -445,8 +446,7 @@ __global__ void __launch_bounds__(1024) k_triu_solve_vec(const double *W, int64_
             double xl = 0.0;                         // x of column `lane` once solved
             for (int r = m - 1; r >= 0; r--) {
                 double t = (lane > r && lane < m) ? blk[r * TS_B + lane] * xl : 0.0;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+                t = wave_butterfly<OpAdd>(t);
                 const double d = blk[r * TS_B + r];
                 if (!(fabs(d) > 0.0) && lane == 0) atomicOr(status, ST_NOT_PSD);   // (zero or NaN pivot)
                 const double xr = (ts_x[i0 + r] - part[r] - t) / d;

@@ -18,6 +18,7 @@
 // f64 MFMA layout: A lane l -> A[i=l&15][k=l>>4], B lane l -> B[k=l>>4][j=l&15],
 // C/D reg r of lane l -> row (l>>4)+4r, col l&15.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -40,19 +41,6 @@ struct GemmArgs {
     int b_lower;          // NN only: Bop[k, n] == 0 for k < n (lower-triangular B)
     int cb0;              // first column block of this launch (ncb counts the blocks of the launch)
 };
-
-__device__ __forceinline__ void gm_load4(const double *p, int64_t k, int64_t K, bool ok, int vec_ok,
-                                         double (&v)[4])
-{
-    if (ok && vec_ok && k + 4 <= K) {
-        const double2 a = *reinterpret_cast<const double2 *>(p + k);
-        const double2 b = *reinterpret_cast<const double2 *>(p + k + 2);
-        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = (ok && k + e < K) ? p[k + e] : 0.0;
-    }
-}
 
 template <int B_KN>
 __global__ void __launch_bounds__(256) k_gemm_f64(GemmArgs a)
@@ -97,11 +85,11 @@ __global__ void __launch_bounds__(256) k_gemm_f64(GemmArgs a)
     if (B_KN && a.b_lower) kstart = min((n0 / GM_KB) * GM_KB, ((K - 1) / GM_KB) * GM_KB);
     double av[4], bv[8];
     auto load_tile = [&](int64_t k0) {
-        gm_load4(Ap, k0 + lk, K, a_ok, a.vec_ok, av);
+        load4_padded(Ap, k0 + lk, K, a_ok, a.vec_ok, av);
         if (!B_KN) {
             double t0[4], t1[4];
-            gm_load4(Bp0, k0 + lk, K, b_ok0, a.vec_ok, t0);
-            gm_load4(Bp1, k0 + lk, K, b_ok1, a.vec_ok, t1);
+            load4_padded(Bp0, k0 + lk, K, b_ok0, a.vec_ok, t0);
+            load4_padded(Bp1, k0 + lk, K, b_ok1, a.vec_ok, t1);
 #pragma unroll
             for (int e = 0; e < 4; e++) { bv[e] = t0[e]; bv[4 + e] = t1[e]; }
         } else {

@@ -27,6 +27,7 @@
 // them on the CPU (tests/test_gfcell_program.py).  Rounds 3 / 4 shipped two more consumer programs in this file
 // (k_gfstack_cell, k_gfstack_ml); both were retired in round 5 (docs/design_history.md 3.1d-e keeps what they measured).
 #include "kernels.hpp"
+#include "wave.hpp"
 #include "gfruns_asm.inc"
 
 namespace beatamd {
@@ -241,7 +242,7 @@ __global__ void __launch_bounds__(GC_CUT_TB) k_gc_order(GcOrderArgs a)
         const double s0 = __shfl(f0, 0, 64), s1 = __shfl(f1, 0, 64);      // (a live lane's keys for the dead ones: slot 0 of
         double m0 = live ? f0 : s0, M0 = m0, m1 = live ? f1 : s1, M1 = m1;  //  wavefront 0 is live; later wavefronts see below)
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
+        for (int off = 32; off > 0; off >>= 1) {   // four wave_butterfly<OpFmin / OpFmax> (wave.hpp) in one loop: open-coded
             m0 = fmin(m0, __shfl_xor(m0, off, 64)); M0 = fmax(M0, __shfl_xor(M0, off, 64));
             m1 = fmin(m1, __shfl_xor(m1, off, 64)); M1 = fmax(M1, __shfl_xor(M1, off, 64));
         }
@@ -632,7 +633,7 @@ __global__ void __launch_bounds__(GC_TB) k_gm_tables(GmTabArgs a)
             // start of the run of pairable elements the element is in: inclusive max scan of (run start ? i : 0)
             int st = (in && !pairable) ? i : 0;
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
+            for (int off = 1; off < 64; off <<= 1) {   // a scan: open-coded, see wave.hpp
                 const int o = __shfl_up(st, off, 64);
                 if (lane >= off) st = max(st, o);
             }
@@ -730,14 +731,6 @@ constexpr int64_t GW_DENSE_MAX = 2048;         // D * (S + 1)
 constexpr int GW_KC = 520 * 4;                 // bytes of a [GC_CG] array of words
 constexpr uint32_t GW_PAD = 0x3fffffu;         // 22-bit key of a slot that takes no part (no chain / chain of another pass)
 
-__device__ __forceinline__ void wave_sync()
-{
-    // the lanes of a wavefront run in lockstep: wait for its LDS operations, keep the compiler from moving memory
-    // operations across
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // LDS of a wavefront: kc[GC_CG] (pass of the chain slot << 22 | 22-bit key: (B << 11) | A, GW_PAD: no chain), then
 //   count: the bitsets C / F / X [3 D W], mark [dense], linepass / linesplit [D]
 //   fill : skp[GC_CG] sort words, nmw[32], clist[128] u16, bits[64], wpre[64], the image of a consumer's weight record
@@ -821,7 +814,7 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
         uint8_t *linesplit = linepass + ((a.D + 3) & ~(int64_t)3);
         for (int i = lane; i < 3 * a.D * W; i += 64) bC[i] = 0;
         for (int i = lane; i < a.D; i += 64) { linepass[i] = 0; linesplit[i] = 0; }
-        wave_sync();
+        wave_lds_sync();
         for (int i = lane; i < GC_CG; i += 64) {
             const uint32_t k22 = kc[i] & GW_PAD;
             if (k22 == GW_PAD) continue;
@@ -833,11 +826,11 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
             atomicOr(&bF[df * W + ((sc + 1) >> 5)], 1u << ((sc + 1) & 31));
             atomicOr(&bX[dc * W + (sc >> 5)], 1u << (sc & 31));
         }
-        wave_sync();
+        wave_lds_sync();
         int np = 0;
         if (lane == 0) np = gm_count_passes(bC, bF, bX, mark, linepass, linesplit, (int)a.D, W, S, S1, a.cap, a.S);
-        wave_sync();
-        np = __shfl(np, 0, 64);
+        wave_lds_sync();
+        np = __shfl(np, 0, 64);   // lane broadcast: open-coded, see wave.hpp
         for (int i = lane; i < GC_CG; i += 64) {
             const uint32_t k22 = kc[i] & GW_PAD;
             uint8_t cp = 0xff;
@@ -867,12 +860,12 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
         const int64_t v0 = a.voff ? (int64_t)a.voff[gtp] : p;
         uint32_t moved = 0;
         auto row_of = [&](uint32_t sl) { const uint32_t d = sl / S1u, s1 = sl % S1u; return d * S + (s1 ? s1 - 1 : S - 1); };
-        wave_sync();
+        wave_lds_sync();
         for (int k = 0; k < npass; k++) {
             // dense slots of the pass -> compact slots; the sort words of the pass: (key, pads: all ones) << 6 | slot in the
             // consumer -- unique inside a consumer
             bits[lane] = 0;
-            wave_sync();
+            wave_lds_sync();
             for (int i = lane; i < GC_CG; i += 64) {
                 const uint32_t w = kc[i];
                 const bool mine = (w >> 22) == (uint32_t)k;          // (no chain: pass 0xff)
@@ -884,12 +877,12 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
                 atomicOr(&bits[sb >> 5], 1u << (sb & 31));
                 atomicOr(&bits[(sb + 1) >> 5], 1u << ((sb + 1) & 31));
             }
-            wave_sync();
+            wave_lds_sync();
             const uint32_t word = bits[lane];
             const int cnt = __popc(word);
             int incl = cnt;
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
+            for (int off = 1; off < 64; off <<= 1) {   // a scan: open-coded, see wave.hpp
                 const int o = __shfl_up(incl, off, 64);
                 if (lane >= off) incl += o;
             }
@@ -911,7 +904,7 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
                 for (int q = 0; q < GC_NCHAIN; q++) nmem += (skp[lane * GC_NCHAIN + q] >> 6) != GW_PAD;
                 nmw[lane] = (uint8_t)nmem;
             }
-            wave_sync();
+            wave_lds_sync();
             auto cidx = [&](uint32_t x) { return wpre[x >> 5] + (uint32_t)__popc(bits[x >> 5] & ((1u << (x & 31)) - 1u)); };
             // ---- row requests: pairs of compact neighbours whose rows ascend by less than 256, singles otherwise; elements
             // lane and lane + 64
@@ -929,12 +922,12 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
                 // start of the run of pairable elements the element is in: inclusive max scan of (run start ? i : 0)
                 int st = (in && !pairable) ? i : 0;
 #pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
+                for (int off = 1; off < 64; off <<= 1) {   // a scan: open-coded, see wave.hpp
                     const int o = __shfl_up(st, off, 64);
                     if (lane >= off) st = max(st, o);
                 }
                 st = max(st, carry_st);
-                carry_st = __shfl(st, 63, 64);
+                carry_st = __shfl(st, 63, 64);   // lane broadcast: open-coded, see wave.hpp
                 const bool leads = in && (((i - st) & 1) == 0);        // first row of a pair, or a single
                 uint32_t r_n = 0;
                 bool pair = false;
@@ -997,7 +990,7 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
                 // the word behind the slot's in the walk: the words by position, one LDS round trip (a running minimum of
                 // the larger words inside the loop above cost three more instructions per comparison)
                 if (act) srt[r] = mysk;
-                wave_sync();
+                wave_lds_sync();
                 const uint32_t succ = (act && r + 1 < GC_NCHAIN) ? srt[r + 1] : 0xffffffffu;
                 // (a successor that is a pad -- all ones above the key -- or none at all: the walk's last chain opens nothing)
                 const bool next_opens = mine && succ != 0xffffffffu && (succ >> 6) != GW_PAD && (succ >> 6) != k22;
@@ -1019,17 +1012,17 @@ __global__ void __launch_bounds__(64 * GW_NW) k_gm_tables_w(GmTabArgs a, int wst
                         // chains of the consumer in this step: the walk leaves the step at the first checkpoint behind them
                         if (j == 0) dimg[GR_D_NCH] = (uint32_t)nmem_w;
                     }
-                    wave_sync();
+                    wave_lds_sync();
                     char *wdst = a.wtab + ((gt * GC_NCONS + w) * (a.smax + 1) + s) * (int64_t)GR_WSTRIDE;
                     for (int e = lane; e < GR_WSTRIDE / 16; e += 64)
                         *reinterpret_cast<double2 *>(wdst + e * 16) = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(wimg) + e * 16);
                     uint32_t *ddst = a.dtab + ((gt * GC_NCONS + w) * (a.smax + 1) + s) * GR_DLINE;
                     if (lane < GR_DLINE / 4)
                         *reinterpret_cast<uint4 *>(ddst + lane * 4) = *reinterpret_cast<const uint4 *>(dimg + lane * 4);
-                    wave_sync();
+                    wave_lds_sync();
                 }
             }
-            wave_sync();
+            wave_lds_sync();
         }
         if (lane == 0) a.ucount[gtp] = moved;
         // the request lines behind the last step of the (group, target) stay empty: the loaders read three steps ahead

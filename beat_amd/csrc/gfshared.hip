@@ -36,6 +36,7 @@
 // synthetics (tests/test_gpu_parity.py).
 #include "kernels.hpp"
 #include "misfit.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -62,12 +63,6 @@ struct GroupTabArgs {
     double *w;         // nn: [v][(g*P+p)][CG]   ml: [v][((g*T+t)*P+p)*4 + k][CG]
     int64_t w_var_stride;
 };
-
-__device__ __forceinline__ void wave_lds_fence()
-{
-    // the lanes of a wavefront run in lockstep: wait for its LDS operations, no barrier needed
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
 
 // one workgroup of CG threads per (group, target, patch); thread <-> chain
 __global__ void k_gf_group_tables(GroupTabArgs a)
@@ -164,7 +159,7 @@ __global__ void k_gf_group_tables(GroupTabArgs a)
             if (r1 < total && rank1 < 32) slt[r1] = (uint32_t)rank1;
             if (r0 < total) wsum[rank0] = (uint32_t)r0;   // rank -> list position (wsum is free here)
             if (r1 < total) wsum[rank1] = (uint32_t)r1;
-            wave_lds_fence();
+            wave_lds_sync();
             // window state in lanes 0..31
             uint32_t wmask = 0;
             int wcnt = 0;
@@ -178,8 +173,7 @@ __global__ void k_gf_group_tables(GroupTabArgs a)
                 const uint32_t mm = gmask[lst[ridx]];
                 int cost = (tid < 32 && wcnt < a.depth)
                     ? ((__popc(wmask & mm) << 12) | (wcnt << 6) | tid) : 0x7fffffff;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) cost = min(cost, __shfl_xor(cost, off, 64));
+                cost = wave_butterfly<OpMin>(cost);
                 const int w = cost & 63;
                 if (tid == w) {
                     slt[ridx] = (uint32_t)(w + 32 * wcnt);
@@ -1717,7 +1711,7 @@ __global__ void __launch_bounds__(WS_CG) k_ws_tables(WsTabArgs a)
             if (r1 < n && rank1 < 32) slt[base + r1] = (uint16_t)rank1;
             if (r0 < n) rk2i[wv][rank0] = (uint8_t)r0;
             if (r1 < n) rk2i[wv][rank1] = (uint8_t)r1;
-            wave_lds_fence();
+            wave_lds_sync();
             uint32_t wmask = 0;
             int wcnt = 0;
             if (lane < 32) {
@@ -1728,8 +1722,7 @@ __global__ void __launch_bounds__(WS_CG) k_ws_tables(WsTabArgs a)
                 const int ridx = (int)rk2i[wv][rk];
                 const uint32_t mm = gm[base + ridx];
                 int cost = (lane < 32 && wcnt < depth) ? ((__popc(wmask & mm) << 12) | (wcnt << 6) | lane) : 0x7fffffff;
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) cost = min(cost, __shfl_xor(cost, off, 64));
+                cost = wave_butterfly<OpMin>(cost);
                 const int w = cost & 63;
                 if (lane == w) {
                     slt[base + ridx] = (uint16_t)(w + 32 * wcnt);

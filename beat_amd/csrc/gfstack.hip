@@ -284,7 +284,7 @@ __device__ __forceinline__ void gfstack_tile(const GfArgs &a, const int64_t bid)
                     q = fma(t0, t0, q);
                 }
             }
-        for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
+        for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);   // wave_tree<OpAdd> (wave.hpp); the call changes the code
         __shared__ double red[4];
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = q;
         __syncthreads();

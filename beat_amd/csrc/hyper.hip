@@ -18,6 +18,7 @@
 // hyper_like below, shared with k_hyper_logp).
 #include "kernels.hpp"
 #include "metropolis.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -44,20 +45,10 @@ __device__ __forceinline__ double hyper_like(const double *terms, const LikeGrou
     for (int g = 0; g < grp.n; g++) {
         double s = 0.0;
         for (int k = k0 + lane; k < grp.end[g]; k += 64) s += terms[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        total += s;
+        total += wave_butterfly<OpAdd>(s);
         k0 = grp.end[g];
     }
     return total;
-}
-
-// what one lane wrote to LDS is read by other lanes of ITS wavefront only
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct HyperTables {
@@ -85,7 +76,7 @@ __global__ void __launch_bounds__(64 * HY_WAVES) k_hyper_logp(HyperTables t, int
         terms[k] = v;
         out[k] = v;
     }
-    wave_lds_sync();
+    wave_lds_fence_acqrel();
     const double like = hyper_like(terms, t.grp, lane);
     if (lane == 0) out[t.nterm] = like;
 }
@@ -149,7 +140,7 @@ __global__ void __launch_bounds__(64 * HY_WAVES) k_hyper_chain(HyperChainArgs a)
     const int npair = (nh + 1) / 2;
     const int64_t width = nh + nterm + 1;
     const int64_t first_rec = (a.n_steps - 1) % a.bt;
-    wave_lds_sync();
+    wave_lds_fence_acqrel();
 
     for (int64_t s = 0; s < a.n_steps; s++) {
         // BatchedMetropolis._tune_if_due, ahead of the step's draws
@@ -171,9 +162,9 @@ __global__ void __launch_bounds__(64 * HY_WAVES) k_hyper_chain(HyperChainArgs a)
         const double log_u = philox_log_u(gc, step, k0, k1);
         // outside the box: rejected without evaluation (metropolis.py:341-343, 383-385)
         if (__all(ok ? 1 : 0)) {
-            wave_lds_sync();
+            wave_lds_fence_acqrel();
             for (int k = lane; k < nterm; k += 64) prop[k] = hyper_term(skind[k], sM[k], sslog[k], hp[shp[k]], llk[k]);
-            wave_lds_sync();
+            wave_lds_fence_acqrel();
             const double lp = hyper_like(prop, a.t.grp, lane);
             if (metropolis_accept(1.0, lp, lcur, log_u)) {      // k_accept with beta = 1
                 for (int j = lane; j < npair; j += 64) {      // (the lane that draws a pair owns its h)
@@ -189,14 +180,14 @@ __global__ void __launch_bounds__(64 * HY_WAVES) k_hyper_chain(HyperChainArgs a)
         sut -= 1;
         // the reference's buffer[-1::-buffer_thinning], reversed (beat/backend.py:113-115)
         if (a.trace && (a.n_steps - 1 - s) % a.bt == 0) {
-            wave_lds_sync();
+            wave_lds_fence_acqrel();
             double *row = a.trace + (((s - first_rec) / a.bt) * a.C + c) * width;
             for (int k = lane; k < nh; k += 64) row[k] = h[k];
             for (int k = lane; k < nterm; k += 64) row[nh + k] = cur[k];
             if (lane == 0) row[nh + nterm] = lcur;
         }
     }
-    wave_lds_sync();
+    wave_lds_fence_acqrel();
     for (int k = lane; k < nh; k += 64) a.H[c * nh + k] = h[k];
     for (int k = lane; k < nterm; k += 64) a.LL[c * ld + k] = cur[k];
     if (lane == 0) {

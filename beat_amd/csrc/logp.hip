@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(256) k_scalar_quad(int64_t C, int64_t nd, int6
         const double t = wd * x[k];
         q = fma(t, t, q);
     }
-    for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_down(q, off, 64);   // wave_tree<OpAdd> (wave.hpp); the call changes the code
     if (lane == 0) quad[i] = q;
 }
 

@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -141,13 +142,6 @@ __global__ void __launch_bounds__(256) k_lsq_gram(LsqSeisArgs a)
     }
 }
 
-__device__ __forceinline__ double lsq_wave_sum(double v)
-{
-    // butterfly: every lane ends with the same bits (each level adds the same two values in either lane)
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <int ML>
 __global__ void __launch_bounds__(256) k_lsq_rhs(LsqSeisArgs a)
 {
@@ -164,7 +158,7 @@ __global__ void __launch_bounds__(256) k_lsq_rhs(LsqSeisArgs a)
         const double *d = a.data + t * a.N;
         for (int64_t n = lane; n < a.N; n += 64) s = fma(lsq_row_value<ML>(a.G, ro, fa, a.N, n), d[n], s);
     }
-    s = lsq_wave_sum(s);
+    s = wave_butterfly<OpAdd>(s);
     if (lane == 0) a.b[item] = a.accumulate ? a.b[item] + s : s;
 }
 
@@ -248,7 +242,7 @@ __global__ void __launch_bounds__(256) k_lsq_finish(LsqFinishArgs a)
             const double r = geo_corr_subtract<false>(a.corr, Qc, a.corr.pole + c * a.corr.pole_stride, k, a.dgeo[k]);
             s = fma(g[k], r, s);
         }
-        s = lsq_wave_sum(s);
+        s = wave_butterfly<OpAdd>(s);
     }
     if (lane == 0) a.b[item] = a.has_seis ? a.b[item] + s : s;
 }
@@ -308,8 +302,8 @@ __device__ __forceinline__ bool nnls_append(const double *Nc, double *U, int n, 
         s2 = fma(y[k], y[k], s2);
         sz = fma(y[k], z[k], sz);
     }
-    s2 = lsq_wave_sum(s2);
-    sz = lsq_wave_sum(sz);
+    s2 = wave_butterfly<OpAdd>(s2);
+    sz = wave_butterfly<OpAdd>(sz);
     const double d2 = Nc[(int64_t)j * n + j] - s2;
     if (!(d2 > 0.0) || !isfinite(d2)) return false;
     const double d = sqrt(d2);
@@ -342,7 +336,7 @@ __global__ void __launch_bounds__(64) k_nnls(NnlsArgs a)
         bb[i] = v; w[i] = v; x[i] = 0.0; inP[i] = 0;
         bmax = fmax(bmax, fabs(v));
     }
-    for (int off = 32; off > 0; off >>= 1) bmax = fmax(bmax, __shfl_xor(bmax, off, 64));
+    bmax = wave_butterfly<OpFmax>(bmax);
     int status = __any(bad) ? 2 : 0, np = 0, iter = 0;
     const double tol = 10.0 * n * 2.220446049250313e-16 * bmax;
     __syncthreads();
@@ -353,7 +347,7 @@ __global__ void __launch_bounds__(64) k_nnls(NnlsArgs a)
         int bj = n;
         for (int j = lane; j < n; j += 64)
             if (!inP[j] && w[j] > best) { best = w[j]; bj = j; }
-        for (int off = 32; off > 0; off >>= 1) {
+        for (int off = 32; off > 0; off >>= 1) {   // (value, index) pairs: open-coded, see wave.hpp
             const double ob = __shfl_xor(best, off, 64);
             const int oj = __shfl_xor(bj, off, 64);
             if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
@@ -371,7 +365,7 @@ __global__ void __launch_bounds__(64) k_nnls(NnlsArgs a)
             for (int k = np - 1; k >= 0; k--) {
                 double part = 0.0;
                 for (int i = k + 1 + lane; i < np; i += 64) part = fma(U[(int64_t)k * n + i], sp[i], part);
-                part = lsq_wave_sum(part);
+                part = wave_butterfly<OpAdd>(part);
                 if (lane == 0) sp[k] = (z[k] - part) / U[(int64_t)k * n + k];
                 __syncthreads();
             }
@@ -384,7 +378,7 @@ __global__ void __launch_bounds__(64) k_nnls(NnlsArgs a)
                     alpha = fmin(alpha, xi / (xi - sk));
                 }
             }
-            for (int off = 32; off > 0; off >>= 1) {
+            for (int off = 32; off > 0; off >>= 1) {   // two wave_butterfly<OpFmin> (wave.hpp) in one loop: open-coded
                 smin = fmin(smin, __shfl_xor(smin, off, 64));
                 alpha = fmin(alpha, __shfl_xor(alpha, off, 64));
             }

@@ -9,6 +9,7 @@
 //   HalfSinusoidSTF.discretize_t with exponent = 1 (BEAT's default stf_type), the rule stated at k_moment_rate
 // All arithmetic is FP64 with contraction off: tests/momentrate_ref.py restates every kernel operation by operation.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -66,19 +67,6 @@ int launch_moment_magnitude(beatamd_ctx *ctx, int64_t C, int64_t P, const double
     return BEATAMD_OK;
 }
 
-__device__ __forceinline__ double wave_min(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmin(v, __shfl_xor(v, d));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmax(v, __shfl_xor(v, d));
-    return v;
-}
-
 // ---- fault.py:413-420 (the time axis of a subfault), :461-465 (of the total).  One wavefront <-> one draw.
 // Row s < nsub of spans [C, nsub + 1, 2]:   first = floor(min_p start / deltat),
 //                                           count = ceil((max_p start + max_allP duration) / deltat) + 1 - first
@@ -106,7 +94,7 @@ __global__ void __launch_bounds__(64) k_moment_rate_span(int64_t P, int nsub, co
         if (!(d >= 0.0 && d <= 1.79769313486231570815e+308) || !(fabs(t) <= 1.79769313486231570815e+308)) bad = 1;
         dmax = fmax(dmax, d);
     }
-    dmax = wave_max(dmax);
+    dmax = wave_butterfly<OpFmax>(dmax);
     bad = __any(bad);
     int64_t tfirst = 0, tend = 0;
     bool any = false;
@@ -117,8 +105,8 @@ __global__ void __launch_bounds__(64) k_moment_rate_span(int64_t P, int nsub, co
             lo = fmin(lo, st[p]);
             hi = fmax(hi, st[p]);
         }
-        lo = wave_min(lo);
-        hi = wave_max(hi);
+        lo = wave_butterfly<OpFmin>(lo);
+        hi = wave_butterfly<OpFmax>(hi);
         const double a = floor(lo / deltat), b = ceil((hi + dmax) / deltat);
         if (!(fabs(a) <= MR_INDEX_MAX) || !(fabs(b) <= MR_INDEX_MAX)) {
             bad = 1;
@@ -226,8 +214,7 @@ __global__ void __launch_bounds__(64) k_moment_rate(int64_t P, int nsub, const i
                 if (i == lane) a0 = a;
                 part = part + a;
             }
-#pragma unroll
-            for (int dd = 32; dd > 0; dd >>= 1) part = part + __shfl_xor(part, dd);
+            part = wave_butterfly<OpAdd>(part);
             for (int64_t i = lane; i < nt; i += 64) {
                 double a = i == lane ? a0 : mr_amplitude(i, tmin, t0, t1, w, deltat);
                 a = a / part;

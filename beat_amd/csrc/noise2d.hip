@@ -4,6 +4,7 @@
 // (n, n, 2) distance temporary and asks a KD-tree once per point; here every dataset of a composite goes through three
 // launches.  What follows the statistic (autocovariance, scaled Toeplitz, factorisation) is logp.hip's and chol.hip's.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -22,15 +23,6 @@ namespace beatamd {
 // <-> point.  The dataset passes through LDS in tiles of NB_TILE points (east, north, value: 24 KiB), so n is not bounded
 // by LDS; NB_TILE is a multiple of 64, so lane l meets j == l (mod 64) in ascending order across the tiles.
 constexpr int NB_WAVES = 4, NB_THREADS = NB_WAVES * 64, NB_TILE = 1024;
-
-// the halving tree over the 64 partials of a wavefront; lane 0 holds the result (the other lanes' values are not used)
-__device__ __forceinline__ double ball_tree(double v)
-{
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h, 64);
-    return __shfl(v, 0, 64);
-}
 
 // tile [j0, j0 + NB_TILE) of the dataset -> LDS (behind the dataset's end: not read)
 __device__ __forceinline__ void ball_stage(const BallSet s, int64_t j0, const double *coords, const double *data, double *sx,
@@ -70,7 +62,7 @@ __global__ void __launch_bounds__(NB_THREADS) k_ball_maxd2(const BallSet *sets, 
         __syncthreads();
     }
 #pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) {
+    for (int h = 32; h >= 1; h >>= 1) {   // wave_tree<OpSelGreater> (wave.hpp); the call changes the generated code
         const double o = __shfl_down(m, h, 64);
         m = o > m ? o : m;
     }
@@ -136,11 +128,9 @@ __global__ void __launch_bounds__(NB_THREADS) k_ball_rms(const BallSet *sets, co
             }
             __syncthreads();
         }
-        acc = ball_tree(acc);
+        acc = wave_tree_bcast<OpAdd>(acc);   // the halving tree of the order above, lane 0's sum in every lane
         if (pass == 0) {
-#pragma unroll
-            for (int h = 32; h >= 1; h >>= 1) cnt += __shfl_down(cnt, h, 64);
-            cnt = __shfl(cnt, 0, 64);
+            cnt = wave_tree_bcast<OpAdd>(cnt);
             mean = acc / (double)cnt;
         }
     }

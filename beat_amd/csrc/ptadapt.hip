@@ -24,6 +24,7 @@
 // Every accumulator entry is owned by one thread of one workgroup whose geometry is fixed, and sees the rows of its group in
 // index order: the sums depend on (group, replica, order of the calls) alone.  No atomics.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -50,20 +51,6 @@ __global__ void __launch_bounds__(GM_TB) k_gm_ref(const double *Q, int64_t R, in
     double acc = 0.0;
     for (int64_t r = 0; r < R; r++) acc += Q[(g * R + r) * n + j];
     ref[g * n + j] = acc / (double)R;
-}
-
-// fixed-shape tree over the 256 partial values of a workgroup (the same order whatever the launch)
-__device__ __forceinline__ double gm_tree_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = GM_TB / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] = red[tid] + red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 __global__ void __launch_bounds__(GM_TB) k_gm_weights(const double *Q, const double *like, int64_t lstride, int64_t R, int64_t n,
@@ -111,10 +98,10 @@ __global__ void __launch_bounds__(GM_TB) k_gm_weights(const double *Q, const dou
         }
         w[g * R + r] = wr;
     }
-    sw = gm_tree_sum(sw, red);
-    sw2 = gm_tree_sum(sw2, red);
-    cnt = gm_tree_sum(cnt, red);
-    nb = gm_tree_sum(nb, red);
+    sw = block_sum_ldstree<GM_TB>(sw, red);
+    sw2 = block_sum_ldstree<GM_TB>(sw2, red);
+    cnt = block_sum_ldstree<GM_TB>(cnt, red);
+    nb = block_sum_ldstree<GM_TB>(nb, red);
     if (tid == 0) {
         // (nothing finite so far: m stays -inf and there is nothing to rescale)
         const double s = (m_new == -INFINITY) ? 1.0 : exp(m_old - m_new);

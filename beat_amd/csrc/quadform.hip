@@ -20,6 +20,7 @@
 // B lane l -> B[k=l>>4][j=l&15], C/D reg r of lane l -> row (l>>4)+4r, col l&15.
 #include "kernels.hpp"
 #include "misfit.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
@@ -37,20 +38,6 @@ struct QfArgs {
     int nrb, ncb;
     int vec_ok;  // rows of A and X are 16-byte aligned -> double2 loads
 };
-
-// 4 doubles of row `p` starting at k (zero beyond M)
-__device__ __forceinline__ void load4(const double *p, int64_t k, int64_t M, bool row_ok, int vec_ok,
-                                      double (&v)[4])
-{
-    if (row_ok && vec_ok && k + 4 <= M) {
-        const double2 a = *reinterpret_cast<const double2 *>(p + k);
-        const double2 b = *reinterpret_cast<const double2 *>(p + k + 2);
-        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; e++) v[e] = (row_ok && k + e < M) ? p[k + e] : 0.0;
-    }
-}
 
 // BC = chains per block (64 or 128); each of the 4 waves owns 16 rows x BC chains
 template <int BC>
@@ -98,9 +85,9 @@ __global__ void __launch_bounds__(256) k_quadform(QfArgs a)
 
     const int64_t kstart = a.upper_tri ? i0 : 0;
     double av[4], xv[XR][4];
-    load4(Ap, kstart + lk, M, arow_ok, a.vec_ok, av);
+    load4_padded(Ap, kstart + lk, M, arow_ok, a.vec_ok, av);
 #pragma unroll
-    for (int r = 0; r < XR; r++) load4(Xp[r], kstart + lk, M, x_ok[r], a.vec_ok, xv[r]);
+    for (int r = 0; r < XR; r++) load4_padded(Xp[r], kstart + lk, M, x_ok[r], a.vec_ok, xv[r]);
     int buf = 0;
     for (int64_t k0 = kstart; k0 < M; k0 += QF_KB) {
         // stage tile k0 (already in registers) into LDS buffer `buf`
@@ -113,9 +100,9 @@ __global__ void __launch_bounds__(256) k_quadform(QfArgs a)
         __syncthreads();
         // global loads of the next tile fly during this tile's MFMAs
         if (k0 + QF_KB < M) {
-            load4(Ap, k0 + QF_KB + lk, M, arow_ok, a.vec_ok, av);
+            load4_padded(Ap, k0 + QF_KB + lk, M, arow_ok, a.vec_ok, av);
 #pragma unroll
-            for (int r = 0; r < XR; r++) load4(Xp[r], k0 + QF_KB + lk, M, x_ok[r], a.vec_ok, xv[r]);
+            for (int r = 0; r < XR; r++) load4_padded(Xp[r], k0 + QF_KB + lk, M, x_ok[r], a.vec_ok, xv[r]);
         }
 #pragma unroll
         for (int kk = 0; kk < QF_KB / 4; kk++) {
@@ -136,7 +123,7 @@ __global__ void __launch_bounds__(256) k_quadform(QfArgs a)
         s = fma(acc[j][1], acc[j][1], s);
         s = fma(acc[j][2], acc[j][2], s);
         s = fma(acc[j][3], acc[j][3], s);
-        s += __shfl_xor(s, 16, 64);
+        s += __shfl_xor(s, 16, 64);   // partial butterfly over the four row groups: open-coded, see wave.hpp
         s += __shfl_xor(s, 32, 64);
         if (lane < 16) red[wave][j * 16 + lane] = s;
     }
@@ -278,7 +265,7 @@ __global__ void __launch_bounds__(64 * QS_MAXW) k_quadform_small(QsArgs a)
         sq = fma(acc[1], acc[1], sq);
         sq = fma(acc[2], acc[2], sq);
         sq = fma(acc[3], acc[3], sq);
-        sq += __shfl_xor(sq, 16, 64);
+        sq += __shfl_xor(sq, 16, 64);   // partial butterfly: open-coded, see wave.hpp
         sq += __shfl_xor(sq, 32, 64);
         wsum += sq;
     }
@@ -384,7 +371,7 @@ __global__ void __launch_bounds__(256) k_band_rowmax(const double *A, int64_t nr
         const unsigned long long u = (v == v) ? (unsigned long long)__double_as_longlong(v) : 0x7ff8000000000000ull;
         m = u > m ? u : m;
     }
-    for (int off = 32; off; off >>= 1) {
+    for (int off = 32; off; off >>= 1) {   // wave_tree<OpSelGreater> (wave.hpp); the call changes the generated code
         const unsigned long long o = __shfl_down(m, off);
         m = o > m ? o : m;
     }
@@ -418,13 +405,10 @@ __global__ void __launch_bounds__(256) k_band_width(const double *A, int64_t nro
         }
     }
     if (PASS == 0) {
-        for (int off = 32; off; off >>= 1) b = max(b, __shfl_down(b, off));
+        b = wave_tree<OpMax>(b);
         if ((threadIdx.x & 63) == 0 && b) atomicMax(band, b);
     } else {
-        for (int off = 32; off; off >>= 1) {
-            const unsigned long long o = __shfl_down(dr, off);
-            dr = o > dr ? o : dr;
-        }
+        dr = wave_tree<OpSelGreater>(dr);
         if ((threadIdx.x & 63) == 0 && dr) atomicMax(dropped, dr);
     }
 }
@@ -517,7 +501,7 @@ __global__ void __launch_bounds__(256) k_quadform_banded(QbArgs a)
 #pragma unroll
     for (int j = 0; j < QB_NC; j++) {
         double v = q[j];
-        for (int off = 32; off; off >>= 1) v += __shfl_down(v, off);
+        for (int off = 32; off; off >>= 1) v += __shfl_down(v, off);   // wave_tree<OpAdd> (wave.hpp); the call changes the code
         if ((tid & 63) == 0) red[j][tid >> 6] = v;
     }
     __syncthreads();

@@ -17,38 +17,11 @@
 // gathered arrays.
 #include "kernels.hpp"
 #include "metropolis.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
 
 constexpr int SMC_TB = 1024;  // one workgroup of 16 wavefronts
-
-// deterministic block-wide sum: butterfly inside each wavefront (every lane ends with the same
-// value), then the 16 wavefront sums added in wavefront order by every thread
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();   // previous users of sh are done
-    if ((threadIdx.x & 63) == 0) sh[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < nw; w++) s += sh[w];
-    return s;
-}
-
-__device__ __forceinline__ double block_max(double v, double *sh)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[wave] = v;
-    __syncthreads();
-    double s = sh[0];
-    for (int w = 1; w < nw; w++) s = fmax(s, sh[w]);
-    return s;
-}
 
 // smc.py:133-165.  mode 0: bisection -> out[0] = new beta, out[1] = old beta, weights of the last
 // bisection midpoint (exactly what the reference returns: `temp` of the final loop iteration).
@@ -61,7 +34,7 @@ __global__ void __launch_bounds__(SMC_TB) k_smc_calc_beta(const double *lik, int
     const int tid = threadIdx.x;
     double m = -INFINITY;
     for (int64_t i = tid; i < n; i += SMC_TB) m = fmax(m, lik[i * stride]);
-    const double lmax = block_max(m, sh);
+    const double lmax = block_max_waveorder(m, sh);
 
     double low = beta, up = 2.0, cur = beta, total = 0.0;
     double step = dbeta;
@@ -73,7 +46,7 @@ __global__ void __launch_bounds__(SMC_TB) k_smc_calc_beta(const double *lik, int
         }
         double s = 0.0;
         for (int64_t i = tid; i < n; i += SMC_TB) s += exp(step * (lik[i * stride] - lmax));
-        total = block_sum(s, sh);
+        total = block_sum_waveorder(s, sh);
         if (mode == 1) break;
         const double mean = total / (double)n;
         double q = 0.0;
@@ -81,7 +54,7 @@ __global__ void __launch_bounds__(SMC_TB) k_smc_calc_beta(const double *lik, int
             const double d = exp(step * (lik[i * stride] - lmax)) - mean;
             q += d * d;
         }
-        const double var = block_sum(q, sh) / (double)n;
+        const double var = block_sum_waveorder(q, sh) / (double)n;
         const double cov_temp = sqrt(var) / mean;     // np.std(temp) / np.mean(temp)
         if (cov_temp > cv) up = cur; else low = cur;
         more = up - low > 1e-6;
@@ -171,7 +144,7 @@ __global__ void __launch_bounds__(256) k_pop_factor(const double *X, int64_t ldx
         s2 += wi * wi;
     }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int off = 32; off > 0; off >>= 1) {   // two wave_butterfly<OpAdd> (wave.hpp) in one loop: open-coded
         s1 += __shfl_xor(s1, off, 64);
         s2 += __shfl_xor(s2, off, 64);
     }

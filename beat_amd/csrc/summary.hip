@@ -267,7 +267,7 @@ __device__ __forceinline__ int td_setup(const TdArgs &a, TdSetup &S, const doubl
     int v = cnt;
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
+    for (int d = 1; d < 64; d <<= 1) {   // a scan: open-coded (the reductions are wave.hpp's)
         const int n = __shfl_up(v, d);
         if (lane >= d) v += n;
     }

@@ -15,15 +15,9 @@
 //
 // Built with -ffp-contract=off: no FMA contraction, the C expression order is kept.
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace beatamd {
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    // all lanes of a wavefront run in lockstep; wait for the wave's outstanding LDS
-    // operations and stop the compiler from moving LDS accesses across this point
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
 
 // fast_sweep_ext.c:65-75
 __device__ __forceinline__ double eq_solve(double a, double b, double f, double h)
@@ -249,8 +243,7 @@ __device__ __forceinline__ void sweep_wave(double *t, double *told, const double
             double dlt = t[k] - told[k];
             e += dlt * dlt;
         }
-        for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off, 64);
-        err = e;
+        err = wave_butterfly<OpAdd>(e);
         if (fabs(err - 0.1) <= 1e-9) {
             // the decision is within reach of the summation order: redo the sum in the
             // reference's sequential order

@@ -63,6 +63,40 @@ def test_product_never_imports_oracle():
                 assert "oracle/" not in txt and "oracle." not in txt, path
 
 
+def test_wavefront_reductions_live_in_wave_hpp():
+    """the butterfly, the halving tree and the wavefront-local LDS fence are stated in csrc/wave.hpp; the device sources
+    call them.  Every loop still written out is counted here (shuffle calls per file), so a new one is a decision."""
+    open_coded = {
+        "__shfl_xor(": {
+            "quadform.hip": 4,    # two partial butterflies (xor 16 and 32 only)
+            "lsq.hip": 4,         # the (value, index) argmax; smin and alpha in one loop
+            "smc.hip": 2,         # s1 and s2 in one loop
+            "gfcell.hip": 4,      # the four key extents in one loop
+            "chol.hip": 1,        # k_triu_solve_vec's row sums: a call changes the generated code
+        },
+        "__shfl_down(": {         # a call changes the generated code at each of these
+            "quadform.hip": 2,    # k_band_rowmax, k_quadform_banded
+            "noise2d.hip": 1,     # k_ball_maxd2
+            "logp.hip": 1,        # k_scalar_quad
+            "gfstack.hip": 1,     # the streaming kernel's scalar misfit
+        },
+    }
+    csrc = os.path.join(ROOT, "beat_amd", "csrc")
+    found = {k: {} for k in open_coded}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".hpp")) or f == "wave.hpp":
+            continue
+        txt = open(os.path.join(csrc, f)).read()
+        for call in open_coded:
+            if txt.count(call):
+                found[call][f] = txt.count(call)
+        # the fence as a statement of its own (the BA_* wait macros carry operands and further instructions)
+        assert '"s_waitcnt lgkmcnt(0)"' not in txt, f
+    assert found == open_coded
+    wave = open(os.path.join(csrc, "wave.hpp")).read()
+    assert wave.count('"s_waitcnt lgkmcnt(0)"') == 1
+
+
 def test_parameter_layout_and_bounds():
     from beat_amd.models import ParameterLayout, prior_logp_func
     lay = ParameterLayout({"uparr": 3, "durations": 3, "time": 1})
