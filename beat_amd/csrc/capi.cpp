@@ -2052,6 +2052,9 @@ int beatamd_smc_calc_beta(beatamd_ctx *ctx, int64_t C, const double *likelihoods
     ENTER(ctx);
     BA_CHECK(likelihoods && beta_new && weights && C > 0 && stride > 0, BEATAMD_EINVAL,
              "smc_calc_beta: bad argument");
+    // smc.py:152: the bisection runs while 2 - beta > 1e-6; past that the reference has no midpoint to return (it fails
+    // on an unbound name) and the kernel would divide the weights by a total it never summed
+    BA_CHECK(2.0 - beta > 1e-6, BEATAMD_EINVAL, "smc_calc_beta: beta = %g leaves no tempering step below 2", beta);
     Staging st(ctx);
     const double *d_l;
     double *d_w, *d_out;

@@ -49,6 +49,8 @@ class HostOps(object):
 
     def calc_beta(self, like, beta, coef_variation):
         lk = self._np(like).astype(np.float64)
+        if not 2.0 - beta > 1e-6:   # the bisection interval [beta, 2] is already closed: no midpoint, no weights
+            raise ValueError("calc_beta: beta = %r leaves no tempering step below 2" % (beta,))
         lo, hi, shifted = beta, 2.0, lk - lk.max()
         mid, temp = beta, None
         while hi - lo > 1e-6:

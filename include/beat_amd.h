@@ -626,7 +626,9 @@ int beatamd_ball_rms_batch(beatamd_ctx *ctx, int64_t nd, const int64_t *sizes,
  *   likelihoods: C values `stride` doubles apart (the `like` column of L: stride = nllk)
  *   -> *beta_new (host), weights [C] (importance weights of the last bisection midpoint,
  *      normalised).  exp() is the device's (<= 1 ulp from glibc/numpy): weights agree with
- *      the reference to ~1e-15 relative, beta exactly unless a bisection decision sits on a tie. */
+ *      the reference to ~1e-15 relative, beta exactly unless a bisection decision sits on a tie.
+ *   beta must leave an interval to halve, 2 - beta > 1e-6 (the reference's loop condition; it has
+ *   nothing to return otherwise): BEATAMD_EINVAL. */
 int beatamd_smc_calc_beta(beatamd_ctx *ctx, int64_t C, const double *likelihoods, int64_t stride,
                           double beta, double coef_variation, double *beta_new, double *weights);
 /* final stage (smc.py:526-529): weights = exp(dbeta (l - max l)) / sum */
