@@ -123,6 +123,137 @@ def solution_bound(A, m_ref):
     return 1e3 * EPS * passive_cond(A, m_ref) ** 2 * float(np.abs(m_ref).max())
 
 
+def decision_floor(A, m):
+    """the smallest margin (a fraction of its decision's scale) at which a float64 active set through the normal equations
+    is held to take the decisions of the exact one: the relative error solution_bound allows to a solution.  A condition
+    on the inputs of a decision-exact test, checked on the reference alone."""
+    return 1e3 * EPS * passive_cond(A, m) ** 2
+
+
+def nnls_system(n, seed, rho, frac, noise, rows=None):
+    """a seeded system (A [rows, n], d [rows]) for the active set: entries of B multiples of 1/64 in [-127/64, 127/64],
+    A = B + rho (B one column to the left + B one column to the right, zeros shifted in), x_true uniform in (0.5, 2) with
+    probability frac, else 0, d = A x_true + noise sqrt(n) standard normal.  rho = 0: removals are rare; rho = 0.45:
+    neighbouring columns correlate, variables leave the passive set often, cond_2 of the passive columns stays below 20."""
+    rng = np.random.default_rng(seed)
+    rows = 2 * n if rows is None else int(rows)
+    B = rng.integers(-127, 128, (rows, n)) / 64.0
+    left, right = np.zeros_like(B), np.zeros_like(B)
+    left[:, :-1], right[:, 1:] = B[:, 1:], B[:, :-1]
+    A = B + rho * (left + right)
+    x_true = np.where(rng.random(n) < frac, rng.uniform(0.5, 2.0, n), 0.0)
+    d = A @ x_true + noise * np.sqrt(n) * rng.standard_normal(rows)
+    return A, d
+
+
+LD = np.longdouble
+EPS_LD = float(np.finfo(LD).eps)
+
+
+def _solve_refined(NL, bL, idx):
+    """N_PP s = b_P: a float64 Cholesky solve and two refinements on the long-double residual -> (s, |residual|_2 + the
+    bound of the residual's own rounding: over lambda_min(N_PP) it bounds |s - exact|_2)"""
+    from scipy.linalg import cho_factor, cho_solve
+    Npp = NL[np.ix_(idx, idx)]
+    bp = bL[idx]
+    cf = cho_factor(Npp.astype(np.float64))
+    s = cho_solve(cf, bp.astype(np.float64)).astype(LD)
+    for _ in range(2):
+        s = s + cho_solve(cf, (bp - Npp @ s).astype(np.float64)).astype(LD)
+    res = bp - Npp @ s
+    own = (len(idx) + 2) * EPS_LD * (np.abs(Npp) @ np.abs(s) + np.abs(bp))
+    return s, float(np.sqrt((res * res).sum()) + np.sqrt((own * own).sum()))
+
+
+def nnls_margins(Nm, b, maxiter=None):
+    """nnls_normal with every compared quantity (w, s, alpha, the interpolated x) in long double -> dict:
+    x (float64), iters, status, removed, events (one (passive variables before the step, variables that left) per removal
+    step), entered (the variables in their order of entry, re-entries included), margins (the smallest of each kind of
+    decision, a fraction of that decision's scale, inf where the decision never came up):
+      arg    largest minus second largest candidate w, over max|b|
+      tol    |w_j - tol| at every entry and at the stop, over max|b|
+      neg    min|s_k| over max|s|, at every solve
+      alpha  the gap between the two smallest ratios x / (x - s)
+      keep   min |x_k - tol| over max|s|, over the variables that stay after a removal step
+    and solve_err, the bound of the solves' own error in the same units: the largest over all solves of |ds| / max|s|,
+    |N|_inf |ds| / max|b| and of the error |ds| gives a ratio, with |ds| <= |residual| / lambda_min(N_EE), E the variables
+    that ever entered (Cauchy interlacing: every passive block is a principal block of N_EE)."""
+    NL, bL = np.asarray(Nm, dtype=np.float64).astype(LD), np.asarray(b, dtype=np.float64).astype(LD)
+    n = bL.size
+    maxiter = 3 * n if not maxiter else int(maxiter)
+    bmax = float(np.abs(bL).max())
+    tol = LD(10.0 * n * EPS * bmax)                    # the kernel's float64 number
+    norm_inf = float(np.abs(NL).sum(axis=1).max())
+    mg = dict(arg=np.inf, tol=np.inf, neg=np.inf, alpha=np.inf, keep=np.inf)
+    x, w = np.zeros(n, dtype=LD), bL.copy()
+    passive, inP, entered, events = [], np.zeros(n, dtype=bool), [], []
+    iters = removed = status = 0
+    raw_err = 0.0
+
+    def result():
+        solve_err = 0.0
+        if entered:
+            E = np.unique(entered)
+            ev = np.linalg.eigvalsh(NL[np.ix_(E, E)].astype(np.float64))
+            assert ev[0] > 1e-10 * ev[-1], "nnls_margins: the entered block is not safely positive definite"
+            solve_err = raw_err / float(ev[0])
+        return dict(x=x.astype(np.float64), iters=iters, status=status, removed=removed, events=events, entered=entered,
+                    margins=dict((k, float(v)) for k, v in mg.items()), solve_err=solve_err)
+
+    while len(passive) < n:
+        cand = np.where(~inP, w, -np.inf)
+        j = int(np.argmax(cand))
+        if bmax == 0.0:
+            break
+        mg["tol"] = min(mg["tol"], abs(cand[j] - tol) / bmax)
+        if not cand[j] > tol:
+            break
+        if n - len(passive) > 1:
+            second = np.partition(cand, n - 2)[n - 2]
+            mg["arg"] = min(mg["arg"], (cand[j] - second) / bmax)
+        passive.append(j)
+        entered.append(j)
+        inP[j] = True
+        while True:
+            if iters >= maxiter:
+                status = 1
+                return result()
+            iters += 1
+            idx = np.array(passive)
+            s, ds = _solve_refined(NL, bL, idx)
+            smax = float(np.abs(s).max())
+            raw_err = max(raw_err, ds / smax, norm_inf * ds / bmax)
+            mg["neg"] = min(mg["neg"], np.abs(s).min() / smax)
+            if not s.min() < 0:
+                break
+            neg = s < 0
+            xp = x[idx]
+            ratio = xp[neg] / (xp[neg] - s[neg])
+            raw_err = max(raw_err, float((ds * (np.abs(xp[neg]) + np.abs(s[neg])) / (xp[neg] - s[neg]) ** 2).max()))
+            if ratio.size > 1:
+                two = np.partition(ratio, 1)[:2]
+                mg["alpha"] = min(mg["alpha"], two[1] - two[0])
+            alpha = ratio.min()
+            xp = xp * (1 - alpha) + alpha * s
+            x[idx] = xp
+            keep = xp > tol
+            if keep.any():
+                mg["keep"] = min(mg["keep"], np.abs(xp[keep] - tol).min() / smax)
+            events.append((len(passive), int((~keep).sum())))
+            removed += int((~keep).sum())
+            for k in idx[~keep]:
+                inP[k] = False
+                x[k] = 0
+            passive = [k for k in passive if inP[k]]
+            if not passive:
+                s = np.zeros(0, dtype=LD)
+                break
+        x[:] = 0
+        x[np.array(passive, dtype=int)] = s
+        w = bL - NL[:, passive] @ x[passive]
+    return result()
+
+
 def gram_bound(A):
     """entrywise bound of |fl(A^T A) - A^T A| for two floating-point evaluations in any order of summation: each is within
     (n_rows + 2) 2^-53 (|A|^T |A|)_ij of the exact value (n products, n - 1 sums, a mirrored copy or blend rounding)"""
