@@ -172,6 +172,13 @@ _PROTOS = {
     "beatamd_smoothing_correlated": [_vp, _i64, _vp, _i32, _vp],
     "beatamd_model_resolution": [_vp, _i64, _i64, _vp, _vp, _f64, _vp, _vp],
     "beatamd_division_rating": [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _f64, _vp, _vp, _vp, _vp],
+    "beatamd_column_sort": [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _pi64],
+    "beatamd_column_percentiles": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "beatamd_column_histograms": [_vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "beatamd_pair_hist2d": [_vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _pi64],
+    "beatamd_pair_kde2d": [_vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _pi64],
+    "beatamd_unit_vector_sum": [_vp, _i64, _vp, _vp, _i32, _vp],
+    "beatamd_spherical_kde": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _i32, _vp],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["beatamd_last_error", "beatamd_version"])

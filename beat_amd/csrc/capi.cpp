@@ -2636,4 +2636,271 @@ int beatamd_division_rating(beatamd_ctx *ctx, int64_t P, int64_t nobs, const dou
     return st.finish();
 }
 
+// ------------------------------------------------------------------ posterior marginals (marginals.hip)
+// the K column indices idx (either side) of a population of V columns on the host, each in [0, V)
+static int mg_columns(beatamd_ctx *ctx, const char *who, const int64_t *idx, int64_t K, int64_t V, std::vector<int64_t> &h)
+{
+    BA_TRY(host_copy(ctx, idx, (size_t)K, h));
+    for (int64_t k = 0; k < K; k++)
+        BA_CHECK(h[k] >= 0 && h[k] < V, BEATAMD_EINDEX, "%s: column %lld outside a population of %lld columns", who,
+                 (long long)h[k], (long long)V);
+    return BEATAMD_OK;
+}
+
+// BEATAMD_ENAN naming the first of the K columns d_cols (device; h_cols the same on the host) with a non-finite sample
+static int mg_finite(beatamd_ctx *ctx, const char *who, const double *d_X, int64_t n, int64_t V, const int64_t *d_cols,
+                     const std::vector<int64_t> &h_cols, int64_t *bad_col)
+{
+    const int64_t K = (int64_t)h_cols.size();
+    if (bad_col) *bad_col = -1;
+    if (K == 0 || n == 0) return BEATAMD_OK;
+    int32_t *d_flags;
+    BA_TRY(ctx->scratch(SL_MG_FLAG, (size_t)K, &d_flags));
+    BA_TRY(launch_col_check(ctx, d_X, n, V, d_cols, K, d_flags));
+    std::vector<int32_t> f;
+    BA_TRY(host_copy(ctx, (const int32_t *)d_flags, (size_t)K, f));
+    for (int64_t k = 0; k < K; k++)
+        if (f[k]) {
+            if (bad_col) *bad_col = h_cols[k];
+            BA_CHECK(false, BEATAMD_ENAN, "%s: column %lld holds a non-finite sample", who, (long long)h_cols[k]);
+        }
+    return BEATAMD_OK;
+}
+
+int beatamd_column_sort(beatamd_ctx *ctx, int64_t n, int64_t V, const double *X, int64_t K, const int64_t *cols,
+                        double *sorted, int64_t *bad_col)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && V >= 1 && K >= 0 && X && sorted && (cols || K == 0), BEATAMD_EINVAL, "column_sort: bad argument");
+    BA_CHECK(n <= MG_SORT_MAX_N, BEATAMD_EINVAL, "column_sort: %lld samples, at most %lld", (long long)n,
+             (long long)MG_SORT_MAX_N);
+    std::vector<int64_t> hc;
+    BA_TRY(mg_columns(ctx, "column_sort", cols, K, V, hc));
+    if (K == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_X;
+    const int64_t *d_c;
+    double *d_s;
+    BA_TRY(st.in(X, (size_t)n * V, &d_X));
+    BA_TRY(st.in(cols, (size_t)K, &d_c));
+    BA_TRY(mg_finite(ctx, "column_sort", d_X, n, V, d_c, hc, bad_col));
+    BA_TRY(st.out(sorted, (size_t)K * n, &d_s));
+    BA_TRY(launch_col_sort(ctx, d_X, n, V, d_c, K, d_s));
+    return st.finish();
+}
+
+int beatamd_column_percentiles(beatamd_ctx *ctx, int64_t K, int64_t n, const double *sorted, int64_t Q, const double *q,
+                               double *out)
+{
+    ENTER(ctx);
+    BA_CHECK(K >= 0 && n >= 1 && Q >= 0 && sorted && out && (q || Q == 0), BEATAMD_EINVAL, "column_percentiles: bad argument");
+    std::vector<double> hq;
+    BA_TRY(host_copy(ctx, q, (size_t)Q, hq));
+    for (int64_t i = 0; i < Q; i++)
+        BA_CHECK(hq[i] >= 0.0 && hq[i] <= 100.0, BEATAMD_EINVAL, "Percentiles must be in the range [0, 100]");
+    if (K * Q == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_s, *d_q;
+    double *d_o;
+    BA_TRY(st.in(sorted, (size_t)K * n, &d_s));
+    BA_TRY(st.in(q, (size_t)Q, &d_q));
+    BA_TRY(st.out(out, (size_t)K * Q, &d_o));
+    BA_TRY(launch_col_percentiles(ctx, d_s, K, n, d_q, Q, d_o));
+    return st.finish();
+}
+
+// every row of edges [R, m + 1] finite and non-decreasing (numpy: "bins must increase monotonically")
+static int mg_edges(beatamd_ctx *ctx, const char *who, const double *edges, int64_t R, int64_t m)
+{
+    std::vector<double> h;
+    BA_TRY(host_copy(ctx, edges, (size_t)(R * (m + 1)), h));
+    for (int64_t r = 0; r < R; r++)
+        for (int64_t i = 0; i <= m; i++) {
+            const double e = h[r * (m + 1) + i];
+            BA_CHECK(std::isfinite(e) && (i == 0 || e >= h[r * (m + 1) + i - 1]), BEATAMD_EINVAL,
+                     "%s: the edges of row %lld must be finite and increase monotonically", who, (long long)r);
+        }
+    return BEATAMD_OK;
+}
+
+int beatamd_column_histograms(beatamd_ctx *ctx, int64_t K, int64_t n, const double *sorted, int64_t nb, const double *edges,
+                              int64_t *counts)
+{
+    ENTER(ctx);
+    BA_CHECK(K >= 0 && n >= 1 && nb >= 1 && sorted && edges && counts, BEATAMD_EINVAL, "column_histograms: bad argument");
+    BA_TRY(mg_edges(ctx, "column_histograms", edges, K, nb));
+    if (K == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_s, *d_e;
+    int64_t *d_c;
+    BA_TRY(st.in(sorted, (size_t)K * n, &d_s));
+    BA_TRY(st.in(edges, (size_t)K * (nb + 1), &d_e));
+    BA_TRY(st.out(counts, (size_t)K * nb, &d_c));
+    BA_TRY(launch_col_hist(ctx, d_s, K, n, d_e, nb, d_c));
+    return st.finish();
+}
+
+int beatamd_pair_hist2d(beatamd_ctx *ctx, int64_t n, int64_t V, const double *X, int64_t P, const int64_t *pairs, int32_t bx,
+                        int32_t by, const double *xedges, const double *yedges, int64_t *counts, int64_t *bad_col)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && V >= 1 && P >= 0 && X && counts && xedges && yedges && (pairs || P == 0), BEATAMD_EINVAL,
+             "pair_hist2d: bad argument");
+    BA_CHECK(bx >= 1 && by >= 1 && bx <= MG_HIST2D_MAX_SIDE && by <= MG_HIST2D_MAX_SIDE &&
+                 (int64_t)bx * by <= MG_HIST2D_MAX_CELLS,
+             BEATAMD_EINVAL, "pair_hist2d: a grid of %d x %d bins; at most %d cells (128 x 128) and %d bins a side", bx, by,
+             MG_HIST2D_MAX_CELLS, MG_HIST2D_MAX_SIDE);
+    std::vector<int64_t> hp;
+    BA_TRY(mg_columns(ctx, "pair_hist2d", pairs, 2 * P, V, hp));
+    BA_TRY(mg_edges(ctx, "pair_hist2d", xedges, P, bx));
+    BA_TRY(mg_edges(ctx, "pair_hist2d", yedges, P, by));
+    if (P == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_X, *d_ex, *d_ey;
+    const int64_t *d_p;
+    int64_t *d_c;
+    BA_TRY(st.in(X, (size_t)n * V, &d_X));
+    BA_TRY(st.in(pairs, (size_t)2 * P, &d_p));
+    BA_TRY(st.in(xedges, (size_t)P * (bx + 1), &d_ex));
+    BA_TRY(st.in(yedges, (size_t)P * (by + 1), &d_ey));
+    BA_TRY(mg_finite(ctx, "pair_hist2d", d_X, n, V, d_p, hp, bad_col));
+    BA_TRY(st.out(counts, (size_t)P * bx * by, &d_c));
+    BA_TRY(launch_pair_hist2d(ctx, d_X, n, V, d_p, P, bx, by, d_ex, d_ey, d_c));
+    return st.finish();
+}
+
+// numpy.linspace(a, b, m): i * step + a, the last point b itself
+static void mg_linspace(double a, double b, int m, double *out)
+{
+    const double step = m > 1 ? (b - a) / (double)(m - 1) : 0.0;
+    for (int i = 0; i < m; i++) out[i] = (double)i * step + a;
+    if (m > 1) out[m - 1] = b;
+}
+
+int beatamd_pair_kde2d(beatamd_ctx *ctx, int64_t n, int64_t V, const double *X, int64_t P, const int64_t *pairs, int32_t gx,
+                       int32_t gy, int32_t skip_blocks, int32_t shape, double *Z, double *extents, int32_t *flags, int64_t *bad_col)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && V >= 1 && P >= 0 && X && Z && extents && flags && (pairs || P == 0), BEATAMD_EINVAL,
+             "pair_kde2d: bad argument");
+    BA_CHECK(shape >= 0 && shape <= 2, BEATAMD_EINVAL, "pair_kde2d: launch shape %d (0 chosen here, 1 wide, 2 narrow)", shape);
+    BA_CHECK(gx >= 1 && gy >= 1 && (int64_t)gx * gy <= ((int64_t)1 << 24), BEATAMD_EINVAL,
+             "pair_kde2d: a grid of %d x %d points; at most 2^24", gx, gy);
+    std::vector<int64_t> hp;
+    BA_TRY(mg_columns(ctx, "pair_kde2d", pairs, 2 * P, V, hp));
+    if (P == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_X;
+    const int64_t *d_p;
+    BA_TRY(st.in(X, (size_t)n * V, &d_X));
+    BA_TRY(st.in(pairs, (size_t)2 * P, &d_p));
+    BA_TRY(mg_finite(ctx, "pair_kde2d", d_X, n, V, d_p, hp, bad_col));
+    // moments -> per pair the Cholesky factor of cov * n^(-1/3) (scipy.stats.gaussian_kde: Scott's factor n^(-1/6), the
+    // sample covariance with bias=False, the normalisation 1 / (2 pi n sqrt(det))), the extents and the grid
+    double *d_mom;
+    BA_TRY(ctx->scratch(SL_MG_MOM, (size_t)P * MG_NMOM, &d_mom));
+    BA_TRY(launch_pair_moments(ctx, d_X, n, V, d_p, P, d_mom));
+    std::vector<double> mom;
+    BA_TRY(host_copy(ctx, (const double *)d_mom, (size_t)P * MG_NMOM, mom));
+    std::vector<KdePair> par((size_t)P);
+    std::vector<double> grid((size_t)P * (gx + gy)), ext((size_t)P * 4);
+    std::vector<int32_t> fl((size_t)P);
+    const double f2 = std::pow((double)n, -1.0 / 6.0) * std::pow((double)n, -1.0 / 6.0);
+    int64_t nbad = 0;
+    for (int64_t p = 0; p < P; p++) {
+        const double *m = &mom[p * MG_NMOM];
+        KdePair &q = par[p];
+        q = KdePair();
+        q.mx = m[0];
+        q.my = m[1];
+        bool ok = n >= 3 && hp[2 * p] != hp[2 * p + 1];
+        if (ok) {
+            const double c11 = m[2] / (double)(n - 1) * f2, c12 = m[3] / (double)(n - 1) * f2, c22 = m[4] / (double)(n - 1) * f2;
+            ok = std::isfinite(c11) && std::isfinite(c22) && std::isfinite(c12) && c11 > 0.0 && c22 > 0.0;
+            if (ok) {
+                q.l11 = std::sqrt(c11);
+                q.l21 = c12 / q.l11;
+                const double d = c22 - q.l21 * q.l21;
+                // (a remainder within rounding of c22 is a column that is a multiple of the other)
+                ok = d > 4.0 * 2.220446049250313e-16 * c22;
+                if (ok) {
+                    q.l22 = std::sqrt(d);
+                    q.scale = 1.0 / (2.0 * M_PI * (double)n * (q.l11 * q.l22));
+                    ok = std::isfinite(q.scale) && q.scale > 0.0;
+                }
+            }
+        }
+        q.ok = ok ? 1 : 0;
+        fl[p] = ok ? 0 : 1;
+        nbad += !ok;
+        for (int e = 0; e < 4; e++) ext[p * 4 + e] = m[5 + e];
+        mg_linspace(m[5], m[6], gx, &grid[p * (gx + gy)]);
+        mg_linspace(m[7], m[8], gy, &grid[p * (gx + gy) + gx]);
+    }
+    KdePair *d_par;
+    double *d_grid, *d_W, *d_box, *d_Z, *d_ext;
+    int32_t *d_fl;
+    BA_TRY(ctx->scratch(SL_MG_PAR, (size_t)P, &d_par));
+    BA_TRY(ctx->scratch(SL_MG_GRID, grid.size(), &d_grid));
+    BA_TRY(ctx->scratch(SL_MG_W, (size_t)P * n * 2, &d_W));
+    BA_TRY(ctx->scratch(SL_MG_BOX, (size_t)P * kde_sample_blocks(n) * 4, &d_box));
+    BA_HIP(hipMemcpyAsync(d_par, par.data(), par.size() * sizeof(KdePair), hipMemcpyHostToDevice, ctx->stream));
+    BA_HIP(hipMemcpyAsync(d_grid, grid.data(), grid.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    BA_TRY(st.out(Z, (size_t)P * gx * gy, &d_Z));
+    BA_TRY(st.out(extents, (size_t)P * 4, &d_ext));
+    BA_TRY(st.out(flags, (size_t)P, &d_fl));
+    BA_HIP(hipMemcpyAsync(d_ext, ext.data(), ext.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    BA_HIP(hipMemcpyAsync(d_fl, fl.data(), fl.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    BA_TRY(launch_pair_kde2d(ctx, d_X, n, V, d_p, P, d_par, d_W, d_box, d_grid, gx, gy, skip_blocks != 0, shape, d_Z));
+    BA_HIP(hipStreamSynchronize(ctx->stream));   // the host vectors above have gone up
+    BA_TRY(st.finish());
+    BA_CHECK(nbad == 0, BEATAMD_ENOTPSD,
+             "pair_kde2d: %lld of %lld pairs have a scaled covariance without a Cholesky factor (a constant column, a column "
+             "paired with itself or a multiple of the other, fewer than 3 samples); their flags are set and their Z is NaN",
+             (long long)nbad, (long long)P);
+    return BEATAMD_OK;
+}
+
+int beatamd_unit_vector_sum(beatamd_ctx *ctx, int64_t n, const double *lats, const double *lons, int32_t transform, double *S)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && lats && lons && S, BEATAMD_EINVAL, "unit_vector_sum: bad argument");
+    Staging st(ctx);
+    const double *d_la, *d_lo;
+    double *d_U, *d_S;
+    BA_TRY(st.in(lats, (size_t)n, &d_la));
+    BA_TRY(st.in(lons, (size_t)n, &d_lo));
+    BA_TRY(st.out(S, 3, &d_S));
+    BA_TRY(ctx->scratch(SL_MG_W, (size_t)n * 3, &d_U));
+    BA_TRY(launch_sph_unit(ctx, n, d_la, d_lo, transform != 0, d_U));
+    BA_TRY(launch_sph_sum(ctx, n, d_U, d_S));
+    return st.finish();
+}
+
+int beatamd_spherical_kde(beatamd_ctx *ctx, int64_t n, const double *lats0, const double *lons0, int64_t m, const double *lats,
+                          const double *lons, double norm, double sigma2, int32_t shape, double *kde)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && m >= 0 && lats0 && lons0 && kde && ((lats && lons) || m == 0), BEATAMD_EINVAL,
+             "spherical_kde: bad argument");
+    BA_CHECK(shape >= 0 && shape <= 2, BEATAMD_EINVAL, "spherical_kde: launch shape %d (0 chosen here, 1 wide, 2 narrow)", shape);
+    BA_CHECK(std::isfinite(norm) && sigma2 > 0.0 && std::isfinite(sigma2), BEATAMD_EINVAL,
+             "spherical_kde: sigma^2 = %g, norm = %g", sigma2, norm);
+    if (m == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_la0, *d_lo0, *d_la, *d_lo;
+    double *d_U0, *d_Ug, *d_k;
+    BA_TRY(st.in(lats0, (size_t)n, &d_la0));
+    BA_TRY(st.in(lons0, (size_t)n, &d_lo0));
+    BA_TRY(st.in(lats, (size_t)m, &d_la));
+    BA_TRY(st.in(lons, (size_t)m, &d_lo));
+    BA_TRY(st.out(kde, (size_t)m, &d_k));
+    BA_TRY(ctx->scratch(SL_MG_W, (size_t)n * 3, &d_U0));
+    BA_TRY(ctx->scratch(SL_MG_GRID, (size_t)m * 3, &d_Ug));
+    BA_TRY(launch_sph_unit(ctx, n, d_la0, d_lo0, 1, d_U0));
+    BA_TRY(launch_sph_unit(ctx, m, d_la, d_lo, 1, d_Ug));
+    BA_TRY(launch_sph_kde(ctx, n, d_U0, m, d_Ug, norm, sigma2, shape, d_k));
+    return st.finish();
+}
+
 }  // extern "C"

@@ -421,7 +421,8 @@ enum Slot : int {
     SL_CHOL_A, SL_CHOL_X, SL_CHOL_D, SL_CHOL_T, SL_CHOL_L,
     SL_GC_ORDER, SL_GS_ORDER, SL_GC_STREAM, SL_GC_HDR, SL_GC_META, SL_DELTA, SL_LOGU, SL_EDGES, SL_TSLOT, SL_SPLIT, SL_WS_PACK,
     SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_MR_SPANS,
-    SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_SPEC, SL_COUNT
+    SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_SPEC,
+    SL_MG_FLAG, SL_MG_MOM, SL_MG_PAR, SL_MG_GRID, SL_MG_W, SL_MG_BOX, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

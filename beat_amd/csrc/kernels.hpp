@@ -589,4 +589,46 @@ int launch_nnls(beatamd_ctx *ctx, int64_t C, int64_t n, const double *Nmat, cons
 int launch_lsq_scatter(beatamd_ctx *ctx, int64_t C, int64_t P, const double *x, double *Qout, int64_t nparams, int64_t v_off,
                        int64_t zero_off);
 
+// ---- marginals.hip: sorted columns, percentiles, 1-d and 2-d counts and pairwise KDEs of a population X [n, V]
+// (plotting/common.py:248-461, plotting/marginals.py:131-609)
+constexpr int MG_SORT_TILE = 16384;                    // doubles of a column sorted in LDS by one workgroup (128 KiB)
+constexpr int64_t MG_SORT_MAX_N = (int64_t)1 << 24;    // longest column
+constexpr int MG_HIST2D_MAX_CELLS = 128 * 128, MG_HIST2D_MAX_SIDE = 4096;   // the LDS grid of k_pair_hist2d
+constexpr int MG_NMOM = 9;                             // doubles per pair of k_pair_moments
+constexpr int MG_KDE_SB = 1024;                        // samples of a block staged in LDS
+constexpr int MG_KDE_G = 4, MG_KDE_TILE = MG_KDE_G * 256;   // grid points per lane and per workgroup
+constexpr double MG_KDE_SKIP = 745.2;                  // exp(-x) is an exact zero above
+inline int64_t kde_sample_blocks(int64_t n) { return (n + MG_KDE_SB - 1) / MG_KDE_SB; }
+struct KdePair {
+    double mx, my;          // the column means
+    double l11, l21, l22;   // lower Cholesky factor of cov * n^(-1/3)
+    double scale;           // 1 / (2 pi n l11 l22)
+    int32_t ok, pad;        // 0: no factor, Z of the pair is NaN
+};
+// flags [K] = 1 where column cols[k] holds a non-finite sample
+int launch_col_check(beatamd_ctx *ctx, const double *X, int64_t n, int64_t V, const int64_t *cols, int64_t K, int32_t *flags);
+// out [K, n] = the columns cols[k] ascending
+int launch_col_sort(beatamd_ctx *ctx, const double *X, int64_t n, int64_t V, const int64_t *cols, int64_t K, double *out);
+// out [K, Q] = numpy.percentile(., q) of the sorted columns S [K, n]
+int launch_col_percentiles(beatamd_ctx *ctx, const double *S, int64_t K, int64_t n, const double *q, int64_t Q, double *out);
+// counts [K, nb] of the sorted columns on the edges [K, nb + 1] (non-decreasing rows)
+int launch_col_hist(beatamd_ctx *ctx, const double *S, int64_t K, int64_t n, const double *edges, int64_t nb, int64_t *counts);
+// counts [P, bx, by] of the pairs [P, 2] on xedges [P, bx + 1], yedges [P, by + 1]
+int launch_pair_hist2d(beatamd_ctx *ctx, const double *X, int64_t n, int64_t V, const int64_t *pairs, int64_t P, int bx, int by,
+                       const double *xedges, const double *yedges, int64_t *counts);
+// mom [P, MG_NMOM]: means, centred second sums, extents
+int launch_pair_moments(beatamd_ctx *ctx, const double *X, int64_t n, int64_t V, const int64_t *pairs, int64_t P, double *mom);
+// Z [P, gx, gy]; W [P, n, 2], box [P, kde_sample_blocks(n), 4]: device scratch; grid [P, gx + gy]; skip: 0 adds every block;
+// shape: 0 chosen by the launcher, 1 wide (MG_KDE_G points per lane, 256 lanes), 2 narrow (one point per lane, 64 lanes)
+int launch_pair_kde2d(beatamd_ctx *ctx, const double *X, int64_t n, int64_t V, const int64_t *pairs, int64_t P,
+                      const KdePair *par, double *W, double *box, const double *grid, int gx, int gy, int skip, int shape,
+                      double *Z);
+// U [n, 3]: unit vectors of (lat, lon) in degrees; transform: vonmises_fisher's 90 - lat and mod 360 (0: vonmises_std's none)
+int launch_sph_unit(beatamd_ctx *ctx, int64_t n, const double *lat, const double *lon, int transform, double *U);
+// S [3] = sum of the rows of U [n, 3] in a fixed order
+int launch_sph_sum(beatamd_ctx *ctx, int64_t n, const double *U, double *S);
+// kde [m] = sum_i exp(norm + Ug . U0_i / sigma2)
+int launch_sph_kde(beatamd_ctx *ctx, int64_t n, const double *U0, int64_t m, const double *Ug, double norm, double sigma2,
+                   int shape, double *kde);
+
 }  // namespace beatamd

@@ -1027,6 +1027,52 @@ int beatamd_division_rating(beatamd_ctx *ctx, int64_t P, int64_t nobs, const dou
                             const double *centers, const double *bottom_depth, double depth_penalty,
                             const double *data_en, const double *mean_R, double *rating, double *dmin);
 
+/* ---- posterior marginals of a population or trace (csrc/marginals.hip, which states the orders the kernels promise)
+ * replaces: the arrays behind `beat plot stage_posteriors`, `correlation_hist` and `lune`:
+ *   histplot_op / hist_binning (beat/plotting/common.py:248-397: num.percentile at :303, :361), make_bins and traceplot
+ *   (beat/plotting/marginals.py:131-507, :207-215), hist2d_plot_op (common.py:400-415), kde2plot_op (common.py:445-461)
+ *   per variable pair of correlation_plot / correlation_plot_hist (marginals.py:510-609, 614-851), spherical_kde_op
+ *   (common.py:471-523) with vonmises_fisher / vonmises_std (beat/models/distributions.py:245-337) for draw_lune_kde
+ *   (beat/plotting/seismic.py:2707-2729).
+ * X [n, V] row-major; cols [K] / pairs [P, 2]: column indices in [0, V) (BEATAMD_EINDEX outside), any order, repeats
+ * allowed.  Array arguments may live on either side.  A non-finite sample in a used column is BEATAMD_ENAN, the message
+ * and *bad_col (nullable) name the column (numpy would sort NaN last and return NaN).
+ * column_sort: sorted [K, n] = the columns ascending (n <= 2^24).
+ * column_percentiles: sorted [K, n], q [Q] in [0, 100] -> out [K, Q], bit for bit numpy.percentile's default ("linear").
+ * column_histograms: edges [K, nb + 1], every row finite and non-decreasing -> counts [K, nb]: bin i counts
+ *   edges[i] <= x < edges[i + 1], the last bin closed on the right (numpy.histogram).  Densities stay with the caller.
+ * pair_hist2d: xedges [P, bx + 1], yedges [P, by + 1] -> counts [P, bx, by]: bin = searchsorted(edges, x, 'right') - 1,
+ *   a value on the last edge in the last bin (numpy.histogram2d).  bx * by <= 128 * 128, each side <= 4096.
+ * pair_kde2d: Z [P, gx, gy], Z[p, a, b] = scipy.stats.gaussian_kde of the pair's two columns (Scott's factor n^(-1/6),
+ *   the sample covariance with bias=False, 1 / (2 pi n sqrt(det))) at (linspace(xmin, xmax, gx)[a],
+ *   linspace(ymin, ymax, gy)[b]); extents [P, 4] = (xmin, xmax, ymin, ymax).  One accumulator per grid point, samples in
+ *   ascending order: a Z does not depend on the other pairs of the call.  skip_blocks != 0 leaves out blocks of samples whose
+ *   terms are exact zeros for a tile of the grid (the same bits).  shape: 0 lets the launcher choose between four grid
+ *   points per lane in workgroups of 256 (1) and one per lane in workgroups of 64 (2, for few tiles); the same bits in
+ *   both, here and in spherical_kde.  flags [P]: 1 for a pair whose scaled covariance has no
+ *   Cholesky factor (a constant column, a column paired with itself, n < 3): its Z is NaN, the others hold their results
+ *   and the call returns BEATAMD_ENOTPSD (scipy raises LinAlgError for such a pair).
+ * unit_vector_sum: S [3] = sum_i (sin t cos p, sin t sin p, cos t), (t, p) = deg2rad of (lats, lons) (transform 0, the
+ *   argument order and missing transform of vonmises_std's call in spherical_kde_op) or of (90 - lats, mod(lons, 360))
+ *   (transform 1), summed in a fixed order.
+ * spherical_kde: kde [m] = sum_i exp(norm + (x . x0_i) / sigma2) at the m points (lats, lons) over the n samples
+ *   (lats0, lons0), all in degrees; norm = -log(4 pi sigma^2) - logsinh(1 / sigma^2) comes from the caller.  Samples are
+ *   added in ascending order into one accumulator per point (the reference adds its remainder chunk first). */
+int beatamd_column_sort(beatamd_ctx *ctx, int64_t n, int64_t V, const double *X, int64_t K, const int64_t *cols,
+                        double *sorted, int64_t *bad_col);
+int beatamd_column_percentiles(beatamd_ctx *ctx, int64_t K, int64_t n, const double *sorted, int64_t Q, const double *q,
+                               double *out);
+int beatamd_column_histograms(beatamd_ctx *ctx, int64_t K, int64_t n, const double *sorted, int64_t nb, const double *edges,
+                              int64_t *counts);
+int beatamd_pair_hist2d(beatamd_ctx *ctx, int64_t n, int64_t V, const double *X, int64_t P, const int64_t *pairs, int32_t bx,
+                        int32_t by, const double *xedges, const double *yedges, int64_t *counts, int64_t *bad_col);
+int beatamd_pair_kde2d(beatamd_ctx *ctx, int64_t n, int64_t V, const double *X, int64_t P, const int64_t *pairs, int32_t gx,
+                       int32_t gy, int32_t skip_blocks, int32_t shape, double *Z, double *extents, int32_t *flags,
+                       int64_t *bad_col);
+int beatamd_unit_vector_sum(beatamd_ctx *ctx, int64_t n, const double *lats, const double *lons, int32_t transform, double *S);
+int beatamd_spherical_kde(beatamd_ctx *ctx, int64_t n, const double *lats0, const double *lons0, int64_t m, const double *lats,
+                          const double *lons, double norm, double sigma2, int32_t shape, double *kde);
+
 #ifdef __cplusplus
 }
 #endif
