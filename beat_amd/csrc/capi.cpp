@@ -2903,4 +2903,145 @@ int beatamd_spherical_kde(beatamd_ctx *ctx, int64_t n, const double *lats0, cons
     return st.finish();
 }
 
+// ------------------------------------------------------------------ seismic FFI library producer (seislib.hip)
+// the cascade (ntaps, demean [nstage]; coef [nstage, 2, SL_MAX_TAPS] = b then a, either side) as the kernels take it
+static int sl_stages(beatamd_ctx *ctx, const char *who, int32_t nstage, const int32_t *ntaps, const int32_t *demean,
+                     const double *coef, SlStage *out)
+{
+    BA_CHECK(nstage >= 0 && nstage <= SL_MAX_STAGES, BEATAMD_EINVAL, "%s: %d filter stages (at most %d)", who, nstage,
+             SL_MAX_STAGES);
+    BA_CHECK(nstage == 0 || (ntaps && demean && coef), BEATAMD_EINVAL, "%s: bad argument", who);
+    std::vector<int32_t> nt, dm;
+    std::vector<double> c;
+    BA_TRY(host_copy(ctx, ntaps, (size_t)nstage, nt));
+    BA_TRY(host_copy(ctx, demean, (size_t)nstage, dm));
+    BA_TRY(host_copy(ctx, coef, (size_t)nstage * 2 * SL_MAX_TAPS, c));
+    for (int s = 0; s < nstage; s++) {
+        BA_CHECK(nt[s] >= SL_MIN_TAPS && nt[s] <= SL_MAX_TAPS, BEATAMD_EINVAL, "%s: stage %d has %d taps (%d ... %d)", who, s,
+                 nt[s], SL_MIN_TAPS, SL_MAX_TAPS);
+        SlStage &st = out[s];
+        st.ntaps = nt[s];
+        st.demean = dm[s] != 0;
+        for (int k = 0; k < SL_MAX_TAPS; k++) {
+            st.b[k] = k < nt[s] ? c[(s * 2) * SL_MAX_TAPS + k] : 0.0;
+            st.a[k] = k < nt[s] ? c[(s * 2 + 1) * SL_MAX_TAPS + k] : 0.0;
+            BA_CHECK(std::isfinite(st.b[k]) && std::isfinite(st.a[k]), BEATAMD_EINVAL, "%s: stage %d has a non-finite coefficient",
+                     who, s);
+        }
+        BA_CHECK(st.a[0] == 1.0, BEATAMD_EINVAL, "%s: stage %d is not normalised (a[0] = %g, must be 1)", who, s, st.a[0]);
+    }
+    return BEATAMD_OK;
+}
+
+// *ntm: the longest source-time function of the table's lengths nt [D] (either side), each in [1, ntmax]
+static int sl_lengths(beatamd_ctx *ctx, const char *who, const int32_t *nt, int64_t D, int64_t ntmax, int64_t *ntm)
+{
+    BA_CHECK(D >= 1 && D <= 32767 && ntmax >= 1 && ntmax <= SL_NT_MAX && nt, BEATAMD_EINVAL,
+             "%s: %lld durations (1 ... 32767) of at most %lld samples (1 ... %lld)", who, (long long)D, (long long)ntmax,
+             (long long)SL_NT_MAX);
+    std::vector<int32_t> h;
+    BA_TRY(host_copy(ctx, nt, (size_t)D, h));
+    *ntm = 1;
+    for (int64_t d = 0; d < D; d++) {
+        BA_CHECK(h[d] >= 1 && h[d] <= ntmax, BEATAMD_EINVAL, "%s: duration %lld has %d samples (1 ... %lld)", who, (long long)d,
+                 h[d], (long long)ntmax);
+        *ntm = std::max<int64_t>(*ntm, h[d]);
+    }
+    return BEATAMD_OK;
+}
+
+int beatamd_stf_table(beatamd_ctx *ctx, int64_t D, const double *durations, double deltat, int64_t ntmax, int32_t *nt, double *A)
+{
+    ENTER(ctx);
+    BA_CHECK(D >= 0 && (D == 0 || (durations && nt && A)) && ntmax >= 1 && ntmax <= SL_NT_MAX, BEATAMD_EINVAL,
+             "stf_table: bad argument");
+    BA_CHECK(std::isfinite(deltat) && deltat > 0.0, BEATAMD_EINVAL, "stf_table: deltat = %g", deltat);
+    if (D == 0) return BEATAMD_OK;
+    std::vector<double> h;
+    BA_TRY(host_copy(ctx, durations, (size_t)D, h));
+    for (int64_t d = 0; d < D; d++) {
+        BA_CHECK(std::isfinite(h[d]) && h[d] >= 0.0, BEATAMD_EINVAL, "stf_table: duration %lld is %g", (long long)d, h[d]);
+        BA_CHECK(std::rint(h[d] / deltat) + 1.0 <= (double)ntmax, BEATAMD_EINVAL,
+                 "stf_table: duration %g has %g samples at deltat %g, the table holds %lld", h[d], std::rint(h[d] / deltat) + 1.0,
+                 deltat, (long long)ntmax);
+    }
+    Staging st(ctx);
+    const double *d_dur;
+    int32_t *d_nt;
+    double *d_A;
+    BA_TRY(st.in(durations, (size_t)D, &d_dur));
+    BA_TRY(st.out(nt, (size_t)D, &d_nt));
+    BA_TRY(st.out(A, (size_t)D * ntmax, &d_A));
+    BA_TRY(launch_stf_table(ctx, D, d_dur, deltat, ntmax, d_nt, d_A));
+    return st.finish();
+}
+
+int beatamd_trace_filter_batch(beatamd_ctx *ctx, int64_t R, int64_t L, const double *traces, int64_t D, int64_t ntmax,
+                               const int32_t *nt, const double *A, int32_t nstage, const int32_t *ntaps, const int32_t *demean,
+                               const double *coef, double *Y)
+{
+    ENTER(ctx);
+    BA_CHECK(R >= 0 && L >= 1 && A && Y && (traces || R == 0), BEATAMD_EINVAL, "trace_filter_batch: bad argument");
+    SlStage stages[SL_MAX_STAGES];
+    BA_TRY(sl_stages(ctx, "trace_filter_batch", nstage, ntaps, demean, coef, stages));
+    int64_t ntm;
+    BA_TRY(sl_lengths(ctx, "trace_filter_batch", nt, D, ntmax, &ntm));
+    if (R == 0) return BEATAMD_OK;
+    const int64_t Lcmax = L + ntm - 1;
+    Staging st(ctx);
+    const double *d_x, *d_A;
+    const int32_t *d_nt;
+    double *d_y;
+    BA_TRY(st.in(traces, (size_t)R * L, &d_x));
+    BA_TRY(st.in(nt, (size_t)D, &d_nt));
+    BA_TRY(st.in(A, (size_t)D * ntmax, &d_A));
+    BA_TRY(st.out(Y, (size_t)R * D * Lcmax, &d_y));
+    BA_TRY(launch_stf_convolve(ctx, R, 1, 0, 1, L, d_x, D, ntmax, d_nt, d_A, Lcmax, d_y));
+    for (int s = 0; s < nstage; s++) BA_TRY(launch_trace_filter(ctx, R * D, D, L, ntmax, d_nt, Lcmax, stages[s], d_y));
+    return st.finish();
+}
+
+int beatamd_seis_library_fill(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t L, const double *responses, int64_t D, int64_t ntmax,
+                              const int32_t *nt, const double *A, int32_t nstage, const int32_t *ntaps, const int32_t *demean,
+                              const double *coef, int64_t S, int64_t N, const int64_t *i0, const double *w0, int64_t patch_block,
+                              double *lib)
+{
+    ENTER(ctx);
+    BA_CHECK(T >= 1 && P >= 1 && L >= 1 && S >= 1 && S <= 32767 && N >= 1 && responses && A && i0 && w0 && lib, BEATAMD_EINVAL,
+             "seis_library_fill: bad argument (T, P, L, N >= 1; 1 <= S <= 32767)");
+    SlStage stages[SL_MAX_STAGES];
+    BA_TRY(sl_stages(ctx, "seis_library_fill", nstage, ntaps, demean, coef, stages));
+    int64_t ntm;
+    BA_TRY(sl_lengths(ctx, "seis_library_fill", nt, D, ntmax, &ntm));
+    const int64_t Lcmax = L + ntm - 1, pb = patch_block >= 1 ? std::min(patch_block, P) : P;
+    BA_CHECK((double)T * (double)P * (double)D * (double)S * (double)N < 9.0e18 / 8.0, BEATAMD_EINVAL,
+             "seis_library_fill: the library is too large");
+    Staging st(ctx);
+    const double *d_x, *d_A, *d_w0;
+    const int32_t *d_nt;
+    const int64_t *d_i0;
+    double *d_lib;
+    BA_TRY(st.in(responses, (size_t)T * P * L, &d_x));
+    BA_TRY(st.in(nt, (size_t)D, &d_nt));
+    BA_TRY(st.in(A, (size_t)D * ntmax, &d_A));
+    BA_TRY(st.in(i0, (size_t)T * P * S, &d_i0));
+    BA_TRY(st.in(w0, (size_t)T * P * S, &d_w0));
+    BA_TRY(st.out(lib, (size_t)T * P * D * S * N, &d_lib));
+    // the filtered traces of one block of patches; owned here, freed when the call leaves
+    DevMem<double> Y;
+    const hipError_t e = Y.try_alloc((size_t)T * pb * D * Lcmax);
+    BA_CHECK(e == hipSuccess, BEATAMD_ENOMEM,
+             "seis_library_fill: %zu bytes for the filtered traces of %lld patches: %s (a smaller patch_block needs less)",
+             (size_t)T * pb * D * Lcmax * sizeof(double), (long long)pb, hipGetErrorString(e));
+    for (int64_t p0 = 0; p0 < P; p0 += pb) {
+        const int64_t n = std::min(pb, P - p0);
+        BA_TRY(launch_stf_convolve(ctx, T, P, p0, n, L, d_x, D, ntmax, d_nt, d_A, Lcmax, Y.get()));
+        for (int s = 0; s < nstage; s++) BA_TRY(launch_trace_filter(ctx, T * n * D, D, L, ntmax, d_nt, Lcmax, stages[s], Y.get()));
+        BA_TRY(launch_library_windows(ctx, T, P, p0, n, D, L, ntmax, d_nt, Lcmax, Y.get(), S, N, d_i0, d_w0, d_lib));
+    }
+    BA_TRY(st.finish());
+    BA_HIP(hipStreamSynchronize(ctx->stream));   // Y is freed on return
+    return BEATAMD_OK;
+}
+
 }  // extern "C"

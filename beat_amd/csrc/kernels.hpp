@@ -631,4 +631,25 @@ int launch_sph_sum(beatamd_ctx *ctx, int64_t n, const double *U, double *S);
 int launch_sph_kde(beatamd_ctx *ctx, int64_t n, const double *U0, int64_t m, const double *Ug, double norm, double sigma2,
                    int shape, double *kde);
 
+// ---- seislib.hip: the producer of the seismic FFI library (ffi/base.py:1005-1254, heart.py:3466-3525, 4242-4323); the
+// arithmetic contract stands at the head of seislib.hip
+constexpr int SL_MAX_STAGES = 4, SL_MIN_TAPS = 3, SL_MAX_TAPS = 17;   // the filter cascade; taps = filter order + 1
+constexpr int64_t SL_NT_MAX = 65536;                                  // samples of a discretised source-time function
+struct SlStage {
+    double b[SL_MAX_TAPS], a[SL_MAX_TAPS];   // zero beyond ntaps; a[0] = 1
+    int32_t ntaps, demean;
+};
+// nt [D], A [D, ntmax]: the half-sinusoid amplitudes of every duration (k_stf_table)
+int launch_stf_table(beatamd_ctx *ctx, int64_t D, const double *durations, double deltat, int64_t ntmax, int32_t *nt, double *A);
+// Y [T * pb * D, Lcmax] = the responses X [T, P, L] of the patches [p0, p0 + pb) convolved with the rows of A (k_stf_convolve)
+int launch_stf_convolve(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t p0, int64_t pb, int64_t L, const double *X, int64_t D,
+                        int64_t ntmax, const int32_t *nt, const double *A, int64_t Lcmax, double *Y);
+// one filter stage over the first L + nt[q % D] - 1 samples of every row of Y [Q, Lcmax], in place (k_trace_filter)
+int launch_trace_filter(beatamd_ctx *ctx, int64_t Q, int64_t D, int64_t L, int64_t ntmax, const int32_t *nt, int64_t Lcmax,
+                        const SlStage &st, double *Y);
+// lib [T, P, D, S, N], patches [p0, p0 + pb): the windows i0 [T, P, S] of the rows of Y, sample 0 times w0 [T, P, S]
+int launch_library_windows(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t p0, int64_t pb, int64_t D, int64_t L, int64_t ntmax,
+                           const int32_t *nt, int64_t Lcmax, const double *Y, int64_t S, int64_t N, const int64_t *i0,
+                           const double *w0, double *lib);
+
 }  // namespace beatamd

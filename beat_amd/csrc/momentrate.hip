@@ -9,6 +9,7 @@
 //   HalfSinusoidSTF.discretize_t with exponent = 1 (BEAT's default stf_type), the rule stated at k_moment_rate
 // All arithmetic is FP64 with contraction off: tests/momentrate_ref.py restates every kernel operation by operation.
 #include "kernels.hpp"
+#include "stf.hpp"
 #include "wave.hpp"
 
 namespace beatamd {
@@ -160,16 +161,8 @@ int launch_moment_rate_span(beatamd_ctx *ctx, const FfiModel &m, int64_t C, cons
 //
 // A draw whose span (spans row nsub) has count 0 -- chain_bad and the other cases of k_moment_rate_span -- gets NaN rows.
 // A draw whose span does not lie within [kbase, kbase + NT) gets NaN rows and raises ST_SPAN_OOB.  Every cell index is
-// checked against the row before it is used: nothing is written out of bounds.
-__device__ __forceinline__ double mr_amplitude(int64_t i, double tmin, double t0, double t1, double w, double deltat)
-{
-#pragma clang fp contract(off)
-    const double ea = fmax(t0, fmin(t1, tmin + ((double)i - 0.5) * deltat));
-    const double eb = fmax(t0, fmin(t1, tmin + ((double)(i + 1) - 0.5) * deltat));
-    const double fa = -cos((ea - t0) * w), fb = -cos((eb - t0) * w);
-    return fb - fa;
-}
-
+// checked against the row before it is used: nothing is written out of bounds.  (mr_amplitude: stf.hpp, shared with the
+// library producer's k_stf_table.)
 __global__ void __launch_bounds__(64) k_moment_rate(int64_t P, int nsub, const int32_t *sf_off, const int32_t *sf_ndip,
                                                     const int32_t *sf_nstrike, const double *st0, const double *Q, int64_t np,
                                                     int64_t dur_off, MrComps comps, const double *k, double deltat,

@@ -1073,6 +1073,34 @@ int beatamd_unit_vector_sum(beatamd_ctx *ctx, int64_t n, const double *lats, con
 int beatamd_spherical_kde(beatamd_ctx *ctx, int64_t n, const double *lats0, const double *lons0, int64_t m, const double *lats,
                           const double *lons, double norm, double sigma2, int32_t shape, double *kde);
 
+/* ---- producer of the seismic FFI Green's-function library (csrc/seislib.hip, which states the arithmetic contract)
+ * replaces: seis_construct_gf_linear / _process_patch_seismic (beat/ffi/base.py:1005-1254) after the elementary
+ *   waveforms: the convolution with the half-sinusoid source-time function of every duration (patch.stf.anchor = -1,
+ *   base.py:1013), the filters of heart.Filter / BandstopFilter (beat/heart.py:366-412) and the taper, zero extension and
+ *   [b, c] cut of post_process_trace / taper_filter_traces (beat/heart.py:3466-3525, 4242-4323), with
+ *   ArrivalTaper.nsamples (beat/heart.py:295-304).  The waveforms themselves (pyrocko's engine.process) are the caller's.
+ * Array arguments may live on either side.
+ * stf_table: durations [D] >= 0 -> nt [D] = rint(duration / deltat) + 1 (each <= ntmax <= 65536, BEATAMD_EINVAL beyond)
+ *   and A [D, ntmax], the normalised amplitudes (zero beyond nt; [1] for nt == 1).
+ * trace_filter_batch: traces [R, L]; nt, A as stf_table wrote them (D = 1, ntmax = 1, nt = [1], A = [1]: no source-time
+ *   function) -> Y [R, D, Lcmax], Lcmax = L + max(nt) - 1: row (r, d) holds the L + nt[d] - 1 samples of trace r convolved
+ *   with row d of A and run through the cascade, zeros behind them.  The cascade: nstage <= 4 stages; ntaps [nstage] in
+ *   [3, 17]; demean [nstage] (!= 0: the stage subtracts its input's mean first); coef [nstage, 2, 17] = b then a of every
+ *   stage, a[0] = 1, entries beyond ntaps ignored.
+ * seis_library_fill: responses [T, P, L]; i0, w0 [T, P, S]: first sample and the weight of sample 0 of every window ->
+ *   lib [T, P, D, S, N]: lib[t, p, d, s, n] = Y[(t, p), d, i0 + n] inside the trace, 0 outside; sample 0 times w0.
+ *   S, D <= 32767 (the library's int16 grid indices).  patch_block (<= 0: all P): the patches filtered at a time, which
+ *   bounds the intermediate Y (T * patch_block * D * Lcmax doubles, allocated and freed by the call; BEATAMD_ENOMEM
+ *   names the size).  The result does not depend on patch_block. */
+int beatamd_stf_table(beatamd_ctx *ctx, int64_t D, const double *durations, double deltat, int64_t ntmax, int32_t *nt, double *A);
+int beatamd_trace_filter_batch(beatamd_ctx *ctx, int64_t R, int64_t L, const double *traces, int64_t D, int64_t ntmax,
+                               const int32_t *nt, const double *A, int32_t nstage, const int32_t *ntaps, const int32_t *demean,
+                               const double *coef, double *Y);
+int beatamd_seis_library_fill(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t L, const double *responses, int64_t D,
+                              int64_t ntmax, const int32_t *nt, const double *A, int32_t nstage, const int32_t *ntaps,
+                              const int32_t *demean, const double *coef, int64_t S, int64_t N, const int64_t *i0,
+                              const double *w0, int64_t patch_block, double *lib);
+
 #ifdef __cplusplus
 }
 #endif
