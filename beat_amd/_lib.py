@@ -179,6 +179,8 @@ _PROTOS = {
     "beatamd_pair_kde2d": [_vp, _i64, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _pi64],
     "beatamd_unit_vector_sum": [_vp, _i64, _vp, _vp, _i32, _vp],
     "beatamd_spherical_kde": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _f64, _f64, _i32, _vp],
+    "beatamd_mt_decompose": [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "beatamd_fuzzy_amps": [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "beatamd_stf_table": [_vp, _i64, _vp, _f64, _i64, _vp, _vp],
     "beatamd_trace_filter_batch": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "beatamd_seis_library_fill": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp,

@@ -2903,6 +2903,71 @@ int beatamd_spherical_kde(beatamd_ctx *ctx, int64_t n, const double *lats0, cons
     return st.finish();
 }
 
+// ------------------------------------------------------------------ mechanism ensembles (mechanisms.hip)
+int beatamd_mt_decompose(beatamd_ctx *ctx, int64_t n, int32_t kind, const double *X, double *evals, double *evecs,
+                         double *moments, double *ratios, double *parts, double *unit, double *uv)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 0 && (X || n == 0) && (kind == 0 || kind == 1), BEATAMD_EINVAL,
+             "mt_decompose: bad argument (kind 0: tensors [n, 6], 1: strike, dip, rake [n, 3])");
+    BA_CHECK(n <= MC_MAX_N, BEATAMD_EINVAL, "mt_decompose: %lld draws, at most %lld", (long long)n, (long long)MC_MAX_N);
+    if (n == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_X;
+    BA_TRY(st.in(X, (size_t)n * (kind == 1 ? 3 : 6), &d_X));
+    uint32_t *d_bad;
+    BA_TRY(ctx->scratch(SL_MC_FLAG, 1, &d_bad));
+    BA_TRY(launch_mt_check(ctx, d_X, n, kind, d_bad));
+    std::vector<uint32_t> bad;
+    BA_TRY(host_copy(ctx, (const uint32_t *)d_bad, 1, bad));
+    BA_CHECK(bad[0] == 0xffffffffu, BEATAMD_ENAN,
+             kind == 1 ? "mt_decompose: row %u holds a non-finite angle"
+                       : "mt_decompose: row %u is not a moment tensor (a non-finite entry, or all six zero)",
+             bad[0]);
+    double *d_ev, *d_vec, *d_mom, *d_rat, *d_par, *d_unit, *d_uv;
+    BA_TRY(st.out(evals, (size_t)n * 3, &d_ev));
+    BA_TRY(st.out(evecs, (size_t)n * 9, &d_vec));
+    BA_TRY(st.out(moments, (size_t)n * MC_NPART, &d_mom));
+    BA_TRY(st.out(ratios, (size_t)n * MC_NPART, &d_rat));
+    BA_TRY(st.out(parts, (size_t)n * MC_NPART * 6, &d_par));
+    BA_TRY(st.out(unit, (size_t)n * MC_NPART * 6, &d_unit));
+    BA_TRY(st.out(uv, (size_t)n * 2, &d_uv));
+    BA_TRY(launch_mt_decompose(ctx, n, kind, d_X, d_ev, d_vec, d_mom, d_rat, d_par, d_unit, d_uv));
+    return st.finish();
+}
+
+int beatamd_fuzzy_amps(beatamd_ctx *ctx, int64_t n, int32_t P, const double *unit, int64_t npix, const double *rw,
+                       const int64_t *pixel_index, int32_t ny, int32_t nx, int32_t mask, int32_t shape, double *amps)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && P >= 1 && P <= 65535 && unit && amps && npix >= 0 && ((rw && pixel_index) || npix == 0),
+             BEATAMD_EINVAL, "fuzzy_amps: bad argument");
+    BA_CHECK(n <= MC_MAX_N, BEATAMD_EINVAL, "fuzzy_amps: %lld draws, at most %lld", (long long)n, (long long)MC_MAX_N);
+    BA_CHECK(ny >= 1 && nx >= 1 && ny <= MC_MAX_RES && nx <= MC_MAX_RES, BEATAMD_EINVAL,
+             "fuzzy_amps: a grid of %d x %d pixels (each side 1 to %d)", ny, nx, MC_MAX_RES);
+    BA_CHECK(shape >= 0 && shape <= 2, BEATAMD_EINVAL, "fuzzy_amps: launch shape %d (0 chosen here, 1 wide, 2 narrow)", shape);
+    const int64_t cells = (int64_t)ny * nx;
+    BA_CHECK(npix <= cells, BEATAMD_EINVAL, "fuzzy_amps: %lld pixels in a grid of %lld", (long long)npix, (long long)cells);
+    std::vector<int64_t> hp;
+    BA_TRY(host_copy(ctx, pixel_index, (size_t)npix, hp));
+    for (int64_t j = 0; j < npix; j++)
+        BA_CHECK(hp[j] >= 0 && hp[j] < cells, BEATAMD_EINDEX, "fuzzy_amps: pixel_index[%lld] = %lld outside a grid of %lld",
+                 (long long)j, (long long)hp[j], (long long)cells);
+    Staging st(ctx);
+    const double *d_unit, *d_rw;
+    const int64_t *d_pi;
+    double *d_amps, *d_sum = nullptr;
+    uint32_t *d_count = nullptr;
+    BA_TRY(st.in(unit, (size_t)n * P * 6, &d_unit));
+    BA_TRY(st.in(rw, (size_t)6 * npix, &d_rw));
+    BA_TRY(st.in(pixel_index, (size_t)npix, &d_pi));
+    BA_TRY(st.out(amps, (size_t)P * cells, &d_amps));
+    if (mask) BA_TRY(ctx->scratch(SL_MC_COUNT, (size_t)P * npix + 1, &d_count));
+    else BA_TRY(ctx->scratch(SL_MC_SUM, (size_t)P * npix + 1, &d_sum));
+    BA_TRY(launch_fuzzy_amps(ctx, n, P, d_unit, npix, d_rw, d_pi, cells, mask != 0, shape, d_count, d_sum, d_amps));
+    return st.finish();
+}
+
 // ------------------------------------------------------------------ seismic FFI library producer (seislib.hip)
 // the cascade (ntaps, demean [nstage]; coef [nstage, 2, SL_MAX_TAPS] = b then a, either side) as the kernels take it
 static int sl_stages(beatamd_ctx *ctx, const char *who, int32_t nstage, const int32_t *ntaps, const int32_t *demean,

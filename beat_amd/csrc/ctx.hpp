@@ -414,7 +414,7 @@ const GfKnobs &gf_knobs(beatamd_ctx *ctx);
 // scratch slot map (one per logical temporary so slots never alias within a call)
 enum Slot : int {
     SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_IN4, SL_IN5, SL_IN6, SL_IN7,
-    SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3,
+    SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, SL_OUT4, SL_OUT5, SL_OUT6, SL_OUT7,
     SL_ROWOFF, SL_WEIGHTS, SL_ST0, SL_RESID, SL_PARTIAL, SL_PARTIAL2, SL_QUAD, SL_MU, SL_SLIPS,
     SL_QPROP, SL_LPROP, SL_MISC, SL_GS_UROWS, SL_GS_UCOUNT, SL_GS_SLOT, SL_GS_W, SL_GS_UMAX, SL_GS_USLOT,
     SL_CHAINBAD, SL_Z, SL_ROWSCALE, SL_CUM, SL_STAGE2, SL_WHITEN,
@@ -422,7 +422,8 @@ enum Slot : int {
     SL_GC_ORDER, SL_GS_ORDER, SL_GC_STREAM, SL_GC_HDR, SL_GC_META, SL_DELTA, SL_LOGU, SL_EDGES, SL_TSLOT, SL_SPLIT, SL_WS_PACK,
     SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_MR_SPANS,
     SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_SPEC,
-    SL_MG_FLAG, SL_MG_MOM, SL_MG_PAR, SL_MG_GRID, SL_MG_W, SL_MG_BOX, SL_COUNT
+    SL_MG_FLAG, SL_MG_MOM, SL_MG_PAR, SL_MG_GRID, SL_MG_W, SL_MG_BOX,
+    SL_MC_FLAG, SL_MC_COUNT, SL_MC_SUM, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

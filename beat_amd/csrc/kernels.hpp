@@ -631,6 +631,23 @@ int launch_sph_sum(beatamd_ctx *ctx, int64_t n, const double *U, double *S);
 int launch_sph_kde(beatamd_ctx *ctx, int64_t n, const double *U0, int64_t m, const double *Ug, double norm, double sigma2,
                    int shape, double *kde);
 
+// ---- mechanisms.hip: eigen-systems, standard decompositions, Hudson points and fuzzy-beachball grids of an ensemble of
+// moment tensors (plotting/seismic.py:1334-1425, 1664-1850, 2183-2310); the per-draw arithmetic is mechanism.hpp's
+constexpr int MC_NPART = 5;                                  // iso, dc, clvd, dev, full
+constexpr int MC_G = 4, MC_TILE = MC_G * 256;                // pixels per lane and per workgroup of the wide shape
+constexpr int64_t MC_CHUNK = 512;                            // draws a workgroup of k_fuzzy_accum counts before its atomics
+constexpr int64_t MC_MAX_N = (int64_t)1 << 24;               // draws of a call
+constexpr int MC_MAX_RES = 4096;                             // pixels a side of the focal-sphere grid
+// *bad (device) = the first row of X [n, 6] (kind 0) / [n, 3] (kind 1) that is non-finite or, kind 0, all zero; 0xffffffff
+int launch_mt_check(beatamd_ctx *ctx, const double *X, int64_t n, int kind, uint32_t *bad);
+// evals [n, 3], evecs [n, 3, 3], moments, ratios [n, 5], parts, unit [n, 5, 6], uv [n, 2]; each may be NULL
+int launch_mt_decompose(beatamd_ctx *ctx, int64_t n, int kind, const double *X, double *evals, double *evecs, double *moments,
+                        double *ratios, double *parts, double *unit, double *uv);
+// amps [P, cells] = NaN, then count / n (mask) or sum / n at pixel_index [npix]; unit [n, P, 6], rw [6, npix]; count
+// [P, npix] (mask) and sum [P, npix] (!mask): device scratch; shape: 0 chosen here, 1 wide, 2 narrow
+int launch_fuzzy_amps(beatamd_ctx *ctx, int64_t n, int P, const double *unit, int64_t npix, const double *rw,
+                      const int64_t *pixel_index, int64_t cells, int mask, int shape, uint32_t *count, double *sum, double *amps);
+
 // ---- seislib.hip: the producer of the seismic FFI library (ffi/base.py:1005-1254, heart.py:3466-3525, 4242-4323); the
 // arithmetic contract stands at the head of seislib.hip
 constexpr int SL_MAX_STAGES = 4, SL_MIN_TAPS = 3, SL_MAX_TAPS = 17;   // the filter cascade; taps = filter order + 1

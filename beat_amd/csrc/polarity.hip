@@ -27,6 +27,7 @@
 // stations.  A chain's numbers depend on its own row alone: how chains are batched changes no bit.  The work is a dozen
 // transcendental calls per chain plus erf and two logarithms per station -- FP64 VALU bound, a few microseconds.
 #include "kernels.hpp"
+#include "mechanism.hpp"
 
 namespace beatamd {
 
@@ -96,20 +97,8 @@ __device__ __forceinline__ void pol_mtqt(double w, double v, double kappa, doubl
 #undef POL_M
 }
 
-__device__ __forceinline__ void pol_dc(double strike, double dip, double rake, double *m)
-{
-#pragma clang fp contract(off)
-    const double d2r = 3.14159265358979323846 / 180.0;
-    const double ph = strike * d2r, de = dip * d2r, la = rake * d2r;
-    const double sp = sin(ph), cp = cos(ph), sd = sin(de), cd = cos(de), sl = sin(la), cl = cos(la);
-    const double s2p = 2.0 * (sp * cp), c2p = cp * cp - sp * sp, s2d = 2.0 * (sd * cd), c2d = cd * cd - sd * sd;
-    m[0] = -((sd * cl) * s2p + (s2d * sl) * (sp * sp));
-    m[1] = (sd * cl) * s2p - (s2d * sl) * (cp * cp);
-    m[2] = s2d * sl;
-    m[3] = (sd * cl) * c2p + (0.5 * (s2d * sl)) * s2p;
-    m[4] = -((cd * cl) * cp + (c2d * sl) * sp);
-    m[5] = -((cd * cl) * sp - (c2d * sl) * cp);
-}
+// the unit double couple of (strike, dip, rake) [deg]: mechanism.hpp states it once (k_mt_decompose reads it too)
+__device__ __forceinline__ void pol_dc(double strike, double dip, double rake, double *m) { mech_dc_m6(strike, dip, rake, m); }
 
 __device__ __forceinline__ void pol_m6(const PolSource &s, const double *Qc, const double *utab, const double *btab, int ntab,
                                        double *m)

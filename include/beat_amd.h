@@ -1073,6 +1073,28 @@ int beatamd_unit_vector_sum(beatamd_ctx *ctx, int64_t n, const double *lats, con
 int beatamd_spherical_kde(beatamd_ctx *ctx, int64_t n, const double *lats0, const double *lons0, int64_t m, const double *lats,
                           const double *lons, double norm, double sigma2, int32_t shape, double *kde);
 
+/* ---- mechanism ensembles (csrc/mechanisms.hip; the per-draw arithmetic is csrc/mechanism.hpp's)
+ * replaces: the arrays behind `beat plot fuzzy_beachball`, `fuzzy_mt_decomp` and `hudson`: the per-draw loop of mts2amps
+ *   over lower_focalsphere_angles (beat/plotting/seismic.py:1334-1425), MomentTensor.standard_decomposition as
+ *   fuzzy_mt_decomposition reads it (seismic.py:1664-1850, :1689-1696) and the (u, v) of draw_hudson (seismic.py:2183-2310).
+ *   The decomposition and Hudson's projection restate pyrocko from memory and are pinned to multi-precision evaluations of
+ *   the stated rules only (see mechanism.hpp).  Array arguments may live on either side.
+ * mt_decompose: X [n, 6] = (mnn, mee, mdd, mne, mnd, med) (kind 0) or [n, 3] = strike, dip, rake in degrees (kind 1, the
+ *   unit double couple of the polarity likelihood); n <= 2^24.  Outputs, each nullable: evals [n, 3] ascending and evecs
+ *   [n, 3, 3] (columns) of the full tensor; moments, ratios [n, 5] and parts [n, 5, 6] in the order iso, dc, clvd, dev,
+ *   full; unit [n, 5, 6], each part over sqrt(sum m9^2) / sqrt 2 (seismic.py:1410-1417; NaN for an all-zero part, as numpy
+ *   gives); uv [n, 2], Hudson's (u, v).  A row with a non-finite entry or, kind 0, all six zero is BEATAMD_ENAN; the
+ *   message names the first such row (numpy would spread NaN over the whole grid).
+ * fuzzy_amps: unit [n, P, 6]; rw [6, npix], the propagation coefficients of the npix pixels inside the unit disc;
+ *   pixel_index [npix], their cells iy * nx + ix in the (ny, nx) grid (BEATAMD_EINDEX outside), ny, nx <= 4096 -> amps
+ *   [P, ny, nx]: NaN outside the pixels; mask != 0: the fraction of draws with a > 0, a = ((((r0 u0 + r1 u1) + r2 u2) +
+ *   r3 u3) + r4 u4) + r5 u5 (seismic.py:1417-1423; integer counts, exact whatever the launch); mask == 0: sum of a over the
+ *   draws in ascending order, one accumulator per pixel, over n.  shape as in pair_kde2d; the same bits in all three. */
+int beatamd_mt_decompose(beatamd_ctx *ctx, int64_t n, int32_t kind, const double *X, double *evals, double *evecs,
+                         double *moments, double *ratios, double *parts, double *unit, double *uv);
+int beatamd_fuzzy_amps(beatamd_ctx *ctx, int64_t n, int32_t P, const double *unit, int64_t npix, const double *rw,
+                       const int64_t *pixel_index, int32_t ny, int32_t nx, int32_t mask, int32_t shape, double *amps);
+
 /* ---- producer of the seismic FFI Green's-function library (csrc/seislib.hip, which states the arithmetic contract)
  * replaces: seis_construct_gf_linear / _process_patch_seismic (beat/ffi/base.py:1005-1254) after the elementary
  *   waveforms: the convolution with the half-sinusoid source-time function of every duration (patch.stf.anchor = -1,
