@@ -11,7 +11,9 @@ leg may import this module.  The product (``beat_amd/``) never does.
 
 Pinned by: tests/test_oracle_golden.py (reference numpy path golden vectors),
 tests/test_oracle_kat.py (the reference test-suite's known-answer tests) and
-tests/test_oracle_ref.py (oracle/_ref = reference C extension compiled in place).
+tests/test_oracle_ref.py (oracle/_ref = reference C extension compiled in place);
+fast_sweep_exact by tests/test_sweep_ref_host.py (a second writing in numpy, and its
+distance from the reference's pow arithmetic).
 """
 import ctypes as C
 import os
@@ -67,17 +69,45 @@ def positions2idxs(positions, cell_size, min_pos=0.0):
     return out
 
 
-def fast_sweep(slowness, patch_size, h_strk, h_dip, num_strk, num_dip):
-    """fast_sweep_ext.c:120-245; same argument order as the reference extension."""
+def fast_sweep(slowness, patch_size, h_strk, h_dip, num_strk, num_dip, with_iters=False):
+    """fast_sweep_ext.c:120-245; same argument order as the reference extension.  with_iters: (times, outer iterations)"""
     s = _f64(slowness).ravel()
     assert s.size == num_strk * num_dip
     if not (0 <= h_strk < num_strk and 0 <= h_dip < num_dip):
         raise IndexError("hypocentre index outside the grid")
     out = np.empty(s.size)
-    lib().bo_fast_sweep(_p(s), C.c_double(patch_size), C.c_long(int(h_strk)),
-                        C.c_long(int(h_dip)), C.c_long(int(num_strk)), C.c_long(int(num_dip)),
-                        _p(out))
-    return out
+    it = lib().bo_fast_sweep(_p(s), C.c_double(patch_size), C.c_long(int(h_strk)),
+                             C.c_long(int(h_dip)), C.c_long(int(num_strk)), C.c_long(int(num_dip)),
+                             _p(out))
+    return (out, it) if with_iters else out
+
+
+def fast_sweep_exact(slowness, patch_size, h_strk, h_dip, num_strk, num_dip, with_err=False, snap_iter=None):
+    """fast_sweep with sqrt(x) for pow(x, 0.5) and d*d for pow(d, 2.0) (bo_fast_sweep_exact): the expressions the device
+    sweep promises bit for bit.  -> times; with_err: (times, outer iterations, err of every iteration); snap_iter = k >= 1
+    appends the times after outer iteration k, the loop carried on past its stop where k lies beyond it (the err list
+    then runs to iteration k)."""
+    s = _f64(slowness).ravel()
+    assert s.size == num_strk * num_dip
+    if not (0 <= h_strk < num_strk and 0 <= h_dip < num_dip):
+        raise IndexError("hypocentre index outside the grid")
+    fn = lib().bo_fast_sweep_exact
+    fn.restype = C.c_int
+    out = np.empty(s.size)
+    snap = np.empty(s.size) if snap_iter is not None else None
+    room = 64
+    while True:
+        errs = np.full(room, np.nan)
+        it = fn(_p(s), C.c_double(patch_size), C.c_long(int(h_strk)), C.c_long(int(h_dip)),
+                C.c_long(int(num_strk)), C.c_long(int(num_dip)), _p(out), _p(errs), C.c_long(room),
+                C.c_long(int(snap_iter or 0)), _p(snap) if snap is not None else None)
+        if max(it, snap_iter or 0) <= room:
+            break
+        room = max(it, snap_iter or 0)
+    if not with_err and snap_iter is None:
+        return out
+    res = (out, it, errs[:max(it, snap_iter or 0)].copy())
+    return res + (snap,) if snap_iter is not None else res
 
 
 def time2idx(x, xmin, dx, interpolation="nearest_neighbor"):

@@ -6,9 +6,14 @@ every comparison is np.array_equal on the float64 times: no tolerance.
 The model path (mode 1 of the kernel: slowness = 1 / velocities, hypocentre index from the nucleation position, + time)
 is read through CompiledModel.start_times."""
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from sweep_ref import host_sweep  # noqa: E402  (the numpy restatement of the reference's loops: counts iterations here)
 
 pytestmark = pytest.mark.gpu
 
@@ -60,40 +65,6 @@ def _case(ni, nj):
             hj.append(b)
             names.append("%s@%d,%d" % (fname, a, b))
     return np.array(slow), np.array(hi, dtype=np.int32), np.array(hj, dtype=np.int32), names
-
-
-def host_sweep(slow, h, hi, hj, ni, nj):
-    """fast_sweep_ext.c:120-206 restated for a batch (cells in the reference's order, the chains side by side):
-    -> times [C, ni*nj], outer iterations of every grid.  sqrt for the reference's pow(x, 0.5): counts iterations, the
-    times are not compared with anything."""
-    C = slow.shape[0]
-    f = slow.reshape(C, ni, nj)
-    t = np.full((C, ni, nj), np.inf)
-    t[np.arange(C), hi, hj] = 0.0
-    iters = np.zeros(C, dtype=int)
-    running = np.ones(C, dtype=bool)
-    orders = ((range(ni), range(nj)), (range(ni - 1, -1, -1), range(nj)),
-              (range(ni - 1, -1, -1), range(nj - 1, -1, -1)), (range(ni), range(nj - 1, -1, -1)))
-    with np.errstate(all="ignore"):
-        while running.any():
-            told = t.copy()
-            for ri, rj in orders:
-                for i in ri:
-                    for j in rj:
-                        a1, a2 = t[:, max(i - 1, 0), j], t[:, min(i + 1, ni - 1), j]
-                        b1, b2 = t[:, i, max(j - 1, 0)], t[:, i, min(j + 1, nj - 1)]
-                        a, b = np.where(a1 < a2, a1, a2), np.where(b1 < b2, b1, b2)
-                        fh = f[:, i, j] * h
-                        dab = a - b
-                        v = np.where(np.abs(dab) >= fh, np.where(a < b, a, b) + fh,
-                                     (a + b + np.sqrt(2.0 * f[:, i, j] * f[:, i, j] * h * h - dab * dab)) / 2.0)
-                        t[:, i, j] = np.where(v < t[:, i, j], v, t[:, i, j])
-            # a grid that has converged keeps its times: the reference would have stopped
-            t[~running] = told[~running]
-            err = ((t - told) ** 2).reshape(C, -1).sum(axis=1)
-            iters += running
-            running &= err > 0.1        # (NaN, from inf - inf of a cell that was not reached, ends the loop as in C)
-    return t.reshape(C, -1), iters
 
 
 def _both(ctx, monkeypatch, call):
