@@ -2111,7 +2111,13 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &
             BA_HIP(hipHostMalloc((void **)&ctx->h_umax, sizeof(uint32_t), hipHostMallocDefault));
             BA_HIP(hipEventCreateWithFlags(&ctx->umax_event, hipEventDisableTiming));
         }
-        if (ctx->umax_pending && hipEventQuery(ctx->umax_event) == hipSuccess) {
+        // inside a graph capture the mailbox is left alone: a read-back recorded there would be an event of the capture,
+        // and querying such an event (the next step of the same capture does) invalidates the capture.  The history the
+        // eager step in front of the capture left sizes the fitted twin of every captured step; the guards decide
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        BA_HIP(hipStreamIsCapturing(ctx->stream, &cap));
+        const bool capturing = cap != hipStreamCaptureStatusNone;
+        if (!capturing && ctx->umax_pending && hipEventQuery(ctx->umax_event) == hipSuccess) {
             ctx->umax_hist = (int)*ctx->h_umax;
             ctx->umax_pending = false;
         }
@@ -2123,7 +2129,7 @@ int launch_gfstack_shared(beatamd_ctx *ctx, const GfStackCall &k, const GfPlan &
             const int want = ctx->umax_hist + 1;
             if (want < ucap) ucap_fit = std::max(want, 2);
         }
-        if (!ctx->umax_pending) {
+        if (!capturing && !ctx->umax_pending) {
             BA_HIP(hipMemcpyAsync(ctx->h_umax, ga.umax, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
             BA_HIP(hipEventRecord(ctx->umax_event, ctx->stream));
             ctx->umax_pending = true;
