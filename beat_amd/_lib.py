@@ -185,6 +185,10 @@ _PROTOS = {
     "beatamd_trace_filter_batch": [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "beatamd_seis_library_fill": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
                                   _i64, _vp],
+    "beatamd_rupture_minmax": [_vp, _i64, _i64, _vp, _i32, _vp, _vp],
+    "beatamd_contour_count": [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
+    "beatamd_contour_fill": [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "beatamd_polyline_density": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _f64, _vp, _vp],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["beatamd_last_error", "beatamd_version"])

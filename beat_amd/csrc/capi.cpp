@@ -1747,6 +1747,167 @@ int beatamd_trace_density_update_ranges(beatamd_ctx *ctx, int64_t E, int64_t T, 
     return ctx->check_status();
 }
 
+// ------------------------------------------------------------------ rupture fronts (rupture.hip)
+// the subfault table on the host, checked: shapes, the blocks inside the start times and the coordinate arrays
+static int rupture_subs(beatamd_ctx *ctx, const char *who, int32_t nsub, const int64_t *subs, int64_t ncells_total, int64_t nx_total,
+                        int64_t ny_total, std::vector<int64_t> &sb, int64_t *max_nodes)
+{
+    BA_CHECK(subs && nsub >= 1 && nsub <= 4096 && ncells_total >= 0, BEATAMD_EINVAL, "%s: bad subfault table", who);
+    BA_TRY(host_copy(ctx, subs, (size_t)nsub * CT_SUB_FIELDS, sb));
+    *max_nodes = 0;
+    for (int32_t k = 0; k < nsub; k++) {
+        const int64_t *r = sb.data() + (size_t)CT_SUB_FIELDS * k;
+        BA_CHECK(r[0] >= 1 && r[1] >= 1 && r[0] <= 32768 && r[1] <= 32768, BEATAMD_EINVAL, "%s: subfault %d of %lld x %lld patches",
+                 who, (int)k, (long long)r[0], (long long)r[1]);
+        BA_CHECK(r[2] >= 0 && r[2] + r[0] * r[1] <= ncells_total, BEATAMD_EINVAL,
+                 "%s: subfault %d's patches [%lld, %lld) outside the %lld start times of a draw", who, (int)k, (long long)r[2],
+                 (long long)(r[2] + r[0] * r[1]), (long long)ncells_total);
+        BA_CHECK(nx_total < 0 || (r[3] >= 0 && r[3] + r[1] <= nx_total && r[4] >= 0 && r[4] + r[0] <= ny_total), BEATAMD_EINVAL,
+                 "%s: subfault %d's coordinates outside x (%lld) or y (%lld)", who, (int)k, (long long)nx_total, (long long)ny_total);
+        *max_nodes = std::max(*max_nodes, r[0] * r[1]);
+    }
+    return BEATAMD_OK;
+}
+
+int beatamd_rupture_minmax(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int32_t nsub, const int64_t *subs,
+                           double *out)
+{
+    ENTER(ctx);
+    BA_CHECK(sts && out && E >= 0, BEATAMD_EINVAL, "rupture_minmax: bad argument");
+    std::vector<int64_t> sb;
+    int64_t max_nodes = 0;
+    BA_TRY(rupture_subs(ctx, "rupture_minmax", nsub, subs, ncells_total, -1, -1, sb, &max_nodes));
+    if (E == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_s;
+    const int64_t *d_sb;
+    double *d_o;
+    BA_TRY(st.in(sts, (size_t)E * ncells_total, &d_s));
+    BA_TRY(st.in(subs, (size_t)nsub * CT_SUB_FIELDS, &d_sb));
+    BA_TRY(st.out(out, (size_t)E * nsub * 2, &d_o));
+    BA_TRY(launch_rupture_minmax(ctx, E, ncells_total, d_s, nsub, d_sb, d_o));
+    return st.finish();
+}
+
+int beatamd_contour_count(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int32_t nsub, const int64_t *subs,
+                          const double *levels, const int32_t *nlevels, int32_t *counts)
+{
+    ENTER(ctx);
+    BA_CHECK(sts && levels && nlevels && counts && E >= 0, BEATAMD_EINVAL, "contour_count: bad argument");
+    std::vector<int64_t> sb;
+    std::vector<int32_t> nl;
+    int64_t max_nodes = 0;
+    BA_TRY(rupture_subs(ctx, "contour_count", nsub, subs, ncells_total, -1, -1, sb, &max_nodes));
+    if (E == 0) return BEATAMD_OK;
+    BA_TRY(host_copy(ctx, nlevels, (size_t)E * nsub, nl));
+    for (size_t k = 0; k < nl.size(); k++)
+        BA_CHECK(nl[k] >= 0 && nl[k] <= CT_LMAX, BEATAMD_EINVAL, "contour_count: %d levels for draw %lld (at most %d)", (int)nl[k],
+                 (long long)(k / nsub), CT_LMAX);
+    Staging st(ctx);
+    const double *d_s, *d_l;
+    const int64_t *d_sb;
+    const int32_t *d_n;
+    int32_t *d_c;
+    BA_TRY(st.in(sts, (size_t)E * ncells_total, &d_s));
+    BA_TRY(st.in(subs, (size_t)nsub * CT_SUB_FIELDS, &d_sb));
+    BA_TRY(st.in(levels, (size_t)E * nsub * CT_LMAX, &d_l));
+    BA_TRY(st.in(nlevels, (size_t)E * nsub, &d_n));
+    BA_TRY(st.out(counts, (size_t)E * nsub * CT_LMAX * 2, &d_c));
+    BA_TRY(launch_contours(ctx, E, ncells_total, d_s, nsub, d_sb, max_nodes, nullptr, nullptr, d_l, d_n, d_c, nullptr, nullptr, 0, 0,
+                           nullptr, nullptr));
+    return st.finish();
+}
+
+int beatamd_contour_fill(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int32_t nsub, const int64_t *subs,
+                         int64_t nx_total, const double *x, int64_t ny_total, const double *y, const double *levels,
+                         const int32_t *nlevels, const int64_t *line_base, const int64_t *vert_base, int64_t nlines, int64_t nverts,
+                         double *vertices, int64_t *line_offsets)
+{
+    ENTER(ctx);
+    BA_CHECK(sts && x && y && levels && nlevels && line_base && vert_base && vertices && line_offsets && E >= 0 && nlines >= 0 &&
+             nverts >= 0 && nx_total >= 0 && ny_total >= 0, BEATAMD_EINVAL, "contour_fill: bad argument");
+    std::vector<int64_t> sb, lb, vb;
+    std::vector<int32_t> nl;
+    int64_t max_nodes = 0;
+    BA_TRY(rupture_subs(ctx, "contour_fill", nsub, subs, ncells_total, nx_total, ny_total, sb, &max_nodes));
+    if (E == 0) return BEATAMD_OK;
+    // the bases are the caller's scan of beatamd_contour_count's output: non-decreasing and inside the arrays they index.
+    // The kernel writes what it counts again from the same start times, so a level's lines end where the next begin
+    const size_t W = (size_t)E * nsub * CT_LMAX;
+    BA_TRY(host_copy(ctx, line_base, W, lb));
+    BA_TRY(host_copy(ctx, vert_base, W, vb));
+    BA_TRY(host_copy(ctx, nlevels, (size_t)E * nsub, nl));
+    for (size_t k = 0; k < W; k++) {
+        BA_CHECK(lb[k] >= 0 && lb[k] <= nlines && vb[k] >= 0 && vb[k] <= nverts && (k == 0 || (lb[k] >= lb[k - 1] && vb[k] >= vb[k - 1])),
+                 BEATAMD_EINVAL, "contour_fill: line_base / vert_base are not the scans of contour_count's counts");
+        const size_t cap = 2 * (size_t)max_nodes;     // (a level has at most two segments a cell, each at most two vertices)
+        BA_CHECK((k + 1 < W ? (size_t)(vb[k + 1] - vb[k]) : (size_t)(nverts - vb[k])) <= 2 * cap, BEATAMD_EINVAL,
+                 "contour_fill: a level with more vertices than its subfault can give");
+    }
+    for (size_t k = 0; k < nl.size(); k++)
+        BA_CHECK(nl[k] >= 0 && nl[k] <= CT_LMAX, BEATAMD_EINVAL, "contour_fill: %d levels for draw %lld (at most %d)", (int)nl[k],
+                 (long long)(k / nsub), CT_LMAX);
+    Staging st(ctx);
+    const double *d_s, *d_l, *d_x, *d_y;
+    const int64_t *d_sb, *d_lb, *d_vb;
+    const int32_t *d_n;
+    double *d_v;
+    int64_t *d_lo;
+    BA_TRY(st.in(sts, (size_t)E * ncells_total, &d_s));
+    BA_TRY(st.in(subs, (size_t)nsub * CT_SUB_FIELDS, &d_sb));
+    BA_TRY(st.in(x, (size_t)nx_total, &d_x));
+    BA_TRY(st.in(y, (size_t)ny_total, &d_y));
+    BA_TRY(st.in(levels, W, &d_l));
+    BA_TRY(st.in(nlevels, (size_t)E * nsub, &d_n));
+    BA_TRY(st.in(line_base, W, &d_lb));
+    BA_TRY(st.in(vert_base, W, &d_vb));
+    BA_TRY(st.out(vertices, (size_t)nverts * 2, &d_v));
+    BA_TRY(st.out(line_offsets, (size_t)nlines + 1, &d_lo, true));
+    BA_TRY(launch_contours(ctx, E, ncells_total, d_s, nsub, d_sb, max_nodes, d_x, d_y, d_l, d_n, nullptr, d_lb, d_vb, nlines, nverts, d_v,
+                           d_lo));
+    return st.finish();
+}
+
+int beatamd_polyline_density(beatamd_ctx *ctx, int64_t nverts, const double *vertices, int64_t nlines, const int64_t *line_offsets,
+                             int64_t nsel, const int64_t *sel, const double *extent, int64_t ny, int64_t nx, double linewidth,
+                             double *grid, int32_t *coverage)
+{
+    ENTER(ctx);
+    BA_CHECK(line_offsets && extent && grid && nverts >= 0 && nlines >= 0 && nsel >= 0 && ny > 0 && nx > 0 && (vertices || !nverts),
+             BEATAMD_EINVAL, "polyline_density: bad argument");
+    // the offsets and the selection index device arrays: checked here, on the host
+    std::vector<int64_t> lo, se;
+    std::vector<double> ext;
+    BA_TRY(host_copy(ctx, line_offsets, (size_t)nlines + 1, lo));
+    BA_TRY(host_copy(ctx, extent, 4, ext));
+    BA_CHECK(lo[0] >= 0 && lo[nlines] <= nverts, BEATAMD_EINDEX, "polyline_density: line_offsets [%lld, %lld] outside %lld vertices",
+             (long long)lo[0], (long long)lo[nlines], (long long)nverts);
+    for (int64_t k = 0; k < nlines; k++)
+        BA_CHECK(lo[k] <= lo[k + 1], BEATAMD_EINDEX, "polyline_density: line_offsets decrease at line %lld", (long long)k);
+    if (sel) {
+        BA_TRY(host_copy(ctx, sel, (size_t)nsel, se));
+        for (int64_t k = 0; k < nsel; k++)
+            BA_CHECK(se[k] >= 0 && se[k] < nlines, BEATAMD_EINDEX, "polyline_density: polyline %lld of %lld", (long long)se[k],
+                     (long long)nlines);
+    } else {
+        BA_CHECK(nsel == nlines, BEATAMD_EINVAL, "polyline_density: no selection, but %lld of %lld polylines", (long long)nsel,
+                 (long long)nlines);
+    }
+    Staging st(ctx);
+    const double *d_v;
+    const int64_t *d_lo, *d_se = nullptr;
+    double *d_g;
+    int32_t *d_c = nullptr;
+    BA_TRY(st.in(vertices, (size_t)nverts * 2, &d_v));
+    BA_TRY(st.in(line_offsets, (size_t)nlines + 1, &d_lo));
+    if (sel) BA_TRY(st.in(sel, (size_t)nsel, &d_se));
+    BA_TRY(st.out(grid, (size_t)ny * nx, &d_g, true));
+    if (coverage) BA_TRY(st.out(coverage, (size_t)ny * nx, &d_c, true));
+    BA_TRY(launch_polyline_density(ctx, nsel, d_se, d_lo, d_v, ext.data(), ny, nx, linewidth, d_g, d_c));
+    BA_TRY(st.finish());
+    return ctx->check_status();   // (device arrays too: a line outside the grid is the caller's TypeError now, not later)
+}
+
 // ------------------------------------------------------------------ the hyper-parameter model (hyper.hip)
 int beatamd_hyper_model_create(beatamd_ctx *ctx, int64_t nterm, int64_t nh, const int64_t *M, const double *slog,
                                const int32_t *kind, const int32_t *hp_index, int32_t ngroups, const int32_t *group_end,

@@ -326,7 +326,7 @@ constexpr int KNOB_UNSET = -2147483647;
     X(gc_sort, "BEATAMD_GC_SORT") X(gc_keys, "BEATAMD_GC_KEYS") X(gc_bands, "BEATAMD_GC_BANDS") X(gr_cap, "BEATAMD_GR_CAP") \
     X(gr_pass_alloc, "BEATAMD_GR_PASS_ALLOC") X(gr_var, "BEATAMD_GR_VAR") X(sweep_v1, "BEATAMD_SWEEP_V1") X(qf_band, "BEATAMD_QF_BAND") \
     X(qf_fuse, "BEATAMD_QF_FUSE") X(gf_split, "BEATAMD_GF_SPLIT") X(gm_wave, "BEATAMD_GM_WAVE") X(skip_parked, "BEATAMD_SKIP_PARKED") \
-    X(td_strip, "BEATAMD_TD_STRIP")
+    X(td_strip, "BEATAMD_TD_STRIP") X(pd_strip, "BEATAMD_PD_STRIP") X(pd_rows, "BEATAMD_PD_ROWS")
 struct GfKnobs {
 #define X(member, env) int member = KNOB_UNSET;
     BEATAMD_GF_KNOBS(X)
@@ -423,7 +423,7 @@ enum Slot : int {
     SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_MR_SPANS,
     SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_SPEC,
     SL_MG_FLAG, SL_MG_MOM, SL_MG_PAR, SL_MG_GRID, SL_MG_W, SL_MG_BOX,
-    SL_MC_FLAG, SL_MC_COUNT, SL_MC_SUM, SL_COUNT
+    SL_MC_FLAG, SL_MC_COUNT, SL_MC_SUM, SL_PD_BOX, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

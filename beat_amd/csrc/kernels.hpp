@@ -648,6 +648,30 @@ int launch_mt_decompose(beatamd_ctx *ctx, int64_t n, int kind, const double *X, 
 int launch_fuzzy_amps(beatamd_ctx *ctx, int64_t n, int P, const double *unit, int64_t npix, const double *rw,
                       const int64_t *pixel_index, int64_t cells, int mask, int shape, uint32_t *count, double *sum, double *amps);
 
+// ---- rupture.hip: contour lines of the start times of an ensemble and the density grid of polylines (plotting/ffi.py:338-398,
+// :599-615; plotting/common.py:619-801)
+constexpr int CT_LMAX = 16;                 // levels of a (draw, subfault): matplotlib's automatic rule gives at most 10
+constexpr int CT_SUB_FIELDS = 5;            // int64 per subfault: n_dip, n_strike, first patch, first x, first y
+constexpr int CT_MAX_NODES = 2304;          // patches of a subfault (48 x 48): 56 bytes of LDS each, see ct_lds_bytes
+// LDS of a wavefront of the contour kernels: the start times (8 bytes a node) and six int tables of two slots a cell
+inline size_t ct_lds_bytes(int64_t nodes) { return (size_t)nodes * (8 + 2 * 6 * 4); }
+constexpr int PD_STRIP = 32, PD_ROWS = 64;  // the tile of a workgroup of k_polyline_density: columns x rows
+constexpr int PD_LDS_BYTES = 150 * 1024;    // the owner map's share of LDS
+// out [E, nsub, 2] = (min, max) of every (draw, subfault), both NaN where a start time is not finite (k_rupture_minmax)
+int launch_rupture_minmax(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int nsub, const int64_t *subs,
+                          double *out);
+// counts != nullptr: the count pass, counts [E, nsub, CT_LMAX, 2] = (lines, vertices) (k_contour_count); else the fill pass
+// with the exclusive scans line_base / vert_base [E, nsub, CT_LMAX] (k_contour_fill).  max_nodes: the largest subfault
+int launch_contours(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int nsub, const int64_t *subs,
+                    int64_t max_nodes, const double *x, const double *y, const double *levels, const int32_t *nlevels,
+                    int32_t *counts, const int64_t *line_base, const int64_t *vert_base, int64_t nlines, int64_t nverts, double *vertices,
+                    int64_t *line_offsets);
+// grid [ny, nx] += the images of the polylines sel [nsel] (nullptr: 0 ... nsel - 1) in that order, coverage (nullable) += 1
+// per polyline where its image is positive (k_polyline_check, k_polyline_density); extent: host (xmin, xmax, ymin, ymax)
+int launch_polyline_density(beatamd_ctx *ctx, int64_t nsel, const int64_t *sel, const int64_t *line_offsets,
+                            const double *vertices, const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid,
+                            int32_t *coverage);
+
 // ---- seislib.hip: the producer of the seismic FFI library (ffi/base.py:1005-1254, heart.py:3466-3525, 4242-4323); the
 // arithmetic contract stands at the head of seislib.hip
 constexpr int SL_MAX_STAGES = 4, SL_MIN_TAPS = 3, SL_MAX_TAPS = 17;   // the filter cascade; taps = filter order + 1

@@ -1123,6 +1123,43 @@ int beatamd_seis_library_fill(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t L,
                               const int32_t *demean, const double *coef, int64_t S, int64_t N, const int64_t *i0,
                               const double *w0, int64_t patch_block, double *lib);
 
+/* ---- rupture fronts and polyline densities (csrc/rupture.hip, which states the orders the kernels promise)
+ * replaces: the arrays behind `beat plot slip_dist`: the per-draw loop of fault.point2starttimes and matplotlib's
+ *   ax.contour(xgr, ygr, sts) with automatic levels   fault_slip_distribution   beat/plotting/ffi.py:599-611, :645-648
+ *   and the loop of draw_line_on_array over every contour line   fuzzy_rupture_fronts   beat/plotting/ffi.py:338-398
+ *   (draw_line_on_array / _weighted_line beat/plotting/common.py:619-801, positions2idxs beat/utility.py:1556).
+ *   The marching squares restate contourpy's "mpl2014" algorithm from its behaviour (a node is above iff z > level, a saddle
+ *   is split by the mean of its corners, vertices by linear interpolation along the edge); the order of the lines and where a
+ *   closed line starts are this library's own (see rupture.hip), not contourpy's.
+ * sts [E, ncells_total]: the start times of E draws as they leave beatamd_ffi_start_times_batch; subs [nsub, 5] (int64) =
+ *   (n_dip, n_strike, first patch, first x, first y) of every subfault, its patches row-major i * n_strike + j; x / y: the
+ *   centre coordinates along strike / dip of all subfaults.  A subfault holds at most 2304 patches (BEATAMD_EINVAL above).
+ * rupture_minmax: out [E, nsub, 2] = (min, max) of every (draw, subfault), both NaN where a start time is not finite.
+ * contour_count: levels [E, nsub, 16], nlevels [E, nsub] (0 ... 16) -> counts [E, nsub, 16, 2] (int32) = (lines, vertices)
+ *   of every level.  contour_fill: line_base / vert_base [E, nsub, 16] = the exclusive scans of those counts, nlines / nverts
+ *   their totals -> vertices [nverts, 2] = (x, y) and line_offsets [nlines + 1] (entries 0 ... nlines - 1 are written; the last,
+ *   nverts, is the caller's).  A closed line repeats its first vertex.  The output is a function of (draw, subfault, level,
+ *   line, rank in the line) alone: bit for bit independent of how the draws are cut into calls.  Array arguments may live
+ *   on either side.
+ * polyline_density: grid [ny, nx] += the image of every selected polyline (sel [nsel] indices into the nlines lines, in
+ *   drawing order; NULL: all, nsel == nlines), each drawn into an image of its own as beatamd_trace_density_update draws a
+ *   trace -- the same cell indices, limits and arithmetic, the grid equals draw_line_on_array's called line by line bit
+ *   for bit --; coverage [ny, nx] (int32, nullable) += 1 per polyline where its image is positive.  extent [4] = (xmin, xmax,
+ *   ymin, ymax).  Errors as beatamd_trace_density_update: BEATAMD_EOUTSIDE for a vertex above the last cell or below
+ *   -32768, BEATAMD_EINVAL for a vertex or extent that is not finite, ny, nx outside 2 ... 4096, linewidth outside (0, 64];
+ *   BEATAMD_EINDEX for offsets or a selection outside their arrays. */
+int beatamd_rupture_minmax(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int32_t nsub,
+                           const int64_t *subs, double *out);
+int beatamd_contour_count(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int32_t nsub,
+                          const int64_t *subs, const double *levels, const int32_t *nlevels, int32_t *counts);
+int beatamd_contour_fill(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const double *sts, int32_t nsub, const int64_t *subs,
+                         int64_t nx_total, const double *x, int64_t ny_total, const double *y, const double *levels,
+                         const int32_t *nlevels, const int64_t *line_base, const int64_t *vert_base, int64_t nlines,
+                         int64_t nverts, double *vertices, int64_t *line_offsets);
+int beatamd_polyline_density(beatamd_ctx *ctx, int64_t nverts, const double *vertices, int64_t nlines,
+                             const int64_t *line_offsets, int64_t nsel, const int64_t *sel, const double *extent, int64_t ny,
+                             int64_t nx, double linewidth, double *grid, int32_t *coverage);
+
 #ifdef __cplusplus
 }
 #endif
