@@ -189,6 +189,9 @@ _PROTOS = {
     "beatamd_contour_count": [_vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp],
     "beatamd_contour_fill": [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "beatamd_polyline_density": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _f64, _vp, _vp],
+    "beatamd_autocov_lags_batch": [_vp, _i64, _i64, _vp, _i64, _i64, _vp],
+    "beatamd_rank_normalize": [_vp, _i64, _vp, _vp, _vp],
+    "beatamd_convergence_summary": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _f64, _f64, _i64, _i64, _vp, _vp, _pi64],
 }
 
 EXPORTS = sorted(list(_PROTOS) + ["beatamd_last_error", "beatamd_version"])

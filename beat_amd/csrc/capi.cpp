@@ -3270,4 +3270,73 @@ int beatamd_seis_library_fill(beatamd_ctx *ctx, int64_t T, int64_t P, int64_t L,
     return BEATAMD_OK;
 }
 
+// ------------------------------------------------------------------ convergence summary (convergence.hip)
+// what arviz.summary computes for summary.txt (apps/beat.py:1338-1363) from the result trace (backend.py:1401-1415)
+int beatamd_autocov_lags_batch(beatamd_ctx *ctx, int64_t R, int64_t n, const double *Y, int64_t lag0, int64_t nlags, double *out)
+{
+    ENTER(ctx);
+    BA_CHECK(R >= 0 && n >= 1 && lag0 >= 0 && nlags >= 0 && ((Y && out) || R == 0 || nlags == 0), BEATAMD_EINVAL,
+             "autocov_lags_batch: bad argument (R, lag0, nlags >= 0; n >= 1)");
+    BA_CHECK((double)R * (double)std::max(n, nlags) < 9.0e18 / 8.0, BEATAMD_EINVAL, "autocov_lags_batch: the batch is too large");
+    if (R == 0 || nlags == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_Y;
+    double *d_o;
+    BA_TRY(st.in(Y, (size_t)R * n, &d_Y));
+    BA_TRY(st.out(out, (size_t)R * nlags, &d_o));
+    BA_TRY(launch_autocov_lags(ctx, R, n, d_Y, lag0, nlags, d_o));
+    return st.finish();
+}
+
+int beatamd_rank_normalize(beatamd_ctx *ctx, int64_t n, const double *A, double *z, double *ranks)
+{
+    ENTER(ctx);
+    BA_CHECK(n >= 1 && A && z, BEATAMD_EINVAL, "rank_normalize: bad argument (n >= 1)");
+    BA_CHECK(n <= MG_SORT_MAX_N, BEATAMD_EINVAL, "rank_normalize: %lld values, at most %lld", (long long)n,
+             (long long)MG_SORT_MAX_N);
+    Staging st(ctx);
+    const double *d_A;
+    double *d_z, *d_r = nullptr;
+    int64_t *d_c;
+    BA_TRY(st.in(A, (size_t)n, &d_A));
+    BA_TRY(ctx->scratch(SL_CV_OFF, (size_t)1, &d_c));
+    BA_HIP(hipMemsetAsync(d_c, 0, sizeof(int64_t), ctx->stream));
+    BA_TRY(mg_finite(ctx, "rank_normalize", d_A, n, 1, d_c, std::vector<int64_t>(1, 0), nullptr));
+    BA_TRY(st.out(z, (size_t)n, &d_z));
+    if (ranks) BA_TRY(st.out(ranks, (size_t)n, &d_r));
+    BA_TRY(launch_rank_normalize(ctx, n, d_A, d_z, d_r));
+    return st.finish();
+}
+
+int beatamd_convergence_summary(beatamd_ctx *ctx, int64_t C, int64_t D, int64_t V, const double *X, int64_t K,
+                                const int64_t *cols, double hdi_prob, double tau_floor, int64_t var_batch, int64_t first_lags,
+                                double *out, int32_t *flags, int64_t *rounds)
+{
+    ENTER(ctx);
+    BA_CHECK(C >= 1 && D >= 1 && V >= 1 && K >= 0 && X && (K == 0 || (cols && out && flags)), BEATAMD_EINVAL,
+             "convergence_summary: bad argument (C, D, V >= 1; K >= 0)");
+    BA_CHECK(hdi_prob > 0.0 && hdi_prob < 1.0, BEATAMD_EINVAL, "convergence_summary: hdi_prob %g outside (0, 1)", hdi_prob);
+    BA_CHECK(var_batch >= 0 && first_lags >= 2, BEATAMD_EINVAL, "convergence_summary: var_batch %lld < 0 or first_lags %lld < 2",
+             (long long)var_batch, (long long)first_lags);
+    BA_CHECK((double)C * (double)D <= (double)MG_SORT_MAX_N, BEATAMD_EINVAL,
+             "convergence_summary: %lld x %lld samples a variable, at most %lld", (long long)C, (long long)D,
+             (long long)MG_SORT_MAX_N);
+    BA_CHECK((double)C * (double)D * (double)V < 9.0e18 / 8.0, BEATAMD_EINVAL, "convergence_summary: the trace is too large");
+    std::vector<int64_t> hc;
+    BA_TRY(mg_columns(ctx, "convergence_summary", cols, K, V, hc));
+    if (rounds) *rounds = 0;
+    if (K == 0) return BEATAMD_OK;
+    Staging st(ctx);
+    const double *d_X;
+    const int64_t *d_c;
+    double *d_o;
+    int32_t *d_f;
+    BA_TRY(st.in(X, (size_t)C * D * V, &d_X));
+    BA_TRY(st.in(cols, (size_t)K, &d_c));
+    BA_TRY(st.out(out, (size_t)K * CV_NCOL, &d_o));
+    BA_TRY(st.out(flags, (size_t)K, &d_f));
+    BA_TRY(launch_convergence_summary(ctx, C, D, V, d_X, K, d_c, hdi_prob, tau_floor, var_batch, first_lags, d_o, d_f, rounds));
+    return st.finish();
+}
+
 }  // extern "C"

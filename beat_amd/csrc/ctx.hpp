@@ -423,7 +423,9 @@ enum Slot : int {
     SL_GM_W, SL_GM_SCALE, SL_GM_FLAG, SL_LSQ_N, SL_LSQ_B, SL_LSQ_X, SL_LSQ_U, SL_MR_SPANS,
     SL_RES_GG, SL_RES_N, SL_RES_W, SL_RES_T, SL_RES_U, SL_RATE_DMIN, SL_SPEC,
     SL_MG_FLAG, SL_MG_MOM, SL_MG_PAR, SL_MG_GRID, SL_MG_W, SL_MG_BOX,
-    SL_MC_FLAG, SL_MC_COUNT, SL_MC_SUM, SL_PD_BOX, SL_COUNT
+    SL_MC_FLAG, SL_MC_COUNT, SL_MC_SUM, SL_PD_BOX,
+    SL_CV_W, SL_CV_SA, SL_CV_SB, SL_CV_Q, SL_CV_CM, SL_CV_RM, SL_CV_OFF, SL_CV_ESS, SL_CV_ACT, SL_CV_STATE, SL_CV_MAC0, SL_CV_MAC1,
+    SL_CV_AC, SL_CV_RHO, SL_CV_PART, SL_COUNT
 };
 constexpr int SL_NIN = SL_OUT0 - SL_IN0, SL_NOUT = SL_ROWOFF - SL_OUT0;   // the slots of Staging
 

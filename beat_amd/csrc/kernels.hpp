@@ -631,6 +631,25 @@ int launch_sph_sum(beatamd_ctx *ctx, int64_t n, const double *U, double *S);
 int launch_sph_kde(beatamd_ctx *ctx, int64_t n, const double *U0, int64_t m, const double *Ug, double norm, double sigma2,
                    int shape, double *kde);
 
+// ---- convergence.hip: ESS, R-hat and highest-density intervals of a trace X [C, D, V] (apps/beat.py:1338-1363,
+// backend.py:1401-1415)
+constexpr int CV_NT = 6;                    // row sets of a variable: raw, squared deviation, <= q05, <= q95, z raw, z folded
+constexpr int CV_NCOL = 11;                 // columns of the summary table
+constexpr int CV_ACOV_TILE = 512;           // values of a row staged in LDS at a time by k_acov_lags
+constexpr int64_t CV_ACOV_CHUNK = 4096;     // consecutive i summed into one partial sum of a lag: part of what a lag's bits are
+constexpr int64_t CV_WORKSPACE_BYTES = (int64_t)1 << 30;   // the budget that sizes a batch of variables
+constexpr int64_t CV_PART_BYTES = (int64_t)256 << 20;      // the chunk sums of one range of lags (k_acov_lags -> k_acov_combine)
+// out [R, nlags] = the biased autocovariance of the rows Y [R, n] at the lags lag0 .. lag0 + nlags
+int launch_autocov_lags(beatamd_ctx *ctx, int64_t R, int64_t n, const double *Y, int64_t lag0, int64_t nlags, double *out);
+// z [n] (and ranks [n] unless NULL) of A [n]
+int launch_rank_normalize(beatamd_ctx *ctx, int64_t n, const double *A, double *z, double *ranks);
+// the variables of a pass when the caller fixes none
+int64_t convergence_batch(int64_t C, int64_t D, int64_t K);
+// out [K, CV_NCOL], flags [K], cols [K]: device; rounds: host, nullable
+int launch_convergence_summary(beatamd_ctx *ctx, int64_t C, int64_t D, int64_t V, const double *X, int64_t K,
+                               const int64_t *d_cols, double hdi_prob, double tau_floor, int64_t var_batch, int64_t first_lags,
+                               double *out, int32_t *flags, int64_t *rounds);
+
 // ---- mechanisms.hip: eigen-systems, standard decompositions, Hudson points and fuzzy-beachball grids of an ensemble of
 // moment tensors (plotting/seismic.py:1334-1425, 1664-1850, 2183-2310); the per-draw arithmetic is mechanism.hpp's
 constexpr int MC_NPART = 5;                                  // iso, dc, clvd, dev, full

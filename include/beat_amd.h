@@ -1160,6 +1160,33 @@ int beatamd_polyline_density(beatamd_ctx *ctx, int64_t nverts, const double *ver
                              const int64_t *line_offsets, int64_t nsel, const int64_t *sel, const double *extent, int64_t ny,
                              int64_t nx, double linewidth, double *grid, int32_t *coverage);
 
+/* ---- convergence summary of a trace (csrc/convergence.hip): the table ``beat summarize`` writes to summary.txt with
+ * arviz.summary(idata, round_to=4, skipna=True) (apps/beat.py:1338-1363) from the result trace turned into inference data
+ * (multitrace_to_inference_data, backend.py:1401-1415).  The statistics are restated from memory of arviz's
+ * stats/diagnostics.py and of Vehtari, Gelman, Simpson, Carpenter & Buerkner (2021), unverified against an installed arviz.
+ * Arrays live on either side.
+ * autocov_lags_batch (apps/beat.py:1338-1363, backend.py:1401-1415: the autocovariance behind every ESS): out [R, nlags],
+ *   out[r, k] = (1/n) sum_i (y_i - m)(y_{i + lag0 + k} - m) of the R rows Y [R, n], m the row's mean, the biased estimate;
+ *   a lag >= n gives 0.  Each lag is summed over ascending i in chunks of 4096 added in ascending order, one accumulator per
+ *   lag: the value of a lag does not depend on lag0, nlags or R.
+ * rank_normalize (apps/beat.py:1338-1363, backend.py:1401-1415: the transform of ess_bulk and r_hat): z [n] =
+ *   normcdfinv((r - 3/8) / (n + 1/4)), r the average ranks (scipy.stats.rankdata "average"; -0.0 and 0.0 tie) of A [n], also
+ *   written to ranks [n] where that is not NULL.  BEATAMD_ENAN for a non-finite value; n <= 2^24.
+ * convergence_summary (apps/beat.py:1338-1363, backend.py:1401-1415): X [C, D, V] = C chains of D draws of V variables;
+ *   out [K, 11] for the K columns cols = mean, sd, hdi_lo, hdi_hi, mcse_mean, mcse_sd, ess_bulk, ess_tail, r_hat, ess_mean,
+ *   ess_sd.  The two mcse columns come back NaN: the caller forms them from sd, ess_mean and ess_sd.  hdi_prob in (0, 1).
+ *   tau_floor = 1 / log10(2 C (D / 2)), the smallest autocorrelation time of an ESS, computed by the caller (<= 0: here).
+ *   flags [K] = 1 for a column with a non-finite sample: its row is NaN (arviz's skipna would skip the sample).  D < 4: the
+ *   diagnostics are NaN; mean, sd and the interval are filled.  var_batch > 0 fixes the variables of a pass over the
+ *   workspace (0: sized to a budget), first_lags >= 2 the lags of the first round of the on-demand autocovariance (the next
+ *   rounds take four times as many for the scans that have not stopped); neither changes a bit of out.  rounds (nullable):
+ *   the largest number of rounds a pass took.  C D <= 2^24. */
+int beatamd_autocov_lags_batch(beatamd_ctx *ctx, int64_t R, int64_t n, const double *Y, int64_t lag0, int64_t nlags, double *out);
+int beatamd_rank_normalize(beatamd_ctx *ctx, int64_t n, const double *A, double *z, double *ranks);
+int beatamd_convergence_summary(beatamd_ctx *ctx, int64_t C, int64_t D, int64_t V, const double *X, int64_t K,
+                                const int64_t *cols, double hdi_prob, double tau_floor, int64_t var_batch, int64_t first_lags,
+                                double *out, int32_t *flags, int64_t *rounds);
+
 #ifdef __cplusplus
 }
 #endif
