@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "devmath.hpp"
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -148,19 +149,6 @@ __global__ void __launch_bounds__(CV_TB) k_conv_write_derived(double *W, int64_t
     w[5 * n2 + e] = fabs(x - med[k]);
 }
 
-// first index with s[i] >= x (right: s[i] > x) in the ascending s [n] (marginals.hip's mg_bound)
-__device__ __forceinline__ int64_t cv_bound(const double *s, int64_t n, double x, bool right)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t m = lo + ((hi - lo) >> 1);
-        const double v = s[m];
-        if (right ? v <= x : v < x) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
-
 // z[e] = normcdfinv((rank - 3/8) / (n + 1/4)) of vals[e] among the sorted values of its set; set k: vals + k * vstride [n],
 // sorted S + k * n, z + k * zstride (z may be vals: every element is read once, by the thread that writes it);
 // ranks != nullptr: the average ranks [K, n] as well
@@ -172,7 +160,7 @@ __global__ void __launch_bounds__(CV_TB) k_conv_rank_z(const double *vals, int64
     if (e >= n) return;
     const double x = vals[k * vstride + e];
     const double *s = S + k * n;
-    const int64_t lo = cv_bound(s, n, x, false), hi = cv_bound(s, n, x, true);
+    const int64_t lo = sorted_bound(s, n, x, false), hi = sorted_bound(s, n, x, true);
     const double r = (double)(lo + hi + 1) / 2.0;   // the mean of the ranks lo + 1 .. hi
     if (ranks) ranks[k * n + e] = r;
     z[k * zstride + e] = normcdfinv((r - 0.375) / ((double)n + 0.25));

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ctx.hpp"
+#include "devmath.hpp"
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -24,8 +25,6 @@ constexpr int MG_SORT_TB = 1024;   // threads of a sorting workgroup
 constexpr int MG_TB = 256;         // threads of every other workgroup here
 constexpr double MG_INF = __builtin_huge_val();
 
-__device__ __forceinline__ bool mg_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
-
 // ---------------------------------------------------------------------------------------------- finite check
 // flags[k] = 1 where column cols[k] of X holds a non-finite sample (flags zeroed by the caller; every writer stores 1)
 __global__ void __launch_bounds__(MG_TB) k_col_check(const double *X, int64_t n, int64_t V, const int64_t *cols, int32_t *flags)
@@ -34,7 +33,7 @@ __global__ void __launch_bounds__(MG_TB) k_col_check(const double *X, int64_t n,
     const double *x = X + cols[k];
     bool bad = false;
     for (int64_t i = (int64_t)blockIdx.x * MG_TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * MG_TB)
-        bad = bad || !mg_finite(x[i * V]);
+        bad = bad || !is_finite(x[i * V]);
     if (bad) flags[k] = 1;
 }
 
@@ -132,27 +131,14 @@ __global__ void __launch_bounds__(MG_TB) k_col_percentiles(const double *S, int6
 }
 
 // ---------------------------------------------------------------------------------------------- histograms
-// first index with s[i] >= x (right: s[i] > x) in the ascending s [n]
-__device__ __forceinline__ int64_t mg_bound(const double *s, int64_t n, double x, bool right)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t m = lo + ((hi - lo) >> 1);
-        const double v = s[m];
-        if (right ? v <= x : v < x) lo = m + 1;
-        else hi = m;
-    }
-    return lo;
-}
-
 // counts[k, i] = #{edges[k, i] <= x < edges[k, i + 1]}, the last bin closed on the right (numpy.histogram)
 __global__ void __launch_bounds__(MG_TB) k_col_hist(const double *S, int64_t n, const double *edges, int64_t nb, int64_t *counts)
 {
     const int64_t i = (int64_t)blockIdx.x * MG_TB + threadIdx.x, k = blockIdx.y;
     if (i >= nb) return;
     const double *s = S + k * n, *e = edges + k * (nb + 1);
-    const int64_t a = mg_bound(s, n, e[i], false);
-    const int64_t b = mg_bound(s, n, e[i + 1], i + 1 == nb);
+    const int64_t a = sorted_bound(s, n, e[i], false);
+    const int64_t b = sorted_bound(s, n, e[i + 1], i + 1 == nb);
     counts[k * nb + i] = b - a;
 }
 

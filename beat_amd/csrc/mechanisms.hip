@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ctx.hpp"
+#include "devmath.hpp"
 #include "kernels.hpp"
 #include "mechanism.hpp"
 
@@ -24,8 +25,6 @@ namespace {
 
 constexpr int MC_TB = 256;
 
-__device__ __forceinline__ bool mc_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // false for NaN
-
 // *bad = min(*bad, first bad row) (set to 0xffffffff by the caller)
 __global__ void __launch_bounds__(MC_TB) k_mt_check(const double *X, int64_t n, int w, int zero_is_bad, uint32_t *bad)
 {
@@ -34,7 +33,7 @@ __global__ void __launch_bounds__(MC_TB) k_mt_check(const double *X, int64_t n, 
     bool fin = true, zero = true;
     for (int k = 0; k < w; k++) {
         const double x = X[i * w + k];
-        fin = fin && mc_finite(x);
+        fin = fin && is_finite(x);
         zero = zero && x == 0.0;
     }
     if (!fin || (zero && zero_is_bad)) atomicMin(bad, (uint32_t)i);

@@ -8,6 +8,7 @@
 //   moment_to_magnitude(M0) = log10(M0 * 1e7) / 1.5 - 10.7
 //   HalfSinusoidSTF.discretize_t with exponent = 1 (BEAT's default stf_type), the rule stated at k_moment_rate
 // All arithmetic is FP64 with contraction off: tests/momentrate_ref.py restates every kernel operation by operation.
+#include "devmath.hpp"
 #include "kernels.hpp"
 #include "stf.hpp"
 #include "wave.hpp"
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(64) k_moment_rate_span(int64_t P, int nsub, co
     int bad = 0;
     for (int64_t p = lane; p < P; p += 64) {
         const double d = dur[p], t = st[p];
-        if (!(d >= 0.0 && d <= 1.79769313486231570815e+308) || !(fabs(t) <= 1.79769313486231570815e+308)) bad = 1;
+        if (!(d >= 0.0 && is_finite(d)) || !is_finite(t)) bad = 1;
         dmax = fmax(dmax, d);
     }
     dmax = wave_butterfly<OpFmax>(dmax);

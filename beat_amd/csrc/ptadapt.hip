@@ -23,6 +23,7 @@
 //
 // Every accumulator entry is owned by one thread of one workgroup whose geometry is fixed, and sees the rows of its group in
 // index order: the sums depend on (group, replica, order of the calls) alone.  No atomics.
+#include "devmath.hpp"
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -32,8 +33,6 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 constexpr int GM_TB = 256;
 constexpr int GM_T = 64, GM_KS = 16, GM_P = GM_KS + 1;   // S2 tile edge, rows per LDS stage, LDS pitch
-
-__device__ __forceinline__ bool gm_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // (false for NaN)
 
 __global__ void __launch_bounds__(GM_TB) k_gm_reset(double *state, int64_t stride)
 {
@@ -65,8 +64,8 @@ __global__ void __launch_bounds__(GM_TB) k_gm_weights(const double *Q, const dou
     for (int64_t r = wave; r < R; r += GM_TB / 64) {
         const double *x = Q + (g * R + r) * n;
         const double lk = like[(g * R + r) * lstride];
-        int bad = gm_finite(lk) ? 0 : 1;
-        for (int64_t j = lane; j < n; j += 64) bad |= gm_finite(x[j]) ? 0 : 1;
+        int bad = is_finite(lk) ? 0 : 1;
+        for (int64_t j = lane; j < n; j += 64) bad |= is_finite(x[j]) ? 0 : 1;
         bad = __any(bad);
         if (lane == 0) wl[r] = bad ? NAN : lk;
     }
@@ -262,12 +261,12 @@ __global__ void __launch_bounds__(GM_TB) k_gm_check(const double *state, int64_t
     __shared__ int any;
     const double *st = state + (int64_t)blockIdx.x * stride;
     const double S0 = st[1], fact = 1.0 - st[2] / (S0 * S0);
-    if (threadIdx.x == 0) any = (!gm_finite(st[0]) || !gm_finite(S0) || !(fact > 0.0) || st[4] > 0.0) ? 1 : 0;
+    if (threadIdx.x == 0) any = (!is_finite(st[0]) || !is_finite(S0) || !(fact > 0.0) || st[4] > 0.0) ? 1 : 0;
     __syncthreads();
     int mine = 0;
     for (int64_t e = threadIdx.x; e < n * n; e += GM_TB) {
         const int64_t i = e / n, j = e - i * n;
-        if (j <= i && !gm_finite(gm_cov_entry(st, n, i, j, S0, fact))) mine = 1;
+        if (j <= i && !is_finite(gm_cov_entry(st, n, i, j, S0, fact))) mine = 1;
     }
     if (mine) any = 1;   // (every writer stores the same value)
     __syncthreads();

@@ -2,7 +2,9 @@
 // fault_slip_distribution): contour lines of the start times of an ensemble of draws (what the reference gets from one
 // matplotlib contour call per draw, :599-611) and the density grid of arbitrary polylines (its loop of draw_line_on_array
 // over the contour lines, plotting/common.py:619-801).  The orders the kernels promise are stated at each kernel.
+#include "devmath.hpp"
 #include "kernels.hpp"
+#include "raster.hpp"
 #include "wave.hpp"
 
 namespace beatamd {
@@ -21,7 +23,7 @@ __global__ void __launch_bounds__(64) k_rupture_minmax(int64_t ncells_total, con
     int bad = 0;
     for (int64_t k = lane; k < n; k += 64) {
         const double v = z[k];
-        if (!(fabs(v) <= 1.79769313486231570815e+308)) bad = 1;
+        if (!is_finite(v)) bad = 1;
         lo = fmin(lo, v);
         hi = fmax(hi, v);
     }
@@ -263,9 +265,9 @@ int launch_contours(beatamd_ctx *ctx, int64_t E, int64_t ncells_total, const dou
 // ---- density grid of polylines (plotting/ffi.py:374-385: draw_line_on_array once per contour line).  Every selected
 // polyline is drawn as its segments, anti-aliased, into an image of its own -- a pixel keeps the value of the
 // highest-numbered segment that writes it -- and the image is added to the grid, polylines in the order given; coverage
-// gets 1 per polyline wherever its image is positive.  The per-pixel arithmetic is k_trace_density's (summary.hip),
-// operation by operation; what differs is where the segments come from: the vertices are arbitrary, so a workgroup cannot
-// find its segments by bisection on a time axis.
+// gets 1 per polyline wherever its image is positive.  The rasteriser is raster.hpp's, the one k_trace_density
+// (summary.hip) draws with; what is here is where the segments come from: the vertices are arbitrary, so a workgroup
+// cannot find its segments by bisection on a time axis.
 struct PdArgs {
     int64_t nsel;
     const int64_t *sel, *line_offsets;   // sel [nsel]: the polylines to draw, in order (nullptr: 0 ... nsel - 1)
@@ -277,18 +279,9 @@ struct PdArgs {
     int32_t *bbox;                       // [nsel, 4] = (first column, last column, first row, last row) of the cell indices
     int *status;
 };
-constexpr int PD_THREADS = 256;
-constexpr double PD_INDEX_MIN = -32768.0;   // below: the reference's int32 products overflow
 
-// utility.py:1556: round((pos - min - cell / 2) / cell), half to even -- as a double
-__device__ __forceinline__ double pd_cell(double pos, double lo, double step)
-{
-#pragma clang fp contract(off)
-    return rint((pos - lo - step / 2.0) / step);
-}
-
-// one wavefront <-> a selected polyline: every vertex's cell indices are checked (above the grid or below PD_INDEX_MIN ->
-// ST_LINE_OOB, check_line_in_grid's TypeError; not finite -> ST_LINE_NONFINITE) and their bounding box is kept
+// one wavefront <-> a selected polyline: every vertex's cell indices are checked (rs_index_status; a vertex raises one word,
+// not finite before out of the grid) and their bounding box is kept
 __global__ void __launch_bounds__(256) k_polyline_check(PdArgs a)
 {
 #pragma clang fp contract(off)
@@ -300,10 +293,10 @@ __global__ void __launch_bounds__(256) k_polyline_check(PdArgs a)
     int bad = 0, cmin = 0x7fffffff, cmax = -0x7fffffff, rmin = 0x7fffffff, rmax = -0x7fffffff;
     if (!(a.xstep > 0.0) && n > 0) bad |= ST_LINE_NONFINITE;
     for (int64_t k = lane; k < n; k += 64) {
-        const double c = pd_cell(a.vertices[2 * (v0 + k)], a.xmin, a.xstep);
-        const double r = pd_cell(a.vertices[2 * (v0 + k) + 1], a.ymin, a.ystep);
-        if (!(fabs(c) <= 1.79769313486231570815e+308) || !(fabs(r) <= 1.79769313486231570815e+308)) bad |= ST_LINE_NONFINITE;
-        else if (c > (double)(a.nx - 1) || c < PD_INDEX_MIN || r > (double)(a.ny - 1) || r < PD_INDEX_MIN) bad |= ST_LINE_OOB;
+        const double c = rs_cell(a.vertices[2 * (v0 + k)], a.xmin, a.xstep);
+        const double r = rs_cell(a.vertices[2 * (v0 + k) + 1], a.ymin, a.ystep);
+        const int st = rs_index_status(c, a.nx - 1) | rs_index_status(r, a.ny - 1);
+        if (st) bad |= st & ST_LINE_NONFINITE ? ST_LINE_NONFINITE : ST_LINE_OOB;
         else {
             cmin = min(cmin, (int)c); cmax = max(cmax, (int)c);
             rmin = min(rmin, (int)r); rmax = max(rmax, (int)r);
@@ -318,119 +311,37 @@ __global__ void __launch_bounds__(256) k_polyline_check(PdArgs a)
     }
 }
 
-// The segments of one polyline for the workgroup's tile, rows [t0, t1) x columns [s0, s1), PD_THREADS at a time -- the
-// set-up and the two passes of k_trace_density:
-//   set-up  lane <-> segment: cell indices of its two vertices, the roles of rows and columns, slope, width, intercept, and
-//           the range of x (the line's long axis) that lies inside the tile; a segment whose bounding box, widened by the
-//           reach of its line, misses the tile gets no x at all.  An inclusive scan of the lengths numbers the (segment, x)
-//           pairs: the segments that can touch the tile are the only ones the passes see
-//   pass    lane <-> (segment, x) pair, found by bisection in the scan; the lane walks the 2 th + 3 pixels across the
-//           line.  PASS 0: every pixel written gets the segment number through an LDS atomic max; PASS 1: where the
-//           segment is the owner its value is added to the grid, the coverage counted and the entry cleared.
-struct PdSetup {
-    double slope[PD_THREADS], b[PD_THREADS], hw[PD_THREADS];
-    int xlo[PD_THREADS], meta[PD_THREADS], pre[PD_THREADS];    // meta = th | transposed << 8; pre = scan of the lengths
-    int wtot[PD_THREADS / 64];
-};
-
-// -> pairs of the PD_THREADS segments from seg0 on (the last is ihi); segment i joins the vertices i - 1 and i of v
-__device__ __forceinline__ int pd_setup(const PdArgs &a, PdSetup &S, const double *v, int64_t seg0, int64_t ihi, int s0, int s1,
+// The set-up (raster.hpp) of the RS_THREADS segments of the polyline v from seg0 on (the last is ihi) for the workgroup's
+// tile; segment i joins the vertices i - 1 and i.  -> its pairs: the segments that can touch the tile are the only ones
+// the passes see
+__device__ __forceinline__ int pd_setup(const PdArgs &a, RsSetup &S, const double *v, int64_t seg0, int64_t ihi, int s0, int s1,
                                         int t0, int t1)
 {
-#pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-    const int64_t i = seg0 + tid;
-    int cnt = 0;
-    if (i <= ihi) {
-        int c0 = (int)pd_cell(v[2 * (i - 1)], a.xmin, a.xstep);
-        int c1 = (int)pd_cell(v[2 * i], a.xmin, a.xstep);
-        int r0 = (int)pd_cell(v[2 * (i - 1) + 1], a.ymin, a.ystep);
-        int r1 = (int)pd_cell(v[2 * i + 1], a.ymin, a.ystep);
-        if (r0 != r1 || c0 != c1) {                             // (else the reference's ValueError branch: nothing drawn)
-            const bool tr = abs(c1 - c0) < abs(r1 - r0);        // steep: rows and columns change roles, limits included
-            if (tr) { int s = r0; r0 = c0; c0 = s; s = r1; r1 = c1; c1 = s; }
-            if (c0 > c1) { int s = r0; r0 = r1; r1 = s; s = c0; c0 = c1; c1 = s; }
-            const double slope = (double)(r1 - r0) / (double)(c1 - c0);
-            const double w = a.linewidth * sqrt(1.0 + fabs(slope)) / 2.0;
-            const double b = (double)((int64_t)c1 * r0 - (int64_t)c0 * r1) / (double)(c1 - c0);
-            const double hw = w / 2.0;
-            const int th = (int)ceil(hw);
-            // x runs along the long axis (columns, or rows when steep), y across it: both are cut to the tile, x here, y in
-            // the pass.  Across the line the pixels lie within th + 2 of the end points' (th + 1 pixels and the centre's rounding)
-            const int xa = tr ? t0 : s0, xb = tr ? t1 : s1, ya = tr ? s0 : t0, yb = tr ? s1 : t1;
-            const int xlo = max(c0, xa), xhi = min(c1, xb - 1);
-            const bool off = max(r0, r1) + th + 2 < ya || min(r0, r1) - th - 2 >= yb;
-            if (xhi >= xlo && !off) cnt = xhi - xlo + 1;
-            S.slope[tid] = slope; S.b[tid] = b; S.hw[tid] = hw; S.xlo[tid] = xlo; S.meta[tid] = th | (tr ? 256 : 0);
-        }
+    const int64_t i = seg0 + threadIdx.x;
+    const bool have = i <= ihi;
+    int c0 = 0, r0 = 0, c1 = 0, r1 = 0;
+    if (have) {
+        c0 = (int)rs_cell(v[2 * (i - 1)], a.xmin, a.xstep);
+        c1 = (int)rs_cell(v[2 * i], a.xmin, a.xstep);
+        r0 = (int)rs_cell(v[2 * (i - 1) + 1], a.ymin, a.ystep);
+        r1 = (int)rs_cell(v[2 * i + 1], a.ymin, a.ystep);
     }
-    int sc = cnt;
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {   // a scan: open-coded (the reductions are wave.hpp's)
-        const int n = __shfl_up(sc, d);
-        if (lane >= d) sc += n;
-    }
-    if (lane == 63) S.wtot[wave] = sc;
-    __syncthreads();
-    for (int k = 0; k < wave; k++) sc += S.wtot[k];
-    S.pre[tid] = sc;
-    __syncthreads();
-    return S.pre[PD_THREADS - 1];
-}
-
-template <int PASS>
-__device__ __forceinline__ void pd_pass(const PdArgs &a, const PdSetup &S, uint32_t *owner, int64_t seg0, int total, int s0,
-                                        int s1, int t0, int t1)
-{
-#pragma clang fp contract(off)
-    for (int it = threadIdx.x; it < total; it += PD_THREADS) {
-        int k = 0;                                              // the first segment whose scan exceeds `it`
-#pragma unroll
-        for (int s = PD_THREADS / 2; s > 0; s >>= 1)
-            if (S.pre[k + s - 1] <= it) k += s;
-        const int meta = S.meta[k], th = meta & 255;
-        const bool tr = meta >> 8;
-        const int x = S.xlo[k] + (it - (k ? S.pre[k - 1] : 0));
-        const double slope = S.slope[k], b = S.b[k], hw = S.hw[k];
-        const uint32_t seg = (uint32_t)(seg0 + k);
-        const double ylo = tr ? (double)s0 : (double)t0, yhi = tr ? (double)s1 : (double)t1;
-        const double yv = (double)x * slope + b;
-        const double fl = floor(yv);
-        for (int o = -th - 1; o <= th + 1; o++) {
-            const double yy = fl + (double)o;
-            const double up = yy + 1.0 + hw - yv, dn = -yy + 1.0 + hw + yv;
-            double v = up < dn ? up : dn;
-            v = v > 1.0 ? 1.0 : v;
-            if (!(v > 0.0) || yy < ylo || !(yy < yhi)) continue;
-            const int iy = (int)yy;
-            const int row = tr ? x : iy, col = tr ? iy : x;
-            uint32_t *own = owner + (row - t0) * a.strip + (col - s0);
-            if (PASS == 0) {
-                atomicMax(own, seg);
-            } else if (*(volatile uint32_t *)own == seg) {
-                const int64_t at = (int64_t)row * a.nx + col;
-                a.grid[at] = a.grid[at] + v;
-                if (a.coverage) a.coverage[at] = a.coverage[at] + 1;
-                *own = 0u;
-            }
-        }
-    }
+    return rs_setup(S, have, c0, r0, c1, r1, a.linewidth, s0, s1, t0, t1);
 }
 
 // One workgroup <-> a tile of the grid; it walks the polylines in order, so every pixel's sum has the reference's order
 // without atomics on doubles, and the tile is the workgroup's alone.  A polyline whose bounding box (k_polyline_check),
 // widened by `pad` cells, misses the tile is passed over without a barrier.  The result does not depend on the tile's
 // shape or on the chunking.
-__global__ void __launch_bounds__(PD_THREADS) k_polyline_density(PdArgs a)
+__global__ void __launch_bounds__(RS_THREADS) k_polyline_density(PdArgs a)
 {
     extern __shared__ uint32_t pd_owner[];
-    __shared__ PdSetup S;
+    __shared__ RsSetup S;
     if (*(volatile int *)a.status & (ST_LINE_OOB | ST_LINE_NONFINITE)) return;   // (k_polyline_check, uniform)
     const int s0 = blockIdx.x * a.strip, s1 = min(s0 + a.strip, a.nx - 1);
     const int t0 = blockIdx.y * a.rows, t1 = min(t0 + a.rows, a.ny - 1);
     if (s0 >= s1 || t0 >= t1) return;
-    for (int k = threadIdx.x; k < a.rows * a.strip; k += PD_THREADS) pd_owner[k] = 0u;
+    for (int k = threadIdx.x; k < a.rows * a.strip; k += RS_THREADS) pd_owner[k] = 0u;
     __syncthreads();
     for (int64_t li = 0; li < a.nsel; li++) {
         const int32_t *bb = a.bbox + 4 * li;
@@ -439,16 +350,16 @@ __global__ void __launch_bounds__(PD_THREADS) k_polyline_density(PdArgs a)
         const int64_t v0 = a.line_offsets[L], hi = a.line_offsets[L + 1] - v0 - 1;    // segments 1 ... hi
         if (hi < 1) continue;
         const double *v = a.vertices + 2 * v0;
-        const bool single = hi <= PD_THREADS;
+        const bool single = hi <= RS_THREADS;
         int total = 0;
-        for (int64_t seg0 = 1; seg0 <= hi; seg0 += PD_THREADS) {
+        for (int64_t seg0 = 1; seg0 <= hi; seg0 += RS_THREADS) {
             total = pd_setup(a, S, v, seg0, hi, s0, s1, t0, t1);
-            pd_pass<0>(a, S, pd_owner, seg0, total, s0, s1, t0, t1);
+            rs_pass<0>(S, pd_owner, a.strip, a.grid, a.coverage, a.nx, seg0, total, s0, s1, t0, t1);
             __syncthreads();
         }
-        for (int64_t seg0 = 1; seg0 <= hi; seg0 += PD_THREADS) {
+        for (int64_t seg0 = 1; seg0 <= hi; seg0 += RS_THREADS) {
             if (!single) total = pd_setup(a, S, v, seg0, hi, s0, s1, t0, t1);
-            pd_pass<1>(a, S, pd_owner, seg0, total, s0, s1, t0, t1);
+            rs_pass<1>(S, pd_owner, a.strip, a.grid, a.coverage, a.nx, seg0, total, s0, s1, t0, t1);
             __syncthreads();
         }
     }
@@ -458,9 +369,7 @@ int launch_polyline_density(beatamd_ctx *ctx, int64_t nsel, const int64_t *sel, 
                             const double *vertices, const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid,
                             int32_t *coverage)
 {
-    BA_CHECK(ny >= 2 && ny <= 4096 && nx >= 2 && nx <= 4096, BEATAMD_EINVAL, "polyline_density: grid %lld x %lld (2 ... 4096 each)",
-             (long long)ny, (long long)nx);
-    BA_CHECK(linewidth > 0.0 && linewidth <= 64.0, BEATAMD_EINVAL, "polyline_density: linewidth %g outside (0, 64]", linewidth);
+    BA_TRY(rs_check_args("polyline_density", ny, nx, linewidth));
     BA_CHECK(nsel >= 0 && (nsel + 3) / 4 < (int64_t)0x7fffffff, BEATAMD_EINVAL, "polyline_density: bad polyline count");
     if (nsel == 0) return BEATAMD_OK;
     PdArgs a;
@@ -470,22 +379,20 @@ int launch_polyline_density(beatamd_ctx *ctx, int64_t nsel, const int64_t *sel, 
     a.ystep = (extent[3] - extent[2]) / (double)(ny - 1);
     a.ny = (int)ny; a.nx = (int)nx; a.grid = grid; a.coverage = coverage; a.status = ctx->d_status;
     BA_TRY(ctx->scratch(SL_PD_BOX, (size_t)4 * nsel, &a.bbox));
-    // a line's half width is at most linewidth * sqrt(2) / 4, its pixels reach ceil(that) + 1 cells from the centre line;
-    // one more for the centre line's rounding
-    a.pad = (int)std::ceil(linewidth * 1.4142135623730951 / 4.0) + 2;
+    a.pad = rs_pad(linewidth);
     // BEATAMD_PD_STRIP / BEATAMD_PD_ROWS: test knobs for the tile's shape, the result does not change
     const GfKnobs &kn = gf_knobs(ctx);
     a.strip = std::max(1, std::min(GfKnobs::get(kn.pd_strip, PD_STRIP), (int)nx));
     a.rows = std::max(1, std::min(GfKnobs::get(kn.pd_rows, PD_ROWS), (int)ny));
     a.rows = std::max(1, std::min(a.rows, PD_LDS_BYTES / (4 * a.strip)));
     const size_t lds = (size_t)a.rows * a.strip * sizeof(uint32_t);
-    if (lds + sizeof(PdSetup) > 64 * 1024)
+    if (lds + sizeof(RsSetup) > 64 * 1024)
         BA_HIP(hipFuncSetAttribute((const void *)k_polyline_density, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ScopedTimer tm(ctx, "polyline_density");
     hipLaunchKernelGGL(k_polyline_check, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, ctx->stream, a);
     BA_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_polyline_density, dim3((unsigned)((nx - 1 + a.strip - 1) / a.strip), (unsigned)((ny - 1 + a.rows - 1) / a.rows)),
-                       dim3(PD_THREADS), lds, ctx->stream, a);
+                       dim3(RS_THREADS), lds, ctx->stream, a);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

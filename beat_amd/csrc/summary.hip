@@ -2,6 +2,7 @@
 // standardized residuals, and running moments of an ensemble of synthetics.  The forward model and the quadratic
 // forms are the likelihood's own kernels (capi.cpp); what is here is the arithmetic the reference does after them.
 #include "kernels.hpp"
+#include "raster.hpp"
 
 namespace beatamd {
 
@@ -153,8 +154,9 @@ int launch_moments_finish(beatamd_ctx *ctx, int64_t M, const double *state, int6
 // ---- density grid of an ensemble of traces (plotting/seismic.py:255-316 fuzzy_waveforms; plotting/common.py:619-801
 // draw_line_on_array / _weighted_line; utility.py:1556 positions2idxs).  Every trace Y[e, t, :] is drawn as N - 1
 // anti-aliased segments into an image of its own -- a pixel keeps the value of the highest-numbered segment that writes
-// it -- and the image is added to grid[t]; traces in ensemble order.  The arithmetic below is the reference's numpy
-// arithmetic operation by operation (contraction off, correctly rounded sqrt): the grid is the reference's bit for bit.
+// it -- and the image is added to grid[t]; traces in ensemble order.  The rasteriser is raster.hpp's, the reference's
+// arithmetic operation by operation: the grid is the reference's bit for bit.  What is here is where a workgroup's
+// segments come from: the time axis is uniform.
 struct TdArgs {
     int64_t E, T, N;
     const double *Y, *tmin, *extent;   // [E,T,N], [T], [T,4] = (xmin, xmax, ymin, ymax)
@@ -164,15 +166,6 @@ struct TdArgs {
     double *grid;                      // [T,ny,nx]
     int *status;
 };
-constexpr int TD_THREADS = 256;
-constexpr double TD_INDEX_MIN = -32768.0;   // below: the reference's int32 products overflow
-
-// utility.py:1556: round((pos - min - cell / 2) / cell), half to even -- as a double
-__device__ __forceinline__ double td_cell(double pos, double lo, double step)
-{
-#pragma clang fp contract(off)
-    return rint((pos - lo - step / 2.0) / step);
-}
 
 // the samples [*lo, *hi) of trace `tr` = e * T + t that its range (first, count) leaves inside [0, N); false: fewer than
 // two, the trace draws nothing
@@ -185,8 +178,7 @@ __device__ __forceinline__ bool td_range(const TdArgs &a, int64_t tr, int64_t *l
     return true;
 }
 
-// every sample's row index and every time's column index: above the grid or below TD_INDEX_MIN -> ST_LINE_OOB
-// (check_line_in_grid's TypeError), not finite -> ST_LINE_NONFINITE.  k_trace_density does not start on a raised word.
+// every sample's row index and every time's column index (rs_index_status).  k_trace_density does not start on a raised word.
 // With ranges only the samples inside their trace's range are looked at, each with its time (a time outside every range
 // is never drawn)
 template <bool RANGED>
@@ -197,20 +189,16 @@ __device__ __forceinline__ void td_check(const TdArgs &a)
     if (i >= a.E * a.T * a.N) return;
     const int64_t j = i % a.N, t = (i / a.N) % a.T;
     const double *ext = a.extent + 4 * t;
-    int bad = 0;
     if (RANGED) {
         int64_t lo, hi;
         if (!td_range(a, i / a.N, &lo, &hi) || j < lo || j >= hi) return;
     }
     const double ystep = (ext[3] - ext[2]) / (double)(a.ny - 1);
-    const double q = td_cell(a.Y[i], ext[2], ystep);
-    if (!(fabs(q) <= 1.79769313486231570815e+308)) bad |= ST_LINE_NONFINITE;
-    else if (q > (double)(a.ny - 1) || q < TD_INDEX_MIN) bad |= ST_LINE_OOB;
+    int bad = rs_index_status(rs_cell(a.Y[i], ext[2], ystep), a.ny - 1);
     if (RANGED || i < a.T * a.N) {           // the time axis is the same for every trace of a target
         const double xstep = (ext[1] - ext[0]) / (double)(a.nx - 1);
-        const double c = td_cell(a.tmin[t] + (double)j * a.deltat, ext[0], xstep);
-        if (!(fabs(c) <= 1.79769313486231570815e+308) || !(xstep > 0.0)) bad |= ST_LINE_NONFINITE;
-        else if (c > (double)(a.nx - 1) || c < TD_INDEX_MIN) bad |= ST_LINE_OOB;
+        const double c = rs_cell(a.tmin[t] + (double)j * a.deltat, ext[0], xstep);
+        bad |= xstep > 0.0 ? rs_index_status(c, a.nx - 1) : ST_LINE_NONFINITE;
     }
     if (bad) atomicOr(a.status, bad);
 }
@@ -218,113 +206,32 @@ __device__ __forceinline__ void td_check(const TdArgs &a)
 __global__ void __launch_bounds__(256) k_trace_density_check(TdArgs a) { td_check<false>(a); }
 __global__ void __launch_bounds__(256) k_trace_density_check_ranged(TdArgs a) { td_check<true>(a); }
 
-// The segments of one trace for the workgroup's columns [s0, s1), TD_THREADS at a time:
-//   set-up  lane <-> segment: cell indices of its two samples, the roles of rows and columns, slope, width, intercept, and
-//           the range of x (the line's long axis) that lies inside the grid and the strip -> LDS; an inclusive scan of the
-//           ranges' lengths numbers the (segment, x) pairs
-//   pass    lane <-> (segment, x) pair, found by bisection in the scan -- a long steep segment is spread over the lanes
-//           like many short ones; the lane walks the 2 th + 3 pixels across the line.  PASS 0: every pixel written gets
-//           the segment number through an LDS atomic max; PASS 1: the same pixels again, and where the segment is the
-//           owner its value is added to the grid and the entry cleared.  owner [ny, strip], 0 = nobody (segments count
-//           from 1).
-struct TdSetup {
-    double slope[TD_THREADS], b[TD_THREADS], hw[TD_THREADS];
-    int xlo[TD_THREADS], meta[TD_THREADS], pre[TD_THREADS];    // meta = th | transposed << 8; pre = scan of the lengths
-    int wtot[TD_THREADS / 64];
-};
-
-// -> pairs of the TD_THREADS segments from seg0 on (the last is ihi)
-__device__ __forceinline__ int td_setup(const TdArgs &a, TdSetup &S, const double *y, int64_t seg0, int64_t ihi, double tmin,
+// The set-up (raster.hpp) of the RS_THREADS segments of trace y from seg0 on (the last is ihi) for the workgroup's columns
+// [s0, s1) and all rows; segment i joins samples i - 1 and i.  -> its pairs
+__device__ __forceinline__ int td_setup(const TdArgs &a, RsSetup &S, const double *y, int64_t seg0, int64_t ihi, double tmin,
                                         double xmin, double xstep, double ymin, double ystep, int s0, int s1)
 {
 #pragma clang fp contract(off)
-    const int tid = threadIdx.x;
-    const int64_t i = seg0 + tid;
-    int cnt = 0;
-    if (i <= ihi) {
-        int c0 = (int)td_cell(tmin + (double)(i - 1) * a.deltat, xmin, xstep);
-        int c1 = (int)td_cell(tmin + (double)i * a.deltat, xmin, xstep);
-        int r0 = (int)td_cell(y[i - 1], ymin, ystep);
-        int r1 = (int)td_cell(y[i], ymin, ystep);
-        if (r0 != r1 || c0 != c1) {                             // (else the reference's ValueError branch: nothing drawn)
-            const bool tr = abs(c1 - c0) < abs(r1 - r0);        // steep: rows and columns change roles, limits included
-            if (tr) { int s = r0; r0 = c0; c0 = s; s = r1; r1 = c1; c1 = s; }
-            if (c0 > c1) { int s = r0; r0 = r1; r1 = s; s = c0; c0 = c1; c1 = s; }
-            const double slope = (double)(r1 - r0) / (double)(c1 - c0);
-            const double w = a.linewidth * sqrt(1.0 + fabs(slope)) / 2.0;
-            const double b = (double)((int64_t)c1 * r0 - (int64_t)c0 * r1) / (double)(c1 - c0);
-            const double hw = w / 2.0;
-            const int th = (int)ceil(hw);
-            // only pixels inside the grid less its last row and column, and inside the strip, are written: x is cut to
-            // them here, the position across the line in the pass
-            const int xlo = max(c0, tr ? 0 : s0), xhi = min(c1, (tr ? a.ny - 1 : s1) - 1);
-            // a steep segment's columns lie within th + 2 of its end points' (th + 1 pixels and the centre's rounding)
-            const bool off = tr && (max(r0, r1) + th + 2 < s0 || min(r0, r1) - th - 2 >= s1);
-            if (xhi >= xlo && !off) cnt = xhi - xlo + 1;
-            S.slope[tid] = slope; S.b[tid] = b; S.hw[tid] = hw; S.xlo[tid] = xlo; S.meta[tid] = th | (tr ? 256 : 0);
-        }
+    const int64_t i = seg0 + threadIdx.x;
+    const bool have = i <= ihi;
+    int c0 = 0, r0 = 0, c1 = 0, r1 = 0;
+    if (have) {
+        c0 = (int)rs_cell(tmin + (double)(i - 1) * a.deltat, xmin, xstep);
+        c1 = (int)rs_cell(tmin + (double)i * a.deltat, xmin, xstep);
+        r0 = (int)rs_cell(y[i - 1], ymin, ystep);
+        r1 = (int)rs_cell(y[i], ymin, ystep);
     }
-    int v = cnt;
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {   // a scan: open-coded (the reductions are wave.hpp's)
-        const int n = __shfl_up(v, d);
-        if (lane >= d) v += n;
-    }
-    if (lane == 63) S.wtot[wave] = v;
-    __syncthreads();
-    for (int k = 0; k < wave; k++) v += S.wtot[k];
-    S.pre[tid] = v;
-    __syncthreads();
-    return S.pre[TD_THREADS - 1];
-}
-
-template <int PASS>
-__device__ __forceinline__ void td_pass(const TdArgs &a, const TdSetup &S, uint32_t *owner, double *g, int64_t seg0, int total,
-                                        int s0, int s1)
-{
-#pragma clang fp contract(off)
-    for (int it = threadIdx.x; it < total; it += TD_THREADS) {
-        int k = 0;                                              // the first segment whose scan exceeds `it`
-#pragma unroll
-        for (int s = TD_THREADS / 2; s > 0; s >>= 1)
-            if (S.pre[k + s - 1] <= it) k += s;
-        const int meta = S.meta[k], th = meta & 255;
-        const bool tr = meta >> 8;
-        const int x = S.xlo[k] + (it - (k ? S.pre[k - 1] : 0));
-        const double slope = S.slope[k], b = S.b[k], hw = S.hw[k];
-        const uint32_t seg = (uint32_t)(seg0 + k);
-        const double ylo = tr ? (double)s0 : 0.0, yhi = tr ? (double)s1 : (double)(a.ny - 1);
-        const double yv = (double)x * slope + b;
-        const double fl = floor(yv);
-        for (int o = -th - 1; o <= th + 1; o++) {
-            const double yy = fl + (double)o;
-            const double up = yy + 1.0 + hw - yv, dn = -yy + 1.0 + hw + yv;
-            double v = up < dn ? up : dn;
-            v = v > 1.0 ? 1.0 : v;
-            if (!(v > 0.0) || yy < ylo || !(yy < yhi)) continue;
-            const int iy = (int)yy;
-            const int row = tr ? x : iy, col = tr ? iy : x;
-            uint32_t *own = owner + row * a.strip + (col - s0);
-            if (PASS == 0) {
-                atomicMax(own, seg);
-            } else if (*(volatile uint32_t *)own == seg) {
-                double *p = g + (int64_t)row * a.nx + col;
-                *p = *p + v;
-                *own = 0u;
-            }
-        }
-    }
+    return rs_setup(S, have, c0, r0, c1, r1, a.linewidth, s0, s1, 0, a.ny - 1);
 }
 
 // One workgroup <-> (a strip of grid columns, a target); it walks the traces in ensemble order, so every pixel's sum has
 // the reference's order without atomics on doubles, and the strip of grid[t] is the workgroup's alone.  The time axis is
 // uniform: the segments that can touch the strip (widened by `pad` columns, the reach of the widest line) are one index
-// range, found by bisection once.  Per trace: pass 0 over the range in chunks of TD_THREADS segments, then pass 1 (with
+// range, found by bisection once.  Per trace: pass 0 over the range in chunks of RS_THREADS segments, then pass 1 (with
 // one chunk, on the set-up that pass 0 left).  The result does not depend on the strip width or on the chunking.
 // RANGED: the kernel with per-trace ranges (k_trace_density_ranged); without them the code is the plain kernel's
 template <bool RANGED>
-__device__ __forceinline__ void td_draw(const TdArgs &a, uint32_t *td_owner, TdSetup &S)
+__device__ __forceinline__ void td_draw(const TdArgs &a, uint32_t *td_owner, RsSetup &S)
 {
 #pragma clang fp contract(off)
     if (*(volatile int *)a.status & (ST_LINE_OOB | ST_LINE_NONFINITE)) return;   // (k_trace_density_check, uniform)
@@ -334,23 +241,23 @@ __device__ __forceinline__ void td_draw(const TdArgs &a, uint32_t *td_owner, TdS
     const double *ext = a.extent + 4 * t;
     const double xmin = ext[0], ymin = ext[2], tmin = a.tmin[t];
     const double xstep = (ext[1] - xmin) / (double)(a.nx - 1), ystep = (ext[3] - ymin) / (double)(a.ny - 1);
-    for (int k = tid; k < a.ny * a.strip; k += TD_THREADS) td_owner[k] = 0u;
+    for (int k = tid; k < a.ny * a.strip; k += RS_THREADS) td_owner[k] = 0u;
     // first sample whose column is >= lo / > hi (columns do not decrease with the sample index)
     const double clo = (double)(s0 - a.pad), chi = (double)(s1 - 1 + a.pad);
     int64_t jlo = 0, n = a.N;
     while (n > 0) {
         const int64_t h = n / 2;
-        if (td_cell(tmin + (double)(jlo + h) * a.deltat, xmin, xstep) < clo) { jlo += h + 1; n -= h + 1; } else n = h;
+        if (rs_cell(tmin + (double)(jlo + h) * a.deltat, xmin, xstep) < clo) { jlo += h + 1; n -= h + 1; } else n = h;
     }
     int64_t jhi = jlo;
     n = a.N - jlo;
     while (n > 0) {
         const int64_t h = n / 2;
-        if (td_cell(tmin + (double)(jhi + h) * a.deltat, xmin, xstep) <= chi) { jhi += h + 1; n -= h + 1; } else n = h;
+        if (rs_cell(tmin + (double)(jhi + h) * a.deltat, xmin, xstep) <= chi) { jhi += h + 1; n -= h + 1; } else n = h;
     }
     const int64_t ilo = jlo > 1 ? jlo : 1, ihi = jhi < a.N - 1 ? jhi : a.N - 1;    // segment i joins samples i - 1 and i
     if (ilo > ihi) return;
-    const bool one = ihi - ilo < TD_THREADS;
+    const bool one = ihi - ilo < RS_THREADS;
     double *g = a.grid + (int64_t)t * a.ny * a.nx;
     __syncthreads();
     for (int64_t e = 0; e < a.E; e++) {
@@ -366,36 +273,36 @@ __device__ __forceinline__ void td_draw(const TdArgs &a, uint32_t *td_owner, TdS
             lo = ilo > rf + 1 ? ilo : rf + 1;
             hi = ihi < rend - 1 ? ihi : rend - 1;
             if (lo > hi) continue;
-            single = hi - lo < TD_THREADS;
+            single = hi - lo < RS_THREADS;
         }
-        for (int64_t seg0 = lo; seg0 <= hi; seg0 += TD_THREADS) {
+        for (int64_t seg0 = lo; seg0 <= hi; seg0 += RS_THREADS) {
             total = td_setup(a, S, y, seg0, hi, tmin, xmin, xstep, ymin, ystep, s0, s1);
-            td_pass<0>(a, S, td_owner, g, seg0, total, s0, s1);
+            rs_pass<0>(S, td_owner, a.strip, g, nullptr, a.nx, seg0, total, s0, s1, 0, a.ny - 1);
             __syncthreads();
         }
-        for (int64_t seg0 = lo; seg0 <= hi; seg0 += TD_THREADS) {
+        for (int64_t seg0 = lo; seg0 <= hi; seg0 += RS_THREADS) {
             if (!single) total = td_setup(a, S, y, seg0, hi, tmin, xmin, xstep, ymin, ystep, s0, s1);
-            td_pass<1>(a, S, td_owner, g, seg0, total, s0, s1);
+            rs_pass<1>(S, td_owner, a.strip, g, nullptr, a.nx, seg0, total, s0, s1, 0, a.ny - 1);
             __syncthreads();
         }
     }
 }
 
-__global__ void __launch_bounds__(TD_THREADS) k_trace_density(TdArgs a)
+__global__ void __launch_bounds__(RS_THREADS) k_trace_density(TdArgs a)
 {
     extern __shared__ uint32_t td_owner[];
-    __shared__ TdSetup S;
+    __shared__ RsSetup S;
     td_draw<false>(a, td_owner, S);
 }
 
-__global__ void __launch_bounds__(TD_THREADS) k_trace_density_ranged(TdArgs a)
+__global__ void __launch_bounds__(RS_THREADS) k_trace_density_ranged(TdArgs a)
 {
     extern __shared__ uint32_t td_owner[];
-    __shared__ TdSetup S;
+    __shared__ RsSetup S;
     td_draw<true>(a, td_owner, S);
 }
 
-// the owner map's share of the 160 KiB of LDS (TdSetup takes 10 KiB)
+// the owner map's share of the 160 KiB of LDS (RsSetup takes 10 KiB)
 constexpr int TD_LDS_BYTES = 150 * 1024, TD_STRIP = 32, TD_STRIP_MIN = 8;
 
 int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
@@ -407,11 +314,9 @@ int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, cons
 int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, const double *Y, const double *tmin, double deltat,
                          const double *extent, int64_t ny, int64_t nx, double linewidth, double *grid, const int64_t *ranges)
 {
-    BA_CHECK(ny >= 2 && ny <= 4096 && nx >= 2 && nx <= 4096, BEATAMD_EINVAL, "trace_density: grid %lld x %lld (2 ... 4096 each)",
-             (long long)ny, (long long)nx);
-    BA_CHECK(linewidth > 0.0 && linewidth <= 64.0, BEATAMD_EINVAL, "trace_density: linewidth %g outside (0, 64]", linewidth);
+    BA_TRY(rs_check_args("trace_density", ny, nx, linewidth));
     BA_CHECK(N >= 2 && N < (int64_t)0x7fffffff, BEATAMD_EINVAL, "trace_density: %lld samples (at least 2)", (long long)N);
-    BA_CHECK(deltat > 0.0 && deltat <= 1.79769313486231570815e+308, BEATAMD_EINVAL, "trace_density: deltat %g", deltat);
+    BA_CHECK(deltat > 0.0 && deltat <= DBL_MAX, BEATAMD_EINVAL, "trace_density: deltat %g", deltat);
     BA_CHECK(E >= 0 && T >= 0 && T <= 65535, BEATAMD_EINVAL, "trace_density: bad ensemble or target count");
     if (E == 0 || T == 0) return BEATAMD_OK;
     const int64_t nchk = (E * T * N + 255) / 256;
@@ -419,27 +324,25 @@ int launch_trace_density(beatamd_ctx *ctx, int64_t E, int64_t T, int64_t N, cons
     TdArgs a;
     a.E = E; a.T = T; a.N = N; a.Y = Y; a.ranges = ranges; a.tmin = tmin; a.extent = extent; a.deltat = deltat; a.linewidth = linewidth;
     a.ny = (int)ny; a.nx = (int)nx; a.grid = grid; a.status = ctx->d_status;
-    // a line's half width is at most linewidth * sqrt(2) / 4, its pixels reach ceil(that) + 1 cells from the centre line;
-    // one more for the centre line's rounding
-    a.pad = (int)std::ceil(linewidth * 1.4142135623730951 / 4.0) + 2;
+    a.pad = rs_pad(linewidth);
     // strip: TD_STRIP columns where segments are long (a workgroup per trace has a fixed cost: fewer workgroups), narrower
     // where samples are dense, so that the (strip + 2 pad) N / nx segments of a strip fill 3/4 of one chunk -- a second
     // chunk costs a second set-up in both passes (measured, 500 x 500, width 7, 200 x 64 traces: N = 4096 16.1 ms at 32
     // columns, 18.1 at 24, 11.4 at 12; N = 120 3.1 ms at 32, 4.0 at 12) -- and as the owner map allows.
     // BEATAMD_TD_STRIP: a test knob, the result does not change
     const int fit = (int)(TD_LDS_BYTES / (4 * ny));
-    const int64_t dense = (int64_t)(TD_THREADS * 3 / 4) * nx / N - 2 * a.pad;
+    const int64_t dense = (int64_t)(RS_THREADS * 3 / 4) * nx / N - 2 * a.pad;
     const int want = GfKnobs::get(gf_knobs(ctx).td_strip, (int)std::max<int64_t>(TD_STRIP_MIN, std::min<int64_t>(TD_STRIP, dense)));
     a.strip = std::max(1, std::min(std::min(want, fit), (int)nx));
     const size_t lds = (size_t)ny * a.strip * sizeof(uint32_t);
     const auto check = ranges ? k_trace_density_check_ranged : k_trace_density_check;
     const auto draw = ranges ? k_trace_density_ranged : k_trace_density;
-    if (lds + sizeof(TdSetup) > 64 * 1024)
+    if (lds + sizeof(RsSetup) > 64 * 1024)
         BA_HIP(hipFuncSetAttribute((const void *)draw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     ScopedTimer tm(ctx, "density");
     hipLaunchKernelGGL(check, dim3((unsigned)nchk), dim3(256), 0, ctx->stream, a);
     BA_HIP(hipGetLastError());
-    hipLaunchKernelGGL(draw, dim3((unsigned)((nx - 1 + a.strip - 1) / a.strip), (unsigned)T), dim3(TD_THREADS), lds, ctx->stream, a);
+    hipLaunchKernelGGL(draw, dim3((unsigned)((nx - 1 + a.strip - 1) / a.strip), (unsigned)T), dim3(RS_THREADS), lds, ctx->stream, a);
     BA_HIP(hipGetLastError());
     return BEATAMD_OK;
 }

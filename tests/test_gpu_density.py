@@ -148,14 +148,37 @@ def test_3_grid_widths_off_the_strip_width(ctx, ny, nx, lw):
 
 
 # ------------------------------------------------------------------------------------------------- 5 clipping
-def test_5_extent_narrower_than_the_data_on_the_low_side_clips(ctx):
+def _flat_segments_below_reach(Y, tmin, deltat, extent, ny, nx, lw):
+    """how many segments are flat (|dc| >= |dr|, not a point), reach a grid column (>= 0) and have both row indices below
+    -(th + 2), th = ceil(w / 2) of _weighted_line: the set-up gives them no pixel column at all"""
+    n = 0
+    for t in range(Y.shape[1]):
+        xstep, ystep = dref.steps(extent[t], ny, nx)
+        cols = dref.cell_indices(tmin[t] + np.arange(Y.shape[2]) * deltat, extent[t, 0], xstep, nx - 1, "x")
+        dc = np.abs(np.diff(cols))
+        for e in range(Y.shape[0]):
+            rows = dref.cell_indices(Y[e, t], extent[t, 2], ystep, ny - 1, "y")
+            dr = np.abs(np.diff(rows))
+            flat = (dc >= dr) & (dc > 0) & (np.maximum(cols[1:], cols[:-1]) >= 0)
+            th = np.ceil(lw * np.sqrt(1.0 + dr / np.maximum(dc, 1)) / 2.0 / 2.0)
+            n += int((flat & (np.maximum(rows[1:], rows[:-1]) < -(th + 2))).sum())
+    return n
+
+
+def test_5_extent_narrower_than_the_data_on_the_low_side_clips(ctx, monkeypatch):
+    """also at 1 and 7 columns per workgroup; some flat segments lie wholly below the reach of row 0"""
     Y, tmin, deltat, extent = _problem(5, 6, 3, 65)
     extent[:, 0] += 0.3 * (extent[:, 1] - extent[:, 0])
     extent[:, 2] *= 0.4
     assert (Y.min(axis=(0, 2)) < extent[:, 2]).all()
+    assert _flat_segments_below_reach(Y, tmin, deltat, extent, 40, 24, 7) >= 1
     ref = dref.trace_density(Y, tmin, deltat, extent, (40, 24), 7)
     for got in _both_sides(ctx, Y, tmin, deltat, extent, (40, 24), 7):
         assert np.array_equal(got, ref)
+    for strip in ("1", "7"):
+        monkeypatch.setenv("BEATAMD_TD_STRIP", strip)
+        for got in _both_sides(ctx, Y, tmin, deltat, extent, (40, 24), 7):
+            assert np.array_equal(got, ref), "strip %s: %d pixels differ" % (strip, (got != ref).sum())
 
 
 # ------------------------------------------------------------------------------------------------- 6 errors
