@@ -70,6 +70,16 @@ def lfilter(b, a, x):
     return out
 
 
+def tap_count_filters(lower=0.05, upper=0.4):
+    """(ntaps, order, wn, btype) of single Butterworth sections covering every tap count 3 ... 17 of the device cascade: the
+    band-pass of order 1 ... 8 (3, 5, ..., 17 taps), the low-pass at ``upper`` and the high-pass at ``lower`` of odd order
+    3 ... 15 (4, 6, ..., 16 taps); wn in units of the Nyquist frequency (0.1 and 0.8 Hz at deltat = 0.25 s)"""
+    cases = [(2 * order + 1, order, [lower, upper], "band") for order in range(1, 9)]
+    for order in range(3, 16, 2):
+        cases += [(order + 1, order, upper, "low"), (order + 1, order, lower, "high")]
+    return cases
+
+
 def cascade(x, stages):
     """the stages (b, a, demean) one after the other over the rows of x [R, n]"""
     for b, a, demean in stages:

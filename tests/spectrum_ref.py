@@ -130,7 +130,9 @@ def bin_bound(y, ntrans):
 
 
 # ---- the cases of the kernel test (tests/test_gpu_spectrum.py test 1; tools/spectrum_timing.py records their bound ratios)
-KERNEL_SIZES = (2, 3, 5, 8, 120, 127, 128, 129, 4096, 4097)
+# nextpow2 of these is every power of two from 2 to 8192; N = ntrans and N = ntrans / 2 + 1 for 16, 32, 64 (one wavefront, less
+# than a quad per lane), 512 (the largest one-wavefront shape), 1024 (the smallest one-workgroup shape, odd stage count), 2048
+KERNEL_SIZES = (2, 3, 5, 8, 9, 16, 17, 32, 33, 64, 120, 127, 128, 129, 257, 512, 513, 1024, 1025, 2048, 4096, 4097)
 KERNEL_ROWS = (1, 7, 130)
 _TRACES = {}
 

@@ -5,8 +5,7 @@ that mixes time and spectrum wavemaps; every path that evaluates the model; a sh
 The bound of the kernel against numpy, per bin:   |dev - numpy| <= 8 max(1, log2 ntrans) 2^-53 |y|_2
 -- the classical O(eps log n |y|_2) error of an FFT with a constant of 8; a radix-2 double FFT and numpy's rfft each sit 2.8
 (ntrans 8) to 10.8 (ntrans 4096) units of 2^-53 |y|_2 from a long-double transform, the bound is 24 to 104.
-Largest |diff| / bound observed on an MI355X, per ntrans: see profiles/spectrum_timing.json ("bound_ratio"), quoted in
-test_1_kernel_against_numpy's docstring."""
+Largest |diff| / bound observed on an MI355X, per ntrans: in test_1_kernel_against_numpy's docstring."""
 import os
 import sys
 
@@ -45,9 +44,11 @@ def _model(name, interp="nn", weights="scalar", hps=False):
 # ------------------------------------------------------------------------------------------------- 1 kernel against numpy
 @pytest.mark.parametrize("N", sr.KERNEL_SIZES)
 def test_1_kernel_against_numpy(N):
-    """every (R, band) of a trace length within the bound of the module docstring.  Largest |diff| / bound observed on an
-    MI355X: 0.21 (ntrans 128; 0.15 .. 0.21 for every ntrans from 4 to 8192, 0 for ntrans 2; per ntrans in
-    profiles/spectrum_timing.json "bound_ratio")"""
+    """every (R, band) of a trace length within the bound of the module docstring; the trace lengths cover every ntrans
+    from 2 to 8192.  Largest |diff| / bound this test printed on an MI355X, per ntrans: 2: 0, 4: 0.16, 8: 0.19, 16: 0.25
+    (N = 9), 32: 0.21, 64: 0.18, 128: 0.20, 256: 0.18, 512: 0.21 (the largest one-wavefront shape), 1024: 0.19 (the smallest
+    one-workgroup shape, odd stage count), 2048: 0.21, 4096: 0.17, 8192: 0.15 (profiles/spectrum_timing.json "bound_ratio"
+    holds the lengths that tools/spectrum_timing.py was last run with)"""
     ntrans, worst, where = sr.kernel_bound_ratio(_ctx(), N)
     print("N %d ntrans %d: largest |diff| / bound %.3g at (R, band) = %s" % (N, ntrans, worst, where))
     assert worst <= 1.0, (N, where, worst)
@@ -63,7 +64,7 @@ def test_1_bad_arguments_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------------- 2 exact cases
-@pytest.mark.parametrize("N", (5, 120, 129, 4096, 4097))
+@pytest.mark.parametrize("N", (5, 120, 129, 512, 513, 4096, 4097))      # 512 | 513: one wavefront | one workgroup a trace
 def test_2_exact_cases(N):
     ctx = _ctx()
     ntrans = sr.nextpow2(N)
@@ -83,7 +84,7 @@ def test_2_exact_cases(N):
     assert abs(got[4, 0] - N * 0.75) <= bound[4]            # DC of a constant row
 
 
-@pytest.mark.parametrize("ntrans", (8, 128, 1024, 8192))
+@pytest.mark.parametrize("ntrans", (8, 128, 512, 1024, 2048, 8192))
 def test_2_padding_is_never_read(ntrans):
     """N = ntrans and N = ntrans/2 + 1: the same bits as the same samples handed in zero padded to ntrans"""
     ctx = _ctx()
@@ -97,7 +98,7 @@ def test_2_padding_is_never_read(ntrans):
 
 
 # ------------------------------------------------------------------------------------------------- 3 independence
-@pytest.mark.parametrize("N", (5, 120, 129, 4096))
+@pytest.mark.parametrize("N", (5, 120, 129, 512, 513, 4096))
 def test_3_rows_do_not_depend_on_the_batch(N):
     import torch
     ctx = _ctx()

@@ -35,6 +35,39 @@ def test_filter_recurrence_is_scipys_lfilter_bit_for_bit():
             np.testing.assert_array_equal(ref.lfilter(b, a, x), ss.lfilter(b, a, x, axis=1), err_msg="%d %s" % (order, btype))
 
 
+def test_filter_recurrence_is_scipys_lfilter_for_every_tap_count():
+    """the sections tests/test_gpu_trace_lengths.py runs on the device, 3 ... 17 taps: the odd-order low- and high-passes
+    (even tap counts) are not among the orders above"""
+    ss = pytest.importorskip("scipy.signal")
+    x = np.random.default_rng(2).standard_normal((3, 150))
+    seen = set()
+    for ntaps, order, wn, btype in ref.tap_count_filters():
+        b, a = sl.butter_coefficients(order, wn, btype)
+        assert b.size == a.size == ntaps
+        np.testing.assert_array_equal(ref.lfilter(b, a, x), ss.lfilter(b, a, x, axis=1), err_msg="%d %s" % (order, btype))
+        seen.add(ntaps)
+    assert seen == set(range(sb.MIN_TAPS, sb.MAX_TAPS + 1))
+
+
+@pytest.mark.parametrize("L,duration", [(5, 3.3), (5, 20.0), (500, 3.3), (700, 20.0)])
+def test_convolution_is_numpys_within_the_summation_order(L, duration):
+    """a source-time function longer than the response (nt = 14, 81 > L = 5) and Lc = 513, 780 > 512.  Both sides add the
+    products a_i g[n - i], in different orders: a sum of at most nt terms in any order is within (nt - 1) 2^-53
+    sum_i |a_i g[n - i]| of the exact one to first order.  The bound held here, nt 2^-53 sum_i |a_i g[n - i]| per sample,
+    is about half of the two worst cases added: a wrong index or a dropped term misses it by thirteen orders of magnitude"""
+    nt, A = ref.stf_table([duration], 0.25)
+    a = A[0, :nt[0]]
+    assert (a.size > L) == (L == 5) and (L + a.size - 1 > 512) == (L > 5)
+    g = np.random.default_rng(L + a.size).standard_normal((3, L))
+    got = ref.convolve(g, a)
+    assert got.shape == (3, L + a.size - 1)
+    for r in range(3):
+        want, mag = np.convolve(g[r], a), np.convolve(np.abs(g[r]), np.abs(a))
+        ratio = float((np.abs(got[r] - want) / (a.size * 2.0 ** -53 * mag)).max())
+        print("L %d nt %d row %d: largest |diff| / bound %.3g" % (L, a.size, r, ratio))
+        assert ratio <= 1.0
+
+
 def test_butter_coefficients_are_scipys_bit_for_bit():
     """measured where this was written: the largest |delta| / max|coef| over the sets below is 0 -- the restatement is
     bit-equal, so array_equal is asserted"""
